@@ -8,7 +8,13 @@ DoA grid 360 (BASELINE's nominal grid; `--grid 449` selects the script-exact one
 hot path over the 1100-trial batch (inputs resident in HBM): STHT, band-pass, RZCC, LIF, beamforming,
 power, arg-max, DoA error / MAE.  Weak scaling: every rank processes its own 1100-trial batch.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--no-cpu-baseline] [--config noisy|speech|stress]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--config noisy|speech|stress|xylo] [--dump-outputs DIR] [--full]
+
+A plain run sets up (ending with `--settle-seconds` of headline steps), warms up, times ONE region of exactly K steps, optionally
+writes the last step's outputs (`--dump-outputs`) and prints the line: `value` / `ms_per_step` and what is known without further runs.  `--full` adds everything else this file
+measures: five timed regions (median), the sustained region with clock / power telemetry, the end-to-end and variant clocks, the
+per-kernel stage times and roofline (with live rocprofv3 traffic passes), the CPU baselines, the reference-MAE / per-call /
+complex-beamformer / streaming blocks and the other workloads as child runs.
 
 `--gpus N` (N > 1) without a launcher: this process stays GPU-free and starts N ranks of itself (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, RCCL process group); under `python -m torch.distributed.run`
@@ -20,7 +26,7 @@ Other workloads (same JSON contract, their own `config.workload`, not the headli
   --config xylo     BASELINE configs[3], target_xylo_localization.py: 1 s chirp (T = 48 000), order-1 band-pass, bipolar RZCC,
                     integer LIF hidden layer (one neuron per DoA), find_peak_location -- PARITY UNPINNED for the LIF stage
 
-`value` times the hot path on a batch resident in HBM (the driver's contract); `value_e2e` adds everything in front of
+`value` times the hot path on a batch resident in HBM (the driver's contract); `value_e2e` (--full) adds everything in front of
 it inside the same captured graph: DoA draw, array-signal synthesis and AWGN on the device, fresh numbers every step.
 """
 import argparse
@@ -53,8 +59,15 @@ def parse(argv=None):
     ap.add_argument("--trials", type=int, default=None, help="trials per rank per step (default: 1100 = 11 SNRs x 100; speech 125; stress 256)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of each cpu_baseline leg")
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is run this many times; ms_per_step / value are the median")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the speech / xylo / stress child runs and the reference-MAE / per-call blocks")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: see the module docstring (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step (rank 0) as "
+                    "DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--settle-seconds", type=float, default=0.25, help="end the set-up with about this long of headline steps before the "
+                    "--warmup steps, so that a short timed region does not start while clock and power management settle; 0: none "
+                    "(the timed region follows the warm-up steps cold); the count is reported as config.settle_steps")
+    ap.add_argument("--repeats", type=int, default=None, help="the K-step timed region is run this many times; ms_per_step / value are the median "
+                    "(default 1; 5 with --full)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the speech / xylo / stress child runs and the reference-MAE / per-call blocks")
     ap.add_argument("--streams", type=int, default=None, help="HIP streams consecutive steps are pipelined over (1 = serial; default 3, "
                     "4 with the scan-lane schedule)")
     ap.add_argument("--schedule", choices=["auto", "graphs", "scan-lane"], default="auto", help="graphs: one captured hipGraph per stream, replayed "
@@ -70,8 +83,8 @@ def parse(argv=None):
                     "ranks (strong scaling: total work fixed) instead of a fixed batch per rank")
     ap.add_argument("--encoder-chunk", type=int, default=None, help="frames per time chunk of the band-pass / RZCC stage (default: the library's automatic choice; < 0: never chunk)")
     ap.add_argument("--traffic-bytes", type=float, default=None, help="override roofline.traffic (HBM bytes per dominant-kernel launch)")
-    ap.add_argument("--sustained-seconds", type=float, default=5.0, help="length of the `sustained` region (one long run of headline steps with the "
-                    "shader clock / socket power sampled in-process); 0 disables it")
+    ap.add_argument("--sustained-seconds", type=float, default=None, help="length of the `sustained` region (one long run of headline steps with the "
+                    "shader clock / socket power sampled in-process); 0 disables it (default 0; 5 with --full)")
     ap.add_argument("--other-sustained-seconds", type=float, default=10.0, help="length of the sustained region of each `other_configs` child run "
                     "(speech / xylo / stress: their steady-state ms per step with clock and power telemetry); 0 disables it")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not measure roofline.traffic in a rocprofv3 child of this run; read the "
@@ -88,6 +101,10 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.sustained_seconds is None:
+        args.sustained_seconds = 5.0 if args.full else 0.0
     if args.schedule == "auto":
         args.schedule = "scan-lane" if args.config == "speech" else "graphs"
     args.streams_given = args.streams is not None
@@ -240,8 +257,9 @@ def build_workload(args, rank, device):
                 make_batch=make_batch)
 
 
-def make_step(wl, nstreams, variants=True, scan_lane=0):
-    # variants: True = covariance + fp32 tails (noisy workload), None = covariance only, False = none (debugging)
+def make_step(wl, nstreams, variants=True, scan_lane=0, e2e=True):
+    # variants: True = covariance + fp32 tails (noisy workload), None = covariance only, False = none (a plain run, debugging)
+    # e2e: also the end-to-end step (input side inside the graph); a plain run does not build it
     """One step = one pass of the hot path over the batch.  Consecutive steps are independent batches, so they are
     dispatched round-robin over `nstreams` HIP streams (one plan/workspace each): the latency-bound RZCC kernel of
     one step overlaps the throughput-bound STHT / beamforming kernels of its neighbours."""
@@ -292,12 +310,14 @@ def make_step(wl, nstreams, variants=True, scan_lane=0):
     beamf = wl["beamf"]
     dev = x.device
     B, T, M = x.shape
-    t_in, s_in = synthesis._resample(*wl["template"], beamf.fs)
-    tpl = runtime.Template(t_in, s_in, beamf.fs, device=dev)
-    geo = runtime.Geometry(beamf.geometry, device=dev)
-    snr_dev = torch.from_numpy(np.ascontiguousarray(wl["snr_db"])).to(dev)
+    tpl = geo = snr_dev = None
     e2e_state = {}
-    for i, p in enumerate(plans):
+    if e2e:
+        t_in, s_in = synthesis._resample(*wl["template"], beamf.fs)
+        tpl = runtime.Template(t_in, s_in, beamf.fs, device=dev)
+        geo = runtime.Geometry(beamf.geometry, device=dev)
+        snr_dev = torch.from_numpy(np.ascontiguousarray(wl["snr_db"])).to(dev)
+    for i, p in enumerate(plans if e2e else []):
         e2e_state[id(p)] = dict(x=torch.empty_like(x), doa=torch.empty((B,), dtype=torch.float64, device=dev),
                                 shift=torch.empty((B,), dtype=torch.float64, device=dev),
                                 epoch=torch.full((1,), (wl["rank"] * 64 + i) << 20, dtype=torch.int32, device=dev),
@@ -315,7 +335,7 @@ def make_step(wl, nstreams, variants=True, scan_lane=0):
         _, mae = runtime.doa_error(out["argmax"], doa_list, st["doa"], groups=S, want_err=False)
         return out, mae
 
-    replay_e2e = pipe.capture(body_e2e) if not scan_lane else None
+    replay_e2e = pipe.capture(body_e2e) if (e2e and not scan_lane) else None
 
     # scan-lane schedule (long recordings): the same calls launched eagerly, the serial scan of every batch on the pipeline's lane
     # (runtime.StreamPipeline.snn_pipeline); a step is a handful of millisecond-scale launches, a graph saves nothing here
@@ -703,6 +723,53 @@ def memory_gb(device):
     free, total = torch.cuda.mem_get_info(device)
     return {"peak_reserved": torch.cuda.max_memory_reserved(device) / 1e9, "peak_allocated": torch.cuda.max_memory_allocated(device) / 1e9,
             "free_at_end": free / 1e9, "device_total": total / 1e9}
+
+
+def settle(step, sync, period, seconds):
+    """End of the set-up (--settle-seconds): replay the step for about `seconds` of device time before the --warmup steps.  The
+    set-up leaves the device mostly idle, and a short timed region right after it runs about 1.5 % slow until clock and power
+    management settle (headline, 50-step regions, three runs on one MI355X, not a committed profile: the first region 1.489-1.491 ms,
+    the next four 1.465-1.470; `--settle-seconds 0 --repeats 5` shows it).  The count is a multiple of `period` (the streams the
+    steps rotate over), so the timed steps read the same batches whatever the count.  Returns the steps replayed (0 if seconds <= 0)."""
+    n, chunk = 0, 1
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < seconds:
+        t1 = time.perf_counter()
+        for _ in range(chunk):
+            step()
+        sync()
+        n += chunk
+        chunk = max(1, min(64, int(0.05 / max(1e-6, (time.perf_counter() - t1) / chunk))))  # ~50 ms per synchronisation
+    while n % period:
+        step()
+        n += 1
+    sync()
+    return n
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays the timed path returned in its last step, as DIR/<name>.npy in float64 (integer outputs are exact).
+    Should they exceed `limit` bytes in all, the arrays whose leading axis is the trial axis (the longest leading axis) keep the same
+    fixed, seeded sample of trials, whose numbers go to DIR/sample_rows.npy.  Returns the names written."""
+    host = {k: np.ascontiguousarray(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float64))
+            for k, v in arrays.items() if v is not None}
+    os.makedirs(directory, exist_ok=True)
+    if sum(a.nbytes for a in host.values()) > limit:
+        n = max(a.shape[0] for a in host.values() if a.ndim)
+        per_trial = [k for k, a in host.items() if a.ndim and a.shape[0] == n]
+        fixed = sum(a.nbytes for k, a in host.items() if k not in per_trial)
+        row_bytes = sum(host[k].nbytes // n for k in per_trial) + 8
+        keep = max(1, min(n, (limit - fixed) // row_bytes))
+        rows = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        for k in per_trial:
+            host[k] = np.ascontiguousarray(host[k][rows])
+        host["sample_rows"] = rows.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(host)
 
 
 def sustained_over_ranks(sustained, grp, device, frames_per_step, ms_region):
@@ -1162,7 +1229,7 @@ def other_configs_block(args):
     #  finish together, which is not the steady state -- xylo 18.0 ms/step at 3 steps, 17.0 at 12)
     for cfg, steps in (("speech", 16), ("xylo", 12), ("stress", 9)):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(steps), "--warmup", "4" if cfg == "speech" else "3", "--repeats", "3",
-               "--no-cpu-baseline", "--no-other-configs", "--sustained-seconds", str(args.other_sustained_seconds)] + \
+               "--full", "--no-cpu-baseline", "--no-other-configs", "--sustained-seconds", str(args.other_sustained_seconds)] + \
               (["--streams", str(args.streams)] if args.streams_given else [])
         t0 = time.perf_counter()
         try:
@@ -1262,6 +1329,7 @@ def run_xylo(args, rank, local_rank, world):
         grp.barrier()
         torch.cuda.synchronize()
 
+    settle_steps = settle(replay, pipe.synchronize, nstreams, args.settle_seconds)
     for _ in range(args.warmup):
         replay()
     dt_all = []
@@ -1276,6 +1344,8 @@ def run_xylo(args, rank, local_rank, world):
         per_rank.append([float(v.item()) for v in grp.gather(dt)])
         grp.max_(dt)
         dt_all.append(float(dt.item()))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"counts": counts, "peak_index": idx, "mae": mae})  # the last step's outputs (this rank's MAE)
     mae = torch.stack(grp.gather(mae)).mean(dim=0)
     dt = float(np.median(dt_all))
     frames = group_size * B * T * args.steps
@@ -1286,7 +1356,8 @@ def run_xylo(args, rank, local_rank, world):
         sustained = sustained_over_ranks(sustained, grp, device, group_size * B * T, dt / args.steps * 1e3)
         barrier()
     result = None
-    if rank == 0:
+    roof = queue_gave_up = None
+    if rank == 0 and args.full:
         def timed(fn, iters=5):
             fn()
             torch.cuda.synchronize()
@@ -1331,6 +1402,7 @@ def run_xylo(args, rank, local_rank, world):
                              f"{lif_ginstr:.0f} of {valu_peak:.0f} G wave-instructions/s = {lif_ginstr / valu_peak:.2f} of the issue bound; " + lif_note)
         roof["avg_launch_ms"] = st[dom]
         roof["stages_ms"] = st
+    if rank == 0:
         value = frames / dt
         result = {
             "metric": "audio samples/sec through STHT+RZCC+SNN beamform, 7-mic 48kHz 360-DoA; DoA MAE vs ref",
@@ -1338,6 +1410,8 @@ def run_xylo(args, rank, local_rank, world):
             "n_gpus": group_size, "rccl_ranks": group_size if (use_dist and not grp.staged) else 0, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "ms_per_step_repeats": [t / args.steps * 1e3 for t in dt_all],
             "ms_per_step_per_rank": (np.median(np.asarray(per_rank), axis=0) / args.steps * 1e3).tolist(),
+            "timing_note": f"median of {len(dt_all)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both sides, max over "
+                           f"ranks), after {settle_steps} settle steps (--settle-seconds {args.settle_seconds:g}) and {args.warmup} warm-up steps",
             "cpu_cores_per_rank": args.cpu_cores or usable_cores(),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64 encoder + int16 LIF state / int8 weights", "data": "synthetic",
@@ -1346,10 +1420,12 @@ def run_xylo(args, rank, local_rank, world):
                                    f"{B} trials/GPU/step, {G} hidden neurons = DoA grid, {4 * M} input channels, find_peak_location(win={win})",
                        "trials_per_gpu": B, "frames_per_trial": T, "num_mic": M, "num_doa": G, "mic_samples_per_s": value * M,
                        "parallelism": f"trial-sharded x{group_size}", "hip_streams": nstreams, "hip_graphs": True,
-                       "w_rec_quantised": int(net.w_rec), "lif_launch": args.xylo_lif, "lif_queue_workers_gave_up": int(queue_gave_up)},
+                       "w_rec_quantised": int(net.w_rec), "lif_launch": args.xylo_lif, "settle_steps": settle_steps},
             "mae_deg_per_snr": [float(v) for v in (mae * 180 / np.pi).cpu().numpy()],
-            "roofline": roof,
         }
+        if roof is not None:
+            result["roofline"] = roof
+            result["config"]["lif_queue_workers_gave_up"] = int(queue_gave_up)
         if sustained is not None:
             result["sustained"] = sustained
             result["config"]["sustained_ms_per_step"] = sustained["ms_per_step"]
@@ -1371,7 +1447,7 @@ def run(args):
     if args.traffic_child:
         return run_traffic_child(args)
     np_pool, np_workers = None, 0
-    if args.config == "noisy" and world == 1 and rank == 0 and not args.no_cpu_baseline and os.environ.get("MICLOC_FORCE_DIST") != "1":
+    if args.full and args.config == "noisy" and world == 1 and rank == 0 and not args.no_cpu_baseline and os.environ.get("MICLOC_FORCE_DIST") != "1":
         # the NumPy leg's worker processes: started while this process is still GPU-free (nothing above touched HIP)
         try:
             np_workers = usable_cores()
@@ -1416,14 +1492,16 @@ def run(args):
     # long recordings: the encoder's serial scan on a stream with compute units of its own (when the encoder is time-chunked at all)
     scan_lane = args.scan_lane_cus if (args.schedule == "scan-lane" and nstreams > 1 and
                                        wl["plan"].encoder_chunks(wl["x"].shape[0], wl["x"].shape[1]) > 1) else 0
+    # a plain run captures the headline step only; --full adds the covariance / fp32 variants and the end-to-end step
+    variants = (True if noisy else None) if args.full else False
     try:
-        step, pipe = make_step(wl, nstreams, variants=True if noisy else None, scan_lane=scan_lane)
+        step, pipe = make_step(wl, nstreams, variants=variants, scan_lane=scan_lane, e2e=args.full)
     except Exception as e:  # (a box that refuses compute-unit masks: the schedule is an optimisation, not a requirement)
         if not scan_lane:
             raise
         print(f"bench.py: scan-lane schedule unavailable ({type(e).__name__}: {e}); falling back to graphs", file=sys.stderr)
         scan_lane = 0
-        step, pipe = make_step(wl, nstreams, variants=True if noisy else None, scan_lane=0)
+        step, pipe = make_step(wl, nstreams, variants=variants, scan_lane=0, e2e=args.full)
     B, T, M = wl["x"].shape
     G = wl["bf_mat"].shape[1]
 
@@ -1453,11 +1531,15 @@ def run(args):
             times.append(float(t.item()))
         return float(np.median(times)), times, res
 
+    settle_steps = settle(step, pipe.synchronize, nstreams, args.settle_seconds)
     dt, dt_all, (out, mae) = timed_steps(step, args.repeats)
+    if rank == 0 and args.dump_outputs:
+        # what the timed path returned in its last step (graph outputs are static buffers: before anything else replays them)
+        dump_outputs(args.dump_outputs, {"power": out["power"], "argmax": out["argmax"], "mae": mae})
     ms_per_rank = (np.median(np.asarray(per_rank[: len(dt_all)]), axis=0) / args.steps * 1e3).tolist()
     exchange = None
     uuids = [str(getattr(torch.cuda.get_device_properties(device), "uuid", "n/a"))]
-    if use_dist:
+    if use_dist and args.full:
         # the sweep's one exchange step (ref:paper_plots/target_snn_localization.py:447-467 keeps doa / arg-max per trial): every
         # rank's per-trial {doa f64, p_max f64, argmax i32} of its last step as ONE struct-of-arrays record, one all_gather_into_tensor
         # (RCCL over xGMI), timed between two barriers; rank 0 recomputes the MAE per SNR from the gathered trials
@@ -1488,6 +1570,7 @@ def run(args):
                     "transport": grp.backend,
                     "note": "pack on the device + one all_gather_into_tensor + one D2H, between two barriers; not inside the timed steps "
                             "(a sweep exchanges once, at its end)"}
+    if use_dist:
         uuids = [str(u) for u in grp.gather_object(uuids[0])]
         mae = torch.stack(grp.gather(mae)).mean(dim=0)
     frames = group_size * B * T * args.steps
@@ -1501,100 +1584,104 @@ def run(args):
         sustained = sustained_block(step, pipe, args, dt / args.steps * 1e3, group_size * B * T, dev_index)
         sustained = sustained_over_ranks(sustained, grp, device, group_size * B * T, dt / args.steps * 1e3)
         barrier()
-    # comparisons between the variants and with the CPU baseline use stream 0's batch (wl["x"]): every stream has its own trials
-    out, _ = step(index=0)
-    pipe.synchronize()
-    argmax_direct = out["argmax"].clone()  # graph outputs are static buffers: keep a copy for the comparisons below
-    power_direct = out["power"].clone()
-
-    # the same K steps with the input side inside the graph (synthesis + noise regenerated every step)
-    dte, _, (out_e, mae_e) = timed_steps(lambda: step(cov="e2e"), min(args.repeats, 3))
-    mae_e = torch.stack(grp.gather(mae_e)).mean(dim=0)
-    e2e = {"value": frames / dte, "unit": "frames/s", "ms_per_step": dte / args.steps * 1e3,
-           "mae_deg_per_snr": [float(v) for v in (mae_e * 180 / np.pi).cpu().numpy()],
-           "note": "per step, inside the same HIP graph: DoA draw (Philox), delayed-template synthesis with in-kernel delays fused with the AWGN "
-                   "(Philox + Box-Muller at the trial's SNR; the noise-free signal is never stored), then the hot path and the DoA error; "
-                   "fresh trials every step"}
-
-    cov_variant = f32_variant = None
-    if M * 2 <= 128:
-        # separately reported algorithmic variant: covariance-form power, same K steps, same inputs
-        dtc, _, _ = timed_steps(lambda: step(cov=True))
-        out_c, _ = step(cov=True, index=0)
+    e2e = cov_variant = f32_variant = argmax_direct = None
+    if args.full:
+        # comparisons between the variants and with the CPU baseline use stream 0's batch (wl["x"]): every stream has its own trials
+        out, _ = step(index=0)
         pipe.synchronize()
-        cov_variant = {"value": frames / dtc, "unit": "frames/s", "ms_per_step": dtc / args.steps * 1e3,
-                       "argmax_equal_to_direct": bool(torch.equal(out_c["argmax"], argmax_direct)),
-                       "max_rel_power_diff_vs_direct": float((out_c["power"] / power_direct - 1).abs().max().item()),
-                       "note": "power = w^T (V^T V / T) w instead of mean_t (V w)^2: algebraically identical, 2C^2 instead of 2CG flops per frame; not the headline"}
-    if noisy and M * 2 <= 64:
-        # second separately reported variant: fp32-MFMA beamforming tail (fp64 up to the spikes)
-        dtf, _, _ = timed_steps(lambda: step(cov="f32"))
-        out_f, _ = step(cov="f32", index=0)
-        pipe.synchronize()
-        relerr = float((out_f["power"] / power_direct - 1).abs().max().item())
-        f32_variant = {"value": frames / dtf, "unit": "frames/s", "ms_per_step": dtf / args.steps * 1e3,
-                       "argmax_equal_to_f64": int((out_f["argmax"] == argmax_direct).sum().item()), "trials": int(B),
-                       "max_rel_power_err_vs_f64": relerr,
-                       "note": "LIF + beamforming + power on v_mfma_f32_16x16x4_f32 (157 TF peak); STHT / band-pass / RZCC stay fp64; not the headline"}
+        argmax_direct = out["argmax"].clone()  # graph outputs are static buffers: keep a copy for the comparisons below
+        power_direct = out["power"].clone()
+
+        # the same K steps with the input side inside the graph (synthesis + noise regenerated every step)
+        dte, _, (out_e, mae_e) = timed_steps(lambda: step(cov="e2e"), min(args.repeats, 3))
+        mae_e = torch.stack(grp.gather(mae_e)).mean(dim=0)
+        e2e = {"value": frames / dte, "unit": "frames/s", "ms_per_step": dte / args.steps * 1e3,
+               "mae_deg_per_snr": [float(v) for v in (mae_e * 180 / np.pi).cpu().numpy()],
+               "note": "per step, inside the same HIP graph: DoA draw (Philox), delayed-template synthesis with in-kernel delays fused with the AWGN "
+                       "(Philox + Box-Muller at the trial's SNR; the noise-free signal is never stored), then the hot path and the DoA error; "
+                       "fresh trials every step"}
+
+        if M * 2 <= 128:
+            # separately reported algorithmic variant: covariance-form power, same K steps, same inputs
+            dtc, _, _ = timed_steps(lambda: step(cov=True))
+            out_c, _ = step(cov=True, index=0)
+            pipe.synchronize()
+            cov_variant = {"value": frames / dtc, "unit": "frames/s", "ms_per_step": dtc / args.steps * 1e3,
+                           "argmax_equal_to_direct": bool(torch.equal(out_c["argmax"], argmax_direct)),
+                           "max_rel_power_diff_vs_direct": float((out_c["power"] / power_direct - 1).abs().max().item()),
+                           "note": "power = w^T (V^T V / T) w instead of mean_t (V w)^2: algebraically identical, 2C^2 instead of 2CG flops per frame; not the headline"}
+        if noisy and M * 2 <= 64:
+            # second separately reported variant: fp32-MFMA beamforming tail (fp64 up to the spikes)
+            dtf, _, _ = timed_steps(lambda: step(cov="f32"))
+            out_f, _ = step(cov="f32", index=0)
+            pipe.synchronize()
+            relerr = float((out_f["power"] / power_direct - 1).abs().max().item())
+            f32_variant = {"value": frames / dtf, "unit": "frames/s", "ms_per_step": dtf / args.steps * 1e3,
+                           "argmax_equal_to_f64": int((out_f["argmax"] == argmax_direct).sum().item()), "trials": int(B),
+                           "max_rel_power_err_vs_f64": relerr,
+                           "note": "LIF + beamforming + power on v_mfma_f32_16x16x4_f32 (157 TF peak); STHT / band-pass / RZCC stay fp64; not the headline"}
 
     result = None
     if rank == 0:
-        st = stage_times(wl, max(5, min(args.steps, 20)))
-        n_nir = len(wl["nir"])
-        C = 2 * M
-        # algorithmic work per frame (SURVEY 8d / DESIGN.md): dense-tap STHT as the reference computes it
-        flops = {
-            "stht_kernel": 2 * len(wl["beamf"].kernel) * M,
-            "bandpass_rzcc_kernel": 17 * C,
-            "beamform_kernel": 2 * n_nir * C + 2 * C * G + 2 * G,
-        }
-        dom = max(st, key=st.get)
-        frames_launch = B * T
-        traffic_src = None
-        serial_stage = None
-        if dom == "bandpass_rzcc_kernel":
-            # The longest BRACKET is the band-pass / RZCC stage: a serial dependency chain per (trial, channel) stream (DF2T +
-            # running sum; long streams are cut into chunks behind a serial scan, rzcc_scan_kernel, on a handful of CUs).  It is
-            # latency, not throughput, and in the pipelined step it runs beside the neighbouring steps' kernels -- it sits on no
-            # roof.  The roofline object therefore prices the dominant THROUGHPUT kernel; the stage is reported beside it.
-            serial_stage = {"stage": "bandpass_rzcc", "ms": st[dom], "algorithmic_GBs": frames_launch * (8 * C + C) / (st[dom] * 1e-3) / 1e9,
-                            "encoder_chunks": int(wl["plan"].encoder_chunks(B, T)),
-                            "note": "serial-latency stage (scan + chunked encoder), overlapped with the other kernels of neighbouring steps; see DESIGN.md 4.2"}
-            dom = max((k for k in st if k != "bandpass_rzcc_kernel"), key=st.get)
-        achieved = frames_launch * flops[dom] / (st[dom] * 1e-3) / 1e12
-        traffic = args.traffic_bytes
-        traffic_detail = None
-        if traffic is None and dom == "beamform_kernel" and C <= 16:
-            # launch size of beamform_ws_kernel: 256-frame chunks x 512 work-items per trial
-            if noisy and group_size == 1 and not args.no_live_traffic and not args.no_other_configs:
-                torch.cuda.synchronize()
-                traffic, traffic_detail = live_traffic(KERNEL_SYMBOL[dom], B, T, M, G, wl["fs"])
-                traffic_src = "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over a child of this run (bench.py --traffic-child)"
-            if traffic is None:
-                # a COMMITTED profile -- only if its MANIFEST says it was taken on the kernel source this run executes
-                t2, src = traffic_from_profiles(KERNEL_SYMBOL[dom], -(-T // 256) * 512 * B, args.pmc_summary)
-                ent = manifest_entry(src) if src else None
-                cur = source_sha256("haghighatshoarmuir2024_amd/csrc/beamform.hip")
-                if t2 is not None and ent and ent.get("sources_sha256", {}).get("haghighatshoarmuir2024_amd/csrc/beamform.hip") == cur:
-                    traffic, traffic_src = t2, f"{src} (MANIFEST: git {ent.get('git_sha', '?')[:10]}, csrc/beamform.hip unchanged since)"
-                else:
-                    traffic_src = (f"none: {src} has no MANIFEST entry for the current csrc/beamform.hip (stale or unlisted profile refused)"
-                                   if src else "none: no committed PMC summary")
-        sym = KERNEL_SYMBOL.get(dom, dom)
-        if dom == "beamform_kernel" and C > 16:
-            sym = "beamform_gen_kernel"
-        roof = dict(kernel=sym, bound="mfma", achieved=achieved, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
-                    frac=achieved / FP64_MFMA_PEAK_TFLOPS, traffic=traffic)
-        if dom == "stht_kernel":
-            roof["note"] = "fp64 vector FMAs (the fp64 vector and matrix peaks of gfx950 are the same 78.6 TF); dense-tap flops as the reference computes them"
-        if serial_stage:
-            roof["serial_stage"] = serial_stage
-        roof["traffic_source"] = traffic_src
-        if traffic_detail:
-            roof["traffic_detail"] = traffic_detail
-        roof["algorithmic_bytes_per_launch"] = (frames_launch * C + B * G * 8) if dom == "beamform_kernel" else None  # int8 raster in, power out
-        roof["avg_launch_ms"] = st[dom]
-        roof["stages_ms"] = st
+        roof = None
+        if args.full:
+            # the per-kernel stage times (runs of their own) and the roofline of the dominant kernel
+            st = stage_times(wl, max(5, min(args.steps, 20)))
+            n_nir = len(wl["nir"])
+            C = 2 * M
+            # algorithmic work per frame (SURVEY 8d / DESIGN.md): dense-tap STHT as the reference computes it
+            flops = {
+                "stht_kernel": 2 * len(wl["beamf"].kernel) * M,
+                "bandpass_rzcc_kernel": 17 * C,
+                "beamform_kernel": 2 * n_nir * C + 2 * C * G + 2 * G,
+            }
+            dom = max(st, key=st.get)
+            frames_launch = B * T
+            traffic_src = None
+            serial_stage = None
+            if dom == "bandpass_rzcc_kernel":
+                # The longest BRACKET is the band-pass / RZCC stage: a serial dependency chain per (trial, channel) stream (DF2T +
+                # running sum; long streams are cut into chunks behind a serial scan, rzcc_scan_kernel, on a handful of CUs).  It is
+                # latency, not throughput, and in the pipelined step it runs beside the neighbouring steps' kernels -- it sits on no
+                # roof.  The roofline object therefore prices the dominant THROUGHPUT kernel; the stage is reported beside it.
+                serial_stage = {"stage": "bandpass_rzcc", "ms": st[dom], "algorithmic_GBs": frames_launch * (8 * C + C) / (st[dom] * 1e-3) / 1e9,
+                                "encoder_chunks": int(wl["plan"].encoder_chunks(B, T)),
+                                "note": "serial-latency stage (scan + chunked encoder), overlapped with the other kernels of neighbouring steps; see DESIGN.md 4.2"}
+                dom = max((k for k in st if k != "bandpass_rzcc_kernel"), key=st.get)
+            achieved = frames_launch * flops[dom] / (st[dom] * 1e-3) / 1e12
+            traffic = args.traffic_bytes
+            traffic_detail = None
+            if traffic is None and dom == "beamform_kernel" and C <= 16:
+                # launch size of beamform_ws_kernel: 256-frame chunks x 512 work-items per trial
+                if noisy and group_size == 1 and not args.no_live_traffic and not args.no_other_configs:
+                    torch.cuda.synchronize()
+                    traffic, traffic_detail = live_traffic(KERNEL_SYMBOL[dom], B, T, M, G, wl["fs"])
+                    traffic_src = "live: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over a child of this run (bench.py --traffic-child)"
+                if traffic is None:
+                    # a COMMITTED profile -- only if its MANIFEST says it was taken on the kernel source this run executes
+                    t2, src = traffic_from_profiles(KERNEL_SYMBOL[dom], -(-T // 256) * 512 * B, args.pmc_summary)
+                    ent = manifest_entry(src) if src else None
+                    cur = source_sha256("haghighatshoarmuir2024_amd/csrc/beamform.hip")
+                    if t2 is not None and ent and ent.get("sources_sha256", {}).get("haghighatshoarmuir2024_amd/csrc/beamform.hip") == cur:
+                        traffic, traffic_src = t2, f"{src} (MANIFEST: git {ent.get('git_sha', '?')[:10]}, csrc/beamform.hip unchanged since)"
+                    else:
+                        traffic_src = (f"none: {src} has no MANIFEST entry for the current csrc/beamform.hip (stale or unlisted profile refused)"
+                                       if src else "none: no committed PMC summary")
+            sym = KERNEL_SYMBOL.get(dom, dom)
+            if dom == "beamform_kernel" and C > 16:
+                sym = "beamform_gen_kernel"
+            roof = dict(kernel=sym, bound="mfma", achieved=achieved, peak=FP64_MFMA_PEAK_TFLOPS, unit="TFLOP/s",
+                        frac=achieved / FP64_MFMA_PEAK_TFLOPS, traffic=traffic)
+            if dom == "stht_kernel":
+                roof["note"] = "fp64 vector FMAs (the fp64 vector and matrix peaks of gfx950 are the same 78.6 TF); dense-tap flops as the reference computes them"
+            if serial_stage:
+                roof["serial_stage"] = serial_stage
+            roof["traffic_source"] = traffic_src
+            if traffic_detail:
+                roof["traffic_detail"] = traffic_detail
+            roof["algorithmic_bytes_per_launch"] = (frames_launch * C + B * G * 8) if dom == "beamform_kernel" else None  # int8 raster in, power out
+            roof["avg_launch_ms"] = st[dom]
+            roof["stages_ms"] = st
         names = {"noisy": "target_snn_localization noisy sweep", "speech": "target_snn_localization speech sweep (LibriSpeech 84-121123-0020, per-GPU share of 1000 trials)",
                  "stress": "stress shape (64-mic Random2DArray r=0.2 m after np.random.seed(1), 96 kHz)"}
         result = {
@@ -1610,7 +1697,8 @@ def run(args):
             "ms_per_step_repeats": [t / args.steps * 1e3 for t in dt_all],
             "ms_per_step_per_rank": ms_per_rank,
             "cpu_cores_per_rank": args.cpu_cores or usable_cores(),
-            "timing_note": f"median of {len(dt_all)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both sides, max over ranks)",
+            "timing_note": f"median of {len(dt_all)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both sides, max over ranks), "
+                           f"after {settle_steps} settle steps (--settle-seconds {args.settle_seconds:g}) and {args.warmup} warm-up steps",
             "higher_is_better": True,
             "scaling": "strong" if (args.baseline_total and args.config in ("speech", "stress")) else "weak",
             "vs_baseline": None,
@@ -1625,32 +1713,33 @@ def run(args):
                        "schedule": (f"scan-lane: eager launches on {nstreams} streams restricted to {32 - scan_lane} compute units per XCD, the "
                                     f"serial checkpoint scans of all batches on one stream that owns the other {scan_lane}") if scan_lane
                                    else "one captured hipGraph per stream, replayed round-robin",
-                       # SURVEY 8d's clock (first kernel of the input side -> results): the same K steps with DoA draw, synthesis and noise
-                       # regenerated on the device every step, MAE left on the device like `value`
-                       "value_e2e": e2e["value"], "e2e_ms_per_step": e2e["ms_per_step"],
-                       "clocks": "`value` = hot path on batches resident in HBM (the driver's contract); `config.value_e2e` = input side included (SURVEY 8d)",
                        "device_uuid_per_rank": uuids,
+                       "settle_steps": settle_steps,
                        "memory_gb": memory_gb(device),
                        "design_from_template_seconds": wl["design_seconds"],
                        "design_note": "bf_mat from the 1 s chirp for all G DoAs, entirely on the device (reference: 24.8 s for 449 DoAs on 8 vCPUs, SURVEY 6)"},
             "mae_deg_per_snr": [float(v) for v in (mae * 180 / np.pi).cpu().numpy()],
-            "value_e2e": e2e["value"],
-            "e2e": e2e,
-            "roofline": roof,
             # the north star also asks for the fraction of the HBM roofline: algorithmic bytes of the fused sweep
             # (one fp64 frame in, int8 spikes out and back in = 8M + 2M bytes per frame) over the whole job
             "hbm_fraction": {"bytes_per_frame": 10 * M, "achieved_GBs": value / group_size * 10 * M / 1e9, "peak_GBs": HBM_PEAK_GBS,
                              "frac_per_gpu": value / group_size * 10 * M / 1e9 / HBM_PEAK_GBS,
-                             "note": "compute-bound path (about 300 flop/B): small by construction, the binding roof is in `roofline`"},
-            "variants": {"covariance_power": cov_variant, "f32_mfma_beamform": f32_variant},
+                             "note": "compute-bound path (about 300 flop/B): small by construction, the binding roof is in `roofline` (--full)"},
         }
+        if args.full:
+            # SURVEY 8d's clock (first kernel of the input side -> results): the same K steps with DoA draw, synthesis and noise
+            # regenerated on the device every step, MAE left on the device like `value`
+            result["config"].update(value_e2e=e2e["value"], e2e_ms_per_step=e2e["ms_per_step"],
+                                    clocks="`value` = hot path on batches resident in HBM (the driver's contract); `config.value_e2e` = input side "
+                                           "included (SURVEY 8d)")
+            result.update(value_e2e=e2e["value"], e2e=e2e, roofline=roof,
+                          variants={"covariance_power": cov_variant, "f32_mfma_beamform": f32_variant})
         if exchange is not None:
             result["exchange"] = exchange
             result["exchange_ms"] = exchange["exchange_ms"]
         if sustained is not None:
             result["sustained"] = sustained
             tw = (sustained.get("telemetry") or {}).get("whole")
-            if tw and roof.get("unit") == "TFLOP/s":
+            if tw and roof and roof.get("unit") == "TFLOP/s":
                 # the datasheet peak assumes the 2.4 GHz boost clock; the chip reports what it actually held during the long region
                 pk = FP64_MFMA_PEAK_TFLOPS * tw["sclk_mhz_mean"] / 2400.0
                 roof["peak_at_measured_clock"] = pk
@@ -1676,15 +1765,15 @@ def run(args):
             else:
                 result["value_source"] = (f"median of the K-step regions (the sustained region of {sustained['seconds']:.1f} s agrees within 2 %: "
                                           f"ratio {sustained['ratio_to_timed_regions']:.4f})")
-        if noisy and M * 2 <= 16:
+        if args.full and noisy and M * 2 <= 16:
             result["variants"]["beamformer_c128"] = beamformer_c128_block(wl, args)
             result["variants"]["streaming_live"] = streaming_live_block(wl)
-        if noisy and group_size == 1 and not args.no_other_configs:
+        if args.full and noisy and group_size == 1 and not args.no_other_configs:
             torch.cuda.synchronize()
             result["mae_ref"] = reference_mae_block(device)
             result["api_per_call_ms"] = api_per_call_block(device)
             result["other_configs"] = other_configs_block(args)
-        if not args.no_cpu_baseline and group_size == 1 and noisy:
+        if args.full and not args.no_cpu_baseline and group_size == 1 and noisy:
             try:
                 cb, am = cpu_baseline(wl, args.cpu_seconds, np_pool, np_workers)
             except Exception as e:  # (a stuck worker pool must not take the line down: the other legs are repeated without it)

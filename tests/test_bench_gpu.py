@@ -7,19 +7,20 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra, env_extra):
+def _run(extra, env_extra, full=True):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577", **env_extra)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline",
-                        "--no-other-configs", "--sustained-seconds", "0.4"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=env)
+    base = ["--steps", "2", "--warmup", "1", "--repeats", "2", "--full", "--no-cpu-baseline", "--no-other-configs", "--sustained-seconds", "0.4"] if full else []
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=env)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
     lines = [ln for ln in p.stdout.decode(errors="replace").splitlines() if ln.startswith("{")]
     assert lines, p.stdout.decode(errors="replace")[-2000:]
@@ -110,3 +111,42 @@ def test_other_workloads_report_a_sustained_region():
     x = _run(["--config", "xylo", "--trials", "110", "--sustained-seconds", "0.6"], {})
     assert x["sustained"]["seconds"] >= 0.6 and x["config"]["sustained_ms_per_step"] == x["sustained"]["ms_per_step"]
     assert x["parity"].startswith("UNPINNED")
+
+
+def test_plain_run_times_k_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): ONE timed region of exactly --steps steps, the headline keys, nothing measured besides them, and
+    --dump-outputs writes the LAST timed step's outputs (power [B, G], arg-max [B], MAE per SNR) as float64 arrays: the same arrays
+    from a second run with the same arguments, the MAE the line reports for that step, and another batch when the last step falls
+    on another stream."""
+    def plain(tag, *extra):
+        return _run(["--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / tag), *extra], {}, full=False)
+
+    def dump(tag):
+        return {n: np.load(tmp_path / tag / f"{n}.npy") for n in ("power", "argmax", "mae")}
+
+    d = plain("a")
+    assert d["steps"] == 4 and d["warmup"] == 1 and len(d["ms_per_step_repeats"]) == 1 and d["ms_per_step"] == d["ms_per_step_repeats"][0]
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["metric"].startswith("audio samples/sec through STHT+RZCC+SNN beamform")
+    frames = d["config"]["trials_per_gpu"] * d["config"]["frames_per_trial"]
+    assert abs(d["value"] - frames / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not {"roofline", "sustained", "e2e", "variants", "cpu_baseline", "other_configs", "exchange"} & set(d)
+    S = d["config"]["hip_streams"]
+    assert S == 3 and d["config"]["settle_steps"] > 0 and d["config"]["settle_steps"] % S == 0
+    assert f"after {d['config']['settle_steps']} settle steps" in d["timing_note"]
+    B, G = d["config"]["trials_per_gpu"], d["config"]["num_doa"]
+    a = dump("a")
+    assert a["power"].shape == (B, G) and a["argmax"].shape == (B,) and a["mae"].shape == (11,)
+    assert a["power"].dtype == a["argmax"].dtype == a["mae"].dtype == np.float64 and np.all(a["power"] >= 0)
+    assert np.array_equal(a["power"][np.arange(B), a["argmax"].astype(np.int64)], a["power"].max(axis=1))  # the arg-max points at each trial's maximum
+    np.testing.assert_allclose(a["mae"] * 180 / np.pi, d["mae_deg_per_snr"], rtol=1e-14, atol=0)  # the step the line's MAE comes from
+    # the same arguments: the same inputs and the same outputs, array for array (two builds compare this way)
+    d2 = plain("b")
+    b = dump("b")
+    assert d2["config"]["settle_steps"] % S == 0 and all(np.array_equal(a[n], b[n]) for n in a)
+    # no settle, one warm-up step, 3 timed steps: the last step is replay 3 of the rotation (stream 0); in run a it was replay
+    # settle_steps + 4 (stream 1), so the dump holds another batch
+    d3 = plain("c", "--settle-seconds", "0", "--steps", "3")
+    c = dump("c")
+    assert d3["config"]["settle_steps"] == 0 and "after 0 settle steps" in d3["timing_note"]
+    assert not np.array_equal(a["power"], c["power"])
+    np.testing.assert_allclose(c["mae"] * 180 / np.pi, d3["mae_deg_per_snr"], rtol=1e-14, atol=0)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -91,3 +92,43 @@ def test_schedule_defaults():
     assert (a.schedule, a.streams) == ("graphs", 3)
     a = bench.parse(["--config", "stress", "--schedule", "scan-lane", "--streams", "5", "--scan-lane-cus", "6"])
     assert (a.schedule, a.streams, a.streams_given, a.scan_lane_cus) == ("scan-lane", 5, True, 6)
+
+
+def test_plain_and_full_defaults():
+    """A plain run times ONE region and has no sustained region; --full restores five regions and the 5 s sustained region; explicit
+    values hold either way.  The set-up's settle defaults to 0.25 s; 0 turns it off."""
+    sys.path.insert(0, os.path.dirname(BENCH))
+    import bench
+
+    a = bench.parse(["--steps", "7"])
+    assert (a.full, a.steps, a.repeats, a.sustained_seconds, a.dump_outputs, a.settle_seconds) == (False, 7, 1, 0.0, None, 0.25)
+    assert bench.parse(["--settle-seconds", "0"]).settle_seconds == 0.0
+    a = bench.parse(["--full"])
+    assert (a.full, a.repeats, a.sustained_seconds) == (True, 5, 5.0)
+    a = bench.parse(["--repeats", "3", "--sustained-seconds", "2", "--dump-outputs", "out"])
+    assert (a.full, a.repeats, a.sustained_seconds, a.dump_outputs) == (False, 3, 2.0, "out")
+
+
+def test_dump_outputs_float64_and_capped(tmp_path):
+    """--dump-outputs writes float64 arrays (integer outputs exactly); above the byte limit every per-trial array keeps the same
+    seeded sample of trials, listed in sample_rows.npy, and the sample is the same from run to run."""
+    sys.path.insert(0, os.path.dirname(BENCH))
+    import bench
+
+    rng = np.random.RandomState(3)
+    power, argmax, mae = rng.rand(500, 40), rng.randint(0, 40, 500).astype(np.int32), rng.rand(11)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"power": power, "argmax": argmax, "mae": mae, "y": None}) == ["argmax", "mae", "power"]
+    got = np.load(tmp_path / "a" / "argmax.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, argmax)
+    assert np.array_equal(np.load(tmp_path / "a" / "power.npy"), power)
+    limit = 64 * 1024
+    names = bench.dump_outputs(str(tmp_path / "b"), {"power": power, "argmax": argmax, "mae": mae}, limit=limit)
+    assert "sample_rows" in names
+    rows = np.load(tmp_path / "b" / "sample_rows.npy").astype(np.int64)
+    assert len(rows) < 500 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "b" / "power.npy"), power[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "argmax.npy"), argmax[rows])
+    assert np.array_equal(np.load(tmp_path / "b" / "mae.npy"), mae)
+    assert sum(os.path.getsize(tmp_path / "b" / (n + ".npy")) - 128 for n in names) <= limit
+    bench.dump_outputs(str(tmp_path / "c"), {"power": power, "argmax": argmax, "mae": mae}, limit=limit)
+    assert np.array_equal(np.load(tmp_path / "c" / "sample_rows.npy"), rows)

@@ -3,7 +3,7 @@
 # usage (on the GPU box, from the repo root): bash tools/dev/e2e_prof.sh
 OUT=gpurun_out/e2e_prof
 mkdir -p $OUT
-python bench.py --no-other-configs --no-cpu-baseline > $OUT/bench.log 2>&1
+python bench.py --full --no-other-configs --no-cpu-baseline > $OUT/bench.log 2>&1
 python - <<PY
 import json
 l = [x for x in open("$OUT/bench.log") if x.startswith("{")][-1]

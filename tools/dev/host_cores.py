@@ -25,10 +25,10 @@ sys.exit(bench.run(args))
 """ % ROOT
 for cores in tuple(int(c) for c in (sys.argv[1].split(",") if len(sys.argv) > 1 else ["16", "4", "2", "1"])):
     for flag, name in ((0, "default"), (4, "blocking sync"), (2, "yield")):
-        cmd = [sys.executable, "-c", CHILD, str(flag), "--cpu-cores", str(cores), "--steps", (sys.argv[2] if len(sys.argv) > 2 else "40"), "--warmup", "5", "--repeats", "3", "--no-cpu-baseline", "--no-other-configs"]
+        cmd = [sys.executable, "-c", CHILD, str(flag), "--cpu-cores", str(cores), "--steps", (sys.argv[2] if len(sys.argv) > 2 else "40"), "--warmup", "5", "--repeats", "3", "--full", "--no-cpu-baseline", "--no-other-configs"]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
         try:
             d = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1])
             print(f"{cores:2d} cores, {name:13s}: {d['ms_per_step']:.4f} ms/step  e2e {d['e2e']['ms_per_step']:.4f}", flush=True)
         except Exception as e:
-            print(cores, name, "failed", p.stderr.decode()[-300:], flush=True)
+            print(cores, name, "failed", f"{type(e).__name__}: {e}", p.stderr.decode()[-300:], flush=True)

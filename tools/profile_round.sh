@@ -14,21 +14,21 @@ python3 tools/make_manifest.py --record $OUT
 cmd() { printf '%s\t%s\n' "$1" "$2" >> $OUT/COMMANDS.tsv; }
 : > $OUT/COMMANDS.tsv
 want() { [ $PART = all ] || [ $PART = $1 ]; }
-cmd bench_n1.json "python3 bench.py --steps 20 --warmup 5"
-cmd bench_n1_streams1.json "python3 bench.py --steps 40 --warmup 4 --streams 1 --no-cpu-baseline --no-other-configs"
-cmd bench_n1_grid449.json "python3 bench.py --steps 40 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs"
-cmd bench_n1_speech.json "python3 bench.py --config speech --steps 16 --warmup 4"
-cmd bench_n1_speech_graphs.json "python3 bench.py --config speech --steps 16 --warmup 4 --schedule graphs --no-cpu-baseline"
-cmd bench_n1_stress.json "python3 bench.py --config stress --steps 9 --warmup 3"
-cmd bench_n1_xylo.json "python3 bench.py --config xylo --steps 12 --warmup 3"
-cmd bench_n1_sustained60.json "python3 bench.py --steps 20 --warmup 5 --sustained-seconds 60 --no-cpu-baseline --no-other-configs"
-cmd bench_n1_stress_sustained20.json "python3 bench.py --config stress --steps 9 --warmup 3 --sustained-seconds 20 --no-cpu-baseline --no-other-configs"
-cmd kernel_trace_summary_by_shape.csv "rocprofv3 --output-format csv --kernel-trace --stats -- python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-other-configs --streams 1 | tools/summarize_profiles.py trace"
+cmd bench_n1.json "python3 bench.py --full --steps 20 --warmup 5"
+cmd bench_n1_streams1.json "python3 bench.py --full --steps 40 --warmup 4 --streams 1 --no-cpu-baseline --no-other-configs"
+cmd bench_n1_grid449.json "python3 bench.py --full --steps 40 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs"
+cmd bench_n1_speech.json "python3 bench.py --full --config speech --steps 16 --warmup 4"
+cmd bench_n1_speech_graphs.json "python3 bench.py --full --config speech --steps 16 --warmup 4 --schedule graphs --no-cpu-baseline"
+cmd bench_n1_stress.json "python3 bench.py --full --config stress --steps 9 --warmup 3"
+cmd bench_n1_xylo.json "python3 bench.py --full --config xylo --steps 12 --warmup 3"
+cmd bench_n1_sustained60.json "python3 bench.py --full --steps 20 --warmup 5 --sustained-seconds 60 --no-cpu-baseline --no-other-configs"
+cmd bench_n1_stress_sustained20.json "python3 bench.py --full --config stress --steps 9 --warmup 3 --sustained-seconds 20 --no-cpu-baseline --no-other-configs"
+cmd kernel_trace_summary_by_shape.csv "rocprofv3 --output-format csv --kernel-trace --stats -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --no-other-configs --streams 1 | tools/summarize_profiles.py trace"
 cmd kernel_stats_bench_steps40_streams1.csv "rocprofv3 --kernel-trace --stats (the same run): rocprofv3's own kernel_stats.csv"
-cmd kernel_trace_summary_grid449.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs --streams 1 | summarize_profiles.py trace"
-cmd kernel_trace_summary_speech.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --config speech --steps 3 --warmup 1 --streams 1 | summarize_profiles.py trace"
-cmd kernel_trace_summary_stress.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --config stress --steps 3 --warmup 1 --streams 1 | summarize_profiles.py trace"
-cmd kernel_trace_summary_xylo.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --config xylo --steps 2 --warmup 1 --streams 1 | summarize_profiles.py trace"
+cmd kernel_trace_summary_grid449.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs --streams 1 | summarize_profiles.py trace"
+cmd kernel_trace_summary_speech.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config speech --steps 3 --warmup 1 --streams 1 | summarize_profiles.py trace"
+cmd kernel_trace_summary_stress.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config stress --steps 3 --warmup 1 --streams 1 | summarize_profiles.py trace"
+cmd kernel_trace_summary_xylo.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config xylo --steps 2 --warmup 1 --streams 1 | summarize_profiles.py trace"
 cmd y_store.txt "python3 tools/k3_time.py {360,449} 1100 {1,0}"
 cmd store_bw.txt "hipcc tools/store_bw.hip && ./store_bw"
 cmd ablation_kstep.txt "bash tools/dev/ab_lib.sh tools/_variants/libmicloc_hip_ws_k4.so '--steps 40 --warmup 4'"
@@ -41,29 +41,29 @@ cmd product_sweeps.txt "python3 tools/dev/speech_sweep_time.py 91; python3 tools
 cmd speech_lanes.txt "bash tools/dev/speech_lanes.sh 2 4"
 cmd stht_fetch.txt "bash tools/dev/stht_fetch_ab.sh; STHT_T=48000 bash tools/dev/stht_fetch_ab.sh"
 cmd clock_sources.txt "python3 tools/dev/clock_sources.py"
-cmd bench_n2_share_device.json "python3 bench.py --gpus 2 --share-device --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs  (REHEARSAL of the N > 1 launch: both ranks on device 0, gloo)"
-cmd bench_share_stress2048.json "python3 bench.py --config stress --baseline-total --trials 2048 --steps 6 --warmup 2 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs  (a rank's share of the 16 384-trial sweep at 8 ranks)"
-cmd bench_share_speech125.json "python3 bench.py --config speech --baseline-total --trials 125 --steps 16 --warmup 4 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs  (a rank's share of the 1000-trial sweep at 8 ranks)"
+cmd bench_n2_share_device.json "python3 bench.py --full --gpus 2 --share-device --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs  (REHEARSAL of the N > 1 launch: both ranks on device 0, gloo)"
+cmd bench_share_stress2048.json "python3 bench.py --full --config stress --baseline-total --trials 2048 --steps 6 --warmup 2 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs  (a rank's share of the 16 384-trial sweep at 8 ranks)"
+cmd bench_share_speech125.json "python3 bench.py --full --config speech --baseline-total --trials 125 --steps 16 --warmup 4 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs  (a rank's share of the 1000-trial sweep at 8 ranks)"
 cmd ablation_stht_wide2.txt "bash tools/dev/ab_stress_stht.sh"
 cmd track_time.txt "python3 tools/dev/track_time.py"
-for c in "" _stress _speech _xylo; do cmd pmc_summary$c.csv "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE | SQ_* ...> (one pass each) -- python3 bench.py --config <cfg> --steps <n> --warmup 1 --repeats 1 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 | summarize_profiles.py pmc"; done
+for c in "" _stress _speech _xylo; do cmd pmc_summary$c.csv "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE | SQ_* ...> (one pass each) -- python3 bench.py --full --config <cfg> --steps <n> --warmup 1 --repeats 1 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 | summarize_profiles.py pmc"; done
 if want bench; then
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err   # the driver's command: all blocks (other configs as child runs)
-python3 bench.py --steps 40 --warmup 4 --streams 1 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_streams1.json 2> $OUT/bench_n1_streams1.err
-python3 bench.py --steps 40 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_grid449.json 2> $OUT/bench_n1_grid449.err
-python3 bench.py --config speech --steps 16 --warmup 4 > $OUT/bench_n1_speech.json 2> $OUT/bench_n1_speech.err   # (scan-lane schedule, four batches in flight)
-python3 bench.py --config speech --steps 16 --warmup 4 --schedule graphs --no-cpu-baseline > $OUT/bench_n1_speech_graphs.json 2> $OUT/bench_n1_speech_graphs.err
-python3 bench.py --config stress --steps 9 --warmup 3 > $OUT/bench_n1_stress.json 2> $OUT/bench_n1_stress.err
-python3 bench.py --config xylo --steps 12 --warmup 3 > $OUT/bench_n1_xylo.json 2> $OUT/bench_n1_xylo.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_n1.json 2> $OUT/bench_n1.err   # every block (other configs as child runs)
+python3 bench.py --full --steps 40 --warmup 4 --streams 1 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_streams1.json 2> $OUT/bench_n1_streams1.err
+python3 bench.py --full --steps 40 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_grid449.json 2> $OUT/bench_n1_grid449.err
+python3 bench.py --full --config speech --steps 16 --warmup 4 > $OUT/bench_n1_speech.json 2> $OUT/bench_n1_speech.err   # (scan-lane schedule, four batches in flight)
+python3 bench.py --full --config speech --steps 16 --warmup 4 --schedule graphs --no-cpu-baseline > $OUT/bench_n1_speech_graphs.json 2> $OUT/bench_n1_speech_graphs.err
+python3 bench.py --full --config stress --steps 9 --warmup 3 > $OUT/bench_n1_stress.json 2> $OUT/bench_n1_stress.err
+python3 bench.py --full --config xylo --steps 12 --warmup 3 > $OUT/bench_n1_xylo.json 2> $OUT/bench_n1_xylo.err
 # one minute of headline steps / twenty seconds of the stress step in one uninterrupted region each (clock, power, temperature per segment)
-python3 bench.py --steps 20 --warmup 5 --sustained-seconds 60 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_sustained60.json 2> $OUT/bench_n1_sustained60.err
-python3 bench.py --config stress --steps 9 --warmup 3 --sustained-seconds 20 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_stress_sustained20.json 2> $OUT/bench_n1_stress_sustained20.err
+python3 bench.py --full --steps 20 --warmup 5 --sustained-seconds 60 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_sustained60.json 2> $OUT/bench_n1_sustained60.err
+python3 bench.py --full --config stress --steps 9 --warmup 3 --sustained-seconds 20 --no-cpu-baseline --no-other-configs > $OUT/bench_n1_stress_sustained20.json 2> $OUT/bench_n1_stress_sustained20.err
 # per-kernel times: serial steps so that every launch is timed alone
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 > $OUT/trace.log 2>&1
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_g449 -o run -- python3 bench.py --steps 20 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 > $OUT/trace_g449.log 2>&1
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_speech -o run -- python3 bench.py --config speech --steps 3 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_speech.log 2>&1
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_stress -o run -- python3 bench.py --config stress --steps 3 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_stress.log 2>&1
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_xylo -o run -- python3 bench.py --config xylo --steps 2 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_xylo.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 > $OUT/trace.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_g449 -o run -- python3 bench.py --full --steps 20 --warmup 4 --grid 449 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0 > $OUT/trace_g449.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_speech -o run -- python3 bench.py --full --config speech --steps 3 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_speech.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_stress -o run -- python3 bench.py --full --config stress --steps 3 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_stress.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_xylo -o run -- python3 bench.py --full --config xylo --steps 2 --warmup 1 --streams 1 --sustained-seconds 0 --no-cpu-baseline --no-other-configs > $OUT/trace_xylo.log 2>&1
 python3 tools/summarize_profiles.py trace $OUT/trace $OUT/kernel_trace_summary_by_shape.csv
 python3 tools/summarize_profiles.py trace $OUT/trace_g449 $OUT/kernel_trace_summary_grid449.csv
 python3 tools/summarize_profiles.py trace $OUT/trace_speech $OUT/kernel_trace_summary_speech.csv
@@ -88,9 +88,9 @@ bash tools/dev/ab_bf.sh default tools/_variants/libmicloc_hip_ws_sparse_lif.so >
 python3 tools/dev/clock_sources.py > $OUT/clock_sources.txt 2>&1
 # round 6: the N > 1 launch rehearsed on this one GPU, the strong-scaling shares an 8-rank run gives every rank, the rejected two-tile form of
 # the 480-tap STHT, the moving-target read-out at the script's shape
-python3 bench.py --gpus 2 --share-device --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $OUT/bench_n2_share_device.json 2> $OUT/bench_n2_share_device.err
-python3 bench.py --config stress --baseline-total --trials 2048 --steps 6 --warmup 2 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs > $OUT/bench_share_stress2048.json 2> $OUT/bench_share_stress2048.err
-python3 bench.py --config speech --baseline-total --trials 125 --steps 16 --warmup 4 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs > $OUT/bench_share_speech125.json 2> $OUT/bench_share_speech125.err
+python3 bench.py --full --gpus 2 --share-device --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > $OUT/bench_n2_share_device.json 2> $OUT/bench_n2_share_device.err
+python3 bench.py --full --config stress --baseline-total --trials 2048 --steps 6 --warmup 2 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs > $OUT/bench_share_stress2048.json 2> $OUT/bench_share_stress2048.err
+python3 bench.py --full --config speech --baseline-total --trials 125 --steps 16 --warmup 4 --repeats 3 --sustained-seconds 10 --no-cpu-baseline --no-other-configs > $OUT/bench_share_speech125.json 2> $OUT/bench_share_speech125.err
 bash tools/dev/ab_stress_stht.sh 2>&1 | grep -v amdgpu.ids > $OUT/ablation_stht_wide2.txt
 python3 tools/dev/track_time.py 2>&1 | grep -v amdgpu.ids > $OUT/track_time.txt
 # round 4: the complex Beamformer's contraction alone, the Xylo LIF launch forms, config 5's design
@@ -106,7 +106,7 @@ if want pmc; then
 # counters: separate passes, nothing but --pmc (+ kernel trace)
 for cfg in noisy stress speech xylo; do
   steps=6; [ $cfg = speech ] && steps=2; [ $cfg = xylo ] && steps=2
-  extra="--config $cfg --steps $steps --warmup 1 --repeats 1 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0"
+  extra="--full --config $cfg --steps $steps --warmup 1 --repeats 1 --no-cpu-baseline --no-other-configs --streams 1 --sustained-seconds 0"
   rocprofv3 --output-format csv --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch_$cfg -o run -- python3 bench.py $extra > $OUT/pmc_fetch_$cfg.log 2>&1
   rocprofv3 --output-format csv --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write_$cfg -o run -- python3 bench.py $extra > $OUT/pmc_write_$cfg.log 2>&1
   rocprofv3 --output-format csv --kernel-trace --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE -d $OUT/pmc_sq_$cfg -o run -- python3 bench.py $extra > $OUT/pmc_sq_$cfg.log 2>&1
