@@ -1078,3 +1078,77 @@ int micloc_peak_location_i32(const int32_t *rate, int B, int G, int bands, int w
 }
 
 }  // extern "C"
+
+namespace {
+
+bool music_dims(int B, int T, int M, int L, int hop, int S, int N, int nbin, int G, int k, MusicDims *d)
+{
+    if (bad_batch(B) || T < 1 || M < 1 || L < 1 || hop < 1 || S < 1 || N < 2 || nbin < 1 || nbin > N || nbin > 8192 || G < 1 || k < 0)
+        return false;
+    d->B = B, d->T = T, d->M = M, d->S = S, d->L = L, d->hop = hop, d->N = N;
+    d->Np = (N + 63) / 64 * 64;
+    d->Fmax = (L < T ? L : T) / N;
+    d->nbin = nbin;
+    d->Cp = (2 * nbin + 15) / 16 * 16;
+    d->G = G;
+    d->ksel = (k == 0 || k > nbin) ? nbin : k;
+    return true;
+}
+
+// every slice starts inside the signal and holds at least one frame (the last slice is the shortest)
+bool music_slices_ok(const MusicDims &d)
+{
+    const long long last = (long long)(d.S - 1) * d.hop;
+    if (last >= d.T) return false;
+    const long long len = d.T - last < d.L ? d.T - last : d.L;
+    return len >= d.N && d.Fmax >= 1;
+}
+
+size_t music_ws(const MusicDims &d)
+{
+    const MusicBuffers L = music_layout(d);
+    return align256(L.xf_bytes) + align256(L.X_bytes) + align256(L.sel_bytes) + align256(L.spec_bytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t micloc_music_workspace_bytes(int B, int T, int M, int L, int hop, int S, int N, int nbin, int G, int k)
+{
+    MusicDims d{};
+    if (!music_dims(B, T, M, L, hop, S, N, nbin, G, k, &d)) return 0;
+    return music_ws(d);
+}
+
+int micloc_music_f64(const double *x, int B, int T, int M, const double *b, const double *a, int n, int L, int hop, int S, int N,
+                     const double *W, int nbin, const double *steer_re, const double *steer_im, int G, int k, int32_t *sel, double *spec,
+                     double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+{
+    MusicDims d{};
+    if (!x || !b || !a || !W || !steer_re || !steer_im || n < 1 || n > MICLOC_MAX_IIR || a[0] == 0.0 ||
+        !music_dims(B, T, M, L, hop, S, N, nbin, G, k, &d))
+        return MICLOC_ERR_INVALID;
+    if (!music_slices_ok(d)) return MICLOC_ERR_SHAPE;
+    if (bad_ws(ws, ws_bytes, music_ws(d))) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(x));
+    IirCoef co{};
+    co.n = n;
+    for (int i = 0; i < n; ++i) {
+        co.b[i] = b[i] / a[0];
+        co.a[i] = a[i] / a[0];
+    }
+    const MusicBuffers Lb = music_layout(d);
+    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
+    double *xf = reinterpret_cast<double *>(base);
+    base += align256(Lb.xf_bytes);
+    double *X = reinterpret_cast<double *>(base);
+    base += align256(Lb.X_bytes);
+    int32_t *sel_ws = reinterpret_cast<int32_t *>(base);
+    base += align256(Lb.sel_bytes);
+    double *spec_ws = reinterpret_cast<double *>(base);
+    HIP_TRY(launch_music(d, co, x, W, steer_re, steer_im, xf, X, sel ? sel : sel_ws, spec ? spec : spec_ws, power, argmax, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+}  // extern "C"

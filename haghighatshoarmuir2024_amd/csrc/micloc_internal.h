@@ -208,4 +208,20 @@ hipError_t launch_envelope_track(const void *y, int kind, int B, int T, int G, d
                                  int32_t *index, hipStream_t stream);
 hipError_t launch_peak_location(const int32_t *rate, int B, int G, int F, int win, int32_t *index, hipStream_t stream);
 
+// ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
+struct MusicDims {
+    int B, T, M;     // trials, samples per trial, microphones
+    int S, L, hop;   // slices per trial, slice length, slice advance (slice s: [s hop, min(s hop + L, T)))
+    int N, Np, Fmax; // FFT length, frame row stride (N rounded up to 64), frames of the longest slice
+    int nbin, Cp;    // in-band bins, W / X columns (2 nbin rounded up to 16)
+    int G, ksel;     // DoAs, selected bins per slice
+};
+struct MusicBuffers {
+    long long R, Rp;  // frame rows, padded to a multiple of 64
+    size_t xf_bytes, X_bytes, sel_bytes, spec_bytes;
+};
+MusicBuffers music_layout(const MusicDims &d);
+hipError_t launch_music(const MusicDims &d, const IirCoef &co, const double *x, const double *W, const double *sre, const double *sim,
+                        double *xf, double *X, int32_t *sel, double *spec, double *power, int32_t *argmax, hipStream_t st);
+
 }  // namespace micloc

@@ -11,7 +11,8 @@ throughput mode  DoAs from a seeded host generator, clean array signals synthesi
                  (csrc/rng.hip), numbered by global trial so that the draw does not depend on the sharding.
 
 Sweeps: noisy_target_sweep (target_snn_localization.py:435-467), speech_target_sweep (:213-245), xylo_target_sweep
-(target_xylo_localization.py:540-608; integer-LIF stage parity-unpinned).
+(target_xylo_localization.py:540-608; integer-LIF stage parity-unpinned), music_noisy_sweep / music_speech_sweep (the MUSIC twins,
+target_localization_MUSIC.py).
 """
 import numpy as np
 
@@ -295,17 +296,18 @@ def _throughput_pipelined(beamf, bf_mat, time_test, sig_test, doa_all, snr_db_tr
 
 
 def _template_sweep(beamf, bf_mat, doa_list, time_test, sig_test, snr_db_trial, num_sim, seed, mode, rank, world_size, group,
-                    localizer, batch_trials, streams=4, scan_lane_cus=4, out_dir=None, sweep_name="template"):
+                    localizer, batch_trials, streams=4, scan_lane_cus=4, out_dir=None, sweep_name="template", store_key=None):
     """The Monte-Carlo loop shared by the noisy-target and the speech sweep (target_snn_localization.py:447-467 / :224-245):
     per trial `doa = rand(1)[0] * 2 pi`, apply_to_template at `snr_db_trial[trial]`, power, arg-max, pi-periodic error.
     Trials are processed in batches of `batch_trials` (host memory: a speech trial is 18.6 MB).  out_dir: per-batch result files and
-    resume (ShardStore): finished trials are loaded, only the missing ones are computed, the result is the uninterrupted run's."""
+    resume (ShardStore): finished trials are loaded, only the missing ones are computed, the result is the uninterrupted run's.
+    store_key: the ShardStore key entries that describe the localizer (default: the hash of bf_mat)."""
     total = len(snr_db_trial)
     lo, hi = shard_range(total, rank, world_size)
     store = None
     if out_dir is not None:
         store = ShardStore(out_dir, sweep_name, total, seed=int(seed), mode=mode, snr_db_trial=np.asarray(snr_db_trial, dtype=np.float64),
-                           doa_list=np.asarray(doa_list, dtype=np.float64), bf_mat=np.asarray(bf_mat), time_test=np.asarray(time_test, dtype=np.float64),
+                           doa_list=np.asarray(doa_list, dtype=np.float64), **(dict(bf_mat=np.asarray(bf_mat)) if store_key is None else store_key), time_test=np.asarray(time_test, dtype=np.float64),
                            sig_test=np.asarray(sig_test, dtype=np.float64), fs=float(beamf.fs), num_mic=len(beamf.geometry),
                            r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64), theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64))
     done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
@@ -437,6 +439,66 @@ def speech_target_sweep(beamf, bf_mat, doa_list, source, snr_db_vec=None, num_si
     return res
 
 
+def music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=100):
+    """Localizer of the MUSIC sweeps: MUSIC.localize_batch (the scripts' read-out power = mean_s |P|^2, arg-max) in device batches
+    of at most `max_batch` trials; the [B, S, G] spectra stay in the workspace."""
+
+    def run(sig_batch, time_vec):
+        am, pm = [], []
+        for s in range(0, len(sig_batch), max_batch):
+            out = music.localize_batch(sig_batch[s : s + max_batch], num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False)
+            a = out["argmax"].cpu().numpy().astype(np.int64)
+            am.append(a)
+            pm.append(out["power"].cpu().numpy()[np.arange(len(a)), a])
+        return np.concatenate(am), np.concatenate(pm)
+
+    return run
+
+
+def _music_store_key(music, num_active_freq, duration_overlap, num_fft_bin):
+    return dict(freq_range=np.asarray(music.freq_range, dtype=np.float64), num_fft_bin=int(num_fft_bin), num_active_freq=int(num_active_freq),
+                duration_overlap=float(duration_overlap), frame_duration=float(music.frame_duration), speed=float(music.geometry.speed))
+
+
+def music_noisy_sweep(music, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None, num_active_freq=1,
+                      num_fft_bin=2048, duration_overlap=0.0, freq_design=2000.0, test_duration=1000e-3, snr_gain_due_to_bandwidth=None,
+                      batch_trials=100, out_dir=None):
+    """The noisy-target MUSIC sweep of paper_plots/target_localization_MUSIC.py (test_noisy_target, statistical part): a 1 s
+    `freq_design` sine, 11 SNRs x num_sim trials, SNR lowered by 10 log10((fs/2) / (f_max - f_min)), per trial `doa = rand(1)[0] * 2 pi`,
+    apply_to_template (k = 1, N = 2048, no overlap), power = mean_s |P|^2, arg-max, arcsin|sin(err)|.  `music` is a MUSIC (the script's:
+    7-mic circular array, band [1600, 2400], 57 DoAs, frame_duration 1.0).  Modes, sharding and out_dir resume as noisy_target_sweep;
+    the ShardStore key also covers band, N, k, overlap and frame duration."""
+    fs = music.fs
+    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    if snr_gain_due_to_bandwidth is None:
+        f_min, f_max = music.freq_range
+        snr_gain_due_to_bandwidth = (fs / 2) / (f_max - f_min)
+    time_test = np.arange(0, test_duration, step=1 / fs)
+    sig_test = np.sin(2 * np.pi * freq_design * time_test)
+    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    loc = music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=batch_trials)
+    res = _template_sweep(music, None, music.doa_list, time_test, sig_test, snr_trial, num_sim, seed, mode, rank, world_size, group, loc,
+                          batch_trials, 0, out_dir=out_dir, sweep_name="music-noisy",
+                          store_key=_music_store_key(music, num_active_freq, duration_overlap, num_fft_bin))
+    res["snr_db_vec"] = snr_db_vec
+    return res
+
+
+def music_speech_sweep(music, source, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None, num_active_freq=1,
+                       num_fft_bin=2048, duration_overlap=0.0, batch_trials=25, out_dir=None):
+    """The speech-target MUSIC sweep of paper_plots/target_localization_MUSIC.py (test_speech_target, statistical part): `source` =
+    (time_fs, sig_test) from `speech_source`, 11 SNRs x num_sim trials, NO bandwidth correction, k = 1, N = 2048 (the script's MUSIC:
+    449 DoAs, frame_duration 1.0: 7 slices per trial).  Modes, sharding and out_dir resume as music_noisy_sweep."""
+    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    time_fs, sig_test = source
+    loc = music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=batch_trials)
+    res = _template_sweep(music, None, music.doa_list, np.asarray(time_fs, dtype=np.float64), np.asarray(sig_test, dtype=np.float64),
+                          np.repeat(snr_db_vec, num_sim), num_sim, seed, mode, rank, world_size, group, loc, batch_trials, 0, out_dir=out_dir,
+                          sweep_name="music-speech", store_key=_music_store_key(music, num_active_freq, duration_overlap, num_fft_bin))
+    res["snr_db_vec"] = snr_db_vec
+    return res
+
+
 def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None,
                       test_duration=1000e-3, snr_gain_due_to_bandwidth=None, batch_trials=None, device_delays=None, peak=None, out_dir=None):
     """The Xylo accuracy sweep of paper_plots/target_xylo_localization.py:540-608 (and its `_unipolar` twin): chirp test
@@ -554,9 +616,9 @@ def main(argv=None):
     import os
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo"], default="noisy")
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech"], default="noisy")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
-    ap.add_argument("--grid", type=int, default=64 * 7 + 1)
+    ap.add_argument("--grid", type=int, default=None, help="DoA grid (default: 449; music-noisy: 57, the MUSIC script's)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mode", choices=["parity", "throughput"], default="parity")
     ap.add_argument("--flac", default=None, help="speech sweep: the LibriSpeech utterance (84-121123-0020.flac of the reference's paper_plots/)")
@@ -579,8 +641,25 @@ def main(argv=None):
     freq_range = [0.5 * freq_design, freq_design]
     tau = 1.0 / (2 * np.pi * freq_design)
     geometry = CenterCircularArray(radius=4.5e-2, num_mic=7)
-    doa_list = np.linspace(-np.pi, np.pi, args.grid)
-    if args.sweep == "xylo":
+    grid = args.grid if args.grid is not None else (8 * 7 + 1 if args.sweep == "music-noisy" else 64 * 7 + 1)
+    doa_list = np.linspace(-np.pi, np.pi, grid)
+    if args.sweep.startswith("music"):
+        # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048
+        from .music_beamformer import MUSIC
+
+        music = MUSIC(geometry=geometry, freq_range=[0.8 * freq_design, 1.2 * freq_design], doa_list=doa_list, frame_duration=1.0, fs=fs)
+        if args.sweep == "music-speech":
+            if args.pcm_npz:
+                z = np.load(args.pcm_npz)
+                src = speech_source(fs, pcm16=z["pcm16"], rate=int(z["rate"]))
+            elif args.flac:
+                src = speech_source(fs, flac_path=args.flac)
+            else:
+                ap.error("--sweep music-speech needs --flac or --pcm-npz")
+            res = music_speech_sweep(music, src, num_sim=args.num_sim or 100, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+        else:
+            res = music_noisy_sweep(music, num_sim=args.num_sim or 100, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+    elif args.sweep == "xylo":
         from .xylo_snn_localization import Demo
 
         demo = Demo(geometry=geometry, freq_bands=[freq_range], doa_list=doa_list, recording_duration=0.25, bipolar_spikes=True, fs=fs)

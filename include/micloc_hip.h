@@ -423,6 +423,23 @@ int micloc_envelope_track_f64(const double *y, int B, int T, int G, double a_ris
 int micloc_envelope_track_any(const void *y, int kind, int B, int T, int G, double a_rise, double i_rise, double a_fall, double *env, int32_t *index,
                               void *stream);
 
+/* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
+/* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
+ * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
+ * (lfilter(b, a) with the host coefficients b, a of length n, DF2T as micloc_lfilter_f64), cut into F_s = len_s / N frames and
+ * transformed at the in-band bins only: W (device) is [Np][Cp] with Np = N rounded up to 64, Cp = 2 nbin rounded up to 16,
+ * W[n][2j] = cos(2 pi ((k_j n) mod N) / N), W[n][2j + 1] = -sin(...) for bin k_j, zero elsewhere.  Bin power = mean over
+ * (mic, frame) of |X|^2; the k strongest bins are taken in np.argsort order (ascending power, exact ties: the later bin sorts
+ * later); k == 0 or k > nbin takes all.  spec[b][s][g] = sum over those bins of mean_f |a^H X[:, f, bin]|^2 with the steering
+ * table steer_re / steer_im [nbin][M][G] (device; a = exp(-1j 2 pi freq delays), conjugated here).  Outputs (device, each may be
+ * NULL): sel [B][S][ksel] int32 (the selected in-band bin indices, in order), spec [B][S][G], power [B][G] = mean_s spec^2 and
+ * argmax [B] (first maximum).  MICLOC_ERR_SHAPE: a slice shorter than N (the reference's broadcast ValueError) or a slice start
+ * outside the signal.  ws from micloc_music_workspace_bytes (256-B aligned); no host synchronisation. */
+size_t micloc_music_workspace_bytes(int B, int T, int M, int L, int hop, int S, int N, int nbin, int G, int k);
+int micloc_music_f64(const double *x, int B, int T, int M, const double *b, const double *a, int n, int L, int hop, int S, int N,
+                     const double *W, int nbin, const double *steer_re, const double *steer_im, int G, int k, int32_t *sel, double *spec,
+                     double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- misc ------------------------------------------------------------------------------------- */
 int micloc_abi_version(void);
 const char *micloc_status_string(int status);
