@@ -122,6 +122,7 @@ SYMBOLS = {
     "micloc_stream_localize_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_design_vectors_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
     "micloc_peak_location_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "micloc_doa_peaks_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
     "micloc_envelope_track_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
     "micloc_envelope_track_any": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
     "micloc_music_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

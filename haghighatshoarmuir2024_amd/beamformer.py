@@ -64,13 +64,18 @@ class Beamformer:
         y = plan.beamformer_pipeline(x, want_y=True, want_power=False)["y"][0]
         return runtime.to_host(y) if to_host else y
 
-    def localize_batch(self, bf_mat, sig_batch):
+    def localize_batch(self, bf_mat, sig_batch, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
+        """sig_batch [B, T, M] -> dict of device tensors: power [B, G], argmax [B] (int32); with num_sources=K (and doa_list [G],
+        the DoAs of bf_mat's columns) also peaks [B, K] int32 and peak_power [B, K] (utils.find_doa_peaks)."""
+        from .utils import _add_peaks
+
         B, T, M = sig_batch.shape
         if bf_mat.shape[0] != M:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {bf_mat.shape[0]}!")
         plan = self.plan()
         plan.set_bf_mat(np.asarray(bf_mat, dtype=np.complex128))
-        return plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True)
+        return _add_peaks(plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True), doa_list, num_sources, min_separation,
+                          rel_threshold)
 
     def apply_to_template(self, bf_mat, template, snr_db, to_host=True):
         try:

@@ -1077,6 +1077,17 @@ int micloc_peak_location_i32(const int32_t *rate, int B, int G, int bands, int w
     return MICLOC_OK;
 }
 
+int micloc_doa_peaks_f64(const double *power, int B, int G, const double *doa_list, int grid_kind, int K, double min_separation,
+                         double rel_threshold, int32_t *index, double *value, void *stream)
+{
+    if (!power || !doa_list || !index || bad_batch(B) || G < 1 || G > 4096 || K < 1 || K > 16) return MICLOC_ERR_INVALID;
+    if (grid_kind < MICLOC_GRID_LINEAR || grid_kind > MICLOC_GRID_CIRCULAR_CLOSED) return MICLOC_ERR_INVALID;
+    if (!(min_separation >= 0.0) || !(rel_threshold >= 0.0) || isinf(rel_threshold)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(device_of(index));
+    HIP_TRY(launch_doa_peaks(power, B, G, doa_list, grid_kind, K, min_separation, rel_threshold, index, value, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
 }  // extern "C"
 
 namespace {

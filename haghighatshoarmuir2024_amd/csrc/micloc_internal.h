@@ -207,6 +207,8 @@ hipError_t launch_rate_from_counts(const int32_t *counts, int B, int G, int F, i
 hipError_t launch_envelope_track(const void *y, int kind, int B, int T, int G, double a_rise, double i_rise, double a_fall, double *env,
                                  int32_t *index, hipStream_t stream);
 hipError_t launch_peak_location(const int32_t *rate, int B, int G, int F, int win, int32_t *index, hipStream_t stream);
+hipError_t launch_doa_peaks(const double *power, int B, int G, const double *doa, int kind, int K, double min_sep, double rel, int32_t *index,
+                            double *value, hipStream_t stream);
 
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
 struct MusicDims {

@@ -190,10 +190,14 @@ class MUSIC:
                                     to_host=to_host)
 
     # ---- batched device entry points (not in the reference) ------------------------------------------------------
-    def localize_batch(self, sig_batch, num_active_freq, duration_overlap, num_fft_bin, want_spectrum=True, want_sel=False):
+    def localize_batch(self, sig_batch, num_active_freq, duration_overlap, num_fft_bin, want_spectrum=True, want_sel=False, num_sources=None,
+                       min_separation=None, rel_threshold=0.0):
         """sig_batch [B, T, M] (numpy or device tensor) -> dict of device tensors: spectrum [B, S, G] (apply_to_signal per trial),
         power [B, G] = np.mean(np.abs(spectrum) ** 2, axis=1) (the scripts' read-out), argmax [B] int32 (first maximum);
-        sel [B, S, k] (in-band bin indices) with want_sel."""
+        sel [B, S, k] (in-band bin indices) with want_sel; with num_sources=K also peaks [B, K] int32 and peak_power [B, K], the K
+        strongest sources over self.doa_list (utils.find_doa_peaks)."""
+        from .utils import _add_peaks
+
         B, T, M = sig_batch.shape
         if M != len(self.geometry):
             raise ValueError("number of channels in the input signal should be the same as the number of microphones!")
@@ -201,8 +205,9 @@ class MUSIC:
         if len(starts) == 0:
             raise ValueError(f"a signal of {T} samples has no slice of at least half a frame ({L} samples)")
         self._check(lens, M, num_active_freq, num_fft_bin)
-        return self._run(sig_batch, L, hop, len(starts), num_active_freq, num_fft_bin, want_spec=want_spectrum, want_readout=True,
-                         want_sel=want_sel)
+        out = self._run(sig_batch, L, hop, len(starts), num_active_freq, num_fft_bin, want_spec=want_spectrum, want_readout=True,
+                        want_sel=want_sel)
+        return _add_peaks(out, self.doa_list, num_sources, min_separation, rel_threshold)
 
     def synthesize_batch(self, template, doas, device_delays=False):
         """Noise-free array signals of a batch of trials on the device (as SNNBeamformer.synthesize_batch)."""

@@ -604,6 +604,31 @@ def peak_location(counts, G, win_size, out=None):
     return idx
 
 
+GRID_KINDS = {"linear": 0, "circular": 1, "circular_closed": 2}  # MICLOC_GRID_*
+
+
+def doa_peaks(power, doa_list, grid_kind, num_sources, min_separation, rel_threshold=0.0, index_out=None, value_out=None):
+    """micloc_doa_peaks_f64: power float64 [B, G] device tensor, doa_list [G] (device tensor or host array) -> (index int32 [B, K],
+    value float64 [B, K]) device tensors: the K strongest peaks of every row (the rule of include/micloc_hip.h).  grid_kind is a
+    key of GRID_KINDS."""
+    torch = _torch()
+    if not isinstance(power, torch.Tensor) or not power.is_cuda or power.dtype != torch.float64 or power.dim() != 2:
+        raise ValueError("doa_peaks: power must be a float64 device tensor [B, G]")
+    if grid_kind not in GRID_KINDS:
+        raise ValueError(f"doa_peaks: grid_kind must be one of {sorted(GRID_KINDS)}")
+    p = power.contiguous()
+    B, G = p.shape
+    K = int(num_sources)
+    d = _as_dev(doa_list, p.device)
+    if d.dim() != 1 or d.shape[0] != G:
+        raise ValueError(f"doa_peaks: doa_list has {tuple(d.shape)} entries for {G} grid points")
+    idx = index_out if index_out is not None else torch.empty((B, K), dtype=torch.int32, device=p.device)
+    val = value_out if value_out is not None else torch.empty((B, K), dtype=torch.float64, device=p.device)
+    _lib.check(_lib.load().micloc_doa_peaks_f64(_ptr(p), B, G, _ptr(d), GRID_KINDS[grid_kind], K, float(min_separation), float(rel_threshold),
+                                                _ptr(idx), _ptr(val), _stream(p.device)), "doa_peaks")
+    return idx, val
+
+
 def envelope_track(y, win_fall, win_rise, want_index=True, env_out=None):
     """micloc_envelope_track_any: y [T, G] or [B, T, G] device tensor (float64: the SNN beamformer's output; complex128: the complex
     Beamformer's, paper_plots/target_localization.py:597-600; uint8 / int32 / int64: a spike raster, paper_plots/target_xylo_localization.py:757-768)

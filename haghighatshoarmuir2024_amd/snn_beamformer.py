@@ -158,9 +158,14 @@ class SNNBeamformer:
         return synthesis.apply_to_template_batch(self.geometry, self.fs, template, doas, device=self.device, device_delays=device_delays)
 
     # ---- batched device entry points (not in the reference) --------------------------------------------------
-    def localize_batch(self, bf_mat, sig_batch, time_vec=None, return_spikes=False, power_mode="direct"):
+    def localize_batch(self, bf_mat, sig_batch, time_vec=None, return_spikes=False, power_mode="direct", num_sources=None, doa_list=None,
+                       min_separation=None, rel_threshold=0.0):
         """sig_batch [B, T, M] (numpy or device tensor, already on the fs grid) -> dict of device tensors:
-        power [B, G] = mean_t |apply_to_signal|^2, argmax [B] (int32), optionally spikes [B, T, 2M] int8."""
+        power [B, G] = mean_t |apply_to_signal|^2, argmax [B] (int32), optionally spikes [B, T, 2M] int8.
+        num_sources=K (with doa_list [G], the DoAs of bf_mat's columns): also peaks [B, K] int32 and peak_power [B, K], the K
+        strongest sources (utils.find_doa_peaks with min_separation and rel_threshold)."""
+        from .utils import _add_peaks
+
         B, T, M = sig_batch.shape
         if bf_mat.shape[0] // 2 != M:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {bf_mat.shape[0] // 2}!")
@@ -172,10 +177,11 @@ class SNNBeamformer:
         x = plan.to_device(sig_batch)
         if power_mode == "covariance":
             # algebraically identical variant: w^T (V^T V / T) w instead of mean_t (V w)^2  (SURVEY 8f.4)
-            return plan.snn_pipeline_cov(x, want_spikes=return_spikes, want_power=True)
+            return _add_peaks(plan.snn_pipeline_cov(x, want_spikes=return_spikes, want_power=True), doa_list, num_sources, min_separation,
+                              rel_threshold)
         if power_mode != "direct":
             raise ValueError("power_mode must be 'direct' or 'covariance'")
-        return plan.snn_pipeline(x, want_spikes=return_spikes, want_power=True)
+        return _add_peaks(plan.snn_pipeline(x, want_spikes=return_spikes, want_power=True), doa_list, num_sources, min_separation, rel_threshold)
 
     def membrane_covariance_batch(self, sig_batch, time_vec=None, t_start=0, out=None):
         """[B, T, M] -> device tensor [B, 2M, 2M] (`out`, if given): V^T V / (T - t_start) of the membrane signal over frames >= t_start."""

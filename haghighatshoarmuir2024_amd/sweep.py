@@ -12,7 +12,8 @@ throughput mode  DoAs from a seeded host generator, clean array signals synthesi
 
 Sweeps: noisy_target_sweep (target_snn_localization.py:435-467), speech_target_sweep (:213-245), xylo_target_sweep
 (target_xylo_localization.py:540-608; integer-LIF stage parity-unpinned), music_noisy_sweep / music_speech_sweep (the MUSIC twins,
-target_localization_MUSIC.py).
+target_localization_MUSIC.py), multi_target_sweep (K simultaneous targets, the statistical counterpart of
+paper_plots/multiple_targets_*.py: K peaks per trial, matched errors and resolution rate).
 """
 import numpy as np
 
@@ -191,14 +192,21 @@ def sharded_design(design_fn, doa_list, rank=0, world_size=1, group=None):
     return flat["cols"].reshape(G, rows).T.copy()
 
 
-def device_localizer(beamf, bf_mat, max_batch=1100):
-    """Default localizer: the HIP pipeline (power + arg-max, no T x G temporary)."""
+def device_localizer(beamf, bf_mat, max_batch=1100, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
+    """Default localizer: the HIP pipeline (power + arg-max, no T x G temporary).  With num_sources=K (and doa_list) it returns the
+    multi-source read-out instead: (peaks [B, K] int64, peak_power [B, K]) (multi_target_sweep)."""
 
     def run(sig_batch, time_vec):
         am, pm = [], []
         for s in range(0, len(sig_batch), max_batch):
             # (the non-spiking complex Beamformer has no neuron kernel, hence no time axis to pass: ref:paper_plots/target_localization.py)
             kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
+            if num_sources is not None:
+                out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], num_sources=num_sources, doa_list=doa_list,
+                                           min_separation=min_separation, rel_threshold=rel_threshold, **kw)
+                am.append(out["peaks"].cpu().numpy().astype(np.int64))
+                pm.append(out["peak_power"].cpu().numpy())
+                continue
             out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], **kw)
             a = out["argmax"].cpu().numpy().astype(np.int64)
             p = out["power"].cpu().numpy()
@@ -439,13 +447,20 @@ def speech_target_sweep(beamf, bf_mat, doa_list, source, snr_db_vec=None, num_si
     return res
 
 
-def music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=100):
+def music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=100, num_sources=None, min_separation=None, rel_threshold=0.0):
     """Localizer of the MUSIC sweeps: MUSIC.localize_batch (the scripts' read-out power = mean_s |P|^2, arg-max) in device batches
-    of at most `max_batch` trials; the [B, S, G] spectra stay in the workspace."""
+    of at most `max_batch` trials; the [B, S, G] spectra stay in the workspace.  With num_sources=K: (peaks [B, K] int64,
+    peak_power [B, K]) instead (multi_target_sweep)."""
 
     def run(sig_batch, time_vec):
         am, pm = [], []
         for s in range(0, len(sig_batch), max_batch):
+            if num_sources is not None:
+                out = music.localize_batch(sig_batch[s : s + max_batch], num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False,
+                                           num_sources=num_sources, min_separation=min_separation, rel_threshold=rel_threshold)
+                am.append(out["peaks"].cpu().numpy().astype(np.int64))
+                pm.append(out["peak_power"].cpu().numpy())
+                continue
             out = music.localize_batch(sig_batch[s : s + max_batch], num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False)
             a = out["argmax"].cpu().numpy().astype(np.int64)
             am.append(a)
@@ -608,15 +623,275 @@ def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity",
     return res
 
 
+# ---- multi-target sweep ---------------------------------------------------------------------------------------------------------
+
+class MultiShardStore(ShardStore):
+    """ShardStore of multi_target_sweep: a record holds K DoAs, K peak indices and K peak values per trial."""
+
+    def __init__(self, out_dir, sweep, total, num_targets, **key):
+        K = int(num_targets)
+        self.REC = np.dtype([("trial", "<i8"), ("doa", "<f8", (K,)), ("index", "<i8", (K,)), ("pmax", "<f8", (K,))])
+        super().__init__(out_dir, sweep, total, num_targets=K, **key)
+
+
+def _method_key(beamf):
+    """ShardStore key entries for the localizer's own parameters: its class, for the beamformers the plan key (Hilbert kernel,
+    band-pass b / a, robust width, bipolar) and tau_vec, for MUSIC its band, frame duration, DoA grid and speed of sound (the
+    per-call parameters k, N and overlap come with store_key, _music_store_key)."""
+    key = dict(method=type(beamf).__name__)
+    if hasattr(beamf, "kernel"):
+        key["kernel"] = np.asarray(beamf.kernel, dtype=np.float64)
+    if hasattr(beamf, "bandpass_filter"):
+        b, a = beamf.bandpass_filter
+        key["iir_b"], key["iir_a"] = np.asarray(b, dtype=np.float64), np.asarray(a, dtype=np.float64)
+    if hasattr(beamf, "spk_encoder"):
+        key["robust_width"], key["bipolar"] = int(beamf.spk_encoder.robust_width), bool(beamf.spk_encoder.bipolar)
+    if hasattr(beamf, "tau_vec"):
+        key["tau_vec"] = np.asarray(beamf.tau_vec, dtype=np.float64)
+    if hasattr(beamf, "frame_duration"):  # MUSIC: band, frame length, DoA grid of the steering table, speed of sound
+        key["freq_range"] = np.asarray(beamf.freq_range, dtype=np.float64)
+        key["frame_duration"] = float(beamf.frame_duration)
+        key["music_doa_list"] = np.asarray(beamf.doa_list, dtype=np.float64)
+        key["speed"] = float(beamf.geometry.speed)
+    return key
+
+
+def _draw_doas(draw, K, min_separation, max_redraws):
+    """`draw(K) * 2 pi`, drawn again while two targets are closer than min_separation in the pi-periodic error."""
+    doa = draw(K) * 2 * np.pi
+    for _ in range(max_redraws):
+        if K < 2 or min(doa_error(doa[i], doa[j]) for i in range(K) for j in range(i + 1, K)) >= min_separation:
+            return doa
+        doa = draw(K) * 2 * np.pi
+    raise ValueError(f"no {K} DoAs at least {min_separation} rad apart in {max_redraws} redraws")
+
+
+def synthesize_targets(geometry, fs, time_test, sig_test, doas, gains):
+    """Noise-free array signal of K constant-DoA targets on the host: every copy is delayed as apply_to_template delays it, with ONE
+    shift (the minimum over all targets' delays), scaled by its gain and summed `sig = 0; sig += g_k * copy_k` in k order.
+    Returns (time_in [T], sig [T, M])."""
+    time_test = np.asarray(time_test, dtype=np.float64)
+    time_in = np.arange(time_test.min(), time_test.max(), step=1 / fs)
+    sig_in = np.interp(time_in, time_test, np.asarray(sig_test, dtype=np.float64))
+    delays = np.stack([geometry.delays(float(d), normalized=False) for d in doas])  # [K, M]
+    delays = delays - delays.min()
+    sig = np.zeros((len(time_in), delays.shape[1]))
+    for k in range(len(doas)):
+        t = time_in.reshape(1, -1) - delays[k].reshape(-1, 1)
+        np.maximum(t, time_in.min(), out=t)
+        sig += gains[k] * np.interp(t.ravel(), time_in, sig_in).reshape(t.shape).T
+    return time_in, sig
+
+
+def synthesize_targets_batch(geometry, fs, time_test, sig_test, doas, gains, device=None):
+    """synthesize_targets for a batch of trials on the device (micloc_synth_targets_f64, APPLY_TO_TEMPLATE, host delays: the same
+    bits).  doas [B, K] -> (time_in [T], x [B, T, M] device tensor)."""
+    from . import runtime, synthesis
+
+    doas = np.asarray(doas, dtype=np.float64)
+    B, K = doas.shape
+    time_in, sig_in = synthesis._resample(time_test, sig_test, fs)
+    tpl = runtime.Template(time_in, sig_in, fs, device=device)
+    delays = geometry.delays(doas.ravel(), normalized=False).reshape(B, K, -1)
+    delays = delays - delays.min(axis=(1, 2), keepdims=True)
+    gains = np.asarray(gains, dtype=np.float64)
+    gain = None
+    if not np.all(gains == 1.0):  # (1 * r is r: no table for unit gains)
+        # the kernel reads gain [B, K, T]: expanded on the device, only K numbers cross PCIe
+        gain = runtime._as_dev(gains, tpl.device).reshape(1, K, 1).expand(B, K, tpl.T).contiguous()
+    return time_in, runtime.synth_targets(tpl, "apply_to_template", delays=delays, gain=gain)
+
+
+def match_errors(doa_true, doa_list, index):
+    """Matched pi-periodic errors of K estimates against K true DoAs: doa_true [N, K], index [N, K] (-1: no peak) -> err [N, K],
+    err[n, k] = the error of truth k under the permutation of the estimates with the least summed error (ties: the first permutation
+    in lexicographic order).  A missing peak costs pi / 2, the metric's maximum."""
+    import itertools
+
+    doa_list = np.asarray(doa_list, dtype=np.float64)
+    N, K = index.shape
+    est = doa_list[np.maximum(index, 0)]
+    best = best_sum = None
+    for perm in itertools.permutations(range(K)):
+        e = np.where(index[:, perm] >= 0, doa_error(est[:, perm], doa_true), np.pi / 2)
+        tot = e[:, 0].copy()
+        for k in range(1, K):
+            tot += e[:, k]
+        if best is None:
+            best, best_sum = e, tot
+        else:
+            better = tot < best_sum
+            best[better], best_sum[better] = e[better], tot[better]
+    return best
+
+
+def multi_target_sweep(beamf, bf_mat, doa_list, num_targets=2, min_separation=np.pi / 4, gains=None, peak_separation=None, tol=None,
+                       rel_threshold=0.0, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None,
+                       freq_design=2000.0, test_duration=100e-3, snr_gain_due_to_bandwidth=None, localizer=None, batch_trials=1100,
+                       out_dir=None, store_key=None, max_redraws=10_000):
+    """The noisy-target sweep with K = num_targets simultaneous targets of the same `freq_design` sine.  Per trial: `doa = rand(K) * 2 pi`,
+    drawn again while two targets are closer than `min_separation` in the pi-periodic error (parity mode: the global MT19937 stream,
+    then randn(T, M) of the noise; throughput mode: RandomState(seed) for every trial on every rank, noise from the Philox kernel by
+    global trial); the array signal sums the K delayed copies with `gains` (synthesize_targets); noise as apply_to_template from
+    the summed signal's power; localize with num_sources=K (peaks at least `peak_separation` apart, `rel_threshold`); estimates
+    are matched to truths by the permutation with the least summed pi-periodic error (match_errors).
+    `localizer(sig_batch, time_vec) -> (index [B, K], value [B, K])` replaces the device pipeline (default: device_localizer with
+    num_sources; MUSIC: music_localizer with num_sources).  Defaults: min_separation 45 deg, gains 1, peak_separation and tol
+    min_separation / 2.  At num_targets = 1 this is noisy_target_sweep, bit for bit, in both modes.
+    Returns dict(doa, peaks, peak_power, err: [num_snr, num_sim, K]; mae_deg (over trials and targets) and resolved_rate (all K
+    peaks found, every matched error <= tol): [num_snr]).  Sharding, the one exchange and out_dir resume as noisy_target_sweep;
+    the ShardStore key also covers K, both separations, tol, gains, rel_threshold and the method's parameters (store_key adds to it)."""
+    K = int(num_targets)
+    if not 1 <= K <= 4:
+        raise ValueError("num_targets must be between 1 and 4")
+    min_separation = float(min_separation)
+    if not (min_separation >= 0.0 and K * min_separation < np.pi):
+        raise ValueError(f"{K} targets cannot be {min_separation} rad apart in the pi-periodic error: need K * min_separation < pi")
+    gains = np.ones(K) if gains is None else np.asarray(gains, dtype=np.float64).reshape(-1)
+    if len(gains) != K:
+        raise ValueError(f"gains has {len(gains)} entries for {K} targets")
+    peak_separation = min_separation / 2 if peak_separation is None else float(peak_separation)
+    tol = min_separation / 2 if tol is None else float(tol)
+    if mode not in ("parity", "throughput"):
+        raise ValueError("mode must be 'parity' or 'throughput'")
+    doa_list = np.asarray(doa_list, dtype=np.float64)
+    fs = beamf.fs
+    M = len(beamf.geometry)
+    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    if snr_gain_due_to_bandwidth is None:
+        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
+    time_test = np.arange(0, test_duration, step=1 / fs)
+    sig_test = np.sin(2 * np.pi * freq_design * time_test)
+    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    total = len(snr_trial)
+    lo, hi = shard_range(total, rank, world_size)
+    store = None
+    if out_dir is not None:
+        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
+        key.update(_method_key(beamf))
+        key.update(store_key or {})
+        store = MultiShardStore(out_dir, "multi-noisy", total, K, seed=int(seed), mode=mode, snr_db_trial=snr_trial, doa_list=doa_list,
+                                min_separation=min_separation, peak_separation=peak_separation, tol=tol, gains=gains,
+                                rel_threshold=float(rel_threshold), time_test=time_test, sig_test=sig_test, fs=float(fs), num_mic=M,
+                                r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
+                                theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
+    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
+    if localizer is None:
+        localizer = device_localizer(beamf, bf_mat, max_batch=batch_trials, num_sources=K, doa_list=doa_list, min_separation=peak_separation,
+                                     rel_threshold=rel_threshold)
+    doa_all = np.zeros((total, K))
+    index = np.full((hi - lo, K), -1, dtype=np.int64)
+    value = np.full((hi - lo, K), np.nan)
+    if store is not None:
+        index[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
+        value[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
+
+    def flush(sig_batch, time_in, trials):
+        trials = np.asarray(trials, dtype=np.int64)
+        a, p = localizer(sig_batch, time_in)
+        a = np.asarray(a, dtype=np.int64).reshape(len(trials), K)
+        p = np.asarray(p, dtype=np.float64).reshape(len(trials), K)
+        index[trials - lo], value[trials - lo] = a, p
+        if store is not None:
+            store.put(trials, doa_all[trials], a, p)
+
+    if mode == "parity":
+        np.random.seed(seed)
+        T = len(np.arange(time_test.min(), time_test.max(), step=1 / fs))
+        sigs, ids, time_in = [], [], None
+        for trial in range(total):
+            doa_all[trial] = _draw_doas(np.random.rand, K, min_separation, max_redraws)
+            if lo <= trial < hi and not done[trial]:
+                time_in, sig = synthesize_targets(beamf.geometry, fs, time_test, sig_test, doa_all[trial], gains)
+                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
+                sigs.append(sig)
+                ids.append(trial)
+                if len(sigs) == batch_trials:
+                    flush(np.stack(sigs), time_in, ids)
+                    sigs, ids = [], []
+            else:
+                np.random.randn(T, M)  # keep the stream aligned
+        if sigs:
+            flush(np.stack(sigs), time_in, ids)
+    else:
+        from . import synthesis
+
+        rng = np.random.RandomState(seed)
+        for trial in range(total):  # every rank draws every trial: the DoAs do not depend on the world size
+            doa_all[trial] = _draw_doas(rng.rand, K, min_separation, max_redraws)
+        ranges = [(s0, min(hi, s0 + batch_trials)) for s0 in range(lo, hi, batch_trials)]
+        for s0, s1 in ranges:
+            if done[s0:s1].all():
+                continue
+            time_in, x = synthesize_targets_batch(beamf.geometry, fs, time_test, sig_test, doa_all[s0:s1], gains, device=getattr(beamf, "device", None))
+            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
+            flush(x, time_in, np.arange(s0, s1))
+
+    # the one exchange step: K index columns and K value columns in ONE all-gather
+    exchange = {}
+    local = {f"index{k}": np.ascontiguousarray(index[:, k]) for k in range(K)}
+    local.update({f"value{k}": np.ascontiguousarray(value[:, k]) for k in range(K)})
+    full = gather_shards(local, total, rank, world_size, group, stats=exchange)
+    peaks = np.stack([full[f"index{k}"] for k in range(K)], axis=1)
+    power = np.stack([full[f"value{k}"] for k in range(K)], axis=1)
+    err = match_errors(doa_all, doa_list, peaks)
+    tol_ok = np.all((peaks >= 0) & (err <= tol), axis=1)
+    S = total // num_sim
+    res = dict(doa=doa_all.reshape(S, num_sim, K), peaks=peaks.reshape(S, num_sim, K), peak_power=power.reshape(S, num_sim, K),
+               err=err.reshape(S, num_sim, K), mae_deg=np.mean(err.reshape(S, num_sim * K), axis=1) * 180 / np.pi,
+               resolved_rate=np.mean(tol_ok.reshape(S, num_sim), axis=1), snr_db_vec=snr_db_vec, exchange=exchange)
+    if store is not None:
+        res["persistence"] = store.stats()
+    return res
+
+
+def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world):
+    """--sweep multi-noisy: multi_target_sweep with the noisy sweep's SNN or complex beamformer (design as --sweep noisy) or the MUSIC
+    noisy sweep's MUSIC (1 s test signal, band [0.8, 1.2] x freq_design, k = 1, N = 2048)."""
+    kw = dict(num_targets=args.num_targets, min_separation=np.deg2rad(args.min_separation_deg), num_sim=args.num_sim or 100, seed=args.seed,
+              mode=args.mode, rank=rank, world_size=world)
+    if args.method == "music":
+        from .music_beamformer import MUSIC
+
+        music = MUSIC(geometry=geometry, freq_range=[0.8 * freq_design, 1.2 * freq_design], doa_list=doa_list, frame_duration=1.0, fs=fs)
+        sep = kw["min_separation"] / 2
+        loc = music_localizer(music, 1, 0.0, 2048, max_batch=100, num_sources=args.num_targets, min_separation=sep)
+        return multi_target_sweep(music, None, doa_list, localizer=loc, test_duration=1000e-3, batch_trials=100,
+                                  snr_gain_due_to_bandwidth=(fs / 2) / (0.4 * freq_design), store_key=_music_store_key(music, 1, 0.0, 2048), **kw)
+    time_temp = np.arange(0, 1.0, step=1 / fs)
+    period = time_temp[-1]
+    freq_inst = freq_range[0] + (freq_range[1] - freq_range[0]) * (time_temp % period) / period
+    sig_temp = np.sin(2 * np.pi * np.cumsum(freq_inst) / fs)
+    if args.method == "snn":
+        from .snn_beamformer import SNNBeamformer
+
+        beamf = SNNBeamformer(geometry, kernel_duration=10.0e-3, tau_vec=np.asarray([tau, tau]), freq_range=freq_range, fs=fs, bipolar_spikes=True)
+        design = lambda doas: beamf.design_from_template((time_temp, sig_temp), doas, svd=args.svd)  # noqa: E731
+    else:
+        from .beamformer import Beamformer
+
+        beamf = Beamformer(geometry, kernel_duration=10.0e-3, freq_range=freq_range, fs=fs)
+        # (complex columns: designed whole on every rank)
+        design = None
+    if design is not None:
+        bf_mat = sharded_design(design, doa_list, rank, world)
+    else:
+        bf_mat, _ = beamf.design_from_template((time_temp, sig_temp), doa_list, svd=args.svd)  # (bf_mat, cov_mat_list)
+    return multi_target_sweep(beamf, bf_mat, doa_list, **kw)
+
+
 def main(argv=None):
-    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo]`: the accuracy sweeps of the paper scripts
+    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy]`: the accuracy sweeps of the paper scripts
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
     import os
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech"], default="noisy")
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy"], default="noisy")
+    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy: the localizer")
+    ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
+    ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
     ap.add_argument("--grid", type=int, default=None, help="DoA grid (default: 449; music-noisy: 57, the MUSIC script's)")
     ap.add_argument("--seed", type=int, default=0)
@@ -641,9 +916,12 @@ def main(argv=None):
     freq_range = [0.5 * freq_design, freq_design]
     tau = 1.0 / (2 * np.pi * freq_design)
     geometry = CenterCircularArray(radius=4.5e-2, num_mic=7)
-    grid = args.grid if args.grid is not None else (8 * 7 + 1 if args.sweep == "music-noisy" else 64 * 7 + 1)
+    music_grid = args.sweep == "music-noisy" or (args.sweep == "multi-noisy" and args.method == "music")
+    grid = args.grid if args.grid is not None else (8 * 7 + 1 if music_grid else 64 * 7 + 1)
     doa_list = np.linspace(-np.pi, np.pi, grid)
-    if args.sweep.startswith("music"):
+    if args.sweep == "multi-noisy":
+        res = _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world)
+    elif args.sweep.startswith("music"):
         # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048
         from .music_beamformer import MUSIC
 
@@ -686,6 +964,8 @@ def main(argv=None):
     if rank == 0:
         print(f"SNR: {res['snr_db_vec']}")
         print(f"Mean aboslute errors: {res['mae_deg']}")
+        if "resolved_rate" in res:
+            print(f"Resolution rate: {res['resolved_rate']}")
     if world > 1:
         dist.destroy_process_group()
 

@@ -1,5 +1,5 @@
 """Host utilities with the reference's call surface (micloc/utils.py: Envelope :15-81,
-find_peak_location :84-121).  Post-processing outside the hot path; the moving-target read-out (Envelope over the T x G beamformer
+find_peak_location :84-121), and the multi-source read-out `find_doa_peaks`.  Post-processing outside the hot path; the moving-target read-out (Envelope over the T x G beamformer
 output + per-step arg-max, paper_plots/target_snn_localization.py:599-622) has a device form so that T x G never crosses PCIe."""
 import warnings
 
@@ -77,3 +77,71 @@ def find_peak_location(sig_in, win_size, periodic=True):
     if periodic:
         index = index % len(sig_in)
     return index
+
+
+def doa_grid_kind(doa_list, tol=1e-9):
+    """The kind of a DoA grid for find_doa_peaks: "circular_closed" when it spans 2 pi end to end (np.linspace(-pi, pi, G): first
+    and last point are one direction), "circular" when its G points cover one period without a duplicate (uniform step, span + step
+    = 2 pi), "linear" otherwise; `tol` applies to the span."""
+    doa = np.asarray(doa_list, dtype=np.float64)
+    G = len(doa)
+    if G < 2:
+        return "linear"
+    span = doa[-1] - doa[0]
+    if abs(span - 2 * np.pi) <= tol:
+        return "circular_closed"
+    if abs(span * G / (G - 1) - 2 * np.pi) <= tol:
+        return "circular"
+    return "linear"
+
+
+def find_doa_peaks(power, doa_list, num_sources, min_separation=None, rel_threshold=0.0, grid=None):
+    """The `num_sources` strongest sources of a DoA power profile: power [G] or [B, G] (host array or device tensor) over doa_list
+    [G] -> (index int32, value float64), [K] or [B, K], where the input was (device tensors for a device tensor, NumPy otherwise).
+
+    Peaks are local maxima (>= each neighbour, a NaN neighbour counts as lower, a NaN point is never a peak), taken largest first
+    (ties: lower index) if their value is >= rel_threshold * max(row) (when rel_threshold > 0) and they lie at least
+    `min_separation` (radians; default: two grid steps, so a peak's immediate neighbours -- a plateau of two points included -- never give a second peak) from
+    every peak already taken.  Unfilled slots hold -1 and NaN.  The grid kind ("linear", "circular", "circular_closed", see
+    doa_grid_kind) is taken from doa_list unless `grid` names it.  For num_sources = 1 and a row without NaN the index is
+    np.argmax.  Runs on the device only (micloc_doa_peaks_f64: include/micloc_hip.h states the rule in full)."""
+    from . import runtime
+
+    doa = np.asarray(doa_list.cpu().numpy() if _is_device_tensor(doa_list) else doa_list, dtype=np.float64)
+    if doa.ndim != 1:
+        raise ValueError("doa_list should be 1-dim!")
+    K = int(num_sources)
+    if not 1 <= K <= 16:
+        raise ValueError("num_sources must be between 1 and 16")
+    if grid is None:
+        grid = doa_grid_kind(doa)
+    if min_separation is None:
+        min_separation = 2 * abs(doa[-1] - doa[0]) / (len(doa) - 1) if len(doa) > 1 else 0.0
+    on_device = _is_device_tensor(power)
+    if on_device:
+        p = power
+        if p.dtype != runtime._torch().float64:
+            p = p.double()
+    else:
+        p = runtime._as_dev(np.asarray(power, dtype=np.float64), runtime.require_gpu())
+    single = p.dim() == 1
+    if single:
+        p = p.reshape(1, -1)
+    if p.dim() != 2 or p.shape[1] != len(doa):
+        raise ValueError(f"power has shape {tuple(power.shape)}, the DoA grid {len(doa)} points")
+    idx, val = runtime.doa_peaks(p, doa, grid, K, min_separation, rel_threshold)
+    if single:
+        idx, val = idx[0], val[0]
+    if on_device:
+        return idx, val
+    return idx.cpu().numpy(), val.cpu().numpy()
+
+
+def _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold):
+    """localize_batch's optional multi-source read-out: out["peaks"] [B, K] int32 and out["peak_power"] [B, K] from out["power"]."""
+    if num_sources is None:
+        return out
+    if doa_list is None:
+        raise ValueError("num_sources needs the DoA grid of bf_mat's columns (doa_list=)")
+    out["peaks"], out["peak_power"] = find_doa_peaks(out["power"], doa_list, num_sources, min_separation=min_separation, rel_threshold=rel_threshold)
+    return out

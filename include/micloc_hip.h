@@ -402,6 +402,25 @@ int micloc_rate_from_counts_f64(const int32_t *counts, int B, int G, int bands, 
  * factors T / fs and 1 / max do not move the arg-max): box-car of win_size samples, FULL non-circular convolution, first
  * maximum, minus win_size // 2, modulo G.  Exact integer window sums.  rate [B][bands * G] int32, index [B] (device). */
 int micloc_peak_location_i32(const int32_t *rate, int B, int G, int bands, int win_size, int32_t *index, void *stream);
+/* Multi-source read-out: the K strongest peaks of every row power [B][G] (fp64) over the DoA grid doa_list [G].
+ * Grid kinds: LINEAR (no wrap: the end points have one neighbour); CIRCULAR (the G points cover one period without a duplicate:
+ * point G-1 neighbours point 0); CIRCULAR_CLOSED (np.linspace(-pi, pi, G): points 0 and G-1 are one direction and are merged
+ * into one ring point whose value is max(p[0], p[G-1]), whose reported index is 0 if p[0] >= p[G-1] (or p[G-1] is NaN) and
+ * G-1 otherwise, and whose ring neighbours are 1 and G-2; G = 1 is taken as CIRCULAR).
+ * A (ring) point is a local maximum when its value is >= each neighbour's; a NaN neighbour counts as lower, a NaN point is
+ * never a peak.  Selection: visit the local maxima in order of value, largest first, ties to the lower reported index; accept
+ * one if (rel_threshold > 0 only) its value is >= rel_threshold * max(row) (the maximum over the non-NaN values) and its
+ * distance to every accepted peak is >= min_separation; stop at K accepted peaks.  Distance in fp64, exactly:
+ * r = |doa[i] - doa[j]| on a linear grid, min(r, 2 pi - r) on a circular one.  For K = 1 and a row without NaN, index[b][0] is
+ * the first maximum (np.argmax) on every grid kind.
+ * Outputs index [B][K] int32 and value [B][K] (may be NULL): the accepted peaks in selection order, unfilled slots -1 and NaN.
+ * Supported: 1 <= G <= 4096, 1 <= K <= 16, min_separation >= 0, rel_threshold >= 0 (MICLOC_ERR_INVALID otherwise, checked
+ * before any device work).  Device buffers; one wave per row, no atomics, no host synchronisation (graph-capturable). */
+#define MICLOC_GRID_LINEAR 0
+#define MICLOC_GRID_CIRCULAR 1
+#define MICLOC_GRID_CIRCULAR_CLOSED 2
+int micloc_doa_peaks_f64(const double *power, int B, int G, const double *doa_list, int grid_kind, int K, double min_separation,
+                         double rel_threshold, int32_t *index, double *value, void *stream);
 
 /* Moving-target tracking: Envelope.evolve (micloc/utils.py:36-81) on the beamformer output and the per-time-step arg-max over the DoA
  * grid, `doa_index = np.argmax(sig_bf_env, axis=1)` (paper_plots/target_snn_localization.py:599-622), without the T x G array ever
