@@ -64,16 +64,25 @@ class Beamformer:
         y = plan.beamformer_pipeline(x, want_y=True, want_power=False)["y"][0]
         return runtime.to_host(y) if to_host else y
 
-    def localize_batch(self, bf_mat, sig_batch, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
+    def localize_batch(self, bf_mat, sig_batch, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0, window=None,
+                       hop=None):
         """sig_batch [B, T, M] -> dict of device tensors: power [B, G], argmax [B] (int32); with num_sources=K (and doa_list [G],
-        the DoAs of bf_mat's columns) also peaks [B, K] int32 and peak_power [B, K] (utils.find_doa_peaks)."""
-        from .utils import _add_peaks
+        the DoAs of bf_mat's columns) also peaks [B, K] int32 and peak_power [B, K] (utils.find_doa_peaks).
+        window=N frames (hop defaults to it; multiples of plan().window_quantum(), ValueError otherwise): also window_power
+        [B, nW, G] (mean |y|^2 over each window of utils.window_bounds), window_argmax [B, nW], window_start [nW] (frames, host) and,
+        with num_sources, window_peaks / window_peak_power [B, nW, K]."""
+        from .utils import _add_peaks, _add_window_peaks, window_bounds
 
         B, T, M = sig_batch.shape
         if bf_mat.shape[0] != M:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {bf_mat.shape[0]}!")
         plan = self.plan()
         plan.set_bf_mat(np.asarray(bf_mat, dtype=np.complex128))
+        if window is not None:
+            out = plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True, window=window, hop=hop)
+            out["window_start"] = window_bounds(T, window, hop)[0]
+            return _add_window_peaks(_add_peaks(out, doa_list, num_sources, min_separation, rel_threshold), doa_list, num_sources,
+                                     min_separation, rel_threshold)
         return _add_peaks(plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True), doa_list, num_sources, min_separation,
                           rel_threshold)
 

@@ -143,6 +143,48 @@ bool bad_ws(const void *ws, size_t have, size_t need)
     return ws == nullptr || have < need || (reinterpret_cast<uintptr_t>(ws) & 255) != 0;
 }
 
+// ---- windowed read-out (windows.hip) ----------------------------------------------------------------------------------
+// Frames per row of partial sums of the kernel family beamform_nchunks_ct describes (the general kernel): the largest T that is one chunk.
+int gen_chunk_frames(int CT)
+{
+    for (int c = 256; c <= 4096; c += 256)
+        if (beamform_nchunks_ct(c, CT) == 1 && beamform_nchunks_ct(c + 1, CT) == 2) return c;
+    return 0;
+}
+
+// The chunk length of the power-only launch that serves this plan and bf_mat: launch_lif_beamform (real bf_mat) or
+// launch_planar_beamform with complex output pairs.  The latter takes its bf_mat-stationary kernel (256-frame chunks, the finest
+// chunking of any kernel: see beamform_partial_bytes) for one channel tile -- a complex table always has an even number of DoA
+// tiles -- and the general kernel otherwise.  window_readout() checks the result against the nchunks the launch reports.
+int window_quantum(const micloc_plan *p)
+{
+    if (!p->W_is_complex) return lif_beamform_chunk_frames(p->W, p->ntab);
+    if (p->W.CT == 1 && (p->W.GT & 1) == 0) return 256;
+    return gen_chunk_frames(p->W.CT);
+}
+
+// MICLOC_OK and *nW, or the status of the window rule's argument errors
+int window_args(int T, int window, int hop, int quantum, int B, int *nW)
+{
+    if (T < 1 || quantum < 1) return MICLOC_ERR_INVALID;
+    if (window < 1 || hop < 1 || window % quantum != 0 || hop % quantum != 0) return MICLOC_ERR_SHAPE;
+    const long long n = window_count(T, window, hop);
+    if (n * (long long)B > 0x7fffffffll) return MICLOC_ERR_SHAPE;
+    *nW = (int)n;
+    return MICLOC_OK;
+}
+
+// both read-outs of one buffer of partial sums: the windows, and (on request) the ordinary whole-recording power / arg-max
+int window_readout(const micloc_plan *p, const double *partial, int B, int T, int nch, int quantum, int window, int hop, double *power_w,
+                   int32_t *argmax_w, double *power, int32_t *argmax, hipStream_t st)
+{
+    if (nch != (T + quantum - 1) / quantum) return MICLOC_ERR_INVALID;  // the launch chose a kernel window_quantum() does not describe
+    const int Gp = 16 * p->W.GT, cp = p->W_is_complex ? 1 : 0;
+    HIP_TRY(launch_window_power(partial, B, T, nch, Gp, p->G_out, cp, cp ? Gp / 2 : 0, quantum, window, hop, power_w, argmax_w, st));
+    if (power || argmax) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, cp, cp ? Gp / 2 : 0, power, argmax, st));
+    return MICLOC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -526,6 +568,123 @@ int micloc_beamformer_pipeline_f64(const micloc_plan *p, const double *x, int B,
     HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, y, 1, partial, st, &nch));
     if (want_power) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 1, Gp / 2, power, argmax, st));
     return MICLOC_OK;
+}
+
+// ---- time-resolved DoA: power and arg-max per window ------------------------------------------------------------------
+int micloc_window_quantum(const micloc_plan *p)
+{
+    if (!p) return MICLOC_ERR_INVALID;
+    if (!p->d_W || (!p->W_is_complex && !p->d_ntab)) return MICLOC_ERR_NOT_SET;
+    const int q = window_quantum(p);
+    return q > 0 ? q : MICLOC_ERR_INVALID;
+}
+
+int micloc_window_count(int T, int window, int hop, int quantum)
+{
+    int nW = 0;
+    const int rc = window_args(T, window, hop, quantum, 1, &nW);
+    return rc == MICLOC_OK ? nW : rc;
+}
+
+size_t micloc_window_workspace_bytes(const micloc_plan *p, int B, int T, int window, int hop, int pipeline)
+{
+    if (!p || bad_batch(B) || T < 1 || micloc_window_quantum(p) < 1) return 0;
+    int nW = 0;
+    if (window_args(T, window, hop, window_quantum(p), B, &nW) != MICLOC_OK) return 0;
+    return pipeline ? ws_layout(p, B, T).total : align256(beamform_partial_bytes(B, T, 16 * p->W.GT));
+}
+
+int micloc_lif_beamform_windows_f64(const micloc_plan *p, const int8_t *spikes, int B, int T, int window, int hop, double *power_w,
+                                    int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!p || !spikes || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
+    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int q = window_quantum(p);
+    int nW = 0;
+    const int rc = window_args(T, window, hop, q, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
+    double *partial = reinterpret_cast<double *>(ws);
+    int nch = 0;
+    HIP_TRY(launch_lif_beamform(p->W, p->ntab, spikes, B, T, nullptr, partial, (hipStream_t)stream, &nch));
+    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, (hipStream_t)stream);
+}
+
+int micloc_beamform_c128_windows_f64(const micloc_plan *p, const double *pre, int B, int T, int Ts, int window, int hop, double *power_w,
+                                     int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!p || !pre || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
+    if (!p->d_W) return MICLOC_ERR_NOT_SET;
+    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int q = window_quantum(p);
+    int nW = 0;
+    const int rc = window_args(T, window, hop, q, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
+    double *partial = reinterpret_cast<double *>(ws);
+    int nch = 0;
+    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, nullptr, 1, partial, (hipStream_t)stream, &nch));
+    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, (hipStream_t)stream);
+}
+
+int micloc_snn_pipeline_windows_f64(const micloc_plan *p, const double *x, int B, int T, int window, int hop, int8_t *spikes,
+                                    double *power_w, int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                    void *stream)
+{
+    if (!p || !x || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
+    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int q = window_quantum(p);
+    int nW = 0;
+    const int rc = window_args(T, window, hop, q, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    const WsLayout w = ws_layout(p, B, T);
+    if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
+    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
+    double *h = reinterpret_cast<double *>(base + w.h);
+    int8_t *spk = spikes ? spikes : reinterpret_cast<int8_t *>(base + w.spikes);
+    const int Ts = micloc_padded_T(T);
+    hipStream_t st = (hipStream_t)stream;
+    // the launches of micloc_snn_pipeline_f64, then both read-outs of its partial sums
+    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
+    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, nullptr, spk, base + w.scratch, st, x,
+                                 p->M, p->taps.shift, p->chunk_frames, RZ_PHASE_ALL));
+    double *partial = reinterpret_cast<double *>(base + w.partial);
+    int nch = 0;
+    HIP_TRY(launch_lif_beamform(p->W, p->ntab, spk, B, T, nullptr, partial, st, &nch));
+    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, st);
+}
+
+int micloc_beamformer_pipeline_windows_f64(const micloc_plan *p, const double *x, int B, int T, int window, int hop, double *power_w,
+                                           int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!p || !x || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (!p->d_W) return MICLOC_ERR_NOT_SET;
+    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int q = window_quantum(p);
+    int nW = 0;
+    const int rc = window_args(T, window, hop, q, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    const WsLayout w = ws_layout(p, B, T);
+    if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
+    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
+    double *h = reinterpret_cast<double *>(base + w.h);
+    double *pre = reinterpret_cast<double *>(base + w.pre);
+    const int Ts = micloc_padded_T(T);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
+    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, pre, nullptr, nullptr, st, x, p->M,
+                                 p->taps.shift));
+    double *partial = reinterpret_cast<double *>(base + w.partial);
+    int nch = 0;
+    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, nullptr, 1, partial, st, &nch));
+    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, st);
 }
 
 // ---- streaming: the band-pass / RZCC stage tile by tile, exact state hand-off -----------------------------------

@@ -129,6 +129,14 @@ int beamform_nchunks(int T);
 int beamform_nchunks_ct(int T, int CT);  // chunking of the kernel family that serves CT channel tiles
 int lif_beamform_chunk_frames(const BeamformW &W, const NeuronTab &nt);  // frames per chunk of the kernel launch_lif_beamform picks (power only)
 
+// ---- windowed read-out of the partial sums (windows.hip) -----------------------------------------------------------
+// windows of the rule in include/micloc_hip.h: 1 if T <= window, else 1 + ceil((T - window) / hop)
+long long window_count(int T, int window, int hop);
+// partial [B][nchunks][Gp] with chunk_frames frames per row -> power_w [B][nW][G], argmax_w [B][nW] (either may be NULL);
+// window and hop must be multiples of chunk_frames (hipErrorInvalidValue otherwise: the API checks first)
+hipError_t launch_window_power(const double *partial, int B, int T, int nchunks, int Gp, int G, int complex_pairs, int Ghalf_pad,
+                               int chunk_frames, int window, int hop, double *power_w, int32_t *argmax_w, hipStream_t stream);
+
 // fp32-MFMA variant of LIF + beamforming + power (up to 64 channels, bf_mat must fit in LDS)
 hipError_t launch_lif_beamform_f32(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T,
                                    double *partial, hipStream_t stream, int *nchunks);

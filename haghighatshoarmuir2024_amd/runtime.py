@@ -169,6 +169,39 @@ class Plan:
     def padded_T(self, T):
         return self.lib.micloc_padded_T(T)
 
+    # ---- time-resolved read-out (the window rule of include/micloc_hip.h) -----------------------------------
+    def window_quantum(self):
+        """Frames that `window` and `hop` must be multiples of: the chunk length of the beamforming kernel that serves this plan and
+        its bf_mat (micloc_window_quantum; needs bf_mat and, for a real one, the neuron kernel)."""
+        q = self.lib.micloc_window_quantum(self.handle)
+        if q <= 0:
+            _lib.check(q, "window_quantum")
+        return q
+
+    def window_count(self, T, window, hop=None):
+        """(nW, window, hop) of the rule for this plan; ValueError -- naming the quantum -- for a window or hop that does not fit it."""
+        window = int(window)
+        hop = window if hop is None else int(hop)
+        q = self.window_quantum()
+        if window < 1 or hop < 1 or window % q or hop % q:
+            raise ValueError(f"window ({window}) and hop ({hop}) must be positive multiples of the plan's window quantum, {q} frames")
+        nW = self.lib.micloc_window_count(int(T), window, hop, q)
+        if nW <= 0:
+            _lib.check(nW, "window_count")
+        return nW, window, hop
+
+    def _window_out(self, B, T, window, hop, out):
+        torch = _torch()
+        nW, window, hop = self.window_count(T, window, hop)
+        if B * nW > 0x7FFFFFFF:
+            raise ValueError(f"{B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
+        if out.get("window_power") is None:
+            out["window_power"] = torch.empty((B, nW, self.G), dtype=torch.float64, device=self.device)
+            out["window_argmax"] = torch.empty((B, nW), dtype=torch.int32, device=self.device)
+        if tuple(out["window_power"].shape) != (B, nW, self.G) or tuple(out["window_argmax"].shape) != (B, nW):
+            raise ValueError("out holds window tensors of another shape")
+        return window, hop
+
     # ---- helpers -----------------------------------------------------------------------------------
     def to_device(self, x):
         """numpy / torch [B, T, M] float64 -> contiguous device tensor."""
@@ -182,8 +215,10 @@ class Plan:
         return x.contiguous()
 
     # ---- pipelines -----------------------------------------------------------------------------------
-    def snn_pipeline(self, x, want_spikes=False, want_y=False, want_power=True, stages=7, out=None):
+    def snn_pipeline(self, x, want_spikes=False, want_y=False, want_power=True, stages=7, out=None, window=None, hop=None):
         """x: device tensor [B, T, M]. Returns dict of device tensors (spikes int8, y, power, argmax).
+        `window` (frames; `hop` defaults to it; multiples of window_quantum()): also window_power [B, nW, G] and window_argmax [B, nW],
+        the power and arg-max per window of the rule in include/micloc_hip.h, from the same beamforming launch (whole pipeline, no y).
         `stages` (MICLOC_STAGE_* bits: 1 STHT, 2 band-pass + RZCC, 4 LIF + beamforming + power; 8 / 16: only the serial scan of a
         chunked band-pass + RZCC stage / the stage without it) launches a part of the pipeline; the parts of one batch share this
         plan's workspace and, via `out`, the output tensors."""
@@ -198,6 +233,17 @@ class Plan:
                        power=torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None,
                        argmax=torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None)
         ws, nbytes = self.workspace(B, T)
+        if window is not None:
+            if out["y"] is not None or int(stages) != 7:
+                raise ValueError("the windowed read-out runs the whole pipeline and has no T x G output (want_y=False, stages=7)")
+            window, hop = self._window_out(B, T, window, hop, out)
+            _lib.check(
+                self.lib.micloc_snn_pipeline_windows_f64(self.handle, _ptr(x), B, T, window, hop, _ptr(out["spikes"]), _ptr(out["window_power"]),
+                                                          _ptr(out["window_argmax"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws), nbytes,
+                                                          _stream(self.device)),
+                "snn_pipeline_windows",
+            )
+            return out
         _lib.check(
             self.lib.micloc_snn_pipeline_stages_f64(self.handle, _ptr(x), B, T, _ptr(out["spikes"]), _ptr(out["y"]), _ptr(out["power"]),
                                                      _ptr(out["argmax"]), _ptr(ws), nbytes, _stream(self.device), int(stages)),
@@ -250,7 +296,8 @@ class Plan:
         )
         return dict(spikes=spikes, cov=cov, power=power, argmax=argmax)
 
-    def beamformer_pipeline(self, x, want_y=False, want_power=True):
+    def beamformer_pipeline(self, x, want_y=False, want_power=True, window=None, hop=None):
+        """The complex Beamformer's pipeline; `window` / `hop` as in snn_pipeline (power per window = mean |y|^2 over its frames)."""
         torch = _torch()
         B, T, M = x.shape
         if M != self.num_mic:
@@ -260,6 +307,18 @@ class Plan:
         power = torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None
         argmax = torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None
         ws, nbytes = self.workspace(B, T)
+        if window is not None:
+            if want_y:
+                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
+            out = dict(y=None, power=power, argmax=argmax)
+            window, hop = self._window_out(B, T, window, hop, out)
+            _lib.check(
+                self.lib.micloc_beamformer_pipeline_windows_f64(self.handle, _ptr(x), B, T, window, hop, _ptr(out["window_power"]),
+                                                                 _ptr(out["window_argmax"]), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
+                                                                 _stream(self.device)),
+                "beamformer_pipeline_windows",
+            )
+            return out
         _lib.check(
             self.lib.micloc_beamformer_pipeline_f64(self.handle, _ptr(x), B, T, _ptr(y), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
                                                      _stream(self.device)),
@@ -267,9 +326,10 @@ class Plan:
         )
         return dict(y=y, power=power, argmax=argmax)
 
-    def beamform_c128(self, pre, T, want_y=False, want_power=True, out=None):
+    def beamform_c128(self, pre, T, want_y=False, want_power=True, out=None, window=None, hop=None):
         """The contraction stage of the complex Beamformer alone (micloc_beamform_c128_f64): planar band-passed rows
-        pre [B, 2M, Ts] -> y [B, T, G] complex128 and / or power [B, G], argmax [B].  `out` reuses a previous result dict."""
+        pre [B, 2M, Ts] -> y [B, T, G] complex128 and / or power [B, G], argmax [B].  `out` reuses a previous result dict.
+        `window` / `hop`: also window_power / window_argmax (micloc_beamform_c128_windows_f64; no y)."""
         torch = _torch()
         B, C, Ts = pre.shape
         G = self.G
@@ -279,6 +339,14 @@ class Plan:
                        argmax=torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None)
         nbytes = self.lib.micloc_lif_beamform_workspace_bytes(self.handle, B, T)
         ws = self.ws.get(nbytes)
+        if window is not None:
+            if out["y"] is not None:
+                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
+            window, hop = self._window_out(B, T, window, hop, out)
+            _lib.check(self.lib.micloc_beamform_c128_windows_f64(self.handle, _ptr(pre), B, T, Ts, window, hop, _ptr(out["window_power"]),
+                                                                 _ptr(out["window_argmax"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws),
+                                                                 nbytes, _stream(self.device)), "beamform_c128_windows")
+            return out
         _lib.check(self.lib.micloc_beamform_c128_f64(self.handle, _ptr(pre), B, T, Ts, _ptr(out["y"]), _ptr(out["power"]), _ptr(out["argmax"]),
                                                      _ptr(ws), nbytes, _stream(self.device)), "beamform_c128")
         return out
@@ -302,7 +370,7 @@ class Plan:
                                                      _stream(self.device)), "bandpass_rzcc")
         return pre, spikes
 
-    def lif_beamform(self, spikes, want_y=False, want_power=True):
+    def lif_beamform(self, spikes, want_y=False, want_power=True, window=None, hop=None):
         torch = _torch()
         B, T, C = spikes.shape
         G = self.G
@@ -310,6 +378,15 @@ class Plan:
         power = torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None
         argmax = torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None
         ws, nbytes = self.workspace(B, T)
+        if window is not None:
+            if want_y:
+                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
+            out = dict(y=None, power=power, argmax=argmax)
+            window, hop = self._window_out(B, T, window, hop, out)
+            _lib.check(self.lib.micloc_lif_beamform_windows_f64(self.handle, _ptr(spikes), B, T, window, hop, _ptr(out["window_power"]),
+                                                                _ptr(out["window_argmax"]), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
+                                                                _stream(self.device)), "lif_beamform_windows")
+            return out
         _lib.check(self.lib.micloc_lif_beamform_f64(self.handle, _ptr(spikes), B, T, _ptr(y), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
                                                     _stream(self.device)), "lif_beamform")
         return dict(y=y, power=power, argmax=argmax)

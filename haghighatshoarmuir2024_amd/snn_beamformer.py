@@ -159,12 +159,15 @@ class SNNBeamformer:
 
     # ---- batched device entry points (not in the reference) --------------------------------------------------
     def localize_batch(self, bf_mat, sig_batch, time_vec=None, return_spikes=False, power_mode="direct", num_sources=None, doa_list=None,
-                       min_separation=None, rel_threshold=0.0):
+                       min_separation=None, rel_threshold=0.0, window=None, hop=None):
         """sig_batch [B, T, M] (numpy or device tensor, already on the fs grid) -> dict of device tensors:
         power [B, G] = mean_t |apply_to_signal|^2, argmax [B] (int32), optionally spikes [B, T, 2M] int8.
         num_sources=K (with doa_list [G], the DoAs of bf_mat's columns): also peaks [B, K] int32 and peak_power [B, K], the K
-        strongest sources (utils.find_doa_peaks with min_separation and rel_threshold)."""
-        from .utils import _add_peaks
+        strongest sources (utils.find_doa_peaks with min_separation and rel_threshold).
+        window=N frames (hop defaults to it; multiples of plan().window_quantum(), ValueError otherwise): the time-resolved read-out
+        of utils.window_bounds -- window_power [B, nW, G], window_argmax [B, nW] and window_start [nW] (frames, host), with
+        num_sources also window_peaks / window_peak_power [B, nW, K] -- from the same beamforming launch, no T x G array."""
+        from .utils import _add_peaks, _add_window_peaks, window_bounds
 
         B, T, M = sig_batch.shape
         if bf_mat.shape[0] // 2 != M:
@@ -175,12 +178,19 @@ class SNNBeamformer:
         plan.set_neuron_kernel(neuron_impulse_response(time_vec, self.tau_vec))
         plan.set_bf_mat(np.asarray(bf_mat, dtype=np.float64))
         x = plan.to_device(sig_batch)
+        if power_mode == "covariance" and window is not None:
+            raise ValueError("the windowed read-out needs power_mode='direct' (the covariance form has no per-chunk sums)")
         if power_mode == "covariance":
             # algebraically identical variant: w^T (V^T V / T) w instead of mean_t (V w)^2  
             return _add_peaks(plan.snn_pipeline_cov(x, want_spikes=return_spikes, want_power=True), doa_list, num_sources, min_separation,
                               rel_threshold)
         if power_mode != "direct":
             raise ValueError("power_mode must be 'direct' or 'covariance'")
+        if window is not None:
+            out = plan.snn_pipeline(x, want_spikes=return_spikes, want_power=True, window=window, hop=hop)
+            out["window_start"] = window_bounds(T, window, hop)[0]
+            return _add_window_peaks(_add_peaks(out, doa_list, num_sources, min_separation, rel_threshold), doa_list, num_sources,
+                                     min_separation, rel_threshold)
         return _add_peaks(plan.snn_pipeline(x, want_spikes=return_spikes, want_power=True), doa_list, num_sources, min_separation, rel_threshold)
 
     def membrane_covariance_batch(self, sig_batch, time_vec=None, t_start=0, out=None):

@@ -13,7 +13,8 @@ throughput mode  DoAs from a seeded host generator, clean array signals synthesi
 Sweeps: noisy_target_sweep (target_snn_localization.py:435-467), speech_target_sweep (:213-245), xylo_target_sweep
 (target_xylo_localization.py:540-608; integer-LIF stage parity-unpinned), music_noisy_sweep / music_speech_sweep (the MUSIC twins,
 target_localization_MUSIC.py), multi_target_sweep (K simultaneous targets, the statistical counterpart of
-paper_plots/multiple_targets_*.py: K peaks per trial, matched errors and resolution rate).
+paper_plots/multiple_targets_*.py: K peaks per trial, matched errors and resolution rate), windowed_target_sweep (the noisy-target
+sweep with the time-resolved read-out: one estimate per window of every trial).
 """
 import numpy as np
 
@@ -192,15 +193,23 @@ def sharded_design(design_fn, doa_list, rank=0, world_size=1, group=None):
     return flat["cols"].reshape(G, rows).T.copy()
 
 
-def device_localizer(beamf, bf_mat, max_batch=1100, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
+def device_localizer(beamf, bf_mat, max_batch=1100, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0, window=None,
+                     hop=None):
     """Default localizer: the HIP pipeline (power + arg-max, no T x G temporary).  With num_sources=K (and doa_list) it returns the
-    multi-source read-out instead: (peaks [B, K] int64, peak_power [B, K]) (multi_target_sweep)."""
+    multi-source read-out instead: (peaks [B, K] int64, peak_power [B, K]) (multi_target_sweep); with window=N (and hop) the
+    time-resolved one: (window_argmax [B, nW] int64, the power at it [B, nW]) (windowed_target_sweep)."""
 
     def run(sig_batch, time_vec):
         am, pm = [], []
         for s in range(0, len(sig_batch), max_batch):
             # (the non-spiking complex Beamformer has no neuron kernel, hence no time axis to pass: ref:paper_plots/target_localization.py)
             kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
+            if window is not None:
+                out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], window=window, hop=hop, **kw)
+                a = out["window_argmax"].long()
+                am.append(a.cpu().numpy())
+                pm.append(out["window_power"].gather(2, a.unsqueeze(2)).squeeze(2).cpu().numpy())
+                continue
             if num_sources is not None:
                 out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], num_sources=num_sources, doa_list=doa_list,
                                            min_separation=min_separation, rel_threshold=rel_threshold, **kw)
@@ -845,6 +854,148 @@ def multi_target_sweep(beamf, bf_mat, doa_list, num_targets=2, min_separation=np
     return res
 
 
+class WindowShardStore(ShardStore):
+    """ShardStore of windowed_target_sweep: a record holds one arg-max and its power per window of the trial."""
+
+    def __init__(self, out_dir, sweep, total, num_windows, **key):
+        nW = int(num_windows)
+        self.REC = np.dtype([("trial", "<i8"), ("doa", "<f8"), ("index", "<i8", (nW,)), ("pmax", "<f8", (nW,))])
+        super().__init__(out_dir, sweep, total, record_width=nW, **key)
+
+
+def median_window_index(doa_list, index):
+    """The median-over-windows estimate of every trial: index [N, nW] -> [N], the window estimate with the least summed pi-periodic
+    error (doa_error, the sweep's metric) to the trial's other window estimates -- the median of a sample on the half circle, where
+    sorting has no meaning at the seam; ties go to the earlier window.  One window: that window's estimate."""
+    doa_list = np.asarray(doa_list, dtype=np.float64)
+    index = np.asarray(index, dtype=np.int64)
+    est = doa_list[index]  # [N, nW]
+    cost = np.zeros(est.shape)
+    for m in range(est.shape[1]):
+        cost += doa_error(est, est[:, m : m + 1])
+    return index[np.arange(len(index)), np.argmin(cost, axis=1)]
+
+
+def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0,
+                          world_size=1, group=None, freq_design=2000.0, test_duration=100e-3, snr_gain_due_to_bandwidth=None,
+                          localizer=None, batch_trials=1100, out_dir=None, store_key=None):
+    """The noisy-target sweep with the time-resolved read-out: the trials of noisy_target_sweep (the same draws in both modes),
+    every one localised per window of `window` frames every `hop` frames (default: `window`; utils.window_bounds, hop <= window so
+    that every window holds frames; the device wants multiples of plan().window_quantum()).
+    `localizer(sig_batch, time_vec) -> (index [B, nW], value [B, nW])` replaces the device pipeline (default: device_localizer with
+    window / hop).  Returns dict(doa [num_snr, num_sim]; window_argmax, window_pmax, window_err [num_snr, num_sim, nW];
+    window_mae_deg [num_snr, nW], the MAE per SNR and window; window_start [nW]; and of the median-over-windows estimate
+    (median_window_index) argmax, pmax (the power of the window that gave it), err [num_snr, num_sim] and mae_deg [num_snr]).  With
+    window >= T there is one window and argmax, pmax, err, mae_deg are noisy_target_sweep's, bit for bit.
+    Sharding, the one exchange and out_dir resume as noisy_target_sweep; the ShardStore key also covers window, hop, the record
+    width nW and the method's parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer)."""
+    from .utils import window_bounds
+
+    if mode not in ("parity", "throughput"):
+        raise ValueError("mode must be 'parity' or 'throughput'")
+    window = int(window)
+    hop = window if hop is None else int(hop)
+    if window < 1 or hop < 1:
+        raise ValueError("window and hop must be at least 1 frame")
+    if hop > window:
+        raise ValueError("the windowed sweep needs hop <= window (a window past the recording would hold no frame)")
+    doa_list = np.asarray(doa_list, dtype=np.float64)
+    fs = beamf.fs
+    M = len(beamf.geometry)
+    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    if snr_gain_due_to_bandwidth is None:
+        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
+    time_test = np.arange(0, test_duration, step=1 / fs)
+    sig_test = np.sin(2 * np.pi * freq_design * time_test)
+    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    total = len(snr_trial)
+    T = len(np.arange(time_test.min(), time_test.max(), step=1 / fs))
+    start, _ = window_bounds(T, window, hop)
+    nW = len(start)
+    lo, hi = shard_range(total, rank, world_size)
+    store = None
+    if out_dir is not None:
+        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
+        key.update(_method_key(beamf))
+        key.update(store_key or {})
+        store = WindowShardStore(out_dir, "windowed-noisy", total, nW, window=window, hop=hop, seed=int(seed), mode=mode, snr_db_trial=snr_trial,
+                                 doa_list=doa_list, time_test=time_test, sig_test=sig_test, fs=float(fs), num_mic=M,
+                                 r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
+                                 theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
+    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
+    if localizer is None:
+        localizer = device_localizer(beamf, bf_mat, max_batch=batch_trials, window=window, hop=hop)
+    doa_all = np.zeros(total)
+    index = np.zeros((hi - lo, nW), dtype=np.int64)
+    value = np.zeros((hi - lo, nW))
+    if store is not None:
+        index[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
+        value[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
+
+    def flush(sig_batch, time_in, trials):
+        trials = np.asarray(trials, dtype=np.int64)
+        a, p = localizer(sig_batch, time_in)
+        a = np.asarray(a, dtype=np.int64).reshape(len(trials), nW)
+        p = np.asarray(p, dtype=np.float64).reshape(len(trials), nW)
+        index[trials - lo], value[trials - lo] = a, p
+        if store is not None:
+            store.put(trials, doa_all[trials], a, p)
+
+    if mode == "parity":
+        # noisy_target_sweep's replay of the reference's global MT19937 stream (_template_sweep)
+        np.random.seed(seed)
+        sigs, ids, time_in = [], [], None
+        for trial in range(total):
+            doa = np.random.rand(1)[0] * 2 * np.pi
+            doa_all[trial] = doa
+            if lo <= trial < hi and not done[trial]:
+                time_in, sig = synthesize_array_signal(beamf.geometry, fs, time_test, sig_test, doa)
+                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
+                sigs.append(sig)
+                ids.append(trial)
+                if len(sigs) == batch_trials:
+                    flush(np.stack(sigs), time_in, ids)
+                    sigs, ids = [], []
+            else:
+                np.random.randn(T, M)  # keep the stream aligned
+        if sigs:
+            flush(np.stack(sigs), time_in, ids)
+    else:
+        from . import synthesis
+
+        rng = np.random.RandomState(seed)
+        doa_all[:] = rng.rand(total) * 2 * np.pi
+        for s0 in range(lo, hi, batch_trials):
+            s1 = min(hi, s0 + batch_trials)
+            if done[s0:s1].all():
+                continue
+            # device synthesis + Philox noise numbered by global trial, as noisy_target_sweep's throughput mode (the same bits)
+            time_in, x = beamf.synthesize_batch((time_test, sig_test), doa_all[s0:s1])
+            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
+            flush(x, time_in, np.arange(s0, s1))
+
+    # the one exchange step: nW index columns and nW value columns in ONE all-gather
+    exchange = {}
+    local = {f"index{n}": np.ascontiguousarray(index[:, n]) for n in range(nW)}
+    local.update({f"value{n}": np.ascontiguousarray(value[:, n]) for n in range(nW)})
+    full = gather_shards(local, total, rank, world_size, group, stats=exchange)
+    w_index = np.stack([full[f"index{n}"] for n in range(nW)], axis=1)
+    w_value = np.stack([full[f"value{n}"] for n in range(nW)], axis=1)
+    w_err = doa_error(doa_list[w_index], doa_all[:, None])
+    med = median_window_index(doa_list, w_index)
+    med_window = np.argmax(w_index == med[:, None], axis=1)  # (the first window that gave the median estimate)
+    err = doa_error(doa_list[med], doa_all)
+    S = total // num_sim
+    shape = (S, num_sim)
+    res = dict(doa=doa_all.reshape(shape), window_argmax=w_index.reshape(S, num_sim, nW), window_pmax=w_value.reshape(S, num_sim, nW),
+               window_err=w_err.reshape(S, num_sim, nW), window_mae_deg=np.mean(w_err.reshape(S, num_sim, nW), axis=1) * 180 / np.pi,
+               window_start=start, argmax=med.reshape(shape), pmax=w_value[np.arange(total), med_window].reshape(shape), err=err.reshape(shape),
+               mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, snr_db_vec=snr_db_vec, exchange=exchange)
+    if store is not None:
+        res["persistence"] = store.stats()
+    return res
+
+
 def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world):
     """--sweep multi-noisy: multi_target_sweep with the noisy sweep's SNN or complex beamformer (design as --sweep noisy) or the MUSIC
     noisy sweep's MUSIC (1 s test signal, band [0.8, 1.2] x freq_design, k = 1, N = 2048)."""
@@ -881,14 +1032,16 @@ def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau,
 
 
 def main(argv=None):
-    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy]`: the accuracy sweeps of the paper scripts
+    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy]`: the accuracy sweeps of the paper scripts
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
     import os
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy"], default="noisy")
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy"], default="noisy")
+    ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
+    ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
     ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy: the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
@@ -959,6 +1112,11 @@ def main(argv=None):
             else:
                 ap.error("--sweep speech needs --flac or --pcm-npz")
             res = speech_target_sweep(beamf, bf_mat, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+        elif args.sweep == "windowed-noisy":
+            if args.window_frames is None:
+                ap.error("--sweep windowed-noisy needs --window-frames")
+            res = windowed_target_sweep(beamf, bf_mat, doa_list, args.window_frames, hop=args.hop_frames, num_sim=args.num_sim or 100, seed=args.seed,
+                                        mode=args.mode, rank=rank, world_size=world)
         else:
             res = noisy_target_sweep(beamf, bf_mat, doa_list, num_sim=args.num_sim or 100, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
     if rank == 0:
@@ -966,6 +1124,9 @@ def main(argv=None):
         print(f"Mean aboslute errors: {res['mae_deg']}")
         if "resolved_rate" in res:
             print(f"Resolution rate: {res['resolved_rate']}")
+        if "window_mae_deg" in res:
+            print(f"Window starts (frames): {res['window_start']}")
+            print(f"Mean aboslute errors per window:\n{res['window_mae_deg']}")
     if world > 1:
         dist.destroy_process_group()
 

@@ -137,6 +137,42 @@ def find_doa_peaks(power, doa_list, num_sources, min_separation=None, rel_thresh
     return idx.cpu().numpy(), val.cpu().numpy()
 
 
+def window_bounds(T, window, hop=None):
+    """The window rule of the time-resolved read-out (include/micloc_hip.h), stated once for Python: frames `window` long starting
+    every `hop` frames (default: `window`), window n = [n hop, min(n hop + window, T)); one window if T <= window, otherwise
+    1 + ceil((T - window) / hop).  Returns (start, stop) int64 arrays [nW]: window n is the frames start[n] : stop[n].  With
+    hop > window the last window of the formula can start at or after T; it is empty (stop == start).  The device additionally
+    wants window and hop to be multiples of the plan's window quantum (runtime.Plan.window_quantum)."""
+    T, window = int(T), int(window)
+    hop = window if hop is None else int(hop)
+    if T < 1 or window < 1 or hop < 1:
+        raise ValueError("T, window and hop must be at least 1")
+    nW = 1 if T <= window else 1 + -(-(T - window) // hop)
+    start = np.arange(nW, dtype=np.int64) * hop
+    stop = np.maximum(np.minimum(start + window, T), start)
+    return start, stop
+
+
+def _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold):
+    """localize_batch's multi-source read-out per window: window_peaks [B, nW, K] int32 and window_peak_power [B, nW, K] from the
+    B nW rows of out["window_power"] (find_doa_peaks, at most 65535 rows per launch)."""
+    if num_sources is None:
+        return out
+    if doa_list is None:
+        raise ValueError("num_sources needs the DoA grid of bf_mat's columns (doa_list=)")
+    from . import runtime
+
+    torch = runtime._torch()
+    wp = out["window_power"]
+    B, nW, G = wp.shape
+    rows = wp.reshape(B * nW, G)
+    parts = [find_doa_peaks(rows[r : r + 65535], doa_list, num_sources, min_separation=min_separation, rel_threshold=rel_threshold)
+             for r in range(0, B * nW, 65535)]
+    out["window_peaks"] = torch.cat([p[0] for p in parts]).reshape(B, nW, -1)
+    out["window_peak_power"] = torch.cat([p[1] for p in parts]).reshape(B, nW, -1)
+    return out
+
+
 def _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold):
     """localize_batch's optional multi-source read-out: out["peaks"] [B, K] int32 and out["peak_power"] [B, K] from out["power"]."""
     if num_sources is None:

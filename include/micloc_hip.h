@@ -442,6 +442,46 @@ int micloc_envelope_track_f64(const double *y, int B, int T, int G, double a_ris
 int micloc_envelope_track_any(const void *y, int kind, int B, int T, int G, double a_rise, double i_rise, double a_fall, double *env, int32_t *index,
                               void *stream);
 
+/* ---- time-resolved DoA: power and arg-max per window ------------------------------------------ */
+/* The read-outs above reduce a whole recording to one power row per trial.  These entries keep the time axis: power and
+ * arg-max per WINDOW of frames, read from the per-chunk partial sums the beamforming kernels already write -- no T x G array.
+ * The window rule:
+ *   - `window` and `hop` are in frames, both >= 1, and both multiples of the plan's window QUANTUM: the chunk length (frames
+ *     per row of partial sums) of the beamforming kernel that serves this plan and bf_mat (micloc_window_quantum; 256 up to 64
+ *     channels, 512 beyond);
+ *   - window n starts at s_n = n hop; there are nW = 1 windows if T <= window, else nW = 1 + ceil((T - window) / hop);
+ *   - window n covers the frames [s_n, min(s_n + window, T));
+ *   - power_w[b][n][g] is `power` restricted to those frames and divided by the window's own frame count: sum y^2 for the real
+ *     (SNN) bf_mat, sum |y|^2 = sum re^2 + sum im^2 for the complex Beamformer;
+ *   - argmax_w[b][n] is the first maximum of the row; a NaN never wins (a row of NaNs gives 0).
+ * With hop > window the last window of the formula can start at or after T; it holds no frame, its power is NaN and its
+ * arg-max 0.  With hop <= window every window holds at least one frame.
+ * Order of the additions (fixed): the chunk rows of a window are added in ascending order inside blocks of 32 chunks counted
+ * from the window's first chunk, the block sums in ascending order onto the total -- the one-shot reduction's order re-based at
+ * the window start.  A single window with window >= T therefore returns the bits of `power` and `argmax`.
+ * power_w [B][nW][G], argmax_w [B][nW] int32, power [B][G], argmax [B] are device buffers and may each be NULL (at least one of
+ * power_w / argmax_w must be given); power / argmax are the ordinary whole-recording results from the SAME partial sums: the
+ * beamforming kernel runs once.  Status: MICLOC_ERR_SHAPE for a window or hop that is not a multiple of the quantum, a hop or
+ * window < 1, or B nW > INT32_MAX; MICLOC_ERR_WORKSPACE for a short or misaligned ws.  One workgroup per (window, trial), no
+ * atomics, no host synchronisation: re-entrant per stream and graph-capturable like the entries they extend. */
+int micloc_window_quantum(const micloc_plan *plan); /* frames (> 0), or MICLOC_ERR_INVALID / MICLOC_ERR_NOT_SET (neuron kernel of a real bf_mat, bf_mat) */
+/* nW of the rule for a given quantum (pure function): > 0, or MICLOC_ERR_INVALID (T or quantum < 1) / MICLOC_ERR_SHAPE */
+int micloc_window_count(int T, int window, int hop, int quantum);
+/* ws bytes of the stage-level (pipeline == 0) or pipeline-level (pipeline != 0) windowed entries; 0 on bad arguments.  The
+ * read-out needs no scratch of its own: these are the sizes of the unwindowed calls (partial sums: B x ceil(T / 256) x Gp doubles). */
+size_t micloc_window_workspace_bytes(const micloc_plan *plan, int B, int T, int window, int hop, int pipeline);
+/* micloc_lif_beamform_f64 / micloc_beamform_c128_f64 with the windowed read-out (no y) */
+int micloc_lif_beamform_windows_f64(const micloc_plan *plan, const int8_t *spikes, int B, int T, int window, int hop, double *power_w,
+                                    int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
+int micloc_beamform_c128_windows_f64(const micloc_plan *plan, const double *pre, int B, int T, int Ts, int window, int hop, double *power_w,
+                                     int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
+/* micloc_snn_pipeline_f64 (spikes may be NULL) / micloc_beamformer_pipeline_f64 with the windowed read-out (no y) */
+int micloc_snn_pipeline_windows_f64(const micloc_plan *plan, const double *x, int B, int T, int window, int hop, int8_t *spikes,
+                                    double *power_w, int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                    void *stream);
+int micloc_beamformer_pipeline_windows_f64(const micloc_plan *plan, const double *x, int B, int T, int window, int hop, double *power_w,
+                                           int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
  * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
