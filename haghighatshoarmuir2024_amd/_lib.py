@@ -136,6 +136,12 @@ SYMBOLS = {
                                                        c_void_p, c_size_t, c_void_p]),
     "micloc_envelope_track_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
     "micloc_envelope_track_any": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+    "micloc_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "micloc_track_is_fused": (c_int, [c_void_p]),
+    "micloc_lif_beamform_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_beamform_c128_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_snn_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_beamformer_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_music_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -86,6 +86,18 @@ class Beamformer:
         return _add_peaks(plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True), doa_list, num_sources, min_separation,
                           rel_threshold)
 
+    def track_batch(self, bf_mat, sig_batch, envelope, want_envelope_last=False, budget_bytes=1 << 30):
+        """The moving-target read-out for a batch, sig_batch [B, T, M]: `np.argmax(envelope.evolve(apply_to_signal(...)), axis=1)` per
+        trial without the T x G arrays (SNNBeamformer.track_batch; |y| = hypot(re, im)).  Returns a dict of device tensors: index [B, T]
+        int32, peak_envelope [B, T] float64, envelope_last [B, G] (or None)."""
+        B, T, M = sig_batch.shape
+        if bf_mat.shape[0] != M:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {bf_mat.shape[0]}!")
+        plan = self.plan()
+        plan.set_bf_mat(np.asarray(bf_mat, dtype=np.complex128))
+        return plan.track(plan.to_device(sig_batch), envelope.win_lens[0], envelope.win_lens[1], want_envelope_last=want_envelope_last,
+                          budget_bytes=budget_bytes)
+
     def apply_to_template(self, bf_mat, template, snr_db, to_host=True):
         try:
             time_temp, sig_temp, doa_temp = template

@@ -218,6 +218,17 @@ hipError_t launch_peak_location(const int32_t *rate, int B, int G, int F, int wi
 hipError_t launch_doa_peaks(const double *power, int B, int G, const double *doa, int kind, int K, double min_sep, double rel, int32_t *index,
                             double *value, hipStream_t stream);
 
+// ---- fused moving-target tracking (track.hip) ---------------------------------------------------------------------
+// true: the fused kernels serve this plan (<= 16 channels, the shapes of the bf_mat-stationary beamforming kernels); false: the two-step route
+bool track_fused_eligible(const BeamformW &W, const NeuronTab &nt, int is_complex);
+int track_col_groups(int G);
+size_t track_pairs_bytes(int B, int T, int G);  // (value, index) pairs [B][T][ceil(G / 64)]
+hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_complex, const void *src, int B, int T, int Ts, int G,
+                              double a_rise, double i_rise, double a_fall, int32_t *index, double *peak, double *env_last, void *pairs,
+                              hipStream_t stream);
+// the read-out of a stored envelope [B][T][G]: first maximum and its value per row, the last row (peak / env_last may be NULL)
+hipError_t launch_track_rows(const double *env, int B, int T, int G, int32_t *index, double *peak, double *env_last, hipStream_t stream);
+
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
 struct MusicDims {
     int B, T, M;     // trials, samples per trial, microphones

@@ -351,6 +351,59 @@ class Plan:
                                                      _ptr(ws), nbytes, _stream(self.device)), "beamform_c128")
         return out
 
+    # ---- moving-target tracking (the tracking rule of include/micloc_hip.h) -----------------------------------
+    def track_is_fused(self):
+        """True when the fused kernels of csrc/track.hip serve this plan and its bf_mat; False: the two-step route inside the call."""
+        r = self.lib.micloc_track_is_fused(self.handle)
+        if r < 0:
+            _lib.check(r, "track_is_fused")
+        return bool(r)
+
+    def track(self, src, win_fall, win_rise, kind="pipeline", T=None, want_envelope_last=False, budget_bytes=1 << 30):
+        """index [B, T] int32, peak_envelope [B, T] float64 (and envelope_last [B, G]) of `np.argmax(Envelope.evolve(y), axis=1)`
+        without y or its envelope in device memory.  kind: "pipeline" (src = x [B, T, M]), "spikes" (src = int8 raster [B, T, 2M],
+        real bf_mat) or "planar" (src = band-passed rows [B, 2M, Ts], complex bf_mat, with T).  Plans the fused kernels do not serve
+        run the two-step route over sub-batches whose y + envelope stay under `budget_bytes` (one trial at least)."""
+        torch = _torch()
+        if int(win_fall) < 1 or int(win_rise) < 1:
+            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        if kind == "planar":
+            B = src.shape[0]
+            Ts = src.shape[2]
+        else:
+            B, T = src.shape[0], src.shape[1]
+            if kind == "pipeline" and src.shape[2] != self.num_mic:
+                raise ValueError(f"number of channels in the input siganl {src.shape[2]} should be the same as the number of microphones {self.num_mic}!")
+        B, T, G = int(B), int(T), self.G
+        if B * T > 0x7FFFFFFF:
+            raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
+        # NumPy's own arithmetic for the filter constants, as envelope_track
+        wl = np.asarray([int(win_fall), int(win_rise)])
+        inv = 1 / wl
+        a = 1 - inv
+        consts = (float(a[1]), float(inv[1]), float(a[0]))
+        nbytes = self.lib.micloc_track_workspace_bytes(self.handle, B, T)
+        if nbytes == 0:
+            raise _lib.MiclocError("track: the plan needs bf_mat (and, for a real one, the neuron kernel) first")
+        if not self.track_is_fused() and B > 1:
+            per_trial = (24 if self.w_complex else 16) * T * G + 512
+            nbytes = max(nbytes, min(nbytes + (B - 1) * per_trial, nbytes - per_trial + max(per_trial, int(budget_bytes))))
+        ws = self.ws.get(nbytes)
+        out = dict(index=torch.empty((B, T), dtype=torch.int32, device=self.device),
+                   peak_envelope=torch.empty((B, T), dtype=torch.float64, device=self.device),
+                   envelope_last=torch.empty((B, G), dtype=torch.float64, device=self.device) if want_envelope_last else None)
+        tail = (_ptr(out["index"]), _ptr(out["peak_envelope"]), _ptr(out["envelope_last"]), _ptr(ws), nbytes, _stream(self.device))
+        if kind == "pipeline":
+            fn = self.lib.micloc_beamformer_pipeline_track_f64 if self.w_complex else self.lib.micloc_snn_pipeline_track_f64
+            _lib.check(fn(self.handle, _ptr(src), B, T, *consts, *tail), "pipeline_track")
+        elif kind == "spikes":
+            _lib.check(self.lib.micloc_lif_beamform_track_f64(self.handle, _ptr(src), B, T, *consts, *tail), "lif_beamform_track")
+        elif kind == "planar":
+            _lib.check(self.lib.micloc_beamform_c128_track_f64(self.handle, _ptr(src), B, T, int(Ts), *consts, *tail), "beamform_c128_track")
+        else:
+            raise ValueError("kind must be 'pipeline', 'spikes' or 'planar'")
+        return out
+
     # ---- single stages (used by tests and by Demo.spike_encoding-style callers) --------------------------
     def stht(self, x):
         torch = _torch()

@@ -193,6 +193,24 @@ class SNNBeamformer:
                                      min_separation, rel_threshold)
         return _add_peaks(plan.snn_pipeline(x, want_spikes=return_spikes, want_power=True), doa_list, num_sources, min_separation, rel_threshold)
 
+    def track_batch(self, bf_mat, sig_batch, envelope, time_vec=None, want_envelope_last=False, budget_bytes=1 << 30):
+        """The moving-target read-out of paper_plots/target_snn_localization.py:595-622 for a batch, sig_batch [B, T, M] (on the fs
+        grid): `np.argmax(envelope.evolve(apply_to_signal(bf_mat, .)), axis=1)` per trial -- the bits of
+        `envelope.track(apply_to_signal(..., to_host=False))` -- without the T x G output or its envelope in device memory
+        (csrc/track.hip; up to 16 channels.  More channels, or more than 512 DoAs, take the two-step route inside the library over
+        sub-batches whose arrays stay under budget_bytes).  `envelope` is a utils.Envelope.  Returns a dict of device tensors:
+        index [B, T] int32, peak_envelope [B, T] float64 (the envelope at the index), envelope_last [B, G] (or None)."""
+        B, T, M = sig_batch.shape
+        if bf_mat.shape[0] // 2 != M:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {bf_mat.shape[0] // 2}!")
+        if time_vec is None:
+            time_vec = np.arange(T) / self.fs
+        plan = self.plan()
+        plan.set_neuron_kernel(neuron_impulse_response(time_vec, self.tau_vec))
+        plan.set_bf_mat(np.asarray(bf_mat, dtype=np.float64))
+        return plan.track(plan.to_device(sig_batch), envelope.win_lens[0], envelope.win_lens[1], want_envelope_last=want_envelope_last,
+                          budget_bytes=budget_bytes)
+
     def membrane_covariance_batch(self, sig_batch, time_vec=None, t_start=0, out=None):
         """[B, T, M] -> device tensor [B, 2M, 2M] (`out`, if given): V^T V / (T - t_start) of the membrane signal over frames >= t_start."""
         B, T, M = sig_batch.shape

@@ -93,8 +93,8 @@ class ShardStore:
     def covered(self, lo, hi):
         return bool(self.have[lo:hi].all())
 
-    def put(self, trials, doa, index, pmax):
-        """Persist one finished batch (any set of trial numbers) and mark it done."""
+    def put(self, trials, doa, index, pmax, **extra):
+        """Persist one finished batch (any set of trial numbers) and mark it done (`extra`: further fields of a subclass's record)."""
         import os
 
         trials = np.asarray(trials, dtype=np.int64)
@@ -102,6 +102,8 @@ class ShardStore:
             return
         a = np.zeros(len(trials), dtype=self.REC)
         a["trial"], a["doa"], a["index"], a["pmax"] = trials, doa, index, pmax
+        for k, v in extra.items():
+            a[k] = v
         # (the name carries a checksum of the trial numbers: two different sets with the same bounds and size -- resumed runs under
         #  different world sizes -- never overwrite each other's records)
         import zlib
@@ -996,6 +998,166 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
     return res
 
 
+class TrackShardStore(ShardStore):
+    """ShardStore of moving_target_sweep: a record holds the trial's phase (`doa`), the mean (`pmax`) and the median (`med`) of its
+    per-frame errors."""
+
+    REC = np.dtype([("trial", "<i8"), ("doa", "<f8"), ("index", "<i8"), ("pmax", "<f8"), ("med", "<f8")])
+
+
+def moving_doa_path(time_vec, duration, doa_max, num_period, phase):
+    """The DoA of the moving target at the times of `time_vec`: doa_max * sin(num_period * pi * t / duration + phase)
+    (paper_plots/target_snn_localization.py:595-597 with a start phase; phase [B] -> [B, T])."""
+    t = np.asarray(time_vec, dtype=np.float64)
+    ph = np.asarray(phase, dtype=np.float64)
+    return doa_max * np.sin(num_period * np.pi * t / duration + ph[..., None])
+
+
+def track_errors(doa_list, index, doa_true, lag_frames, settle_frames):
+    """Per-trial tracking errors: index [B, T] (the estimate per frame: a device tensor or an array), doa_true [B, T] (NumPy) ->
+    (mean [B], median [B]) of arcsin|sin(doa_list[index[:, t]] - doa_true[:, t - lag_frames])| over the frames
+    t >= max(settle_frames, lag_frames).  A device tensor is reduced on the device (only the 2 B scalars come back)."""
+    T = doa_true.shape[1]
+    t0 = max(int(settle_frames), int(lag_frames))
+    lag = int(lag_frames)
+    if not 0 <= t0 < T:
+        raise ValueError(f"no frame to score: settle_frames / lag_frames {t0} of {T} frames")
+    truth = np.ascontiguousarray(doa_true[:, t0 - lag : T - lag])
+    if type(index).__module__.startswith("torch"):
+        import torch
+
+        dl = torch.as_tensor(np.asarray(doa_list, dtype=np.float64), device=index.device)
+        e = torch.asin(torch.abs(torch.sin(dl[index[:, t0:].long()] - torch.as_tensor(truth, device=index.device))))
+        return e.mean(dim=1).cpu().numpy(), e.quantile(0.5, dim=1).cpu().numpy()
+    e = doa_error(np.asarray(doa_list, dtype=np.float64)[np.asarray(index)[:, t0:]], truth)
+    return e.mean(axis=1), np.median(e, axis=1)
+
+
+def track_localizer(beamf, bf_mat, envelope, max_batch=1100):
+    """Default localizer of moving_target_sweep: the fused tracking call (track_batch); index [B, T] stays on the device."""
+
+    def run(sig_batch, time_vec):
+        import torch
+
+        kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
+        parts = [beamf.track_batch(bf_mat, sig_batch[s : s + max_batch], envelope, **kw)["index"] for s in range(0, len(sig_batch), max_batch)]
+        return torch.cat(parts)
+
+    return run
+
+
+def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, num_period=0.5, lag_frames=None, settle_frames=None,
+                        snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None, freq_design=2000.0,
+                        test_duration=100e-3, snr_gain_due_to_bandwidth=None, localizer=None, batch_trials=1100, out_dir=None, store_key=None):
+    """The noisy-target sweep with a MOVING target and the per-frame read-out (paper_plots/target_snn_localization.py:585-628,
+    `test_moving_target`): the test signal and SNR grid of noisy_target_sweep; per trial the DoA follows
+    `doa_max * sin(num_period * pi * t / duration + phase)` (moving_doa_path) with `phase = rand(1)[0] * 2 pi` drawn where the noisy sweep
+    draws its DoA (parity mode: the global MT19937 stream, `rand(1)` then `randn(T, M)`; throughput mode: RandomState(seed) for all
+    trials on every rank, device synthesis with moving delays and Philox noise by global trial).  The estimate of frame t,
+    `doa_list[index[t]]` with index = argmax_g Envelope(y)[t, g], is scored against the truth of frame t - lag_frames (default
+    int(kernel_duration * fs), the script's alignment at :628) over the frames t >= settle_frames (default int(fs * fall_time)) by the
+    pi-periodic error (track_errors: on the device; only per-trial scalars are gathered, in one all-gather).
+    `localizer(sig_batch, time_vec) -> index [B, T]` (device tensor or array) replaces the fused call (track_localizer).
+    Returns dict(phase, err (mean error over frames), med (median over frames): [num_snr, num_sim]; track_mae_deg [num_snr], the mean of
+    err over trials; track_median_deg [num_snr], the median over trials of med; mae_deg = track_mae_deg).  out_dir resume as the other
+    sweeps; the key also covers doa_max, num_period, lag_frames, settle_frames, the envelope's window lengths and the method's
+    parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer)."""
+    if mode not in ("parity", "throughput"):
+        raise ValueError("mode must be 'parity' or 'throughput'")
+    doa_list = np.asarray(doa_list, dtype=np.float64)
+    fs = beamf.fs
+    M = len(beamf.geometry)
+    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    if snr_gain_due_to_bandwidth is None:
+        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
+    time_test = np.arange(0, test_duration, step=1 / fs)
+    sig_test = np.sin(2 * np.pi * freq_design * time_test)
+    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    total = len(snr_trial)
+    time_in = np.arange(time_test.min(), time_test.max(), step=1 / fs)
+    T = len(time_in)
+    lag_frames = int(beamf.kernel_duration * fs) if lag_frames is None else int(lag_frames)
+    settle_frames = int(fs * envelope.fall_time) if settle_frames is None else int(settle_frames)
+    if lag_frames < 0 or settle_frames < 0 or max(lag_frames, settle_frames) >= T:
+        raise ValueError(f"lag_frames ({lag_frames}) and settle_frames ({settle_frames}) must lie in [0, {T}): no frame to score")
+    doa_max, num_period = float(doa_max), float(num_period)
+    lo, hi = shard_range(total, rank, world_size)
+    store = None
+    if out_dir is not None:
+        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
+        key.update(_method_key(beamf))
+        key.update(store_key or {})
+        store = TrackShardStore(out_dir, "moving-noisy", total, doa_max=doa_max, num_period=num_period, lag_frames=lag_frames,
+                                settle_frames=settle_frames, win_fall=int(envelope.win_lens[0]), win_rise=int(envelope.win_lens[1]),
+                                seed=int(seed), mode=mode, snr_db_trial=snr_trial, doa_list=doa_list, time_test=time_test, sig_test=sig_test,
+                                fs=float(fs), num_mic=M, r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
+                                theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
+    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
+    if localizer is None:
+        localizer = track_localizer(beamf, bf_mat, envelope, max_batch=batch_trials)
+    phase = np.zeros(total)
+    err = np.zeros(hi - lo)
+    med = np.zeros(hi - lo)
+    if store is not None:
+        err[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
+        med[done[lo:hi]] = store.rec["med"][lo:hi][done[lo:hi]]
+
+    def flush(sig_batch, trials):
+        trials = np.asarray(trials, dtype=np.int64)
+        truth = moving_doa_path(time_in, test_duration, doa_max, num_period, phase[trials])
+        e, m = track_errors(doa_list, localizer(sig_batch, time_in), truth, lag_frames, settle_frames)
+        err[trials - lo], med[trials - lo] = e, m
+        if store is not None:
+            store.put(trials, phase[trials], np.zeros(len(trials), dtype=np.int64), e, med=m)
+
+    if mode == "parity":
+        np.random.seed(seed)
+        sigs, ids = [], []
+        for trial in range(total):
+            phase[trial] = np.random.rand(1)[0] * 2 * np.pi
+            if lo <= trial < hi and not done[trial]:
+                doa_t = moving_doa_path(time_test, test_duration, doa_max, num_period, phase[trial])
+                _, sig = synthesize_array_signal(beamf.geometry, fs, time_test, sig_test, doa_t)
+                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
+                sigs.append(sig)
+                ids.append(trial)
+                if len(sigs) == batch_trials:
+                    flush(np.stack(sigs), ids)
+                    sigs, ids = [], []
+            else:
+                np.random.randn(T, M)  # keep the stream aligned
+        if sigs:
+            flush(np.stack(sigs), ids)
+    else:
+        from . import synthesis
+
+        rng = np.random.RandomState(seed)
+        phase[:] = rng.rand(total) * 2 * np.pi
+        for s0 in range(lo, hi, batch_trials):
+            s1 = min(hi, s0 + batch_trials)
+            if done[s0:s1].all():
+                continue
+            doas = moving_doa_path(time_test, test_duration, doa_max, num_period, phase[s0:s1])
+            # moving-DoA device synthesis (micloc_synth_targets_f64, moving = 1) + Philox noise numbered by global trial
+            _, x = synthesis.apply_to_template_batch(beamf.geometry, fs, (time_test, sig_test), doas, device=getattr(beamf, "device", None),
+                                                     device_delays=True)
+            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
+            flush(x, np.arange(s0, s1))
+
+    exchange = {}
+    full = gather_shards(dict(err=err, med=med), total, rank, world_size, group, stats=exchange)
+    S = total // num_sim
+    shape = (S, num_sim)
+    e, m = full["err"].reshape(shape), full["med"].reshape(shape)
+    res = dict(phase=phase.reshape(shape), err=e, med=m, track_mae_deg=np.mean(e, axis=1) * 180 / np.pi,
+               track_median_deg=np.median(m, axis=1) * 180 / np.pi, lag_frames=lag_frames, settle_frames=settle_frames, snr_db_vec=snr_db_vec,
+               exchange=exchange)
+    res["mae_deg"] = res["track_mae_deg"]
+    if store is not None:
+        res["persistence"] = store.stats()
+    return res
+
+
 def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world):
     """--sweep multi-noisy: multi_target_sweep with the noisy sweep's SNN or complex beamformer (design as --sweep noisy) or the MUSIC
     noisy sweep's MUSIC (1 s test signal, band [0.8, 1.2] x freq_design, k = 1, N = 2048)."""
@@ -1032,17 +1194,17 @@ def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau,
 
 
 def main(argv=None):
-    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy]`: the accuracy sweeps of the paper scripts
+    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy|moving-noisy]`: the accuracy sweeps of the paper scripts
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
     import os
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy"], default="noisy")
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy"], default="noisy")
     ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
-    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy: the localizer")
+    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy, moving-noisy (snn | beamformer): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
@@ -1072,7 +1234,18 @@ def main(argv=None):
     music_grid = args.sweep == "music-noisy" or (args.sweep == "multi-noisy" and args.method == "music")
     grid = args.grid if args.grid is not None else (8 * 7 + 1 if music_grid else 64 * 7 + 1)
     doa_list = np.linspace(-np.pi, np.pi, grid)
-    if args.sweep == "multi-noisy":
+    if args.sweep == "moving-noisy" and args.method == "beamformer":
+        from .beamformer import Beamformer
+        from .utils import Envelope
+
+        beamf = Beamformer(geometry, kernel_duration=10.0e-3, freq_range=freq_range, fs=fs)
+        time_temp = np.arange(0, 1.0, step=1 / fs)
+        freq_inst = freq_range[0] + (freq_range[1] - freq_range[0]) * (time_temp % time_temp[-1]) / time_temp[-1]
+        bf_mat, _ = beamf.design_from_template((time_temp, np.sin(2 * np.pi * np.cumsum(freq_inst) / fs)), doa_list, svd=args.svd)
+        # (a 0.1 s trial: the script's 10 ms / 100 ms envelope would still be settling at its end)
+        res = moving_target_sweep(beamf, bf_mat, doa_list, Envelope(rise_time=1e-3, fall_time=10e-3, fs=fs), num_sim=args.num_sim or 100,
+                                  seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+    elif args.sweep == "multi-noisy":
         res = _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world)
     elif args.sweep.startswith("music"):
         # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048
@@ -1112,6 +1285,14 @@ def main(argv=None):
             else:
                 ap.error("--sweep speech needs --flac or --pcm-npz")
             res = speech_target_sweep(beamf, bf_mat, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+        elif args.sweep == "moving-noisy":
+            if args.method != "snn":
+                ap.error("--sweep moving-noisy takes --method snn or beamformer")
+            from .utils import Envelope
+
+            # (a 0.1 s trial: the script's 10 ms / 100 ms envelope would still be settling at its end)
+            res = moving_target_sweep(beamf, bf_mat, doa_list, Envelope(rise_time=1e-3, fall_time=10e-3, fs=fs), num_sim=args.num_sim or 100,
+                                      seed=args.seed, mode=args.mode, rank=rank, world_size=world)
         elif args.sweep == "windowed-noisy":
             if args.window_frames is None:
                 ap.error("--sweep windowed-noisy needs --window-frames")
@@ -1124,6 +1305,8 @@ def main(argv=None):
         print(f"Mean aboslute errors: {res['mae_deg']}")
         if "resolved_rate" in res:
             print(f"Resolution rate: {res['resolved_rate']}")
+        if "track_median_deg" in res:
+            print(f"Median tracking errors: {res['track_median_deg']}")
         if "window_mae_deg" in res:
             print(f"Window starts (frames): {res['window_start']}")
             print(f"Mean aboslute errors per window:\n{res['window_mae_deg']}")

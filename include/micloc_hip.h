@@ -482,6 +482,45 @@ int micloc_snn_pipeline_windows_f64(const micloc_plan *plan, const double *x, in
 int micloc_beamformer_pipeline_windows_f64(const micloc_plan *plan, const double *x, int B, int T, int window, int hop, double *power_w,
                                            int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- moving-target tracking: the DoA per time step, without the T x G arrays -------------------- */
+/* paper_plots/target_snn_localization.py:595-622: `np.argmax(Envelope.evolve(sig_bf), axis=1)` for a batch, as ONE read-out of the
+ * beamforming stage.  The rule, for every trial b and DoA column g independently:
+ *   y[t][g]   the beamformer output of frame t: exactly the value micloc_lif_beamform_f64 / micloc_beamform_c128_f64 store in `y`
+ *             (same instruction sequence, same bits);
+ *   m[t][g]   = |y[t][g]|  (real: fabs; complex: hypot(re, im), the device library's, as MICLOC_ENV_C128);
+ *   e[0][g]   = m[0][g];   for t >= 1:  rise = m[t][g] >= e[t-1][g];
+ *   e[t][g]   = rise ? a_rise * e[t-1][g] + i_rise * m[t][g] : a_fall * e[t-1][g]      -- two rounded products, one rounded sum,
+ *             nothing fused: micloc_envelope_track_f64's recurrence; a_rise = 1 - 1/w_rise, i_rise = 1/w_rise, a_fall = 1 - 1/w_fall as
+ *             NumPy computes them (w = int(fs * time) >= 1);
+ *   index[b][t]    = the FIRST g with e[t][g] = max_g e[t][g]; a NaN never wins; a row of NaN only gives 0  (np.argmax without NaN);
+ *   peak_env[b][t] = e[t][index[b][t]]  (NaN for a row of NaN only; may be NULL);
+ *   env_last[b][g] = e[T-1][g]  (may be NULL).
+ * index / peak_env / env_last equal, bit for bit, what micloc_envelope_track_any computes from the stored y.
+ * Plans with up to 16 channels whose y the bf_mat-stationary kernels produce (micloc_track_is_fused() == 1) run the fused kernels of
+ * csrc/track.hip: neither y nor e is stored, the scratch is one (value, index) pair per frame and 64 DoA columns.  Other plans run
+ * the two-step route inside the call -- beamforming with y stored, the envelope kernel, a row read-out -- over sub-batches of
+ * trials: the minimum workspace holds y and e of ONE trial, and a caller that passes more has as many trials per sub-batch as fit
+ * (the results do not depend on it).
+ * Status codes before any launch: MICLOC_ERR_SHAPE for T < 1 or B * T > 2^31 - 1 (and a plan of the other kind, a Ts that is not
+ * micloc_padded_T(T)), MICLOC_ERR_WORKSPACE for a missing, misaligned or short workspace, MICLOC_ERR_INVALID / MICLOC_ERR_NOT_SET as
+ * everywhere.  No atomics on results, no host synchronisation, no allocation: re-entrant per stream with workspaces of their own. */
+/* ws bytes of all four calls below (what the pipeline's first two stages need + the tracking region); 0 on bad arguments or a plan
+ * without bf_mat */
+size_t micloc_track_workspace_bytes(const micloc_plan *plan, int B, int T);
+/* 1: the fused kernels serve this plan and its bf_mat, 0: the two-step route; < 0: a status code */
+int micloc_track_is_fused(const micloc_plan *plan);
+int micloc_lif_beamform_track_f64(const micloc_plan *plan, const int8_t *spikes, int B, int T, double a_rise, double i_rise, double a_fall,
+                                  int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream);
+int micloc_beamform_c128_track_f64(const micloc_plan *plan, const double *pre, int B, int T, int Ts, double a_rise, double i_rise,
+                                   double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes,
+                                   void *stream);
+/* STHT + band-pass (+ RZCC) + the above, x [B][T][M] */
+int micloc_snn_pipeline_track_f64(const micloc_plan *plan, const double *x, int B, int T, double a_rise, double i_rise, double a_fall,
+                                  int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream);
+int micloc_beamformer_pipeline_track_f64(const micloc_plan *plan, const double *x, int B, int T, double a_rise, double i_rise,
+                                         double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes,
+                                         void *stream);
+
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
  * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
