@@ -14,8 +14,17 @@ Sweeps: noisy_target_sweep (target_snn_localization.py:435-467), speech_target_s
 (target_xylo_localization.py:540-608; integer-LIF stage parity-unpinned), music_noisy_sweep / music_speech_sweep (the MUSIC twins,
 target_localization_MUSIC.py), multi_target_sweep (K simultaneous targets, the statistical counterpart of
 paper_plots/multiple_targets_*.py: K peaks per trial, matched errors and resolution rate), windowed_target_sweep (the noisy-target
-sweep with the time-resolved read-out: one estimate per window of every trial).
+sweep with the time-resolved read-out: one estimate per window of every trial), moving_target_sweep (a moving target scored per
+frame, target_snn_localization.py:585-628).
+
+Every sweep runs through ONE trial loop, `_monte_carlo`: shard range, ShardStore and resume, the parity replay of the global stream
+(also across skipped trials), the throughput range loop, the flush of a finished batch, the one all-gather.  A sweep hands it only
+what is its own: how a trial's truth is drawn, a host trial (parity) and a device batch (throughput), the per-trial result fields,
+the read-out that fills them and its store key entries; it builds its result dict from what the loop returns.
 """
+import os
+import zlib
+
 import numpy as np
 
 from .snn_beamformer import synthesize_array_signal
@@ -41,15 +50,15 @@ class ShardStore:
     results and any change of them starts a fresh directory.  A rerun loads what exists and computes only the trials that are
     missing; in parity mode the reference's MT19937 stream is still replayed for the skipped trials, so the results are identical to an
     uninterrupted run -- also when the world size changed in between (coverage is per trial, not per shard).
+    `rec`: the record dtype of a sweep whose trials hold more than that (K or nW columns, a further field); it starts with `trial`.
     The reference keeps its sweeps' results the same way, at the end of the script (ref:paper_plots/snn_localization_benchmark.py:588-592,
     ref:paper_plots/target_snn_localization.py:525); a 16 384-trial sweep over 8 ranks should not restart from zero."""
 
     REC = np.dtype([("trial", "<i8"), ("doa", "<f8"), ("index", "<i8"), ("pmax", "<f8")])
 
-    def __init__(self, out_dir, sweep, total, **key):
+    def __init__(self, out_dir, sweep, total, *, rec=None, **key):
         import hashlib
         import json
-        import os
 
         def h(v):
             if isinstance(v, np.ndarray):
@@ -71,6 +80,7 @@ class ShardStore:
                 f.write(blob)
             os.replace(tmp, meta_path)  # (several ranks may race: they all write the same bytes)
         self.total = int(total)
+        self.REC = self.REC if rec is None else np.dtype(rec)
         self.have = np.zeros(self.total, dtype=bool)
         self.rec = np.zeros(self.total, dtype=self.REC)
         self.files_loaded = 0
@@ -93,10 +103,8 @@ class ShardStore:
     def covered(self, lo, hi):
         return bool(self.have[lo:hi].all())
 
-    def put(self, trials, doa, index, pmax, **extra):
-        """Persist one finished batch (any set of trial numbers) and mark it done (`extra`: further fields of a subclass's record)."""
-        import os
-
+    def put(self, trials, doa, index=0, pmax=0.0, **extra):
+        """Persist one finished batch (any set of trial numbers) and mark it done (`extra`: further fields of the record dtype)."""
         trials = np.asarray(trials, dtype=np.int64)
         if len(trials) == 0:
             return
@@ -106,8 +114,6 @@ class ShardStore:
             a[k] = v
         # (the name carries a checksum of the trial numbers: two different sets with the same bounds and size -- resumed runs under
         #  different world sizes -- never overwrite each other's records)
-        import zlib
-
         name = f"trials_{int(trials.min()):08d}_{int(trials.max()) + 1:08d}_{len(trials)}_{zlib.crc32(np.ascontiguousarray(trials).tobytes()):08x}.npy"
         tmp = os.path.join(self.dir, f".tmp-{os.getpid()}-{name}")
         with open(tmp, "wb") as f:
@@ -125,7 +131,8 @@ class ShardStore:
 
 def gather_shards(local, total, rank, world_size, group=None, bounds=None, stats=None):
     """The sweep's one exchange step: all-gather the per-trial result arrays of contiguous shards; returns the
-    full-length arrays on every rank.  `local` is a dict name -> 1-d numpy array (this rank's shard; any mix of dtypes).
+    full-length arrays on every rank.  `local` is a dict name -> numpy array, 1-d or [n, W] with one row per item (this rank's shard; any
+    mix of dtypes and widths).
     ONE collective whatever the number of arrays: every rank packs its arrays into a struct-of-arrays byte record (each array
     padded to the widest shard and to 8 bytes), one `all_gather_into_tensor` moves the records (RCCL over xGMI when the group is
     "nccl": one host -> device copy, one collective, one device -> host copy), every rank unpacks.  `bounds(r) -> (lo, hi)`
@@ -151,26 +158,26 @@ def gather_shards(local, total, rank, world_size, group=None, bounds=None, stats
     arrs = {k: np.ascontiguousarray(local[k]) for k in keys}
     n_local = spans[rank][1] - spans[rank][0]
     for k in keys:
-        if arrs[k].ndim != 1 or len(arrs[k]) != n_local:
+        if arrs[k].ndim not in (1, 2) or len(arrs[k]) != n_local:
             raise ValueError(f"gather_shards: '{k}' has shape {arrs[k].shape}, this rank's shard holds {n_local} items")
-    # record layout: the arrays one behind the other, each `width` items of its dtype, 8-byte aligned
+    # record layout: the arrays one behind the other, each `width` items (rows) of its dtype, 8-byte aligned
+    item = {k: arrs[k].dtype.itemsize * int(np.prod(arrs[k].shape[1:])) for k in keys}  # bytes per item
     offs, off = {}, 0
     for k in keys:
         offs[k] = off
-        off += (width * arrs[k].dtype.itemsize + 7) & ~7
+        off += (width * item[k] + 7) & ~7
     rec = np.zeros(max(off, 8), dtype=np.uint8)
     for k in keys:
         v = arrs[k]
-        rec[offs[k] : offs[k] + v.nbytes] = v.view(np.uint8)
+        rec[offs[k] : offs[k] + v.nbytes] = v.reshape(-1).view(np.uint8)
     buf = torch.from_numpy(rec).to(dev)
     full = torch.empty(len(rec) * world_size, dtype=torch.uint8, device=dev)
     dist.all_gather_into_tensor(full, buf, group=group)
     full = full.cpu().numpy().reshape(world_size, len(rec))
     out = {}
     for k in keys:
-        dt = arrs[k].dtype
-        parts = [full[r, offs[k] : offs[k] + (hi - lo) * dt.itemsize].view(dt) for r, (lo, hi) in enumerate(spans)]
-        out[k] = np.concatenate(parts)
+        parts = [full[r, offs[k] : offs[k] + (hi - lo) * item[k]].view(arrs[k].dtype) for r, (lo, hi) in enumerate(spans)]
+        out[k] = np.concatenate(parts).reshape((-1,) + arrs[k].shape[1:])
     if stats is not None:
         stats.update(exchange_ms=(time.perf_counter() - t0) * 1e3, bytes_per_rank=int(len(rec)), collectives=1)
     return out
@@ -195,6 +202,30 @@ def sharded_design(design_fn, doa_list, rank=0, world_size=1, group=None):
     return flat["cols"].reshape(G, rows).T.copy()
 
 
+def _in_batches(sig_batch, max_batch, one):
+    """`one(slice)` -> a tuple of per-trial results (arrays, or device tensors) for every slice of at most `max_batch` trials of
+    `sig_batch`; returns the tuple of their concatenations."""
+    parts = [one(sig_batch[s : s + max_batch]) for s in range(0, len(sig_batch), max_batch)]
+
+    def cat(col):
+        if isinstance(col[0], np.ndarray):
+            return np.concatenate(col)
+        import torch
+
+        return torch.cat(col)
+
+    return tuple(cat(col) for col in zip(*parts))
+
+
+def _argmax_and_power(out):
+    a = out["argmax"].cpu().numpy().astype(np.int64)
+    return a, out["power"].cpu().numpy()[np.arange(len(a)), a]
+
+
+def _peaks_and_power(out):
+    return out["peaks"].cpu().numpy().astype(np.int64), out["peak_power"].cpu().numpy()
+
+
 def device_localizer(beamf, bf_mat, max_batch=1100, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0, window=None,
                      hop=None):
     """Default localizer: the HIP pipeline (power + arg-max, no T x G temporary).  With num_sources=K (and doa_list) it returns the
@@ -202,28 +233,20 @@ def device_localizer(beamf, bf_mat, max_batch=1100, num_sources=None, doa_list=N
     time-resolved one: (window_argmax [B, nW] int64, the power at it [B, nW]) (windowed_target_sweep)."""
 
     def run(sig_batch, time_vec):
-        am, pm = [], []
-        for s in range(0, len(sig_batch), max_batch):
-            # (the non-spiking complex Beamformer has no neuron kernel, hence no time axis to pass: ref:paper_plots/target_localization.py)
-            kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
+        # (the non-spiking complex Beamformer has no neuron kernel, hence no time axis to pass: ref:paper_plots/target_localization.py)
+        kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
+
+        def one(x):
             if window is not None:
-                out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], window=window, hop=hop, **kw)
+                out = beamf.localize_batch(bf_mat, x, window=window, hop=hop, **kw)
                 a = out["window_argmax"].long()
-                am.append(a.cpu().numpy())
-                pm.append(out["window_power"].gather(2, a.unsqueeze(2)).squeeze(2).cpu().numpy())
-                continue
+                return a.cpu().numpy(), out["window_power"].gather(2, a.unsqueeze(2)).squeeze(2).cpu().numpy()
             if num_sources is not None:
-                out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], num_sources=num_sources, doa_list=doa_list,
-                                           min_separation=min_separation, rel_threshold=rel_threshold, **kw)
-                am.append(out["peaks"].cpu().numpy().astype(np.int64))
-                pm.append(out["peak_power"].cpu().numpy())
-                continue
-            out = beamf.localize_batch(bf_mat, sig_batch[s : s + max_batch], **kw)
-            a = out["argmax"].cpu().numpy().astype(np.int64)
-            p = out["power"].cpu().numpy()
-            am.append(a)
-            pm.append(p[np.arange(len(a)), a])
-        return np.concatenate(am), np.concatenate(pm)
+                return _peaks_and_power(beamf.localize_batch(bf_mat, x, num_sources=num_sources, doa_list=doa_list,
+                                                             min_separation=min_separation, rel_threshold=rel_threshold, **kw))
+            return _argmax_and_power(beamf.localize_batch(bf_mat, x, **kw))
+
+        return _in_batches(sig_batch, max_batch, one)
 
     return run
 
@@ -314,55 +337,98 @@ def _throughput_pipelined(beamf, bf_mat, time_test, sig_test, doa_all, snr_db_tr
     return am, pw_host.numpy()[np.arange(hi - lo), am]
 
 
-def _template_sweep(beamf, bf_mat, doa_list, time_test, sig_test, snr_db_trial, num_sim, seed, mode, rank, world_size, group,
-                    localizer, batch_trials, streams=4, scan_lane_cus=4, out_dir=None, sweep_name="template", store_key=None):
-    """The Monte-Carlo loop shared by the noisy-target and the speech sweep (target_snn_localization.py:447-467 / :224-245):
-    per trial `doa = rand(1)[0] * 2 pi`, apply_to_template at `snr_db_trial[trial]`, power, arg-max, pi-periodic error.
-    Trials are processed in batches of `batch_trials` (host memory: a speech trial is 18.6 MB).  out_dir: per-batch result files and
-    resume (ShardStore): finished trials are loaded, only the missing ones are computed, the result is the uninterrupted run's.
-    store_key: the ShardStore key entries that describe the localizer (default: the hash of bf_mat)."""
-    total = len(snr_db_trial)
+def _snr_vec(snr_db_vec):
+    return np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+
+
+def _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth, band_hz=1000.0):
+    """The set-up of the sine-target sweeps (target_snn_localization.py:435-449): the SNR grid (default: the scripts' 11 values), the
+    `freq_design` sine of `test_duration` and the SNR of every trial, lowered by the bandwidth gain (default (fs / 2) / band_hz,
+    band_hz = f_max - f_min: the paper's [1, 2] kHz band).  Returns (snr_db_vec, time_test, sig_test, snr_trial)."""
+    snr_db_vec = _snr_vec(snr_db_vec)
+    if snr_gain_due_to_bandwidth is None:
+        snr_gain_due_to_bandwidth = (fs / 2) / band_hz
+    time_test = np.arange(0, test_duration, step=1 / fs)
+    sig_test = np.sin(2 * np.pi * freq_design * time_test)
+    return snr_db_vec, time_test, sig_test, np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)  # :449
+
+
+def _one_doa(rand, n):
+    """The truth draw of the single-target sweeps: `rand(1)[0] * 2 pi` per trial (:450)."""
+    return rand(n) * 2 * np.pi
+
+
+def _with_noise(synthesize):
+    """Host trial of the apply_to_template sweeps (:451-457): `synthesize(truth) -> (time_in, sig [T, M])` plus white noise at the trial's
+    SNR, drawn from the global stream."""
+
+    def trial(truth, snr_db):
+        time_in, sig = synthesize(truth)
+        sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_db / 10)) * np.random.randn(*sig.shape)
+        return time_in, sig
+
+    return trial
+
+
+def _monte_carlo(sweep_name, geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials,
+                 out_dir, key, fields, draw, host_trial, device_batch, read_out, truth_width=(), rec=None, skip_frames=None, pipelined=None):
+    """The Monte-Carlo loop of every sweep (target_snn_localization.py:447-467 / :224-245): the trials [lo, hi) of this rank in
+    batches of `batch_trials`, one all-gather of the per-trial results.  Returns (truth [total, ...], the gathered fields as a dict
+    name -> [total, ...], dict(exchange=..., persistence=... with out_dir)).
+    The sweep's own parts:
+    draw(rand, n)            the truths of n trials drawn from `rand` ([n] or [n, *truth_width]); parity mode draws one trial at a
+                             time from the global stream, throughput mode all trials at once from RandomState(seed), on every rank.
+    host_trial(truth, snr)   parity mode: (time_in, noisy sig [T, M]) of one trial; it consumes randn(T, M) itself.  A trial that is
+                             not computed here consumes randn(skip_frames, M) instead (default: the frames of time_test resampled
+                             at fs).
+    device_batch(truths)     throughput mode: (time_in, noise-free x [B, T, M] on the device); the loop adds the Philox noise.
+    read_out(x, time_in, truths) -> one array [B, ...] per entry of `fields`.
+    fields                   (name, ShardStore column, dtype, width () or (W,), fill of the rows no run finished) per result.
+    key, rec                 the sweep's ShardStore key entries (on top of the common ones below) and record dtype.
+    pipelined(truth, lo, hi, ranges, on_done)  throughput mode, optional: computes all of `ranges` itself (several batches in
+                             flight) and reports every batch through on_done(s0, s1, *field values).
+    out_dir: per-batch result files and resume (ShardStore): finished trials are loaded, only the missing ones are computed, the
+    result is the uninterrupted run's."""
+    if mode not in ("parity", "throughput"):
+        raise ValueError("mode must be 'parity' or 'throughput'")
+    total = len(snr_trial)
+    M = len(geometry)
     lo, hi = shard_range(total, rank, world_size)
     store = None
     if out_dir is not None:
-        store = ShardStore(out_dir, sweep_name, total, seed=int(seed), mode=mode, snr_db_trial=np.asarray(snr_db_trial, dtype=np.float64),
-                           doa_list=np.asarray(doa_list, dtype=np.float64), **(dict(bf_mat=np.asarray(bf_mat)) if store_key is None else store_key), time_test=np.asarray(time_test, dtype=np.float64),
-                           sig_test=np.asarray(sig_test, dtype=np.float64), fs=float(beamf.fs), num_mic=len(beamf.geometry),
-                           r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64), theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64))
+        store = ShardStore(out_dir, sweep_name, total, rec=rec, seed=int(seed), mode=mode, snr_db_trial=np.asarray(snr_trial, dtype=np.float64),
+                           doa_list=np.asarray(doa_list, dtype=np.float64), time_test=np.asarray(time_test, dtype=np.float64),
+                           sig_test=np.asarray(sig_test, dtype=np.float64), fs=float(fs), num_mic=M,
+                           r_vec=np.asarray(geometry.r_vec, dtype=np.float64), theta_vec=np.asarray(geometry.theta_vec, dtype=np.float64), **key)
     done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
-    pipelined = mode == "throughput" and localizer is None and streams > 0 and hi > lo
-    localizer = localizer or device_localizer(beamf, bf_mat, max_batch=batch_trials)
-    M = len(beamf.geometry)
-    doa_all = np.zeros(total)
-    argmax = np.zeros(hi - lo, dtype=np.int64)
-    pmax = np.zeros(hi - lo)
+    truth = np.zeros((total,) + truth_width)
+    local = {name: np.full((hi - lo,) + width, fill, dtype=dtype) for name, _, dtype, width, fill in fields}
     if store is not None:  # what earlier runs finished of this rank's shard
-        argmax[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
-        pmax[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
+        for name, column, *_ in fields:
+            local[name][done[lo:hi]] = store.rec[column][lo:hi][done[lo:hi]]
 
-    def finished(trials, a, p):
+    def finished(trials, values):
         trials = np.asarray(trials, dtype=np.int64)
-        argmax[trials - lo] = np.asarray(a, dtype=np.int64)
-        pmax[trials - lo] = np.asarray(p, dtype=np.float64)
+        columns = {}
+        for (name, column, dtype, width, _), v in zip(fields, values):
+            columns[column] = np.asarray(v, dtype=dtype).reshape((len(trials),) + width)
+            local[name][trials - lo] = columns[column]
         if store is not None:
-            store.put(trials, doa_all[trials], a, p)
+            store.put(trials, truth[trials], **columns)
 
-    def flush(sig_batch, time_in, trials):
-        a, p = localizer(sig_batch, time_in)
-        finished(trials, a, p)
+    def flush(x, time_in, trials):
+        finished(trials, read_out(x, time_in, truth[trials]))
 
     if mode == "parity":
         # the reference's global MT19937 stream, replayed on every rank; a rank keeps the trials of its shard (a resumed sweep: the
         # ones of its shard that no earlier run finished -- the stream is drawn for every trial all the same)
         np.random.seed(seed)
-        T = len(np.arange(time_test.min(), time_test.max(), step=1 / beamf.fs))
+        T = len(np.arange(np.min(time_test), np.max(time_test), step=1 / fs)) if skip_frames is None else skip_frames
         sigs, ids, time_in = [], [], None
         for trial in range(total):
-            doa = np.random.rand(1)[0] * 2 * np.pi
-            doa_all[trial] = doa
+            truth[trial] = draw(np.random.rand, 1)[0]
             if lo <= trial < hi and not done[trial]:
-                time_in, sig = synthesize_array_signal(beamf.geometry, beamf.fs, time_test, sig_test, doa)
-                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_db_trial[trial] / 10)) * np.random.randn(*sig.shape)
+                time_in, sig = host_trial(truth[trial], snr_trial[trial])
                 sigs.append(sig)
                 ids.append(trial)
                 if len(sigs) == batch_trials:
@@ -372,36 +438,61 @@ def _template_sweep(beamf, bf_mat, doa_list, time_test, sig_test, snr_db_trial, 
                 np.random.randn(T, M)  # keep the stream aligned: the reference draws T x M normals for every trial
         if sigs:
             flush(np.stack(sigs), time_in, ids)
-    elif mode == "throughput":
+    else:
         from . import synthesis
 
-        rng = np.random.RandomState(seed)
-        doa_all[:] = rng.rand(total) * 2 * np.pi
+        truth[:] = draw(np.random.RandomState(seed).rand, total)  # every rank draws every trial: no dependence on the world size
         ranges = [(s0, min(hi, s0 + batch_trials)) for s0 in range(lo, hi, batch_trials)]
         ranges = [(s0, s1) for s0, s1 in ranges if not done[s0:s1].all()]  # (a batch with any trial missing is recomputed whole)
-        if pipelined and ranges:
-            # the default localizer: several batches in flight, no host synchronisation between them (same bits)
-            _throughput_pipelined(beamf, bf_mat, time_test, sig_test, doa_all, snr_db_trial, lo, hi, batch_trials, seed, streams, scan_lane_cus,
-                                  ranges=ranges, on_done=lambda s0, s1, a, p: finished(np.arange(s0, s1), a, p))
-        for s0, s1 in (() if pipelined else ranges):
-            # noise-free array signals synthesised on the device (bit-exact with the host np.interp path), noise from the
-            # Philox kernel, numbered by GLOBAL trial: the same draw for any sharding
-            time_in, x = beamf.synthesize_batch((time_test, sig_test), doa_all[s0:s1])
-            synthesis.add_noise_(x, snr_db_trial[s0:s1], seed=seed, first_trial=s0)
-            flush(x, time_in, np.arange(s0, s1))
-    else:
-        raise ValueError("mode must be 'parity' or 'throughput'")
+        if pipelined is not None and ranges:
+            pipelined(truth, lo, hi, ranges, lambda s0, s1, *values: finished(np.arange(s0, s1), values))
+        else:
+            for s0, s1 in ranges:
+                # noise-free array signals synthesised on the device (bit-exact with the host np.interp path), noise from the
+                # Philox kernel, numbered by GLOBAL trial: the same draw for any sharding
+                time_in, x = device_batch(truth[s0:s1])
+                synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
+                flush(x, time_in, np.arange(s0, s1))
 
-    # the one exchange step: {argmax i64, pmax f64} per trial in ONE all-gather (the DoAs come from the shared stream: every rank has them)
-    exchange = {}
-    full = gather_shards({"argmax": argmax, "pmax": pmax}, total, rank, world_size, group, stats=exchange)
-    err = doa_error(np.asarray(doa_list)[full["argmax"]], doa_all)
-    shape = (total // num_sim, num_sim)
-    res = dict(doa=doa_all.reshape(shape), argmax=full["argmax"].reshape(shape), pmax=full["pmax"].reshape(shape), err=err.reshape(shape),
-               mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, exchange=exchange)
+    # the one exchange step: every field of every trial in ONE all-gather (the truths come from the shared stream: every rank has them)
+    extra = dict(exchange={})
+    full = gather_shards(local, total, rank, world_size, group, stats=extra["exchange"])
     if store is not None:
-        res["persistence"] = store.stats()
-    return res
+        extra["persistence"] = store.stats()
+    return truth, full, extra
+
+
+def _one_target(beamf, time_test, sig_test):
+    """The trials of the noisy-target sweep as _monte_carlo takes them (:450-457): `doa = rand(1)[0] * 2 pi`, apply_to_template on the
+    host (parity mode) or on the device (throughput mode)."""
+    return dict(draw=_one_doa, host_trial=_with_noise(lambda doa: synthesize_array_signal(beamf.geometry, beamf.fs, time_test, sig_test, doa)),
+                device_batch=lambda doas: beamf.synthesize_batch((time_test, sig_test), doas))
+
+
+def _template_sweep(beamf, bf_mat, doa_list, time_test, sig_test, snr_db_trial, num_sim, seed, mode, rank, world_size, group,
+                    localizer, batch_trials, streams=4, scan_lane_cus=4, out_dir=None, sweep_name="template", store_key=None):
+    """The noisy-target and the speech sweep, SNN or MUSIC (target_snn_localization.py:447-467 / :224-245): per trial
+    `doa = rand(1)[0] * 2 pi`, apply_to_template at `snr_db_trial[trial]`, power, arg-max, pi-periodic error.
+    Trials are processed in batches of `batch_trials` (host memory: a speech trial is 18.6 MB).  With the default localizer and
+    streams > 0 the throughput mode keeps several batches in flight (_throughput_pipelined).
+    store_key: the ShardStore key entries that describe the localizer (default: the hash of bf_mat)."""
+    pipelined = None
+    if localizer is None and streams > 0:
+        # the default localizer: several batches in flight, no host synchronisation between them (same bits)
+        def pipelined(doa_all, lo, hi, ranges, on_done):
+            _throughput_pipelined(beamf, bf_mat, time_test, sig_test, doa_all, snr_db_trial, lo, hi, batch_trials, seed, streams, scan_lane_cus,
+                                  ranges=ranges, on_done=on_done)
+
+    localizer = localizer or device_localizer(beamf, bf_mat, max_batch=batch_trials)
+    doa_all, full, extra = _monte_carlo(
+        sweep_name, beamf.geometry, beamf.fs, doa_list, time_test, sig_test, snr_db_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
+        key=dict(bf_mat=np.asarray(bf_mat)) if store_key is None else store_key,
+        fields=(("argmax", "index", np.int64, (), 0), ("pmax", "pmax", np.float64, (), 0.0)),
+        read_out=lambda x, time_in, doas: localizer(x, time_in), pipelined=pipelined, **_one_target(beamf, time_test, sig_test))
+    err = doa_error(np.asarray(doa_list)[full["argmax"]], doa_all)
+    shape = (len(snr_db_trial) // num_sim, num_sim)
+    return dict(doa=doa_all.reshape(shape), argmax=full["argmax"].reshape(shape), pmax=full["pmax"].reshape(shape), err=err.reshape(shape),
+                mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, **extra)
 
 
 def noisy_target_sweep(beamf, bf_mat, doa_list, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1,
@@ -410,13 +501,7 @@ def noisy_target_sweep(beamf, bf_mat, doa_list, snr_db_vec=None, num_sim=100, se
     """paper_plots/target_snn_localization.py:435-467.  Returns dict(doa, argmax, err, pmax: [num_snr, num_sim];
     mae_deg [num_snr]) on every rank.  out_dir: every finished batch is written there and a rerun with the same arguments resumes
     (ShardStore; `persistence` in the result says what was loaded and written)."""
-    fs = beamf.fs
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
-    if snr_gain_due_to_bandwidth is None:
-        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0  # (fs/2)/(f_max - f_min) with the paper's [1, 2] kHz band
-    time_test = np.arange(0, test_duration, step=1 / fs)
-    sig_test = np.sin(2 * np.pi * freq_design * time_test)
-    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)  # :449
+    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(beamf.fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
     res = _template_sweep(beamf, bf_mat, doa_list, time_test, sig_test, snr_trial, num_sim, seed, mode, rank, world_size, group,
                           localizer, batch_trials, streams, out_dir=out_dir, sweep_name="noisy")
     res["snr_db_vec"] = snr_db_vec
@@ -449,7 +534,7 @@ def speech_target_sweep(beamf, bf_mat, doa_list, source, snr_db_vec=None, num_si
     out_dir: per-batch result files and resume, as in noisy_target_sweep."""
     if batch_trials is None:
         batch_trials = 125 if mode == "throughput" else 25
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    snr_db_vec = _snr_vec(snr_db_vec)
     time_fs, sig_test = source
     res = _template_sweep(beamf, bf_mat, doa_list, np.asarray(time_fs, dtype=np.float64), np.asarray(sig_test, dtype=np.float64),
                           np.repeat(snr_db_vec, num_sim), num_sim, seed, mode, rank, world_size, group, localizer, batch_trials, streams,
@@ -463,22 +548,13 @@ def music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_b
     of at most `max_batch` trials; the [B, S, G] spectra stay in the workspace.  With num_sources=K: (peaks [B, K] int64,
     peak_power [B, K]) instead (multi_target_sweep)."""
 
-    def run(sig_batch, time_vec):
-        am, pm = [], []
-        for s in range(0, len(sig_batch), max_batch):
-            if num_sources is not None:
-                out = music.localize_batch(sig_batch[s : s + max_batch], num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False,
-                                           num_sources=num_sources, min_separation=min_separation, rel_threshold=rel_threshold)
-                am.append(out["peaks"].cpu().numpy().astype(np.int64))
-                pm.append(out["peak_power"].cpu().numpy())
-                continue
-            out = music.localize_batch(sig_batch[s : s + max_batch], num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False)
-            a = out["argmax"].cpu().numpy().astype(np.int64)
-            am.append(a)
-            pm.append(out["power"].cpu().numpy()[np.arange(len(a)), a])
-        return np.concatenate(am), np.concatenate(pm)
+    def one(x):
+        if num_sources is not None:
+            return _peaks_and_power(music.localize_batch(x, num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False,
+                                                         num_sources=num_sources, min_separation=min_separation, rel_threshold=rel_threshold))
+        return _argmax_and_power(music.localize_batch(x, num_active_freq, duration_overlap, num_fft_bin, want_spectrum=False))
 
-    return run
+    return lambda sig_batch, time_vec: _in_batches(sig_batch, max_batch, one)
 
 
 def _music_store_key(music, num_active_freq, duration_overlap, num_fft_bin):
@@ -494,14 +570,9 @@ def music_noisy_sweep(music, snr_db_vec=None, num_sim=100, seed=0, mode="parity"
     apply_to_template (k = 1, N = 2048, no overlap), power = mean_s |P|^2, arg-max, arcsin|sin(err)|.  `music` is a MUSIC (the script's:
     7-mic circular array, band [1600, 2400], 57 DoAs, frame_duration 1.0).  Modes, sharding and out_dir resume as noisy_target_sweep;
     the ShardStore key also covers band, N, k, overlap and frame duration."""
-    fs = music.fs
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
-    if snr_gain_due_to_bandwidth is None:
-        f_min, f_max = music.freq_range
-        snr_gain_due_to_bandwidth = (fs / 2) / (f_max - f_min)
-    time_test = np.arange(0, test_duration, step=1 / fs)
-    sig_test = np.sin(2 * np.pi * freq_design * time_test)
-    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    f_min, f_max = music.freq_range
+    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(music.fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth,
+                                                              band_hz=f_max - f_min)
     loc = music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=batch_trials)
     res = _template_sweep(music, None, music.doa_list, time_test, sig_test, snr_trial, num_sim, seed, mode, rank, world_size, group, loc,
                           batch_trials, 0, out_dir=out_dir, sweep_name="music-noisy",
@@ -515,7 +586,7 @@ def music_speech_sweep(music, source, snr_db_vec=None, num_sim=100, seed=0, mode
     """The speech-target MUSIC sweep of paper_plots/target_localization_MUSIC.py (test_speech_target, statistical part): `source` =
     (time_fs, sig_test) from `speech_source`, 11 SNRs x num_sim trials, NO bandwidth correction, k = 1, N = 2048 (the script's MUSIC:
     449 DoAs, frame_duration 1.0: 7 slices per trial).  Modes, sharding and out_dir resume as music_noisy_sweep."""
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    snr_db_vec = _snr_vec(snr_db_vec)
     time_fs, sig_test = source
     loc = music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=batch_trials)
     res = _template_sweep(music, None, music.doa_list, np.asarray(time_fs, dtype=np.float64), np.asarray(sig_test, dtype=np.float64),
@@ -540,7 +611,7 @@ def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity",
     from .xylo_snn_localization import signal_from_template
 
     fs = demo.fs
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
+    snr_db_vec = _snr_vec(snr_db_vec)
     f_min, f_max = [float(v) for v in demo.freq_bands[0]]
     if snr_gain_due_to_bandwidth is None:
         snr_gain_due_to_bandwidth = (fs / 2) / (f_max - f_min)
@@ -550,100 +621,52 @@ def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity",
     sig_test = np.sin(2 * np.pi * np.cumsum(freq_inst) * 1 / fs)
     geometry = demo.beamfs[0].geometry
     doa_list = demo.doa_list
-    num_grid = len(doa_list)
-    win_size = 2 * ((num_grid // 32) // 2) + 1
-    total = len(snr_db_vec) * num_sim
+    win_size = 2 * ((len(doa_list) // 32) // 2) + 1
     snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
-    lo, hi = shard_range(total, rank, world_size)
     if batch_trials is None:
         batch_trials = 1100 if mode == "throughput" else 50
     if device_delays is None:
         device_delays = mode == "throughput"
-    doa_all = np.zeros(total)
-    index = np.zeros(hi - lo, dtype=np.int64)
-
     if peak is None:
         peak = "device" if mode == "throughput" else "host"
-    store = None
-    if out_dir is not None:
-        store = ShardStore(out_dir, "xylo", total, seed=int(seed), mode=mode, snr_db_trial=snr_trial, doa_list=np.asarray(doa_list, dtype=np.float64),
-                           bf_mat=np.asarray(demo.bf_mats[0]), fs=float(fs), num_mic=len(geometry), bipolar=bool(demo.bipolar_spikes),
-                           time_test=time_test, sig_test=sig_test, peak=peak, device_delays=bool(device_delays), win_size=int(win_size),
-                           r_vec=np.asarray(geometry.r_vec, dtype=np.float64), theta_vec=np.asarray(geometry.theta_vec, dtype=np.float64))
-    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
-    if store is not None:
-        index[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
 
-    def flush(x, trials):
-        trials = np.asarray(trials, dtype=np.int64)
+    def host_trial(doa, snr_db):
+        sig = signal_from_template(geometry, (time_test, sig_test, doa))
+        noise_sigma = np.sqrt(np.mean(sig**2) / 10 ** (snr_db / 10))
+        return None, sig + noise_sigma * np.random.randn(*sig.shape)
+
+    def read_out(x, time_in, doas):
         if peak == "device":  # find_peak_location on the device (exact integer window sums): only indices come back
             idx = demo.peak_batch(x, win_size).cpu().numpy().astype(np.int64)
             demo.network().check()  # (the copy above synchronised: a broken ticket-queue launch raises here)
-        else:
-            rate = demo.rate_batch(x).cpu().numpy()  # [B, G]: mean(spikes_out) * fs per DoA
-            demo.network().check()
-            idx = []
-            for p in rate:
-                mx = p.max()
-                p = p / mx if mx > 0 else p  # :595 (an all-silent output divides 0 by 0 in the reference)
-                idx.append(int(find_peak_location(sig_in=p, win_size=win_size)))
-            idx = np.asarray(idx, dtype=np.int64)
-        index[trials - lo] = idx
-        if store is not None:
-            store.put(trials, doa_all[trials], idx, np.zeros(len(trials)))
+            return (idx,)
+        rate = demo.rate_batch(x).cpu().numpy()  # [B, G]: mean(spikes_out) * fs per DoA
+        demo.network().check()
+        idx = []
+        for p in rate:
+            mx = p.max()
+            p = p / mx if mx > 0 else p  # :595 (an all-silent output divides 0 by 0 in the reference)
+            idx.append(int(find_peak_location(sig_in=p, win_size=win_size)))
+        return (idx,)
 
-    if mode == "parity":
-        np.random.seed(seed)
-        T, M = len(time_test), len(geometry)
-        sigs, ids = [], []
-        for trial in range(total):
-            doa = np.random.rand(1)[0] * 2 * np.pi
-            doa_all[trial] = doa
-            if lo <= trial < hi and not done[trial]:
-                sig = signal_from_template(geometry, (time_test, sig_test, doa))
-                noise_sigma = np.sqrt(np.mean(sig**2) / 10 ** (snr_trial[trial] / 10))
-                sigs.append(sig + noise_sigma * np.random.randn(*sig.shape))
-                ids.append(trial)
-                if len(sigs) == batch_trials:
-                    flush(np.stack(sigs), ids)
-                    sigs, ids = [], []
-            else:
-                np.random.randn(T, M)
-        if sigs:
-            flush(np.stack(sigs), ids)
-    elif mode == "throughput":
-        rng = np.random.RandomState(seed)
-        doa_all[:] = rng.rand(total) * 2 * np.pi
-        for s0 in range(lo, hi, batch_trials):
-            s1 = min(hi, s0 + batch_trials)
-            if done[s0:s1].all():
-                continue
-            x = synthesis.signal_from_template_batch(geometry, (time_test, sig_test), doa_all[s0:s1], device=demo.device, device_delays=device_delays)
-            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
-            flush(x, np.arange(s0, s1))
-    else:
-        raise ValueError("mode must be 'parity' or 'throughput'")
-
-    full = gather_shards({"index": index}, total, rank, world_size, group)
+    # (the record's `pmax` stays zero: this sweep keeps the peak index alone; a skipped trial consumes the frames of time_test itself)
+    doa_all, full, extra = _monte_carlo(
+        "xylo", geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
+        key=dict(bf_mat=np.asarray(demo.bf_mats[0]), bipolar=bool(demo.bipolar_spikes), peak=peak, device_delays=bool(device_delays),
+                 win_size=int(win_size)),
+        fields=(("index", "index", np.int64, (), 0),), draw=_one_doa, host_trial=host_trial, skip_frames=len(time_test),
+        device_batch=lambda doas: (None, synthesis.signal_from_template_batch(geometry, (time_test, sig_test), doas, device=demo.device,
+                                                                              device_delays=device_delays)),
+        read_out=read_out)
+    del extra["exchange"]  # (this sweep's result has never reported its exchange)
     err = doa_error(np.asarray(doa_list)[full["index"]], doa_all)
     shape = (len(snr_db_vec), num_sim)
-    res = dict(doa=doa_all.reshape(shape), index=full["index"].reshape(shape), err=err.reshape(shape),
-               mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, snr_db_vec=snr_db_vec, win_size=win_size, parity="unpinned (integer LIF)")
-    if store is not None:
-        res["persistence"] = store.stats()
-    return res
+    return dict(doa=doa_all.reshape(shape), index=full["index"].reshape(shape), err=err.reshape(shape),
+                mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, snr_db_vec=snr_db_vec, win_size=win_size, parity="unpinned (integer LIF)",
+                **extra)
 
 
 # ---- multi-target sweep ---------------------------------------------------------------------------------------------------------
-
-class MultiShardStore(ShardStore):
-    """ShardStore of multi_target_sweep: a record holds K DoAs, K peak indices and K peak values per trial."""
-
-    def __init__(self, out_dir, sweep, total, num_targets, **key):
-        K = int(num_targets)
-        self.REC = np.dtype([("trial", "<i8"), ("doa", "<f8", (K,)), ("index", "<i8", (K,)), ("pmax", "<f8", (K,))])
-        super().__init__(out_dir, sweep, total, num_targets=K, **key)
-
 
 def _method_key(beamf):
     """ShardStore key entries for the localizer's own parameters: its class, for the beamformers the plan key (Hilbert kernel,
@@ -665,6 +688,11 @@ def _method_key(beamf):
         key["music_doa_list"] = np.asarray(beamf.doa_list, dtype=np.float64)
         key["speed"] = float(beamf.geometry.speed)
     return key
+
+
+def _localizer_key(beamf, bf_mat, store_key):
+    """ShardStore key entries of a sweep's localizer: bf_mat (where there is one), the method's own parameters, then store_key."""
+    return {**({} if bf_mat is None else dict(bf_mat=np.asarray(bf_mat))), **_method_key(beamf), **(store_key or {})}
 
 
 def _draw_doas(draw, K, min_separation, max_redraws):
@@ -763,106 +791,30 @@ def multi_target_sweep(beamf, bf_mat, doa_list, num_targets=2, min_separation=np
         raise ValueError(f"gains has {len(gains)} entries for {K} targets")
     peak_separation = min_separation / 2 if peak_separation is None else float(peak_separation)
     tol = min_separation / 2 if tol is None else float(tol)
-    if mode not in ("parity", "throughput"):
-        raise ValueError("mode must be 'parity' or 'throughput'")
     doa_list = np.asarray(doa_list, dtype=np.float64)
-    fs = beamf.fs
-    M = len(beamf.geometry)
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
-    if snr_gain_due_to_bandwidth is None:
-        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
-    time_test = np.arange(0, test_duration, step=1 / fs)
-    sig_test = np.sin(2 * np.pi * freq_design * time_test)
-    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
-    total = len(snr_trial)
-    lo, hi = shard_range(total, rank, world_size)
-    store = None
-    if out_dir is not None:
-        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
-        key.update(_method_key(beamf))
-        key.update(store_key or {})
-        store = MultiShardStore(out_dir, "multi-noisy", total, K, seed=int(seed), mode=mode, snr_db_trial=snr_trial, doa_list=doa_list,
-                                min_separation=min_separation, peak_separation=peak_separation, tol=tol, gains=gains,
-                                rel_threshold=float(rel_threshold), time_test=time_test, sig_test=sig_test, fs=float(fs), num_mic=M,
-                                r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
-                                theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
-    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
+    fs, geometry = beamf.fs, beamf.geometry
+    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
     if localizer is None:
         localizer = device_localizer(beamf, bf_mat, max_batch=batch_trials, num_sources=K, doa_list=doa_list, min_separation=peak_separation,
                                      rel_threshold=rel_threshold)
-    doa_all = np.zeros((total, K))
-    index = np.full((hi - lo, K), -1, dtype=np.int64)
-    value = np.full((hi - lo, K), np.nan)
-    if store is not None:
-        index[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
-        value[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
-
-    def flush(sig_batch, time_in, trials):
-        trials = np.asarray(trials, dtype=np.int64)
-        a, p = localizer(sig_batch, time_in)
-        a = np.asarray(a, dtype=np.int64).reshape(len(trials), K)
-        p = np.asarray(p, dtype=np.float64).reshape(len(trials), K)
-        index[trials - lo], value[trials - lo] = a, p
-        if store is not None:
-            store.put(trials, doa_all[trials], a, p)
-
-    if mode == "parity":
-        np.random.seed(seed)
-        T = len(np.arange(time_test.min(), time_test.max(), step=1 / fs))
-        sigs, ids, time_in = [], [], None
-        for trial in range(total):
-            doa_all[trial] = _draw_doas(np.random.rand, K, min_separation, max_redraws)
-            if lo <= trial < hi and not done[trial]:
-                time_in, sig = synthesize_targets(beamf.geometry, fs, time_test, sig_test, doa_all[trial], gains)
-                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
-                sigs.append(sig)
-                ids.append(trial)
-                if len(sigs) == batch_trials:
-                    flush(np.stack(sigs), time_in, ids)
-                    sigs, ids = [], []
-            else:
-                np.random.randn(T, M)  # keep the stream aligned
-        if sigs:
-            flush(np.stack(sigs), time_in, ids)
-    else:
-        from . import synthesis
-
-        rng = np.random.RandomState(seed)
-        for trial in range(total):  # every rank draws every trial: the DoAs do not depend on the world size
-            doa_all[trial] = _draw_doas(rng.rand, K, min_separation, max_redraws)
-        ranges = [(s0, min(hi, s0 + batch_trials)) for s0 in range(lo, hi, batch_trials)]
-        for s0, s1 in ranges:
-            if done[s0:s1].all():
-                continue
-            time_in, x = synthesize_targets_batch(beamf.geometry, fs, time_test, sig_test, doa_all[s0:s1], gains, device=getattr(beamf, "device", None))
-            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
-            flush(x, time_in, np.arange(s0, s1))
-
-    # the one exchange step: K index columns and K value columns in ONE all-gather
-    exchange = {}
-    local = {f"index{k}": np.ascontiguousarray(index[:, k]) for k in range(K)}
-    local.update({f"value{k}": np.ascontiguousarray(value[:, k]) for k in range(K)})
-    full = gather_shards(local, total, rank, world_size, group, stats=exchange)
-    peaks = np.stack([full[f"index{k}"] for k in range(K)], axis=1)
-    power = np.stack([full[f"value{k}"] for k in range(K)], axis=1)
+    # (a trial no run finished reads -1 / NaN: "no peak"; at K = 1 the draws are the noisy sweep's, one rand(1) per trial)
+    doa_all, full, extra = _monte_carlo(
+        "multi-noisy", geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
+        key=dict(num_targets=K, min_separation=min_separation, peak_separation=peak_separation, tol=tol, gains=gains,
+                 rel_threshold=float(rel_threshold), **_localizer_key(beamf, bf_mat, store_key)),
+        rec=[("trial", "<i8"), ("doa", "<f8", (K,)), ("index", "<i8", (K,)), ("pmax", "<f8", (K,))],
+        fields=(("peaks", "index", np.int64, (K,), -1), ("peak_power", "pmax", np.float64, (K,), np.nan)), truth_width=(K,),
+        draw=lambda rand, n: np.stack([_draw_doas(rand, K, min_separation, max_redraws) for _ in range(n)]),
+        host_trial=_with_noise(lambda doas: synthesize_targets(geometry, fs, time_test, sig_test, doas, gains)),
+        device_batch=lambda doas: synthesize_targets_batch(geometry, fs, time_test, sig_test, doas, gains, device=getattr(beamf, "device", None)),
+        read_out=lambda x, time_in, doas: localizer(x, time_in))
+    peaks = full["peaks"]
     err = match_errors(doa_all, doa_list, peaks)
     tol_ok = np.all((peaks >= 0) & (err <= tol), axis=1)
-    S = total // num_sim
-    res = dict(doa=doa_all.reshape(S, num_sim, K), peaks=peaks.reshape(S, num_sim, K), peak_power=power.reshape(S, num_sim, K),
-               err=err.reshape(S, num_sim, K), mae_deg=np.mean(err.reshape(S, num_sim * K), axis=1) * 180 / np.pi,
-               resolved_rate=np.mean(tol_ok.reshape(S, num_sim), axis=1), snr_db_vec=snr_db_vec, exchange=exchange)
-    if store is not None:
-        res["persistence"] = store.stats()
-    return res
-
-
-class WindowShardStore(ShardStore):
-    """ShardStore of windowed_target_sweep: a record holds one arg-max and its power per window of the trial."""
-
-    def __init__(self, out_dir, sweep, total, num_windows, **key):
-        nW = int(num_windows)
-        self.REC = np.dtype([("trial", "<i8"), ("doa", "<f8"), ("index", "<i8", (nW,)), ("pmax", "<f8", (nW,))])
-        super().__init__(out_dir, sweep, total, record_width=nW, **key)
+    S = len(snr_db_vec)
+    return dict(doa=doa_all.reshape(S, num_sim, K), peaks=peaks.reshape(S, num_sim, K), peak_power=full["peak_power"].reshape(S, num_sim, K),
+                err=err.reshape(S, num_sim, K), mae_deg=np.mean(err.reshape(S, num_sim * K), axis=1) * 180 / np.pi,
+                resolved_rate=np.mean(tol_ok.reshape(S, num_sim), axis=1), snr_db_vec=snr_db_vec, **extra)
 
 
 def median_window_index(doa_list, index):
@@ -893,8 +845,6 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
     width nW and the method's parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer)."""
     from .utils import window_bounds
 
-    if mode not in ("parity", "throughput"):
-        raise ValueError("mode must be 'parity' or 'throughput'")
     window = int(window)
     hop = window if hop is None else int(hop)
     if window < 1 or hop < 1:
@@ -903,106 +853,29 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
         raise ValueError("the windowed sweep needs hop <= window (a window past the recording would hold no frame)")
     doa_list = np.asarray(doa_list, dtype=np.float64)
     fs = beamf.fs
-    M = len(beamf.geometry)
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
-    if snr_gain_due_to_bandwidth is None:
-        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
-    time_test = np.arange(0, test_duration, step=1 / fs)
-    sig_test = np.sin(2 * np.pi * freq_design * time_test)
-    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
     total = len(snr_trial)
-    T = len(np.arange(time_test.min(), time_test.max(), step=1 / fs))
-    start, _ = window_bounds(T, window, hop)
+    start, _ = window_bounds(len(np.arange(time_test.min(), time_test.max(), step=1 / fs)), window, hop)
     nW = len(start)
-    lo, hi = shard_range(total, rank, world_size)
-    store = None
-    if out_dir is not None:
-        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
-        key.update(_method_key(beamf))
-        key.update(store_key or {})
-        store = WindowShardStore(out_dir, "windowed-noisy", total, nW, window=window, hop=hop, seed=int(seed), mode=mode, snr_db_trial=snr_trial,
-                                 doa_list=doa_list, time_test=time_test, sig_test=sig_test, fs=float(fs), num_mic=M,
-                                 r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
-                                 theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
-    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
     if localizer is None:
         localizer = device_localizer(beamf, bf_mat, max_batch=batch_trials, window=window, hop=hop)
-    doa_all = np.zeros(total)
-    index = np.zeros((hi - lo, nW), dtype=np.int64)
-    value = np.zeros((hi - lo, nW))
-    if store is not None:
-        index[done[lo:hi]] = store.rec["index"][lo:hi][done[lo:hi]]
-        value[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
-
-    def flush(sig_batch, time_in, trials):
-        trials = np.asarray(trials, dtype=np.int64)
-        a, p = localizer(sig_batch, time_in)
-        a = np.asarray(a, dtype=np.int64).reshape(len(trials), nW)
-        p = np.asarray(p, dtype=np.float64).reshape(len(trials), nW)
-        index[trials - lo], value[trials - lo] = a, p
-        if store is not None:
-            store.put(trials, doa_all[trials], a, p)
-
-    if mode == "parity":
-        # noisy_target_sweep's replay of the reference's global MT19937 stream (_template_sweep)
-        np.random.seed(seed)
-        sigs, ids, time_in = [], [], None
-        for trial in range(total):
-            doa = np.random.rand(1)[0] * 2 * np.pi
-            doa_all[trial] = doa
-            if lo <= trial < hi and not done[trial]:
-                time_in, sig = synthesize_array_signal(beamf.geometry, fs, time_test, sig_test, doa)
-                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
-                sigs.append(sig)
-                ids.append(trial)
-                if len(sigs) == batch_trials:
-                    flush(np.stack(sigs), time_in, ids)
-                    sigs, ids = [], []
-            else:
-                np.random.randn(T, M)  # keep the stream aligned
-        if sigs:
-            flush(np.stack(sigs), time_in, ids)
-    else:
-        from . import synthesis
-
-        rng = np.random.RandomState(seed)
-        doa_all[:] = rng.rand(total) * 2 * np.pi
-        for s0 in range(lo, hi, batch_trials):
-            s1 = min(hi, s0 + batch_trials)
-            if done[s0:s1].all():
-                continue
-            # device synthesis + Philox noise numbered by global trial, as noisy_target_sweep's throughput mode (the same bits)
-            time_in, x = beamf.synthesize_batch((time_test, sig_test), doa_all[s0:s1])
-            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
-            flush(x, time_in, np.arange(s0, s1))
-
-    # the one exchange step: nW index columns and nW value columns in ONE all-gather
-    exchange = {}
-    local = {f"index{n}": np.ascontiguousarray(index[:, n]) for n in range(nW)}
-    local.update({f"value{n}": np.ascontiguousarray(value[:, n]) for n in range(nW)})
-    full = gather_shards(local, total, rank, world_size, group, stats=exchange)
-    w_index = np.stack([full[f"index{n}"] for n in range(nW)], axis=1)
-    w_value = np.stack([full[f"value{n}"] for n in range(nW)], axis=1)
+    doa_all, full, extra = _monte_carlo(
+        "windowed-noisy", beamf.geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
+        key=dict(record_width=nW, window=window, hop=hop, **_localizer_key(beamf, bf_mat, store_key)),
+        rec=[("trial", "<i8"), ("doa", "<f8"), ("index", "<i8", (nW,)), ("pmax", "<f8", (nW,))],
+        fields=(("index", "index", np.int64, (nW,), 0), ("value", "pmax", np.float64, (nW,), 0.0)),
+        read_out=lambda x, time_in, doas: localizer(x, time_in), **_one_target(beamf, time_test, sig_test))
+    w_index, w_value = full["index"], full["value"]
     w_err = doa_error(doa_list[w_index], doa_all[:, None])
     med = median_window_index(doa_list, w_index)
     med_window = np.argmax(w_index == med[:, None], axis=1)  # (the first window that gave the median estimate)
     err = doa_error(doa_list[med], doa_all)
-    S = total // num_sim
+    S = len(snr_db_vec)
     shape = (S, num_sim)
-    res = dict(doa=doa_all.reshape(shape), window_argmax=w_index.reshape(S, num_sim, nW), window_pmax=w_value.reshape(S, num_sim, nW),
-               window_err=w_err.reshape(S, num_sim, nW), window_mae_deg=np.mean(w_err.reshape(S, num_sim, nW), axis=1) * 180 / np.pi,
-               window_start=start, argmax=med.reshape(shape), pmax=w_value[np.arange(total), med_window].reshape(shape), err=err.reshape(shape),
-               mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, snr_db_vec=snr_db_vec, exchange=exchange)
-    if store is not None:
-        res["persistence"] = store.stats()
-    return res
-
-
-class TrackShardStore(ShardStore):
-    """ShardStore of moving_target_sweep: a record holds the trial's phase (`doa`), the mean (`pmax`) and the median (`med`) of its
-    per-frame errors."""
-
-    REC = np.dtype([("trial", "<i8"), ("doa", "<f8"), ("index", "<i8"), ("pmax", "<f8"), ("med", "<f8")])
+    return dict(doa=doa_all.reshape(shape), window_argmax=w_index.reshape(S, num_sim, nW), window_pmax=w_value.reshape(S, num_sim, nW),
+                window_err=w_err.reshape(S, num_sim, nW), window_mae_deg=np.mean(w_err.reshape(S, num_sim, nW), axis=1) * 180 / np.pi,
+                window_start=start, argmax=med.reshape(shape), pmax=w_value[np.arange(total), med_window].reshape(shape), err=err.reshape(shape),
+                mae_deg=np.mean(err.reshape(shape), axis=1) * 180 / np.pi, snr_db_vec=snr_db_vec, **extra)
 
 
 def moving_doa_path(time_vec, duration, doa_max, num_period, phase):
@@ -1037,11 +910,8 @@ def track_localizer(beamf, bf_mat, envelope, max_batch=1100):
     """Default localizer of moving_target_sweep: the fused tracking call (track_batch); index [B, T] stays on the device."""
 
     def run(sig_batch, time_vec):
-        import torch
-
         kw = dict(time_vec=time_vec) if hasattr(beamf, "tau_vec") else {}
-        parts = [beamf.track_batch(bf_mat, sig_batch[s : s + max_batch], envelope, **kw)["index"] for s in range(0, len(sig_batch), max_batch)]
-        return torch.cat(parts)
+        return _in_batches(sig_batch, max_batch, lambda x: (beamf.track_batch(bf_mat, x, envelope, **kw)["index"],))[0]
 
     return run
 
@@ -1062,18 +932,9 @@ def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, nu
     err over trials; track_median_deg [num_snr], the median over trials of med; mae_deg = track_mae_deg).  out_dir resume as the other
     sweeps; the key also covers doa_max, num_period, lag_frames, settle_frames, the envelope's window lengths and the method's
     parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer)."""
-    if mode not in ("parity", "throughput"):
-        raise ValueError("mode must be 'parity' or 'throughput'")
     doa_list = np.asarray(doa_list, dtype=np.float64)
-    fs = beamf.fs
-    M = len(beamf.geometry)
-    snr_db_vec = np.asarray(np.linspace(-10, 20, 11) if snr_db_vec is None else snr_db_vec, dtype=np.float64)
-    if snr_gain_due_to_bandwidth is None:
-        snr_gain_due_to_bandwidth = (fs / 2) / 1000.0
-    time_test = np.arange(0, test_duration, step=1 / fs)
-    sig_test = np.sin(2 * np.pi * freq_design * time_test)
-    snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
-    total = len(snr_trial)
+    fs, geometry = beamf.fs, beamf.geometry
+    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
     time_in = np.arange(time_test.min(), time_test.max(), step=1 / fs)
     T = len(time_in)
     lag_frames = int(beamf.kernel_duration * fs) if lag_frames is None else int(lag_frames)
@@ -1081,80 +942,36 @@ def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, nu
     if lag_frames < 0 or settle_frames < 0 or max(lag_frames, settle_frames) >= T:
         raise ValueError(f"lag_frames ({lag_frames}) and settle_frames ({settle_frames}) must lie in [0, {T}): no frame to score")
     doa_max, num_period = float(doa_max), float(num_period)
-    lo, hi = shard_range(total, rank, world_size)
-    store = None
-    if out_dir is not None:
-        key = dict(bf_mat=np.asarray(bf_mat)) if bf_mat is not None else {}
-        key.update(_method_key(beamf))
-        key.update(store_key or {})
-        store = TrackShardStore(out_dir, "moving-noisy", total, doa_max=doa_max, num_period=num_period, lag_frames=lag_frames,
-                                settle_frames=settle_frames, win_fall=int(envelope.win_lens[0]), win_rise=int(envelope.win_lens[1]),
-                                seed=int(seed), mode=mode, snr_db_trial=snr_trial, doa_list=doa_list, time_test=time_test, sig_test=sig_test,
-                                fs=float(fs), num_mic=M, r_vec=np.asarray(beamf.geometry.r_vec, dtype=np.float64),
-                                theta_vec=np.asarray(beamf.geometry.theta_vec, dtype=np.float64), **key)
-    done = store.have.copy() if store is not None else np.zeros(total, dtype=bool)
     if localizer is None:
         localizer = track_localizer(beamf, bf_mat, envelope, max_batch=batch_trials)
-    phase = np.zeros(total)
-    err = np.zeros(hi - lo)
-    med = np.zeros(hi - lo)
-    if store is not None:
-        err[done[lo:hi]] = store.rec["pmax"][lo:hi][done[lo:hi]]
-        med[done[lo:hi]] = store.rec["med"][lo:hi][done[lo:hi]]
 
-    def flush(sig_batch, trials):
-        trials = np.asarray(trials, dtype=np.int64)
-        truth = moving_doa_path(time_in, test_duration, doa_max, num_period, phase[trials])
-        e, m = track_errors(doa_list, localizer(sig_batch, time_in), truth, lag_frames, settle_frames)
-        err[trials - lo], med[trials - lo] = e, m
-        if store is not None:
-            store.put(trials, phase[trials], np.zeros(len(trials), dtype=np.int64), e, med=m)
+    def path(time_vec, phase):
+        return moving_doa_path(time_vec, test_duration, doa_max, num_period, phase)
 
-    if mode == "parity":
-        np.random.seed(seed)
-        sigs, ids = [], []
-        for trial in range(total):
-            phase[trial] = np.random.rand(1)[0] * 2 * np.pi
-            if lo <= trial < hi and not done[trial]:
-                doa_t = moving_doa_path(time_test, test_duration, doa_max, num_period, phase[trial])
-                _, sig = synthesize_array_signal(beamf.geometry, fs, time_test, sig_test, doa_t)
-                sig += np.sqrt(np.mean(sig**2)) / np.sqrt(10 ** (snr_trial[trial] / 10)) * np.random.randn(*sig.shape)
-                sigs.append(sig)
-                ids.append(trial)
-                if len(sigs) == batch_trials:
-                    flush(np.stack(sigs), ids)
-                    sigs, ids = [], []
-            else:
-                np.random.randn(T, M)  # keep the stream aligned
-        if sigs:
-            flush(np.stack(sigs), ids)
-    else:
+    def device_batch(phase):  # moving-DoA device synthesis (micloc_synth_targets_f64, moving = 1)
         from . import synthesis
 
-        rng = np.random.RandomState(seed)
-        phase[:] = rng.rand(total) * 2 * np.pi
-        for s0 in range(lo, hi, batch_trials):
-            s1 = min(hi, s0 + batch_trials)
-            if done[s0:s1].all():
-                continue
-            doas = moving_doa_path(time_test, test_duration, doa_max, num_period, phase[s0:s1])
-            # moving-DoA device synthesis (micloc_synth_targets_f64, moving = 1) + Philox noise numbered by global trial
-            _, x = synthesis.apply_to_template_batch(beamf.geometry, fs, (time_test, sig_test), doas, device=getattr(beamf, "device", None),
-                                                     device_delays=True)
-            synthesis.add_noise_(x, snr_trial[s0:s1], seed=seed, first_trial=s0)
-            flush(x, np.arange(s0, s1))
+        return synthesis.apply_to_template_batch(geometry, fs, (time_test, sig_test), path(time_test, phase), device=getattr(beamf, "device", None),
+                                                 device_delays=True)
 
-    exchange = {}
-    full = gather_shards(dict(err=err, med=med), total, rank, world_size, group, stats=exchange)
-    S = total // num_sim
-    shape = (S, num_sim)
+    def read_out(x, _, phase):  # (errors reduced where the index is: a device tensor leaves two scalars per trial to copy)
+        return track_errors(doa_list, localizer(x, time_in), path(time_in, phase), lag_frames, settle_frames)
+
+    # the truth kept per trial is its phase (the record's `doa`); the record's `index` stays zero, `pmax` is the mean error
+    phase, full, extra = _monte_carlo(
+        "moving-noisy", geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
+        key=dict(doa_max=doa_max, num_period=num_period, lag_frames=lag_frames, settle_frames=settle_frames, win_fall=int(envelope.win_lens[0]),
+                 win_rise=int(envelope.win_lens[1]), **_localizer_key(beamf, bf_mat, store_key)),
+        rec=[("trial", "<i8"), ("doa", "<f8"), ("index", "<i8"), ("pmax", "<f8"), ("med", "<f8")],
+        fields=(("err", "pmax", np.float64, (), 0.0), ("med", "med", np.float64, (), 0.0)), draw=_one_doa,
+        host_trial=_with_noise(lambda ph: synthesize_array_signal(geometry, fs, time_test, sig_test, path(time_test, ph))),
+        device_batch=device_batch, read_out=read_out)
+    shape = (len(snr_db_vec), num_sim)
     e, m = full["err"].reshape(shape), full["med"].reshape(shape)
     res = dict(phase=phase.reshape(shape), err=e, med=m, track_mae_deg=np.mean(e, axis=1) * 180 / np.pi,
                track_median_deg=np.median(m, axis=1) * 180 / np.pi, lag_frames=lag_frames, settle_frames=settle_frames, snr_db_vec=snr_db_vec,
-               exchange=exchange)
+               **extra)
     res["mae_deg"] = res["track_mae_deg"]
-    if store is not None:
-        res["persistence"] = store.stats()
     return res
 
 
@@ -1198,7 +1015,6 @@ def main(argv=None):
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
-    import os
 
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy"], default="noisy")
