@@ -974,6 +974,80 @@ int micloc_stream_localize_tile_f64(const micloc_plan *p, const void *enc_state,
     return MICLOC_OK;
 }
 
+// ---- streaming windows: the time-resolved read-out of the same chunk rows, emitted while the recording arrives ----------------
+// win_state: [256 B: int windows emitted][B][ceil(window / hop)][2][G] doubles (stream_windows.hip)
+static int stream_window_args(const micloc_plan *p, int window, int hop, int max_windows)
+{
+    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
+    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
+    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int CH = lif_beamform_chunk_frames(p->W, p->ntab);
+    if (window % CH != 0 || hop % CH != 0 || hop > window) return MICLOC_ERR_SHAPE;
+    return MICLOC_OK;
+}
+
+size_t micloc_stream_window_state_bytes(const micloc_plan *p, int B, int window, int hop, int max_windows)
+{
+    if (!p || bad_batch(B) || p->G_out < 1 || stream_window_args(p, window, hop, max_windows) != MICLOC_OK) return 0;
+    return stream_window_state_bytes(B, p->G_out, window, hop);
+}
+
+int micloc_stream_window_reset(const micloc_plan *p, int B, void *win_state, size_t win_bytes, int window, int hop, int max_windows, void *stream)
+{
+    if (!p || !win_state || bad_batch(B)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    const int rc = stream_window_args(p, window, hop, max_windows);
+    if (rc != MICLOC_OK) return rc;
+    const size_t need = stream_window_state_bytes(B, p->G_out, window, hop);
+    if (bad_ws(win_state, win_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_zero_fill(win_state, need, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_localize_tile_windows_f64(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
+                                            int B, int window_frames, int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                            void *win_state, size_t win_bytes, int window, int hop, int max_windows, double *window_power,
+                                            int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *stream)
+{
+    if (!p || !enc_state || !loc_state || !window_raster || !win_state || !window_argmax || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    const int rc = stream_window_args(p, window, hop, max_windows);
+    if (rc != MICLOC_OK) return rc;
+    const int CH = lif_beamform_chunk_frames(p->W, p->ntab);
+    if (window_frames % CH != 0) return MICLOC_ERR_SHAPE;
+    const int G = p->G_out, Gp = 16 * p->W.GT;
+    if (bad_ws(loc_state, loc_bytes, micloc_stream_localize_state_bytes(p, B))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, window_frames, Gp))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(win_state, win_bytes, stream_window_state_bytes(B, G, window, hop))) return MICLOC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    int *ctl = reinterpret_cast<int *>(loc_state);
+    double *acc = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(loc_state) + 256);
+    const int nwin = window_frames / CH;
+    // the launches of micloc_stream_localize_tile_f64 with the window read-out in front of the commit: loc_state, power and argmax
+    // end with the bits of that call
+    HIP_TRY(launch_stream_horizon(enc_state, B * p->C, p->bipolar, 0, final_tile ? 1 : 0, CH, 0, nwin, ctl, st, 1));
+    BeamformW W = p->W;
+    W.chunk_range = ctl + 4;
+    double *partial = reinterpret_cast<double *>(ws);
+    int nch = 0;
+    HIP_TRY(launch_lif_beamform(W, p->ntab, window_raster, B, window_frames, nullptr, partial, st, &nch));
+    HIP_TRY(launch_stream_accumulate(partial, B, nch, Gp, G, ctl + 4, ctl, acc, ctl + 8, power, argmax, st));
+    HIP_TRY(launch_stream_windows(partial, B, nch, Gp, G, CH, ctl, final_tile ? 1 : 0, window, hop, max_windows, win_state, window_power,
+                                  window_argmax, latest_power, latest_argmax, st));
+    HIP_TRY(launch_stream_commit(ctl, STREAM_BLOCK_CHUNKS, st));
+    HIP_TRY(launch_stream_tick(ctl, st));
+    return MICLOC_OK;
+}
+
+/* windows emitted so far (synchronises the stream) */
+int micloc_stream_window_count(const void *win_state, int *count, void *stream)
+{
+    if (!win_state || !count) return MICLOC_ERR_INVALID;
+    HIP_TRY(hipMemcpyAsync(count, win_state, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return MICLOC_OK;
+}
+
 /* status[0] = chunks beamformed, [1] = frames beamformed, [2] = window-lag failures, [3] = chunks in the open reduction block
  * (synchronises the stream) */
 int micloc_stream_localize_status(const void *loc_state, int *status4, void *stream)

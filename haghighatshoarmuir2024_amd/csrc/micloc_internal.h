@@ -137,6 +137,17 @@ long long window_count(int T, int window, int hop);
 hipError_t launch_window_power(const double *partial, int B, int T, int nchunks, int Gp, int G, int complex_pairs, int Ghalf_pad,
                                int chunk_frames, int window, int hop, double *power_w, int32_t *argmax_w, hipStream_t stream);
 
+// ---- the same read-out while the recording arrives (stream_windows.hip) -------------------------------------------------
+// win_state: [256 B: int windows emitted][B][K][2][G] doubles, K = stream_window_slots = ceil(window / hop) open windows per trial
+int stream_window_slots(int window, int hop);
+size_t stream_window_state_bytes(int B, int G, int window, int hop);
+// between launch_stream_accumulate and launch_stream_commit of a tile: ctl is the head of loc_state (chunks done, the chunk range of
+// this call, the clock); window n goes to row n % max_windows of power_w [B][max_windows][G] / argmax_w [B][max_windows], the newest
+// one also to latest_power [B][G] / latest_argmax [B] (each may be NULL).  hop <= window, both multiples of chunk_frames.
+hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp, int G, int chunk_frames, const int *ctl, int final_tile,
+                                 int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
+                                 double *latest_power, int32_t *latest_argmax, hipStream_t stream);
+
 // fp32-MFMA variant of LIF + beamforming + power (up to 64 channels, bf_mat must fit in LDS)
 hipError_t launch_lif_beamform_f32(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T,
                                    double *partial, hipStream_t stream, int *nchunks);

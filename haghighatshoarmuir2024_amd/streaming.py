@@ -25,17 +25,24 @@ absolute time, so a tile of a given length is one replayable hipGraph -- push_re
 
 Memory: the window (default: tile + 4096 frames, 14 B per frame and trial, twice), one tile of fp64 intermediates, 2 x G doubles per
 trial.  push() allocates nothing and never synchronises (the ready range lives on the device); finish() / status() do.
+
+TIME WINDOWS (window=, hop=): the running power is the mean over every frame since the stream began, which barely reacts to a source
+that moves after a minute of audio.  With `window` the localizer also emits the time-resolved read-out of localize_batch(window=, hop=)
+-- power and arg-max per window of the rule in include/micloc_hip.h ("streaming windows"), each window as soon as its last chunk is
+final, bit for bit the one-shot rows -- into a ring of `max_windows` rows: latest_window() / windows() / finish().  The state is
+2 x G doubles per trial and open window (ceil(window / hop) of them) whatever the length of the stream, and a tile is still one graph.
 """
 import ctypes
 
 import numpy as np
 
-from . import _lib, runtime
+from . import _lib, runtime, utils
 from .snn_beamformer import neuron_impulse_response
 
 
 class StreamingLocalizer:
-    def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False):
+    def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False,
+                 window=None, hop=None, max_windows=None):
         """beamf: SNNBeamformer; bf_mat [2M, G]; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself, and the neuron kernel is
                       normalised over exactly that many samples like apply_to_signal does, snn_beamformer.py:342-361); None: a
@@ -44,7 +51,13 @@ class StreamingLocalizer:
         wrap_tail     [batch, L // 2, M]: the last L // 2 frames of every recording (np.roll's wrap-around), or None (zeros).
         max_tile      longest tile push() will be given; lag_frames: how far spikes may trail the input (an open cluster holds
                       its frames back) before status() reports a lag failure.
-        keep_raster   (tests) also assemble the full spike raster [batch, total_frames, 2M]; needs total_frames."""
+        keep_raster   (tests) also assemble the full spike raster [batch, total_frames, 2M]; needs total_frames.
+        window, hop   frames (hop defaults to window; 1 <= hop <= window, both multiples of the plan's window quantum): also emit power
+                      and arg-max per window (module docstring); None: the running estimate only, with exactly the launches it always had.
+        max_windows   rows of the ring the windows are kept in (window n in row n % max_windows); default: every window of the
+                      recording when total_frames is given, else 64."""
+        if window is None and (hop is not None or max_windows is not None):
+            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
         torch = runtime._torch()
         self.beamf = beamf
         self.plan = beamf.new_plan()
@@ -62,6 +75,15 @@ class StreamingLocalizer:
         self.CH = self.lib.micloc_stream_chunk_frames(self.plan.handle)
         if self.CH <= 0:
             _lib.check(self.CH, "stream_chunk_frames")
+        self.window = self.hop = self.max_windows = None
+        if window is not None:
+            # ValueError, naming the quantum, for a window or hop that does not fit it -- before any launch of the stream
+            nW, self.window, self.hop = self.plan.window_count(self.T if self.T is not None else 1, window, hop)
+            if self.hop > self.window:
+                raise ValueError(f"the streaming read-out needs hop <= window (hop {self.hop}, window {self.window})")
+            self.max_windows = int(max_windows) if max_windows is not None else (nW if self.T is not None else 64)
+            if self.max_windows < 1:
+                raise ValueError("max_windows must be at least 1")
         self.max_tile = -(-int(max_tile) // 16) * 16
         # window: the tile being encoded + the frames that may still be waiting for their spikes + one chunk of LIF history
         self.cap = -(-(self.max_tile + int(lag_frames) + 2 * self.CH) // self.CH) * self.CH
@@ -81,6 +103,17 @@ class StreamingLocalizer:
         self.h = torch.empty((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile), dtype=torch.float64, device=dev)
         self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
         self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        if self.window is not None:
+            self.nwst = self.lib.micloc_stream_window_state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows)
+            if self.nwst == 0:
+                raise _lib.MiclocError("micloc stream_window_state_bytes: the plan cannot serve the windowed read-out (a complex bf_mat?)")
+            self.wst = torch.empty(int(self.nwst), dtype=torch.uint8, device=dev)
+            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
+            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
+            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            _lib.check(self.lib.micloc_stream_window_reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
+                                                           self.max_windows, runtime._stream(dev)), "stream_window_reset")
         self.wrap = None
         if wrap_tail is not None:
             wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
@@ -134,9 +167,17 @@ class StreamingLocalizer:
         h_tile = ctypes.c_void_p(h.data_ptr() + 8 * self.halo)
         _lib.check(lib.micloc_stream_encode_tile_f64(plan.handle, h_tile, B, n, Ts, int(final), runtime._ptr(self.win), self.cap, runtime._ptr(self.state),
                                                      self.nstate, runtime._ptr(self.loc), st), "stream_encode_tile")
-        _lib.check(lib.micloc_stream_localize_tile_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B,
-                                                       self.cap, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws),
-                                                       self.nws, st), "stream_localize_tile")
+        if self.window is None:
+            _lib.check(lib.micloc_stream_localize_tile_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B,
+                                                           self.cap, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws),
+                                                           self.nws, st), "stream_localize_tile")
+        else:  # the same launches with the window read-out in front of the commit
+            _lib.check(lib.micloc_stream_localize_tile_windows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc,
+                                                                   runtime._ptr(self.win), B, self.cap, int(final), runtime._ptr(self.power),
+                                                                   runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws, runtime._ptr(self.wst),
+                                                                   self.nwst, self.window, self.hop, self.max_windows, runtime._ptr(self.window_power),
+                                                                   runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
+                                                                   runtime._ptr(self.latest_argmax), st), "stream_localize_tile_windows")
         # history for the next tile's quadrature FIR: the last `halo` frames of [history | tile]
         self.hist.copy_(ext[:, Text - self.halo :, :])
 
@@ -205,8 +246,36 @@ class StreamingLocalizer:
         _lib.check(self.lib.micloc_stream_overflow(runtime._ptr(self.state), ctypes.byref(lost), runtime._stream(self.device)), "stream_overflow")
         return dict(chunks=int(st4[0]), frames=int(st4[1]), lag_failures=int(st4[2]), overflow=int(lost.value))
 
+    def _need_windows(self):
+        if self.window is None:
+            raise ValueError("the localizer was built without window=")
+
+    def latest_window(self):
+        """(power [B, G], argmax [B]) of the most recently emitted window: device tensors, overwritten when the next window is emitted,
+        zeros until the first one exists.  Does not synchronise."""
+        self._need_windows()
+        return self.latest_power, self.latest_argmax
+
+    def windows(self):
+        """dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]): `count` windows have been emitted so far
+        (utils.windows_complete of the frames beamformed); the k = min(count, max_windows) newest of them, windows first .. count - 1 in
+        ascending order, as device tensors (copies: later pushes do not change them); window_start: their first frames, host int64.
+        Synchronises the stream."""
+        self._need_windows()
+        torch = runtime._torch()
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.micloc_stream_window_count(runtime._ptr(self.wst), ctypes.byref(c), runtime._stream(self.device)), "stream_window_count")
+        count = int(c.value)
+        k = min(count, self.max_windows)
+        first = count - k
+        rows = torch.arange(first, count, device=self.device) % self.max_windows
+        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
+                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+
     def finish(self, want_spikes=False):
-        """-> dict(power [B, G], argmax [B] int32, spikes [B, T, 2M] int8 (keep_raster only) or None) as device tensors."""
+        """-> dict(power [B, G], argmax [B] int32, spikes [B, T, 2M] int8 (keep_raster only) or None) as device tensors; with window=
+        also window_power [B, nW, G], window_argmax [B, nW] and window_count = nW, every window of the recording (a live source
+        without total_frames: the max_windows newest, see windows())."""
         if not self.done:
             raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
         s = self.status()
@@ -222,4 +291,13 @@ class StreamingLocalizer:
                 raise ValueError("spikes are only assembled with keep_raster=True")
             self._save_window(self.t)
             spikes = self.raster
-        return dict(power=self.power, argmax=self.argmax, spikes=spikes)
+        out = dict(power=self.power, argmax=self.argmax, spikes=spikes)
+        if self.window is not None:
+            if self.T is not None:
+                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
+                if self.max_windows < nW:
+                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
+                                           "windows() while the stream runs)")
+            w = self.windows()
+            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
+        return out

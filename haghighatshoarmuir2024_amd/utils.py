@@ -153,6 +153,26 @@ def window_bounds(T, window, hop=None):
     return start, stop
 
 
+def windows_complete(frames_final, window, hop=None, T=None):
+    """How many windows the STREAMING form of the rule (include/micloc_hip.h, "streaming windows") has emitted once `frames_final`
+    frames are beamformed: window n is emitted when its last frame n hop + window - 1 is, so 0 while frames_final < window and
+    (frames_final - window) // hop + 1 from then on.  With `T` (the length of the recording) and frames_final >= T the final tile
+    has been beamformed and every window of the rule exists: len(window_bounds(T, window, hop)[0]) -- the leftover window
+    included, the windows that start before T but are not in that count (window = 1024, hop = 256, T = 1100: 2, not 5) excluded.
+    The streaming rule wants 1 <= hop <= window (the device additionally multiples of the plan's window quantum)."""
+    frames_final, window = int(frames_final), int(window)
+    hop = window if hop is None else int(hop)
+    if window < 1 or hop < 1 or (T is not None and int(T) < 1):
+        raise ValueError("T, window and hop must be at least 1")
+    if hop > window:
+        raise ValueError(f"the streaming read-out needs hop <= window (hop {hop}, window {window})")
+    if frames_final < 0:
+        raise ValueError("frames_final must not be negative")
+    if T is not None and frames_final >= int(T):
+        return len(window_bounds(T, window, hop)[0])
+    return 0 if frames_final < window else (frames_final - window) // hop + 1
+
+
 def _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold):
     """localize_batch's multi-source read-out per window: window_peaks [B, nW, K] int32 and window_peak_power [B, nW, K] from the
     B nW rows of out["window_power"] (find_doa_peaks, at most 65535 rows per launch)."""

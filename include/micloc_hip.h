@@ -260,6 +260,51 @@ int micloc_stream_localize_tile_f64(const micloc_plan *plan, const void *enc_sta
 int micloc_stream_overflow(const void *state, int *count, void *stream);
 int micloc_stream_localize_status(const void *loc_state, int *status4, void *stream);
 
+/* ---- streaming windows: a DoA per time window while the recording arrives ------------------------------------------ */
+/* The running power above is the mean over every frame since the stream began: right for a stationary source, all but frozen
+ * for one that moves after a minute of audio.  micloc_stream_localize_tile_windows_f64 is micloc_stream_localize_tile_f64 plus
+ * the time-resolved read-out ("time-resolved DoA" below) of the same per-chunk rows of sum y^2, emitted window by window as
+ * soon as a window's last chunk is final, with the bits of the one-shot call and no T-sized buffer.  The rule:
+ *   Window bounds.
+ *   - The window rule of the time-resolved read-out holds unchanged, with the extra condition 1 <= hop <= window.
+ *   - window and hop are multiples of CH = micloc_stream_chunk_frames(plan), the plan's window quantum (256 frames up to 64
+ *     channels, 512 beyond).
+ *   - Window n covers the frames [n hop, min(n hop + window, T)).
+ *   When a window is emitted.
+ *   - Before the final tile: window n is emitted by the first call after which chunk n hop / CH + window / CH - 1 has been
+ *     beamformed, in ascending n.  With F frames beamformed that is F < window ? 0 : (F - window) / hop + 1 windows.
+ *   - On the final tile (final_tile = 1): every window of micloc_window_count(T, window, hop, CH) not emitted yet is emitted,
+ *     with T taken from the device clock; its frame count is min(window, T - n hop).
+ *   - Windows that start before T but are not in that count are not emitted: window = 1024, hop = 256, T = 1100 has 2
+ *     windows, not 5.
+ *   Values.
+ *   - The value of window n is bit for bit what micloc_snn_pipeline_windows_f64 returns for the whole recording.  The order of
+ *     the additions is that read-out's: total = 0; the chunk rows are added in ascending order inside blocks of 32 chunks
+ *     counted from the window's first chunk; each block sum is added onto the total in ascending order; the result is divided
+ *     by the window's frame count.  The arg-max is the first maximum; a NaN never wins.
+ *   - A row that has been emitted never changes afterwards (until window n + max_windows takes its place in the ring).
+ * State: win_state (micloc_stream_window_state_bytes, 256-B aligned; zero-filled once by micloc_stream_window_reset) holds the
+ * count of windows emitted and, per trial, the K = ceil(window / hop) windows that can be open at a time, window n in slot n % K,
+ * each as {total, open-block sum} rows of G doubles: 256 + B K 2 G 8 bytes, whatever the length of the stream.
+ * Outputs (device): window n goes to row n % max_windows of window_power [B][max_windows][G] (may be NULL) and window_argmax
+ * [B][max_windows] int32; latest_power [B][G] / latest_argmax [B] (may be NULL) take the most recently emitted window and are
+ * untouched until the first one exists.  power / argmax / loc_state end with exactly the bits of micloc_stream_localize_tile_f64:
+ * the launches are horizon -> LIF + beamforming -> accumulate -> window read-out -> commit -> tick, the read-out being one
+ * workgroup per trial whose grid depends on B only -- no atomics, no host synchronisation, no argument that depends on time, so a
+ * tile is still ONE capturable hipGraph.  micloc_stream_window_count: windows emitted so far; synchronises the stream.
+ * Status, before any launch: MICLOC_ERR_INVALID for NULL or non-positive arguments; MICLOC_ERR_NOT_SET without neuron kernel or
+ * bf_mat; MICLOC_ERR_SHAPE for a window or hop that is not a multiple of CH, hop > window, or a complex bf_mat;
+ * MICLOC_ERR_WORKSPACE for a short or misaligned loc_state, ws or win_state. */
+size_t micloc_stream_window_state_bytes(const micloc_plan *plan, int B, int window, int hop, int max_windows); /* 0 on bad arguments */
+int micloc_stream_window_reset(const micloc_plan *plan, int B, void *win_state, size_t win_bytes, int window, int hop, int max_windows,
+                               void *stream);
+int micloc_stream_localize_tile_windows_f64(const micloc_plan *plan, const void *enc_state, void *loc_state, size_t loc_bytes,
+                                            const int8_t *window_raster, int B, int window_frames, int final_tile, double *power,
+                                            int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window,
+                                            int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power,
+                                            int32_t *latest_argmax, void *stream);
+int micloc_stream_window_count(const void *win_state, int *count, void *stream);
+
 /* ---- beamforming vectors from membrane covariances (design_from_template's decomposition step) ------ */
 /* Replaces the per-DoA np.linalg.svd calls of SNNBeamformer.design_from_template (snn_beamformer.py:183-203) and
  * _find_dc_removed_sing_vec (:372-422) by one batched kernel: column g0 + i of bf_mat [C][G] from cov[i] [C][C]
