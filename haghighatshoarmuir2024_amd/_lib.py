@@ -16,6 +16,7 @@ MICLOC_ERR_NOT_SET = -4
 MICLOC_ERR_HIP = -5
 MICLOC_ERR_NO_DEVICE = -6
 MICLOC_MAX_IIR = 9
+MICLOC_MAX_BANDS = 16
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_void_p = ctypes.c_void_p
@@ -147,6 +148,11 @@ SYMBOLS = {
     "micloc_beamform_c128_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_snn_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_beamformer_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_filterbank_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "micloc_band_sum_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "micloc_snn_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
+    "micloc_snn_pipeline_bands_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_music_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -687,6 +687,135 @@ int micloc_beamformer_pipeline_windows_f64(const micloc_plan *p, const double *x
     return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, st);
 }
 
+}  // extern "C"
+
+// ---- wideband: filterbank, one SNN chain per band, band sum (filterbank.hip) ---------------------------------------------------
+namespace {
+
+// host [F][n] coefficient rows -> the kernel's table, divided by a[0] as micloc_lfilter_f64 does
+int filterbank_coef(const double *b, const double *a, int F, int n, FilterbankCoef *co)
+{
+    if (!b || !a || F < 1 || F > MICLOC_MAX_BANDS || n < 1 || n > MICLOC_MAX_IIR) return MICLOC_ERR_INVALID;
+    memset(co, 0, sizeof(*co));
+    co->n = n;
+    for (int f = 0; f < F; ++f) {
+        const double a0 = a[(size_t)f * n];
+        if (a0 == 0.0) return MICLOC_ERR_INVALID;
+        for (int i = 0; i < n; ++i) {
+            co->b[f][i] = b[(size_t)f * n + i] / a0;
+            co->a[f][i] = a[(size_t)f * n + i] / a0;
+        }
+    }
+    return MICLOC_OK;
+}
+
+struct BandsLayout {
+    size_t xf, band_power, pipe, pipe_bytes, total;
+    int nW;       // windows per trial (1 for whole recordings)
+    long long R;  // rows of the band sum
+};
+
+// argument checks of the band pipeline in the header's order; fills the layout
+int bands_layout(const micloc_plan *const *plans, int F, int B, int T, int window, int hop, bool own_band_power, BandsLayout *L)
+{
+    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || T < 1 || window < 0 || hop < 0) return MICLOC_ERR_INVALID;
+    for (int f = 0; f < F; ++f)
+        if (!plans[f]) return MICLOC_ERR_INVALID;
+    for (int f = 0; f < F; ++f)
+        if (!plans[f]->d_ntab || !plans[f]->d_W) return MICLOC_ERR_NOT_SET;
+    const micloc_plan *p0 = plans[0];
+    for (int f = 0; f < F; ++f) {
+        const micloc_plan *p = plans[f];
+        if (p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out || p->W_is_complex) return MICLOC_ERR_SHAPE;
+    }
+    L->nW = 1;
+    if (window > 0) {
+        if (hop == 0) hop = window;
+        for (int f = 0; f < F; ++f) {
+            const int rc = window_args(T, window, hop, window_quantum(plans[f]), B, &L->nW);
+            if (rc != MICLOC_OK) return rc;
+        }
+    }
+    L->R = (long long)B * L->nW;
+    size_t off = 0;
+    L->xf = off;
+    off += align256((size_t)F * B * T * p0->M * sizeof(double));
+    L->band_power = off;
+    if (own_band_power) off += align256((size_t)F * L->R * p0->G_out * sizeof(double));
+    L->pipe = off;
+    L->pipe_bytes = 0;
+    for (int f = 0; f < F; ++f) {
+        const size_t n = ws_layout(plans[f], B, T).total;
+        if (n > L->pipe_bytes) L->pipe_bytes = n;
+    }
+    off += L->pipe_bytes;
+    L->total = off;
+    return MICLOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int micloc_filterbank_f64(const double *b, const double *a, int F, int n, const double *x, int B, int T, int M, double *xf, void *stream)
+{
+    FilterbankCoef co;
+    const int rc = filterbank_coef(b, a, F, n, &co);
+    if (rc != MICLOC_OK) return rc;
+    if (!x || !xf || B < 1 || T < 1 || M < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(device_of(xf));
+    HIP_TRY(launch_filterbank(co, x, F, B, T, M, xf, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_band_sum_f64(const double *band_power, int F, int R, int G, double *power, int32_t *argmax, void *stream)
+{
+    if (!band_power || (!power && !argmax) || F < 1 || F > MICLOC_MAX_BANDS || R < 1 || G < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(device_of(power ? (const void *)power : (const void *)argmax));
+    HIP_TRY(launch_band_sum(band_power, F, R, G, power, argmax, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+size_t micloc_snn_bands_workspace_bytes(const micloc_plan *const *plans, int F, int B, int T, int window, int hop)
+{
+    BandsLayout L{};
+    // (sized for a caller that passes band_power == NULL: enough for either form)
+    return bands_layout(plans, F, B, T, window, hop, true, &L) == MICLOC_OK ? L.total : 0;
+}
+
+int micloc_snn_pipeline_bands_f64(const micloc_plan *const *plans, int F, const double *fb_b, const double *fb_a, int fb_n, const double *x,
+                                  int B, int T, int window, int hop, double *band_power, double *power, int32_t *argmax, void *ws,
+                                  size_t ws_bytes, void *stream)
+{
+    if (!plans || !x || (!power && !argmax)) return MICLOC_ERR_INVALID;
+    FilterbankCoef co;
+    int rc = filterbank_coef(fb_b, fb_a, F, fb_n, &co);
+    if (rc != MICLOC_OK) return rc;
+    BandsLayout L{};
+    rc = bands_layout(plans, F, B, T, window, hop, band_power == nullptr, &L);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(ws, ws_bytes, L.total)) return MICLOC_ERR_WORKSPACE;
+    if (window > 0 && hop == 0) hop = window;
+    const micloc_plan *p0 = plans[0];
+    DeviceGuard guard(p0->device);
+    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
+    double *xf = reinterpret_cast<double *>(base + L.xf);
+    double *bp = band_power ? band_power : reinterpret_cast<double *>(base + L.band_power);
+    void *pipe = base + L.pipe;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(launch_filterbank(co, x, F, B, T, p0->M, xf, st));
+    const size_t band_in = (size_t)B * T * p0->M, band_out = (size_t)L.R * p0->G_out;
+    for (int f = 0; f < F; ++f) {  // one after the other on the stream: they share `pipe`
+        rc = window > 0 ? micloc_snn_pipeline_windows_f64(plans[f], xf + f * band_in, B, T, window, hop, nullptr, bp + f * band_out, nullptr, nullptr,
+                                                          nullptr, pipe, L.pipe_bytes, stream)
+                        : micloc_snn_pipeline_f64(plans[f], xf + f * band_in, B, T, nullptr, nullptr, bp + f * band_out, nullptr, pipe, L.pipe_bytes,
+                                                  stream);
+        if (rc != MICLOC_OK) return rc;
+    }
+    HIP_TRY(launch_band_sum(bp, F, L.R, p0->G_out, power, argmax, st));
+    return MICLOC_OK;
+}
+
 // ---- moving-target tracking: per-step arg-max of the envelope of the beamformer output (track.hip) ---------------------
 }  // extern "C"
 

@@ -1,0 +1,231 @@
+// Wideband front and back end for gfx950: the filterbank of the live demo (micloc/localization_demo_snn.py:160-164,
+// micloc/filterbank.py:25-46: scipy.signal.lfilter per band) as ONE launch for all bands of a batch, and the sum of the per-band
+// angular power patterns with its arg-max (:166-190).
+//
+// filterbank_kernel: x [B][T][M] -> xf [F][B][T][M].  The arithmetic is the project's DF2T contract from zero state, the step of
+// rzcc.hip's Iir restated (that file is pinned by the profile manifest): y = fma(b0, x, z0); z_i = fma(-a_{i+1}, y, fma(b_{i+1}, x,
+// z_{i+1})); z_{n-2} = fma(-a_{n-1}, y, b_{n-1} * x) -- every term, no zero-coefficient skipping, so the results are those of
+// micloc_lfilter_f64 band by band.  Time is serial per (band, trial, microphone) chain: one lane owns one chain.
+//   * A workgroup owns one trial (and a group of `mg` microphones: all of them unless (1 + F) * M > FB_MAX_ROWS) with ALL its
+//     bands: an input tile of FB_TT frames comes from HBM once and every band reads it from LDS (lanes of different bands read the
+//     same address: a broadcast).
+//   * Global traffic goes through LDS time tiles: a tile of a trial is one contiguous run of FB_TT * M doubles in x and in every
+//     band's slice of xf, read and written by all 256 threads 8 bytes per lane in address order (a frame row is M doubles -- 56 B at
+//     M = 7 -- so nothing wider is aligned).  Only the chain lanes (F * mg <= 64: one wave) run the serial recurrence.
+//   * Both LDS tiles are double buffered and there is ONE barrier per tile: while tile k is filtered, the loads of tile k + 1 are in
+//     flight into registers (issued before the recurrence, written to LDS after it) and tile k - 1 is on its way out.
+//   * The chain lanes take the tile in groups of 8 steps: 8 LDS reads, 8 steps in registers, 8 LDS writes -- the reads of a group do
+//     not wait behind the writes of the one before.
+// No time chunking: a lone, very long recording runs at the pace of one chain (the live demo's packs are 12 000 frames).
+//
+// band_sum_kernel: band_power [F][R][G] -> power [R][G] = ((p_0 + p_1) + p_2) + ... in ascending band order (__dadd_rn, starting
+// from p_0: the additions of Demo.power_grid) and argmax [R] with power_argmax_kernel's rule (first maximum, a NaN never wins, a
+// row of NaN only gives 0).  One workgroup per row, no atomics.
+#include "micloc_internal.h"
+
+namespace micloc {
+
+constexpr int FB_TT = 64;         // frames per time tile
+constexpr int FB_THREADS = 256;
+constexpr int FB_MAX_ROWS = 64;   // (1 + F) * mg <= FB_MAX_ROWS: LDS = 2 buffers x (1 + F) mg rows of (FB_TT + 1) doubles <= 65 KB
+constexpr int FB_MAX_MG = 16;     // microphones per workgroup (FB_XREG registers hold a thread's share of an input tile)
+constexpr int FB_XREG = FB_TT * FB_MAX_MG / FB_THREADS;
+constexpr int FB_GROUP = 8;       // steps per register group of the recurrence
+
+template <int N>
+struct FbChain {
+    double b[N], a[N];
+    double z[N > 1 ? N - 1 : 1];
+
+    __device__ __forceinline__ void init(const FilterbankCoef &co, int f)
+    {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            b[i] = co.b[f][i];
+            a[i] = co.a[f][i];
+        }
+#pragma unroll
+        for (int i = 0; i < (N > 1 ? N - 1 : 1); ++i) z[i] = 0.0;
+    }
+
+    // the DF2T step of the contract, operation for operation rzcc.hip's Iir<N>::step
+    __device__ __forceinline__ double step(double xin)
+    {
+        double y;
+        if (N == 1) {
+            y = __builtin_fma(b[0], xin, 0.0);
+        } else {
+            y = __builtin_fma(b[0], xin, z[0]);
+#pragma unroll
+            for (int i = 0; i < N - 2; ++i) z[i] = __builtin_fma(-a[i + 1], y, __builtin_fma(b[i + 1], xin, z[i + 1]));
+            z[N - 2] = __builtin_fma(-a[N - 1], y, b[N - 1] * xin);
+        }
+        return y;
+    }
+};
+
+// LDS: [2][xin: mg rows... ] as time-major tiles.  xin[buf][t * mg + j]; yout[buf][f][t * mg + j] with a band stride of
+// (FB_TT + 1) * mg doubles: lanes (f, j) of one step then write F * mg different banks (up to 16 doubles) instead of F-way conflicts.
+template <int N>
+__global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const FilterbankCoef co, const double *__restrict__ x, int F, int B, int T,
+                                                                  int M, int mg, int ngroups, double *__restrict__ xf)
+{
+    extern __shared__ __attribute__((aligned(16))) double fb_lds[];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / ngroups;
+    const int m0 = (blockIdx.x - b * ngroups) * mg;
+    const int mw = M - m0 < mg ? M - m0 : mg;  // microphones of this workgroup (the last group may be narrower)
+    const bool full = mw == M;                 // the tile is one contiguous run
+    const int xin_sz = FB_TT * mg, bstride = (FB_TT + 1) * mg, yout_sz = F * bstride;
+    double *xin = fb_lds;                      // [2][xin_sz]
+    double *yout = fb_lds + 2 * xin_sz;        // [2][yout_sz]
+    const size_t trial = (size_t)T * M;        // doubles per trial
+    const double *xb = x + (size_t)b * trial + m0;
+    const int ntiles = (T + FB_TT - 1) / FB_TT;
+
+    // chain lanes: lane c = f * mw + j
+    const bool chain = tid < F * mw;
+    const int cf = chain ? tid / mw : 0, cj = chain ? tid - (tid / mw) * mw : 0;
+    FbChain<N> ch;
+    ch.init(co, cf);
+
+    // element e of a tile (e < frames * mw) -> offset from the tile's first frame row
+    auto goff = [&](int e) -> size_t { return full ? (size_t)e : (size_t)(e / mw) * M + (e - (e / mw) * mw); };
+
+    double xr[FB_XREG];
+    auto load_tile = [&](int k) {
+        const int nt = T - k * FB_TT < FB_TT ? T - k * FB_TT : FB_TT;
+        const double *src = xb + (size_t)k * FB_TT * M;
+#pragma unroll
+        for (int r = 0; r < FB_XREG; ++r) {
+            const int e = tid + r * FB_THREADS;
+            xr[r] = e < nt * mw ? src[goff(e)] : 0.0;
+        }
+    };
+    auto stash_tile = [&](int k) {
+        double *dst = xin + (k & 1) * xin_sz;
+#pragma unroll
+        for (int r = 0; r < FB_XREG; ++r) {
+            const int e = tid + r * FB_THREADS;
+            if (e < FB_TT * mw) dst[e] = xr[r];  // (frames past T hold zeros: the recurrence may run over them, nothing is stored)
+        }
+    };
+    auto store_tile = [&](int k) {
+        const int nt = T - k * FB_TT < FB_TT ? T - k * FB_TT : FB_TT;
+        const double *src = yout + (k & 1) * yout_sz;
+        for (int f = 0; f < F; ++f) {
+            double *dst = xf + ((size_t)f * B + b) * trial + (size_t)k * FB_TT * M + m0;
+            for (int e = tid; e < nt * mw; e += FB_THREADS) dst[goff(e)] = src[f * bstride + e];
+        }
+    };
+
+    load_tile(0);
+    stash_tile(0);
+    __syncthreads();
+    for (int k = 0; k < ntiles; ++k) {
+        if (k + 1 < ntiles) load_tile(k + 1);  // in flight during the recurrence below
+        if (k > 0) store_tile(k - 1);
+        if (chain) {
+            const int nt = T - k * FB_TT < FB_TT ? T - k * FB_TT : FB_TT;
+            const double *xi = xin + (k & 1) * xin_sz + cj;
+            double *yo = yout + (k & 1) * yout_sz + cf * bstride + cj;
+            for (int t0 = 0; t0 < nt; t0 += FB_GROUP) {
+                double v[FB_GROUP];
+#pragma unroll
+                for (int u = 0; u < FB_GROUP; ++u) v[u] = xi[(t0 + u) * mw];
+#pragma unroll
+                for (int u = 0; u < FB_GROUP; ++u) v[u] = ch.step(v[u]);
+#pragma unroll
+                for (int u = 0; u < FB_GROUP; ++u) yo[(t0 + u) * mw] = v[u];
+            }
+        }
+        if (k + 1 < ntiles) stash_tile(k + 1);
+        __syncthreads();
+    }
+    store_tile(ntiles - 1);
+}
+
+// microphones per workgroup: all of them when the trial's tiles fit the LDS budget
+static int fb_mic_group(int F, int M)
+{
+    int mg = FB_MAX_ROWS / (1 + F);
+    if (mg > FB_MAX_MG) mg = FB_MAX_MG;
+    if (mg > M) mg = M;
+    return mg < 1 ? 1 : mg;
+}
+
+template <int N>
+static hipError_t fb_launch(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, hipStream_t stream)
+{
+    const int mg = fb_mic_group(F, M);
+    const int ngroups = (M + mg - 1) / mg;
+    const size_t lds = (size_t)2 * (FB_TT * mg + (size_t)F * (FB_TT + 1) * mg) * sizeof(double);
+    const long long blocks = (long long)B * ngroups;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filterbank_kernel<N>, dim3((unsigned)blocks), dim3(FB_THREADS), lds, stream, co, x, F, B, T, M, mg, ngroups, xf);
+    return hipGetLastError();
+}
+
+hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, hipStream_t stream)
+{
+    if (F < 1 || F > MICLOC_MAX_BANDS || B < 1 || T < 1 || M < 1) return hipErrorInvalidValue;
+    switch (co.n) {
+        case 1: return fb_launch<1>(co, x, F, B, T, M, xf, stream);
+        case 2: return fb_launch<2>(co, x, F, B, T, M, xf, stream);
+        case 3: return fb_launch<3>(co, x, F, B, T, M, xf, stream);
+        case 4: return fb_launch<4>(co, x, F, B, T, M, xf, stream);
+        case 5: return fb_launch<5>(co, x, F, B, T, M, xf, stream);
+        case 6: return fb_launch<6>(co, x, F, B, T, M, xf, stream);
+        case 7: return fb_launch<7>(co, x, F, B, T, M, xf, stream);
+        case 8: return fb_launch<8>(co, x, F, B, T, M, xf, stream);
+        case 9: return fb_launch<9>(co, x, F, B, T, M, xf, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- band sum + arg-max ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void band_sum_kernel(const double *__restrict__ band_power, int F, size_t R, int G,
+                                                        double *__restrict__ power, int32_t *__restrict__ argmax)
+{
+    __shared__ double sv[256];
+    __shared__ int si[256];
+    const size_t r = blockIdx.x;
+    const size_t band = R * (size_t)G;  // doubles per band
+    const double *p0 = band_power + r * G;
+    double best = 0.0;
+    int bi = 0x7fffffff;
+    for (int g = threadIdx.x; g < G; g += 256) {
+        double s = p0[g];
+        for (int f = 1; f < F; ++f) s = __dadd_rn(s, p0[(size_t)f * band + g]);
+        if (power) power[r * G + g] = s;
+        if (s == s && (bi == 0x7fffffff || s > best)) {  // ascending g per thread: the first maximum; a NaN never wins
+            best = s;
+            bi = g;
+        }
+    }
+    sv[threadIdx.x] = best;
+    si[threadIdx.x] = bi;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const double ov = sv[threadIdx.x + s];
+            const int oi = si[threadIdx.x + s];
+            const int mi = si[threadIdx.x];
+            if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > sv[threadIdx.x] || (ov == sv[threadIdx.x] && oi < mi))) {
+                sv[threadIdx.x] = ov;
+                si[threadIdx.x] = oi;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && argmax) argmax[r] = si[0] == 0x7fffffff ? 0 : si[0];
+}
+
+hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, double *power, int32_t *argmax, hipStream_t stream)
+{
+    if (F < 1 || F > MICLOC_MAX_BANDS || R < 1 || R > 0x7fffffffll || G < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(band_sum_kernel, dim3((unsigned)R), dim3(256), 0, stream, band_power, F, (size_t)R, G, power, argmax);
+    return hipGetLastError();
+}
+
+}  // namespace micloc

@@ -240,6 +240,18 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
 // the read-out of a stored envelope [B][T][G]: first maximum and its value per row, the last row (peak / env_last may be NULL)
 hipError_t launch_track_rows(const double *env, int B, int T, int G, int32_t *index, double *peak, double *env_last, hipStream_t stream);
 
+// ---- wideband: filterbank and band sum (filterbank.hip) ------------------------------------------------------------------------
+// coefficients of F bands, already divided by a[0]; they travel by value as a kernel argument (2.3 KB: no device table)
+struct FilterbankCoef {
+    double b[MICLOC_MAX_BANDS][MICLOC_MAX_IIR];
+    double a[MICLOC_MAX_BANDS][MICLOC_MAX_IIR];
+    int n;
+};
+// x [B][T][M] -> xf [F][B][T][M], every band from zero state (DF2T, the arithmetic of launch_bandpass_rzcc's `pre`)
+hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, hipStream_t stream);
+// band_power [F][R][G] -> power [R][G] (ascending band order, from p_0), argmax [R] (first maximum; either may be NULL)
+hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, double *power, int32_t *argmax, hipStream_t stream);
+
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
 struct MusicDims {
     int B, T, M;     // trials, samples per trial, microphones

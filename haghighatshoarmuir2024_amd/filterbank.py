@@ -23,6 +23,11 @@ class Filterbank:
             runtime.lfilter(b, a, x, device=dev, out=out[f])
         return out
 
+    def evolve_batch(self, x, out=None):
+        """[B, T, M] (numpy or device tensor) -> device tensor [F, B, T, M]: every band of every trial in ONE launch
+        (micloc_filterbank_f64; the input is read once for all bands), band by band the numbers of `evolve_device`."""
+        return runtime.filterbank(self.ba_list, x, device=self.device, out=out)
+
     def evolve(self, sig_in):
         sig_in = np.asarray(sig_in, dtype=np.float64)
         if sig_in.ndim == 1:

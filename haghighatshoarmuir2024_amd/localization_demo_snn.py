@@ -58,6 +58,29 @@ class Demo:
             return np.nan
         return self.doa_list[int(np.argmax(self.power_grid(sig)))] * 180 / np.pi
 
+    def localizer(self):
+        """The batched form of this demo's chain (wideband.WidebandSNNLocalizer over the same beamformers, matrices and filterbank):
+        B packs per call, the band sum and its arg-max on the device."""
+        from .wideband import WidebandSNNLocalizer
+
+        loc = WidebandSNNLocalizer(self.beamfs, self.bf_mats, self.filterbank)
+        loc.doa_list = self.doa_list
+        return loc
+
+    def process_frames(self, packs, rel_threshold=0.0001):
+        """`process_frame` for a batch of recorded packs [B, T, num_mic + 1] of one length: DoA in degrees per pack [B], NaN for the
+        packs below the activity threshold (tested per pack, on the host, as in the loop); the others go through ONE
+        localizer().localize_batch call."""
+        packs = np.asarray(packs)
+        max_value = np.iinfo(packs.dtype).max if np.issubdtype(packs.dtype, np.integer) else 1.0
+        sig = np.asarray(packs[:, :, :-1], dtype=np.float64)
+        active = np.asarray([np.sqrt(np.mean(s**2)) >= rel_threshold * max_value for s in sig], dtype=bool)  # process_frame's test, pack by pack
+        doa = np.full(len(packs), np.nan)
+        if active.any():
+            idx = self.localizer().localize_batch(np.ascontiguousarray(sig[active]))["argmax"].cpu().numpy()
+            doa[active] = self.doa_list[idx] * 180 / np.pi
+        return doa
+
     def run(self, source, sink=print):
         """`source`: iterable of recorded packs ([T, num_mic + 1] integer arrays); `sink(doa_deg)` replaces the visualiser."""
         for data in source:

@@ -505,6 +505,105 @@ def lfilter(b, a, x, device=None, out=None):
     return y[0] if squeeze else y
 
 
+def pad_ba_list(ba_list):
+    """[(b, a)] * F -> (b [F, n], a [F, n], n): every band zero-padded to the longest section (the host tables of
+    micloc_filterbank_f64)."""
+    if not 1 <= len(ba_list) <= _lib.MICLOC_MAX_BANDS:
+        raise ValueError(f"a filterbank has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {len(ba_list)}")
+    padded = [pad_ba(b, a) for b, a in ba_list]
+    n = max(p[2] for p in padded)
+    bb, aa = np.zeros((len(padded), n)), np.zeros((len(padded), n))
+    for f, (b, a, k) in enumerate(padded):
+        bb[f, :k], aa[f, :k] = b, a
+    return bb, aa, n
+
+
+def filterbank(ba_list, x, device=None, out=None):
+    """scipy.signal.lfilter(b_f, a_f, x, axis=-2) for every band of `ba_list` in ONE launch (micloc_filterbank_f64): x [B, T, M] ->
+    [F, B, T, M] float64 on the device, band by band the numbers of `lfilter`.  `out`: a contiguous float64 device tensor of that
+    shape to write into."""
+    torch = _torch()
+    lib = _lib.load()
+    device = require_gpu(device)
+    bb, aa, n = pad_ba_list(ba_list)
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+    x = x.to(device=device, dtype=torch.float64).contiguous()
+    if x.dim() != 3:
+        raise ValueError("filterbank takes a batch [B, T, M]")
+    B, T, M = x.shape
+    F = len(ba_list)
+    if out is None:
+        out = torch.empty((F, B, T, M), dtype=torch.float64, device=device)
+    elif tuple(out.shape) != (F, B, T, M) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous float64 device tensor [F, B, T, M]")
+    if B * T * M > 0:
+        _lib.check(lib.micloc_filterbank_f64(_dptr(bb), _dptr(aa), F, n, _ptr(x), B, T, M, _ptr(out), _stream(device)), "filterbank")
+    return out
+
+
+def band_sum(band_power, want_power=True, want_argmax=True):
+    """band_power [F, R, G] (device, float64) -> (power [R, G] = ((p_0 + p_1) + p_2) + ..., argmax [R] int32: first maximum, a NaN never
+    wins) through micloc_band_sum_f64; the one not wanted is None."""
+    torch = _torch()
+    lib = _lib.load()
+    if band_power.dim() != 3 or band_power.dtype != torch.float64 or not band_power.is_cuda:
+        raise ValueError("band_power must be a float64 device tensor [F, R, G]")
+    band_power = band_power.contiguous()
+    F, R, G = band_power.shape
+    if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+        raise ValueError(f"1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+    power = torch.empty((R, G), dtype=torch.float64, device=band_power.device) if want_power else None
+    argmax = torch.empty((R,), dtype=torch.int32, device=band_power.device) if want_argmax else None
+    _lib.check(lib.micloc_band_sum_f64(_ptr(band_power), F, R, G, _ptr(power), _ptr(argmax), _stream(band_power.device)), "band_sum")
+    return power, argmax
+
+
+def snn_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
+    """micloc_snn_pipeline_bands_f64: the filterbank `ba_list`, per band the SNN pipeline of plans[f] (neuron kernel and bf_mat set) on its
+    slice, the band sum -- x [B, T, M] on the plans' device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults
+    to it), dict(window_power [B, nW, G], window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G].
+    `ws`: a runtime.Workspace to take the scratch from (default: the first plan's)."""
+    torch = _torch()
+    lib = _lib.load()
+    F = len(plans)
+    if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+        raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+    if len(ba_list) != F:
+        raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
+    bb, aa, n = pad_ba_list(ba_list)
+    p0 = plans[0]
+    if any(p.num_mic != p0.num_mic for p in plans) or any(p.G != p0.G for p in plans):
+        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
+    B, T, M = x.shape
+    if M != p0.num_mic:
+        raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {p0.num_mic}!")
+    G, dev = p0.G, p0.device
+    handles = (ctypes.c_void_p * F)(*[p.handle.value for p in plans])
+    if window is None:
+        nW, win, hp = None, 0, 0
+    else:
+        nW, win, hp = p0.window_count(T, window, hop)
+        for p in plans[1:]:
+            p.window_count(T, window, hop)  # ValueError naming that band's quantum
+        if B * nW > 0x7FFFFFFF:
+            raise ValueError(f"{B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
+    rows = (B,) if nW is None else (B, nW)
+    power = torch.empty(rows + (G,), dtype=torch.float64, device=dev)
+    argmax = torch.empty(rows, dtype=torch.int32, device=dev)
+    bp = torch.empty((F,) + rows + (G,), dtype=torch.float64, device=dev) if want_band_power else None
+    nbytes = lib.micloc_snn_bands_workspace_bytes(handles, F, B, T, win, hp)
+    if nbytes == 0:
+        raise ValueError("micloc snn_bands_workspace_bytes: the plans, the batch or the windows do not fit the band pipeline's rule")
+    buf = (ws or p0.ws).get(nbytes)
+    _lib.check(lib.micloc_snn_pipeline_bands_f64(handles, F, _dptr(bb), _dptr(aa), n, _ptr(x), B, T, win, hp, _ptr(bp), _ptr(power), _ptr(argmax),
+                                                 _ptr(buf), nbytes, _stream(dev)), "snn_pipeline_bands")
+    out = dict(power=power, argmax=argmax) if nW is None else dict(window_power=power, window_argmax=argmax)
+    if want_band_power:
+        out["band_power"] = bp
+    return out
+
+
 def synth_delay(time_in, sig_in, delays, fs, device=None):
     """Device synthesis of noise-free array signals: time_in/sig_in numpy [T] (already on the fs grid), delays numpy
     [B, M] (min-shifted) -> device tensor [B, T, M], bit-exact with np.interp (see csrc/synth.hip)."""

@@ -543,6 +543,72 @@ def speech_target_sweep(beamf, bf_mat, doa_list, source, snr_db_vec=None, num_si
     return res
 
 
+def wideband_localizer(loc, max_batch=25):
+    """Localizer of the wideband sweeps: wideband.WidebandSNNLocalizer.localize_batch (filterbank, one SNN chain per band, band sum
+    and arg-max on the device) in device batches of at most `max_batch` trials.  The neuron kernels are built on the live demo's own
+    time axis, np.arange(T) / fs (micloc/localization_demo_snn.py:149; Demo.power_grid), not on the sweep's: the results are those of
+    Demo.power_grid trial by trial, bit for bit."""
+
+    def run(sig_batch, time_vec):
+        return _in_batches(sig_batch, max_batch, lambda x: _argmax_and_power(loc.localize_batch(x)))
+
+    return run
+
+
+def _wideband_store_key(loc):
+    """ShardStore key entries of a wideband localizer: the band edges (where the filterbank has them), the filterbank's coefficients,
+    every band's plan key (Hilbert kernel, band-pass, robust width, polarity), tau_vec and bf_mat hash -- a resumed sweep never mixes
+    band sets."""
+    import hashlib
+
+    from .runtime import pad_ba_list
+
+    bb, aa, _ = pad_ba_list(loc.filterbank.ba_list)
+    key = dict(method=type(loc).__name__, num_bands=len(loc.beamfs), fb_b=bb, fb_a=aa,
+               band_edges=np.asarray(getattr(loc.filterbank, "freq_bands", np.zeros((0, 2))), dtype=np.float64))
+    for f, (beamf, W) in enumerate(zip(loc.beamfs, loc.bf_mats)):
+        for k, v in _method_key(beamf).items():
+            if k != "method":
+                key[f"band{f}_{k}"] = v
+        key[f"band{f}_bf_mat_sha256"] = hashlib.sha256(np.ascontiguousarray(W, dtype=np.float64).tobytes()).hexdigest()
+    return key
+
+
+def wideband_speech_sweep(loc, doa_list, source, snr_db_vec=None, num_sim=20, seed=0, mode="parity", rank=0, world_size=1, group=None,
+                          localizer=None, batch_trials=None, out_dir=None):
+    """The speech accuracy sweep (speech_target_sweep: paper_plots/target_snn_localization.py:213-245, 11 SNRs x 20 trials, no bandwidth
+    correction) read out by the WIDEBAND localizer `loc` (wideband.WidebandSNNLocalizer: the live demo's filterbank + per-band chains +
+    band sum, micloc/localization_demo_snn.py:125-193) instead of one band.  One batch at a time (the band pipeline runs on one
+    stream).  `localizer`: another read-out with wideband_localizer's signature (tests).  out_dir: resume as in noisy_target_sweep; the
+    store key carries the band edges, the filterbank coefficients and every band's parameters and bf_mat hash."""
+    if batch_trials is None:
+        batch_trials = 125 if mode == "throughput" else 25
+    snr_db_vec = _snr_vec(snr_db_vec)
+    time_fs, sig_test = source
+    res = _template_sweep(loc.beamfs[0], None, doa_list, np.asarray(time_fs, dtype=np.float64), np.asarray(sig_test, dtype=np.float64),
+                          np.repeat(snr_db_vec, num_sim), num_sim, seed, mode, rank, world_size, group,
+                          localizer or wideband_localizer(loc, max_batch=batch_trials), batch_trials, 0, out_dir=out_dir,
+                          sweep_name="wideband-speech", store_key=_wideband_store_key(loc))
+    res["snr_db_vec"] = snr_db_vec
+    return res
+
+
+def parse_bands(text):
+    """`--bands 1000:1600,1600:2400,2400:3400` -> [[1000.0, 1600.0], [1600.0, 2400.0], [2400.0, 3400.0]] (Hz, low:high per band)."""
+    bands = []
+    for part in str(text).split(","):
+        try:
+            lo, hi = (float(v) for v in part.split(":"))
+        except ValueError:
+            raise ValueError(f"--bands takes low:high pairs separated by commas, got {part!r}")
+        if not 0 < lo < hi:
+            raise ValueError(f"a band needs 0 < low < high, got {part!r}")
+        bands.append([lo, hi])
+    if not 1 <= len(bands) <= 16:
+        raise ValueError(f"1 .. 16 bands, got {len(bands)}")
+    return bands
+
+
 def music_localizer(music, num_active_freq, duration_overlap, num_fft_bin, max_batch=100, num_sources=None, min_separation=None, rel_threshold=0.0):
     """Localizer of the MUSIC sweeps: MUSIC.localize_batch (the scripts' read-out power = mean_s |P|^2, arg-max) in device batches
     of at most `max_batch` trials; the [B, S, G] spectra stay in the workspace.  With num_sources=K: (peaks [B, K] int64,
@@ -1011,13 +1077,16 @@ def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau,
 
 
 def main(argv=None):
-    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy|moving-noisy]`: the accuracy sweeps of the paper scripts
+    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy|moving-noisy|wideband-speech]`: the accuracy sweeps of the paper scripts
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy"], default="noisy")
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy", "wideband-speech"],
+                    default="noisy")
+    ap.add_argument("--bands", type=parse_bands, default=parse_bands("1000:1600,1600:2400,2400:3400"),
+                    help="wideband-speech: the bands as low:high pairs in Hz, comma separated (at most 16)")
     ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
     ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy, moving-noisy (snn | beamformer): the localizer")
@@ -1063,6 +1132,20 @@ def main(argv=None):
                                   seed=args.seed, mode=args.mode, rank=rank, world_size=world)
     elif args.sweep == "multi-noisy":
         res = _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world)
+    elif args.sweep == "wideband-speech":
+        from .wideband import WidebandSNNLocalizer
+
+        if args.pcm_npz:
+            z = np.load(args.pcm_npz)
+            src = speech_source(fs, pcm16=z["pcm16"], rate=int(z["rate"]))
+        elif args.flac:
+            src = speech_source(fs, flac_path=args.flac)
+        else:
+            ap.error("--sweep wideband-speech needs --flac or --pcm-npz")
+        # the live demo's set-up per band (micloc/localization_demo_snn.py:40-93): 0.25 s design sines, 10 ms Hilbert kernel, bipolar
+        loc = WidebandSNNLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3,
+                                              bipolar_spikes=True, fs=fs)
+        res = wideband_speech_sweep(loc, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
     elif args.sweep.startswith("music"):
         # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048
         from .music_beamformer import MUSIC

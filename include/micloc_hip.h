@@ -566,6 +566,45 @@ int micloc_beamformer_pipeline_track_f64(const micloc_plan *plan, const double *
                                          double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes,
                                          void *stream);
 
+/* ---- wideband localisation: filterbank, one SNN chain per band, band sum ------------------------ */
+/* The deployed form of the method (micloc/localization_demo_snn.py:125-193): a filterbank splits the recording into F bands
+ * (:160-164, micloc/filterbank.py:25-46), every band runs its own SNNBeamformer.apply_to_signal with its own band-pass, neuron
+ * kernel and bf_mat, the angular power patterns are added and ONE arg-max is taken (:166-190).  The rule:
+ *   Filterbank.
+ *   - xf[f][b] = scipy.signal.lfilter(b_f, a_f, x[b], axis=0) from zero state, f < F <= MICLOC_MAX_BANDS, in the DF2T arithmetic of
+ *     micloc_lfilter_f64 (coefficients divided by a_f[0] on the host): the same numbers, band by band.  b, a are HOST arrays
+ *     [F][n], zero-padded to one length n <= MICLOC_MAX_IIR; they travel as kernel arguments: no device table, no allocation, no
+ *     host synchronisation.  x [B][T][M] -> xf [F][B][T][M], ONE launch for all bands (the input is read from memory once).
+ *   - Time is serial per (band, trial, microphone) chain and is not chunked: a lone long recording runs at one chain's pace.
+ *   Band sum.
+ *   - power[r][g] = ((p_0[r][g] + p_1[r][g]) + p_2[r][g]) + ... in ascending band order, starting FROM p_0 (not from zero), every
+ *     addition rounded to nearest: band_power [F][R][G] -> power [R][G].
+ *   - argmax[r] is the first maximum of the row; a NaN never wins; a row of NaN only gives 0.  power or argmax may be NULL.
+ *   - R = B for whole recordings, B * nW for windows (row r = b * nW + n).
+ *   Pipeline (micloc_snn_pipeline_bands_f64), all on the one stream, in this order: the filterbank; per band f in ascending order
+ *   micloc_snn_pipeline_f64 (window == 0) or micloc_snn_pipeline_windows_f64 (window > 0, the window rule of "time-resolved DoA"
+ *   above) of plans[f] on xf[f], power only; the band sum.  band_power [F][R][G] receives every band's rows (NULL: they stay in
+ *   the workspace).  Each band's rows are bit for bit what that band's own pipeline call returns for xf[f].
+ *   Workspace (micloc_snn_bands_workspace_bytes, 256-B aligned): xf, band_power when the caller passes NULL, and ONE pipeline
+ *   workspace -- the largest micloc_workspace_bytes(plans[f], B, T): the bands run one after the other and share it.
+ *   Status, before any launch: MICLOC_ERR_INVALID for NULL (plans, a plan, coefficients, x, both of power / argmax), F outside
+ *   1..MICLOC_MAX_BANDS, fb_n outside 1..MICLOC_MAX_IIR, a_f[0] == 0, B outside 1..65535, T < 1, window or hop < 0;
+ *   MICLOC_ERR_NOT_SET for a plan without neuron kernel or bf_mat; MICLOC_ERR_SHAPE for plans on different devices, with
+ *   different M or G, with a complex bf_mat, or (window > 0) a window or hop that is not a positive multiple of EVERY plan's
+ *   window quantum (micloc_window_quantum: the common quantum is their least common multiple) or B * nW > INT32_MAX;
+ *   MICLOC_ERR_WORKSPACE for a short or misaligned ws.  hop == 0 means hop = window.
+ * No atomics, no host synchronisation, no allocation: re-entrant per stream with workspaces of their own and capturable in a
+ * hipGraph (on ONE stream: nothing runs side by side).  The stand-alone entries launch on the device that owns their output. */
+#define MICLOC_MAX_BANDS 16
+int micloc_filterbank_f64(const double *b, const double *a, int F, int n, /* host [F][n] each */
+                          const double *x, int B, int T, int M, double *xf, void *stream);
+int micloc_band_sum_f64(const double *band_power, int F, int R, int G, double *power, int32_t *argmax, void *stream);
+size_t micloc_snn_bands_workspace_bytes(const micloc_plan *const *plans, int F, int B, int T, int window, int hop); /* 0 on bad arguments */
+int micloc_snn_pipeline_bands_f64(const micloc_plan *const *plans, int F, const double *fb_b, const double *fb_a, int fb_n,
+                                  const double *x, int B, int T, int window, int hop, /* window 0: whole recording */
+                                  double *band_power /* [F][R][G] or NULL */, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                  void *stream);
+
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
  * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
