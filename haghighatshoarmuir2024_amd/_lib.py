@@ -126,6 +126,7 @@ SYMBOLS = {
     "micloc_stream_localize_tile_windows_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                         c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "micloc_stream_window_count": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "micloc_stream_window_count_ptr": (c_void_p, [c_void_p]),
     "micloc_design_vectors_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
     "micloc_peak_location_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "micloc_doa_peaks_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
@@ -153,6 +154,15 @@ SYMBOLS = {
     "micloc_snn_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
     "micloc_snn_pipeline_bands_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_filterbank_stream_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "micloc_filterbank_stream_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "micloc_filterbank_tile_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "micloc_stream_bands_state_bytes": (c_size_t, []),
+    "micloc_stream_bands_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_band_sum_f64": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(c_void_p),
+                                           ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "micloc_stream_bands_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_music_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -816,6 +816,84 @@ int micloc_snn_pipeline_bands_f64(const micloc_plan *const *plans, int F, const 
     return MICLOC_OK;
 }
 
+// ---- wideband streaming: filterbank state carry (filterbank.hip), band sum per tile (stream_bands.hip) ------------------------------
+size_t micloc_filterbank_stream_state_bytes(int F, int n, int B, int M)
+{
+    if (F < 1 || F > MICLOC_MAX_BANDS || n < 1 || n > MICLOC_MAX_IIR || B < 1 || M < 1) return 0;
+    return filterbank_stream_state_bytes(F, n, B, M);
+}
+
+int micloc_filterbank_stream_reset(void *fb_state, size_t bytes, void *stream)
+{
+    if (!fb_state) return MICLOC_ERR_INVALID;
+    if (bad_ws(fb_state, bytes, 256)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(fb_state));
+    HIP_TRY(launch_zero_fill(fb_state, bytes, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_filterbank_tile_f64(const double *b, const double *a, int F, int n, const double *x_tile, int B, int n_frames, int M, void *fb_state,
+                               size_t fb_bytes, double *xf_tile, void *stream)
+{
+    FilterbankCoef co;
+    const int rc = filterbank_coef(b, a, F, n, &co);
+    if (rc != MICLOC_OK) return rc;
+    if (!x_tile || !xf_tile || !fb_state || B < 1 || n_frames < 1 || M < 1) return MICLOC_ERR_INVALID;
+    if (bad_ws(fb_state, fb_bytes, filterbank_stream_state_bytes(F, n, B, M))) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(xf_tile));
+    HIP_TRY(launch_filterbank_tile(co, x_tile, F, B, n_frames, M, xf_tile, reinterpret_cast<double *>(fb_state), (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+size_t micloc_stream_bands_state_bytes(void) { return STREAM_BANDS_STATE_BYTES; }
+
+int micloc_stream_bands_reset(void *bands_state, size_t bytes, void *stream)
+{
+    if (!bands_state) return MICLOC_ERR_INVALID;
+    if (bad_ws(bands_state, bytes, STREAM_BANDS_STATE_BYTES)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(bands_state));
+    HIP_TRY(launch_zero_fill(bands_state, STREAM_BANDS_STATE_BYTES, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_band_sum_f64(int F, int B, int G, const double *const *band_power, int window, int Kb, int max_windows,
+                               const double *const *band_window_power, const int32_t *const *band_window_count, void *bands_state,
+                               size_t bands_bytes, double *power, int32_t *argmax, double *window_power, int32_t *window_argmax,
+                               double *latest_power, int32_t *latest_argmax, void *stream)
+{
+    if (!band_power || !bands_state || (!power && !argmax) || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || G < 1 || window < 0)
+        return MICLOC_ERR_INVALID;
+    if (window > 0 && (!band_window_power || !band_window_count || !window_argmax || max_windows < 1 || Kb < 1)) return MICLOC_ERR_INVALID;
+    StreamBandsArgs args{};
+    for (int f = 0; f < F; ++f) {
+        if (!band_power[f]) return MICLOC_ERR_INVALID;
+        args.power[f] = band_power[f];
+        if (window > 0) {
+            if (!band_window_power[f] || !band_window_count[f]) return MICLOC_ERR_INVALID;
+            args.rows[f] = band_window_power[f];
+            args.count[f] = band_window_count[f];
+        }
+    }
+    if (bad_ws(bands_state, bands_bytes, STREAM_BANDS_STATE_BYTES)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(bands_state));
+    HIP_TRY(launch_stream_band_sum(args, F, B, G, window > 0, Kb, max_windows, bands_state, power, argmax, window_power, window_argmax, latest_power,
+                                   latest_argmax, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+/* status[0] = wideband windows emitted (or given up) so far, [1] = windows given up because a band's ring had overwritten them
+ * (synchronises the stream) */
+int micloc_stream_bands_status(const void *bands_state, int *status2, void *stream)
+{
+    if (!bands_state || !status2) return MICLOC_ERR_INVALID;
+    int w[2];
+    HIP_TRY(hipMemcpyAsync(w, bands_state, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    status2[0] = w[0];
+    status2[1] = w[1];
+    return MICLOC_OK;
+}
+
 // ---- moving-target tracking: per-step arg-max of the envelope of the beamformer output (track.hip) ---------------------
 }  // extern "C"
 
@@ -1176,6 +1254,9 @@ int micloc_stream_window_count(const void *win_state, int *count, void *stream)
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return MICLOC_OK;
 }
+
+/* device address of the count word micloc_stream_window_count reads (for kernels that follow a band's windows: stream_bands.hip) */
+const int32_t *micloc_stream_window_count_ptr(const void *win_state) { return reinterpret_cast<const int32_t *>(win_state); }
 
 /* status[0] = chunks beamformed, [1] = frames beamformed, [2] = window-lag failures, [3] = chunks in the open reduction block
  * (synchronises the stream) */

@@ -18,6 +18,10 @@
 //     not wait behind the writes of the one before.
 // No time chunking: a lone, very long recording runs at the pace of one chain (the live demo's packs are 12 000 frames).
 //
+// filterbank_tile_kernel: the same tile loop for ONE TILE of a stream, x_tile [B][n][M] -> xf_tile [F][B][n][M], with the DF2T state of
+// every chain loaded from and stored to a device block (micloc_filterbank_tile_f64; the band chains and the band sum of a streamed
+// tile are in stream_bands.hip).
+//
 // band_sum_kernel: band_power [F][R][G] -> power [R][G] = ((p_0 + p_1) + p_2) + ... in ascending band order (__dadd_rn, starting
 // from p_0: the additions of Demo.power_grid) and argmax [R] with power_argmax_kernel's rule (first maximum, a NaN never wins, a
 // row of NaN only gives 0).  One workgroup per row, no atomics.
@@ -66,11 +70,19 @@ struct FbChain {
 
 // LDS: [2][xin: mg rows... ] as time-major tiles.  xin[buf][t * mg + j]; yout[buf][f][t * mg + j] with a band stride of
 // (FB_TT + 1) * mg doubles: lanes (f, j) of one step then write F * mg different banks (up to 16 doubles) instead of F-way conflicts.
-template <int N>
-__global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const FilterbankCoef co, const double *__restrict__ x, int F, int B, int T,
-                                                                  int M, int mg, int ngroups, double *__restrict__ xf)
+//
+// fb_tiles<N, Resume> is the tile loop of both kernels.  Resume = false: the one-shot filterbank_kernel, zero state, exactly the code it
+// always was (`state` is not touched and every `if (Resume)` below is a compile-time false).  Resume = true: filterbank_tile_kernel,
+// one tile of a stream -- each chain lane loads its n - 1 DF2T states from `state` before the first LDS tile and stores them after the
+// last; the steps are the same FbChain<N>::step calls in the same order, so a stream cut into tiles at any frames gives the bits of one
+// call on the whole recording.  The only difference in the loop: the one-shot kernel may run the recurrence over the zero frames that
+// pad its last group of 8 (nothing of them is stored); the stream's state must not see them, so its ragged last group is stepped
+// frame by frame.  state layout: [B][n - 1][F][M] doubles -- element i of chain (f, b, m) at ((b (n - 1) + i) F + f) M + m -- so the
+// F * mw chain lanes c = f * mw + j of a workgroup read and write consecutive addresses per i when the workgroup owns all M microphones.
+template <int N, bool Resume>
+__device__ __forceinline__ void fb_tiles(double *fb_lds, const FilterbankCoef &co, const double *__restrict__ x, int F, int B, int T, int M,
+                                         int mg, int ngroups, double *__restrict__ xf, double *__restrict__ state)
 {
-    extern __shared__ __attribute__((aligned(16))) double fb_lds[];
     const int tid = threadIdx.x;
     const int b = blockIdx.x / ngroups;
     const int m0 = (blockIdx.x - b * ngroups) * mg;
@@ -88,6 +100,12 @@ __global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const Filterbank
     const int cf = chain ? tid / mw : 0, cj = chain ? tid - (tid / mw) * mw : 0;
     FbChain<N> ch;
     ch.init(co, cf);
+    // the chain's state word i (Resume only); all indices size_t
+    auto sidx = [&](int i) -> size_t { return (((size_t)b * (N - 1) + i) * F + cf) * M + m0 + cj; };
+    if (Resume && N > 1 && chain) {
+#pragma unroll
+        for (int i = 0; i < N - 1; ++i) ch.z[i] = state[sidx(i)];
+    }
 
     // element e of a tile (e < frames * mw) -> offset from the tile's first frame row
     auto goff = [&](int e) -> size_t { return full ? (size_t)e : (size_t)(e / mw) * M + (e - (e / mw) * mw); };
@@ -129,7 +147,8 @@ __global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const Filterbank
             const int nt = T - k * FB_TT < FB_TT ? T - k * FB_TT : FB_TT;
             const double *xi = xin + (k & 1) * xin_sz + cj;
             double *yo = yout + (k & 1) * yout_sz + cf * bstride + cj;
-            for (int t0 = 0; t0 < nt; t0 += FB_GROUP) {
+            const int ngrp = Resume ? nt - nt % FB_GROUP : nt;  // (one-shot: the last group may run over the padding zeros)
+            for (int t0 = 0; t0 < ngrp; t0 += FB_GROUP) {
                 double v[FB_GROUP];
 #pragma unroll
                 for (int u = 0; u < FB_GROUP; ++u) v[u] = xi[(t0 + u) * mw];
@@ -138,11 +157,36 @@ __global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const Filterbank
 #pragma unroll
                 for (int u = 0; u < FB_GROUP; ++u) yo[(t0 + u) * mw] = v[u];
             }
+            if (Resume) {
+                for (int t = ngrp; t < nt; ++t) yo[t * mw] = ch.step(xi[t * mw]);  // the ragged end of the stream's tile: no step past it
+            }
         }
         if (k + 1 < ntiles) stash_tile(k + 1);
         __syncthreads();
     }
     store_tile(ntiles - 1);
+    if (Resume && N > 1 && chain) {
+#pragma unroll
+        for (int i = 0; i < N - 1; ++i) state[sidx(i)] = ch.z[i];
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(FB_THREADS) void filterbank_kernel(const FilterbankCoef co, const double *__restrict__ x, int F, int B, int T,
+                                                                  int M, int mg, int ngroups, double *__restrict__ xf)
+{
+    extern __shared__ __attribute__((aligned(16))) double fb_lds[];
+    fb_tiles<N, false>(fb_lds, co, x, F, B, T, M, mg, ngroups, xf, nullptr);
+}
+
+// one tile of a stream: x_tile [B][T][M] -> xf_tile [F][B][T][M] with the chains' states carried in `state` (layout above)
+template <int N>
+__global__ __launch_bounds__(FB_THREADS) void filterbank_tile_kernel(const FilterbankCoef co, const double *__restrict__ x, int F, int B, int T,
+                                                                       int M, int mg, int ngroups, double *__restrict__ xf,
+                                                                       double *__restrict__ state)
+{
+    extern __shared__ __attribute__((aligned(16))) double fb_lds[];
+    fb_tiles<N, true>(fb_lds, co, x, F, B, T, M, mg, ngroups, xf, state);
 }
 
 // microphones per workgroup: all of them when the trial's tiles fit the LDS budget
@@ -179,6 +223,44 @@ hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, i
         case 7: return fb_launch<7>(co, x, F, B, T, M, xf, stream);
         case 8: return fb_launch<8>(co, x, F, B, T, M, xf, stream);
         case 9: return fb_launch<9>(co, x, F, B, T, M, xf, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- the resumable form ----------------------------------------------------------------------------------------------------------
+size_t filterbank_stream_state_bytes(int F, int n, int B, int M)
+{
+    const size_t words = (size_t)F * B * M * (n - 1);
+    const size_t bytes = (words * sizeof(double) + 255) & ~(size_t)255;
+    return bytes < 256 ? 256 : bytes;  // (n = 1 has no state: one unused block, so that 0 can mean "bad arguments")
+}
+
+template <int N>
+static hipError_t fb_tile_launch(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, double *state, hipStream_t stream)
+{
+    const int mg = fb_mic_group(F, M);
+    const int ngroups = (M + mg - 1) / mg;
+    const size_t lds = (size_t)2 * (FB_TT * mg + (size_t)F * (FB_TT + 1) * mg) * sizeof(double);
+    const long long blocks = (long long)B * ngroups;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filterbank_tile_kernel<N>, dim3((unsigned)blocks), dim3(FB_THREADS), lds, stream, co, x, F, B, T, M, mg, ngroups, xf, state);
+    return hipGetLastError();
+}
+
+hipError_t launch_filterbank_tile(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, double *state,
+                                  hipStream_t stream)
+{
+    if (F < 1 || F > MICLOC_MAX_BANDS || B < 1 || T < 1 || M < 1 || !state) return hipErrorInvalidValue;
+    switch (co.n) {
+        case 1: return fb_tile_launch<1>(co, x, F, B, T, M, xf, state, stream);
+        case 2: return fb_tile_launch<2>(co, x, F, B, T, M, xf, state, stream);
+        case 3: return fb_tile_launch<3>(co, x, F, B, T, M, xf, state, stream);
+        case 4: return fb_tile_launch<4>(co, x, F, B, T, M, xf, state, stream);
+        case 5: return fb_tile_launch<5>(co, x, F, B, T, M, xf, state, stream);
+        case 6: return fb_tile_launch<6>(co, x, F, B, T, M, xf, state, stream);
+        case 7: return fb_tile_launch<7>(co, x, F, B, T, M, xf, state, stream);
+        case 8: return fb_tile_launch<8>(co, x, F, B, T, M, xf, state, stream);
+        case 9: return fb_tile_launch<9>(co, x, F, B, T, M, xf, state, stream);
         default: return hipErrorInvalidValue;
     }
 }

@@ -252,6 +252,23 @@ hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, i
 // band_power [F][R][G] -> power [R][G] (ascending band order, from p_0), argmax [R] (first maximum; either may be NULL)
 hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, double *power, int32_t *argmax, hipStream_t stream);
 
+// ---- wideband streaming: the resumable filterbank (filterbank.hip) and the band sum of a stream (stream_bands.hip) ----------------
+// fb_state: [B][n - 1][F][M] doubles (at least 256 B), zero-filled once; one tile x [B][T][M] -> xf [F][B][T][M]
+size_t filterbank_stream_state_bytes(int F, int n, int B, int M);
+hipError_t launch_filterbank_tile(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, double *state,
+                                  hipStream_t stream);
+// per band: running power [B][G], window ring [B][Kb][G], the device word that counts the band's windows -- by value, no device table
+struct StreamBandsArgs {
+    const double *power[MICLOC_MAX_BANDS];
+    const double *rows[MICLOC_MAX_BANDS];
+    const int32_t *count[MICLOC_MAX_BANDS];
+};
+constexpr size_t STREAM_BANDS_STATE_BYTES = 256;  // int words {emitted, given up, pending emitted, pending given up}
+// the running band sum and (windowed) the emission of the wideband windows every band has emitted, then the one-thread commit
+hipError_t launch_stream_band_sum(const StreamBandsArgs &args, int F, int B, int G, int windowed, int Kb, int max_windows, void *state,
+                                  double *power, int32_t *argmax, double *power_w, int32_t *argmax_w, double *latest_power,
+                                  int32_t *latest_argmax, hipStream_t stream);
+
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
 struct MusicDims {
     int B, T, M;     // trials, samples per trial, microphones

@@ -67,6 +67,14 @@ class Demo:
         loc.doa_list = self.doa_list
         return loc
 
+    def streaming_localizer(self, batch=1, **kw):
+        """The live form of this demo's chain: streaming.WidebandStreamingLocalizer over the same bands -- the packs of `batch` sources are
+        tiles of ONE stream each (the filterbank, the STHT, the band-pass, the encoder and the LIF carry their state from pack to pack instead
+        of restarting as `process_frame` does), one graph launch per pack through push_replay.  **kw: WidebandStreamingLocalizer's."""
+        from .streaming import WidebandStreamingLocalizer
+
+        return WidebandStreamingLocalizer(self.localizer(), batch, **kw)
+
     def process_frames(self, packs, rel_threshold=0.0001):
         """`process_frame` for a batch of recorded packs [B, T, num_mic + 1] of one length: DoA in degrees per pack [B], NaN for the
         packs below the activity threshold (tested per pack, on the host, as in the loop); the others go through ONE

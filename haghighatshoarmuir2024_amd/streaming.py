@@ -42,7 +42,7 @@ from .snn_beamformer import neuron_impulse_response
 
 class StreamingLocalizer:
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False,
-                 window=None, hop=None, max_windows=None):
+                 window=None, hop=None, max_windows=None, _share=None):
         """beamf: SNNBeamformer; bf_mat [2M, G]; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself, and the neuron kernel is
                       normalised over exactly that many samples like apply_to_signal does, snn_beamformer.py:342-361); None: a
@@ -55,7 +55,10 @@ class StreamingLocalizer:
         window, hop   frames (hop defaults to window; 1 <= hop <= window, both multiples of the plan's window quantum): also emit power
                       and arg-max per window (module docstring); None: the running estimate only, with exactly the launches it always had.
         max_windows   rows of the ring the windows are kept in (window n in row n % max_windows); default: every window of the
-                      recording when total_frames is given, else 64."""
+                      recording when total_frames is given, else 64.
+        _share        (WidebandStreamingLocalizer) another StreamingLocalizer whose tile-sized scratch (`ext`, `h`, `ws`, the slide's staging
+                      copy) this one uses instead of allocating its own, where it is large enough: for localizers whose tiles run one
+                      after the other on one stream.  None: nothing changes."""
         if window is None and (hop is not None or max_windows is not None):
             raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
         torch = runtime._torch()
@@ -93,14 +96,22 @@ class StreamingLocalizer:
         self.nloc = self.lib.micloc_stream_localize_state_bytes(self.plan.handle, self.B)
         self.loc = torch.empty(int(self.nloc), dtype=torch.uint8, device=dev)
         self.nws = self.lib.micloc_stream_localize_workspace_bytes(self.plan.handle, self.B, self.cap)
-        self.ws = torch.empty(int(self.nws), dtype=torch.uint8, device=dev)
+
+        def scratch(name, shape, dtype):  # a buffer that holds nothing between two tiles
+            other = getattr(_share, name, None)
+            if other is not None and other.dtype == dtype and other.device == dev and other.dim() == len(shape) and other.numel() >= int(np.prod(shape)) \
+                    and (len(shape) == 1 or tuple(other.shape) == tuple(shape)):
+                return other
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        self.ws = scratch("ws", (int(self.nws),), torch.uint8)
         self.win = torch.empty((self.B, self.cap, self.C), dtype=torch.int8, device=dev)
-        self.win_tmp = torch.empty_like(self.win)  # the slide's staging copy
+        self.win_tmp = scratch("win_tmp", (self.B, self.cap, self.C), torch.int8)  # the slide's staging copy
         self.base = 0  # host mirror of the device clock's window base (the schedule depends on the tile sizes only)
         # tile workspace, allocated once: [history | tile] frames and their planar STHT output (+ one spare row, see _tile)
         self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (lfilter's zero state)
-        self.ext = torch.empty(self.B * (self.halo + self.max_tile) * self.M, dtype=torch.float64, device=dev)
-        self.h = torch.empty((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile), dtype=torch.float64, device=dev)
+        self.ext = scratch("ext", (self.B * (self.halo + self.max_tile) * self.M,), torch.float64)
+        self.h = scratch("h", ((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile),), torch.float64)
         self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
         self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         if self.window is not None:
@@ -292,6 +303,249 @@ class StreamingLocalizer:
             self._save_window(self.t)
             spikes = self.raster
         out = dict(power=self.power, argmax=self.argmax, spikes=spikes)
+        if self.window is not None:
+            if self.T is not None:
+                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
+                if self.max_windows < nW:
+                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
+                                           "windows() while the stream runs)")
+            w = self.windows()
+            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
+        return out
+
+
+class WidebandStreamingLocalizer:
+    """The wideband chain (wideband.WidebandSNNLocalizer: a filterbank, one SNNBeamformer chain per band, the power patterns added, one
+    arg-max -- what the reference deploys, micloc/localization_demo_snn.py:125-193) as ONE stream that arrives in tiles, with the results of
+    `WidebandSNNLocalizer.localize_batch` on the whole recording bit for bit, whatever the tiling (include/micloc_hip.h "wideband
+    streaming").  The reference's live loop restarts the filterbank, the STHT, the band-pass, the encoder and the LIF on every pack; here
+    every one of them carries its state across the tiles.
+
+    One tile = the filterbank tile (micloc_filterbank_tile_f64: the DF2T states live on the device), then for f ascending band f's tile
+    launches (a StreamingLocalizer per band with its own plan, encoder and localize state, raster window, running power and window ring;
+    the bands run one after the other on the one stream and share the tile-sized scratch), then the band sum
+    (micloc_stream_band_sum_f64).  push_replay() captures that whole sequence as one graph per tile length.
+
+    The surface is StreamingLocalizer's: push, push_replay, status, latest_window, windows, finish.
+
+    RING DEPTH of the bands (Kb).  Bands finish a window at different calls; a wideband window is emitted once every band has emitted
+    it, so the windows [emitted, count_f) must still be in band f's ring when the band sum runs.  `emitted` is the smallest count after
+    the PREVIOUS tile.  A band without a lag failure of its own has beamformed every frame before the base of its raster window, which
+    is at most `cap` frames behind the frames pushed, so after the previous tile (t' frames pushed) every band had completed the
+    windows of at least t' - cap frames; after this tile (t <= t' + max_tile frames) a band has emitted at most the windows completed by
+    t frames, plus the one cut at the end of the recording on the final tile.  The windows completed by two frame counts that are d
+    apart differ by at most ceil(d / hop), hence count_f - emitted <= ceil((cap + max_tile) / hop) + 1.  Kb is that bound plus one row
+    of slack, or the number of windows of the recording where that is known and smaller.  The band sum counts a failure instead of
+    summing an overwritten row should the bound ever be exceeded (only after a band's own lag failure); finish() then raises."""
+
+    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, window=None, hop=None, max_windows=None):
+        """loc: wideband.WidebandSNNLocalizer; the other arguments as StreamingLocalizer's, except
+        wrap_tail  [F, batch, L // 2, M]: the last L // 2 frames of every band's FILTERED recording (np.roll's wrap-around happens after
+                   the filterbank), or None (zeros, as for a live source)."""
+        if window is None and (hop is not None or max_windows is not None):
+            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+        torch = runtime._torch()
+        self.loc_def = loc
+        F = self.F = len(loc.beamfs)
+        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+            raise ValueError(f"a wideband stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+        self.B, self.M, self.G = int(batch), loc.num_mic, loc.num_grid
+        self.T = None if total_frames is None else int(total_frames)
+        L2 = len(loc.beamfs[0].kernel) // 2
+        if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
+            raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
+        if window is not None and hop is not None and int(hop) > int(window):
+            raise ValueError(f"the streaming read-out needs hop <= window (hop {int(hop)}, window {int(window)})")
+        if max_windows is not None and int(max_windows) < 1:
+            raise ValueError("max_windows must be at least 1")
+        self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
+        if len(loc.filterbank.ba_list) != F:
+            raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
+        # the bands: band 0 checks window / hop against the quantum (ValueError) before anything is launched
+        self.max_tile = -(-int(max_tile) // 16) * 16
+        self.bands = []
+        Kb = None
+        for f, (beamf, W) in enumerate(zip(loc.beamfs, loc.bf_mats)):
+            kw = {}
+            if window is not None:
+                if Kb is None:
+                    Kb = self._ring_depth(window, hop, lag_frames)
+                kw = dict(window=window, hop=hop, max_windows=Kb)
+            tail = None if wrap_tail is None else wrap_tail[f]
+            self.bands.append(StreamingLocalizer(beamf, W, self.B, self.T, wrap_tail=tail, max_tile=max_tile, lag_frames=lag_frames,
+                                                 _share=self.bands[0] if self.bands else None, **kw))
+        b0 = self.bands[0]
+        self.device, self.lib, self.plan = b0.device, b0.lib, b0.plan
+        self.window, self.hop, self.Kb = b0.window, b0.hop, Kb
+        if any(b.window != self.window or b.hop != self.hop or b.CH != b0.CH for b in self.bands):
+            raise ValueError("window and hop must be multiples of every band's chunk length")
+        if any(b.cap > self._cap_bound(lag_frames) for b in self.bands):
+            raise _lib.MiclocError("a band's raster window is longer than the bound the ring depth was derived from")
+        dev = self.device
+        self.max_windows = None
+        if self.window is not None:
+            nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T) if self.T is not None else None
+            self.max_windows = int(max_windows) if max_windows is not None else (nW if nW is not None else 64)
+        self.nfb = int(self.lib.micloc_filterbank_stream_state_bytes(F, self.ncoef, self.B, self.M))
+        if self.nfb == 0:
+            raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
+        self.fb_state = torch.empty(self.nfb, dtype=torch.uint8, device=dev)
+        self.nbs = int(self.lib.micloc_stream_bands_state_bytes())
+        self.bands_state = torch.empty(self.nbs, dtype=torch.uint8, device=dev)
+        self.xf = torch.empty(F * self.B * self.max_tile * self.M, dtype=torch.float64, device=dev)  # the filtered tile [F][B][n][M]
+        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        vp = ctypes.c_void_p
+        self._p_power = (vp * F)(*[b.power.data_ptr() for b in self.bands])
+        self._p_rows = self._p_count = None
+        self.window_power = self.window_argmax = self.latest_power = self.latest_argmax = None
+        if self.window is not None:
+            self._p_rows = (vp * F)(*[b.window_power.data_ptr() for b in self.bands])
+            self._p_count = (vp * F)(*[self.lib.micloc_stream_window_count_ptr(runtime._ptr(b.wst)) for b in self.bands])
+            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
+            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
+            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self.t = 0
+        self.done = False
+        self._seen, self._graphs = set(), {}
+        st = runtime._stream(dev)
+        _lib.check(self.lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, st), "filterbank_stream_reset")
+        _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, st), "stream_bands_reset")
+
+    MAX_CHUNK = 512  # the longest chunk of the beamforming kernels (include/micloc_hip.h: 256 frames up to 64 channels, 512 beyond)
+
+    def _ring_depth(self, window, hop, lag_frames):
+        """Kb of the class docstring, with `cap` bounded from the arguments alone (a chunk is at most MAX_CHUNK frames; the constructor
+        checks the bands' real `cap` against it).  A window or hop that does not fit the quantum is left to band 0's constructor."""
+        hop = int(window if hop is None else hop)
+        if hop < 1 or int(window) < 1:
+            return 1
+        Kb = -(-(self._cap_bound(lag_frames) + self.max_tile) // hop) + 2
+        if self.T is not None and self.T >= 1:
+            Kb = min(Kb, utils.windows_complete(self.T, int(window), hop, T=self.T))
+        return max(1, Kb)
+
+    def _cap_bound(self, lag_frames):
+        return self.max_tile + int(lag_frames) + 3 * self.MAX_CHUNK
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _check_tile(self, B, n, M, final):
+        if self.done:
+            raise _lib.MiclocError("the stream has ended")
+        final = self.bands[0]._check_tile(B, n, M, final)  # the bands advance in lock step: one check serves all
+        return final
+
+    def _tile(self, x, n, final):
+        """The launches of one tile, all on the current stream, in a fixed order: filterbank tile, the bands in ascending order, band
+        sum.  Nothing else (no allocation, no synchronisation, no absolute time), so a tile of a given length is one replayable graph."""
+        lib, F, B, M = self.lib, self.F, self.B, self.M
+        st = runtime._stream(self.device)
+        xf = self.xf[: F * B * n * M].view(F, B, n, M)
+        _lib.check(lib.micloc_filterbank_tile_f64(runtime._dptr(self.bb), runtime._dptr(self.aa), F, self.ncoef, runtime._ptr(x), B, n, M,
+                                                  runtime._ptr(self.fb_state), self.nfb, runtime._ptr(xf), st), "filterbank_tile")
+        for f, band in enumerate(self.bands):
+            band._tile(xf[f], n, final)
+        if self.window is None:
+            _lib.check(lib.micloc_stream_band_sum_f64(F, B, self.G, self._p_power, 0, 0, 0, None, None, runtime._ptr(self.bands_state), self.nbs,
+                                                      runtime._ptr(self.power), runtime._ptr(self.argmax), None, None, None, None, st), "stream_band_sum")
+        else:
+            _lib.check(lib.micloc_stream_band_sum_f64(F, B, self.G, self._p_power, self.window, self.Kb, self.max_windows, self._p_rows, self._p_count,
+                                                      runtime._ptr(self.bands_state), self.nbs, runtime._ptr(self.power), runtime._ptr(self.argmax),
+                                                      runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
+                                                      runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st), "stream_band_sum")
+
+    def _advance(self, n, final):
+        for band in self.bands:
+            band._advance(n, final)
+        self.t += n
+        self.done = bool(final)
+
+    def push(self, x_tile, final=None):
+        """x_tile [batch, n, M] (numpy or device tensor), tiles as StreamingLocalizer.push's.  Returns the running (power, argmax) device
+        tensors of the band sum (overwritten by the next push; every band over the frames IT has beamformed so far)."""
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        final = self._check_tile(B, n, M, final)
+        self._tile(x, n, final)
+        self._seen.add(n)
+        self._advance(n, final)
+        return self.power, self.argmax
+
+    def push_replay(self, x_tile):
+        """push() as ONE graph launch per tile: a non-final tile whose length has been pushed before is captured on its second occurrence
+        (filterbank tile, every band's launches, band sum) and replayed from then on.  Same results as push()."""
+        torch = runtime._torch()
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        if n not in self._seen or (self.T is not None and self.t + n == self.T):
+            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
+        self._check_tile(B, n, M, False)
+        g = self._graphs.get(n)
+        if g is None:
+            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
+            graph = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
+                self._tile(x_in, n, False)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            g = self._graphs[n] = (graph, x_in)
+        g[1].copy_(x)
+        g[0].replay()
+        self._advance(n, False)
+        return self.power, self.argmax
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def _bands_status(self):
+        st2 = (ctypes.c_int * 2)()
+        _lib.check(self.lib.micloc_stream_bands_status(runtime._ptr(self.bands_state), st2, runtime._stream(self.device)), "stream_bands_status")
+        return int(st2[0]), int(st2[1])
+
+    def status(self):
+        """StreamingLocalizer.status() over the bands -- chunks / frames: the slowest band's; lag_failures / overflow: summed -- plus
+        bands (the per-band dicts) and band_sum_failures (windows given up because a band's ring had overwritten them).  Synchronises."""
+        per = [b.status() for b in self.bands]
+        return dict(chunks=min(s["chunks"] for s in per), frames=min(s["frames"] for s in per), lag_failures=sum(s["lag_failures"] for s in per),
+                    overflow=sum(s["overflow"] for s in per), bands=per, band_sum_failures=self._bands_status()[1])
+
+    def _need_windows(self):
+        if self.window is None:
+            raise ValueError("the localizer was built without window=")
+
+    def latest_window(self):
+        """(power [B, G], argmax [B]) of the most recently emitted wideband window: device tensors, zeros until the first one exists."""
+        self._need_windows()
+        return self.latest_power, self.latest_argmax
+
+    def windows(self):
+        """StreamingLocalizer.windows() of the band sum: dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]).
+        `count` is the smallest of the bands' counts at the last push.  Synchronises the stream."""
+        self._need_windows()
+        torch = runtime._torch()
+        count = self._bands_status()[0]
+        k = min(count, self.max_windows)
+        first = count - k
+        rows = torch.arange(first, count, device=self.device) % self.max_windows
+        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
+                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+
+    def finish(self):
+        """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
+        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        torch = runtime._torch()
+        if not self.done:
+            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+        s = self.status()
+        if s["overflow"]:
+            raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
+                                   "one-shot call, which redoes such streams exactly")
+        if s["lag_failures"] or s["frames"] != self.t:
+            raise _lib.MiclocError(f"a band's raster window ({self.bands[0].cap} frames) slid past frames whose spikes were not final yet "
+                                   f"({s['frames']} of {self.t} frames beamformed by the slowest band): raise lag_frames")
+        if s["band_sum_failures"]:
+            raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
+        out = dict(power=self.power, argmax=self.argmax, band_power=torch.stack([b.power for b in self.bands]))
         if self.window is not None:
             if self.T is not None:
                 nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)

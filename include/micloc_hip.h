@@ -304,6 +304,9 @@ int micloc_stream_localize_tile_windows_f64(const micloc_plan *plan, const void 
                                             int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power,
                                             int32_t *latest_argmax, void *stream);
 int micloc_stream_window_count(const void *win_state, int *count, void *stream);
+/* device address of the int32 word micloc_stream_window_count reads (a kernel that follows a band's windows takes it: "wideband
+ * streaming" below); valid as long as win_state is */
+const int32_t *micloc_stream_window_count_ptr(const void *win_state);
 
 /* ---- beamforming vectors from membrane covariances (design_from_template's decomposition step) ------ */
 /* Replaces the per-DoA np.linalg.svd calls of SNNBeamformer.design_from_template (snn_beamformer.py:183-203) and
@@ -604,6 +607,67 @@ int micloc_snn_pipeline_bands_f64(const micloc_plan *const *plans, int F, const 
                                   const double *x, int B, int T, int window, int hop, /* window 0: whole recording */
                                   double *band_power /* [F][R][G] or NULL */, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
                                   void *stream);
+
+/* ---- wideband streaming: filterbank state carry, band sum per tile ------------------------------ */
+/* The wideband chain above for ONE stream that arrives in tiles: the results after the last tile are bit for bit those of
+ * micloc_snn_pipeline_bands_f64 on the whole recording, for any tiling.  One tile of n frames, every launch on the caller's one
+ * stream in this order (nothing side by side: a captured tile is a chain of nodes), no allocation, no host synchronisation, no
+ * atomics, no argument that depends on absolute time:
+ *   micloc_filterbank_tile_f64      x_tile [B][n][M] -> xf_tile [F][B][n][M], n >= 1 of any length
+ *   per band f in ascending order   the tile sequence of "streaming" above (begin_tile .. localize_tile[_windows]) of plans[f] on
+ *                                   xf_tile[f], with that band's own states, raster window, running power and window ring
+ *   micloc_stream_band_sum_f64      the running band sum and the wideband windows every band has emitted
+ *   Filterbank tile.
+ *   - The arithmetic is the filterbank's DF2T step unchanged; the state of every (band, trial, microphone) chain is read from and
+ *     written back to fb_state, so a stream cut into tiles at any frames performs exactly the operations of one
+ *     micloc_filterbank_f64 call on the whole recording: xf is bit-identical.
+ *   - fb_state: micloc_filterbank_stream_state_bytes(F, n_coef, B, M) bytes, 256-B aligned, zero-filled once by
+ *     micloc_filterbank_stream_reset: F B M (n_coef - 1) doubles rounded up to 256 B (at least 256 B), laid out
+ *     [B][n_coef - 1][F][M] -- word i of chain (f, b, m) at ((b (n_coef - 1) + i) F + f) M + m -- so that the chain lanes of a
+ *     workgroup (band-major over the trial's microphones) touch consecutive addresses for every i.  Loaded once before the tile's
+ *     first frame, stored once after its last.
+ *   - Status, before any launch: as micloc_filterbank_f64 (MICLOC_ERR_INVALID for NULL, F outside 1..MICLOC_MAX_BANDS, n outside
+ *     1..MICLOC_MAX_IIR, a_f[0] == 0, B, n_frames or M < 1); MICLOC_ERR_WORKSPACE for a short or misaligned fb_state.
+ *   Band sum, running read-out.
+ *   - power[b][g] = ((p_0[b][g] + p_1[b][g]) + p_2[b][g]) + ... over the bands' running power [B][G] (band_power: a HOST array of F
+ *     device pointers; they travel by value in the kernel argument), ascending band order from p_0, every addition rounded to
+ *     nearest; argmax by micloc_band_sum_f64's rule.  Before the last tile this is the running estimate -- each band's power is
+ *     over the frames THAT band has beamformed so far, which can differ between bands; after the last tile it is bit for bit the
+ *     one-shot power / argmax.  power or argmax may be NULL, not both.
+ *   Band sum, windows (window > 0; window == 0: the running read-out only and the window arguments are ignored).
+ *   - Every band emits its own windows into a ring band_window_power[f] [B][Kb][G] (its micloc_stream_localize_tile_windows_f64
+ *     called with max_windows = Kb: window n in row n % Kb) and counts them in the device word band_window_count[f]
+ *     (micloc_stream_window_count_ptr of its win_state); both are HOST arrays of F device pointers.  Bands finish a window at
+ *     different calls: their horizons depend on their own open clusters.
+ *   - Wideband window n is emitted by the first band-sum launch after which every band has emitted window n: after a launch,
+ *     min_f count_f windows have been emitted, in ascending n, window n into row n % max_windows of window_power
+ *     [B][max_windows][G] (may be NULL) and window_argmax [B][max_windows]; latest_power [B][G] / latest_argmax [B] (may be NULL)
+ *     take the most recently emitted window and are untouched until the first one exists.
+ *   - The value is the ascending band sum of the bands' rows: bit for bit the one-shot window_power / window_argmax.  An emitted row
+ *     never changes until window n + max_windows takes its place.
+ *   - Ring depth: the windows [emitted, count_f) must still be in band f's ring.  Where count_f - emitted > Kb for some band, the
+ *     windows n < max_f count_f - Kb not emitted yet are GIVEN UP: nothing is written for them, they are added to the failure count
+ *     and to the emitted count (emission goes on behind them); a row that holds a later window is never summed.
+ *   - window and hop are multiples of every band's micloc_stream_chunk_frames (checked by the bands' own calls).
+ *   State: bands_state (micloc_stream_bands_state_bytes, 256-B aligned, zero-filled once by micloc_stream_bands_reset): the count of
+ *   windows emitted or given up and the count given up.  The launch is followed by a one-thread commit launch that makes the new
+ *   counts visible, so every workgroup of a launch reads the same count.  micloc_stream_bands_status: {emitted or given up, given
+ *   up}; synchronises the stream.
+ *   Status, before any launch: MICLOC_ERR_INVALID for NULL (band_power, an entry of it, bands_state, both of power / argmax; with
+ *   window > 0 the two window tables, an entry of them, window_argmax), F outside 1..MICLOC_MAX_BANDS, B outside 1..65535, G < 1,
+ *   window < 0, and with window > 0 max_windows < 1 or Kb < 1; MICLOC_ERR_WORKSPACE for a short or misaligned bands_state. */
+size_t micloc_filterbank_stream_state_bytes(int F, int n, int B, int M); /* 0 on bad arguments */
+int micloc_filterbank_stream_reset(void *fb_state, size_t bytes, void *stream);
+int micloc_filterbank_tile_f64(const double *b, const double *a, int F, int n, /* host [F][n] each */
+                               const double *x_tile, int B, int n_frames, int M, void *fb_state, size_t fb_bytes, double *xf_tile,
+                               void *stream);
+size_t micloc_stream_bands_state_bytes(void);
+int micloc_stream_bands_reset(void *bands_state, size_t bytes, void *stream);
+int micloc_stream_band_sum_f64(int F, int B, int G, const double *const *band_power, int window /* 0: running read-out only */, int Kb,
+                               int max_windows, const double *const *band_window_power, const int32_t *const *band_window_count,
+                               void *bands_state, size_t bands_bytes, double *power, int32_t *argmax, double *window_power,
+                               int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *stream);
+int micloc_stream_bands_status(const void *bands_state, int *status2, void *stream);
 
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
