@@ -127,6 +127,19 @@ SYMBOLS = {
                                                         c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "micloc_stream_window_count": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_stream_window_count_ptr": (c_void_p, [c_void_p]),
+    "micloc_stream_complex_state_bytes": (c_size_t, [c_void_p, c_int]),
+    "micloc_stream_complex_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "micloc_stream_complex_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_complex_bandpass_tile_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                                        c_void_p]),
+    "micloc_stream_complex_localize_tile_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                        c_void_p]),
+    "micloc_stream_complex_window_state_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "micloc_stream_complex_window_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "micloc_stream_complex_localize_tile_windows_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                                c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                                c_void_p, c_void_p]),
+    "micloc_stream_complex_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_design_vectors_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
     "micloc_peak_location_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "micloc_doa_peaks_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),

@@ -9,6 +9,7 @@ reference method                      -> what runs here
                                          SVD / generalised eigh on the host (LAPACK, like the reference: its phases), or --
                                          svd="device" -- the batched Jacobi kernel (micloc_design_vectors_f64)
   localize_batch (new)                -> power [B,G], arg-max [B] for a batch of trials, no T x G temporary
+  streaming_localizer (new)           -> the same for recordings that arrive in tiles (streaming.ComplexStreamingLocalizer)
 """
 from numbers import Number
 
@@ -85,6 +86,14 @@ class Beamformer:
                                      min_separation, rel_threshold)
         return _add_peaks(plan.beamformer_pipeline(plan.to_device(sig_batch), want_y=False, want_power=True), doa_list, num_sources, min_separation,
                           rel_threshold)
+
+    def streaming_localizer(self, bf_mat, batch=1, **kw):
+        """localize_batch for recordings that arrive tile by tile: a streaming.ComplexStreamingLocalizer (push / push_replay / finish;
+        total_frames, wrap_tail, max_tile, window, hop, max_windows as there) whose results after the last tile are localize_batch's on
+        the whole recording bit for bit."""
+        from .streaming import ComplexStreamingLocalizer
+
+        return ComplexStreamingLocalizer(self, bf_mat, batch, **kw)
 
     def track_batch(self, bf_mat, sig_batch, envelope, want_envelope_last=False, budget_bytes=1 << 30):
         """The moving-target read-out for a batch, sig_batch [B, T, M]: `np.argmax(envelope.evolve(apply_to_signal(...)), axis=1)` per

@@ -1273,6 +1273,177 @@ int micloc_stream_localize_status(const void *loc_state, int *status4, void *str
     return MICLOC_OK;
 }
 
+// ---- streaming, complex Beamformer (stream_complex.hip; the rule: include/micloc_hip.h) ------------------------------------------------
+// state: [256 B control words][DF2T words][carry][acc] (stream_complex_layout); ws: [staging [B][2M][Ks CH]][partial [B][Ks][Gp]]
+namespace {
+
+struct ScArgs {
+    int CH, Ks, S, Gp;
+    StreamComplexLayout L;
+    size_t ws_partial, ws_total;
+};
+
+// MICLOC_OK and *a, or the status of the rule's argument errors (p non-NULL, B checked)
+int sc_args(const micloc_plan *p, int B, int max_tile, ScArgs *a)
+{
+    if (!p->d_W) return MICLOC_ERR_NOT_SET;
+    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int CH = window_quantum(p);
+    if (CH < 1) return MICLOC_ERR_INVALID;
+    a->CH = CH;
+    a->Gp = 16 * p->W.GT;
+    a->L = stream_complex_layout(B, p->C, p->G_out, p->iir.n, CH);
+    a->Ks = a->S = 0;
+    a->ws_partial = a->ws_total = 0;
+    if (max_tile > 0) {
+        if ((long long)max_tile + 2ll * CH > 0x7fffffffll) return MICLOC_ERR_SHAPE;
+        a->Ks = stream_complex_chunks(max_tile, CH);
+        a->S = a->Ks * CH;
+        a->ws_partial = align256((size_t)B * p->C * a->S * sizeof(double));
+        a->ws_total = a->ws_partial + align256(beamform_partial_bytes(B, a->S, a->Gp));
+    }
+    return MICLOC_OK;
+}
+
+int sc_window_args(int window, int hop, int max_windows, int CH)
+{
+    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
+    if (window % CH != 0 || hop % CH != 0 || hop > window) return MICLOC_ERR_SHAPE;
+    return MICLOC_OK;
+}
+
+// the launches behind the band-pass of a tile: contraction, accumulation, (windows,) slide + commit -- one chain on one stream
+int sc_localize(const micloc_plan *p, const ScArgs &a, void *state, int B, int final_tile, double *power, int32_t *argmax, void *ws,
+                void *win_state, int window, int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power,
+                int32_t *latest_argmax, hipStream_t st)
+{
+    double *staging = reinterpret_cast<double *>(ws);
+    double *partial = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(ws) + a.ws_partial);
+    int nch = 0;
+    // the staging array as a recording of Ks whole chunks: the launch shape depends on max_tile only; the rows past the valid ones are never read
+    HIP_TRY(launch_planar_beamform(p->W, staging, B, a.S, a.S, nullptr, 1, partial, st, &nch));
+    if (nch != a.Ks) return MICLOC_ERR_INVALID;  // the launch chose a kernel window_quantum() does not describe
+    HIP_TRY(launch_stream_complex_accumulate(partial, B, a.Ks, a.Gp, p->G_out, a.CH, final_tile, state, a.L, power, argmax, st));
+    if (win_state)
+        HIP_TRY(launch_stream_complex_windows(partial, B, a.Ks, a.Gp, p->G_out, a.CH, state, final_tile, window, hop, max_windows, win_state,
+                                              window_power, window_argmax, latest_power, latest_argmax, st));
+    HIP_TRY(launch_stream_complex_slide(staging, B * p->C, a.S, a.CH, state, a.L, st));
+    return MICLOC_OK;
+}
+
+}  // namespace
+
+size_t micloc_stream_complex_state_bytes(const micloc_plan *p, int B)
+{
+    ScArgs a;
+    if (!p || bad_batch(B) || sc_args(p, B, 0, &a) != MICLOC_OK) return 0;
+    return a.L.total;
+}
+
+size_t micloc_stream_complex_workspace_bytes(const micloc_plan *p, int B, int max_tile)
+{
+    ScArgs a;
+    if (!p || bad_batch(B) || max_tile < 1 || sc_args(p, B, max_tile, &a) != MICLOC_OK) return 0;
+    return a.ws_total;
+}
+
+int micloc_stream_complex_reset(const micloc_plan *p, int B, void *state, size_t state_bytes, void *stream)
+{
+    if (!p || !state || bad_batch(B)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    ScArgs a;
+    const int rc = sc_args(p, B, 0, &a);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_zero_fill(state, a.L.total, (hipStream_t)stream));  // clock, zero DF2T state (lfilter's), empty carry, accumulators
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_bandpass_tile_f64(const micloc_plan *p, const double *h, int B, int n, int row_stride, int first_col, int max_tile,
+                                            void *state, size_t state_bytes, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!p || !h || !state || !ws || bad_batch(B) || n < 1 || max_tile < 1 || first_col < 0 || row_stride < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    ScArgs a;
+    const int rc = sc_args(p, B, max_tile, &a);
+    if (rc != MICLOC_OK) return rc;
+    if (n > max_tile || (long long)first_col + n > row_stride) return MICLOC_ERR_SHAPE;
+    if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, a.ws_total)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_stream_complex_bandpass(p->iir, h + first_col, B * p->C, n, (size_t)row_stride, reinterpret_cast<double *>(ws), a.S, a.CH,
+                                           state, a.L, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_localize_tile_f64(const micloc_plan *p, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
+                                            double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!p || !state || !ws || bad_batch(B) || max_tile < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    ScArgs a;
+    const int rc = sc_args(p, B, max_tile, &a);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, a.ws_total)) return MICLOC_ERR_WORKSPACE;
+    return sc_localize(p, a, state, B, final_tile, power, argmax, ws, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+size_t micloc_stream_complex_window_state_bytes(const micloc_plan *p, int B, int window, int hop, int max_windows)
+{
+    ScArgs a;
+    if (!p || bad_batch(B) || sc_args(p, B, 0, &a) != MICLOC_OK || sc_window_args(window, hop, max_windows, a.CH) != MICLOC_OK) return 0;
+    return stream_window_state_bytes(B, p->G_out, window, hop);
+}
+
+int micloc_stream_complex_window_reset(const micloc_plan *p, int B, void *win_state, size_t win_bytes, int window, int hop, int max_windows,
+                                       void *stream)
+{
+    if (!p || !win_state || bad_batch(B)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
+    ScArgs a;
+    int rc = sc_args(p, B, 0, &a);
+    if (rc == MICLOC_OK) rc = sc_window_args(window, hop, max_windows, a.CH);
+    if (rc != MICLOC_OK) return rc;
+    const size_t need = stream_window_state_bytes(B, p->G_out, window, hop);
+    if (bad_ws(win_state, win_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_zero_fill(win_state, need, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_localize_tile_windows_f64(const micloc_plan *p, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
+                                                    double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes,
+                                                    int window, int hop, int max_windows, double *window_power, int32_t *window_argmax,
+                                                    double *latest_power, int32_t *latest_argmax, void *stream)
+{
+    if (!p || !state || !ws || !win_state || !window_argmax || bad_batch(B) || max_tile < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
+    ScArgs a;
+    int rc = sc_args(p, B, max_tile, &a);
+    if (rc == MICLOC_OK) rc = sc_window_args(window, hop, max_windows, a.CH);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, a.ws_total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(win_state, win_bytes, stream_window_state_bytes(B, p->G_out, window, hop))) return MICLOC_ERR_WORKSPACE;
+    return sc_localize(p, a, state, B, final_tile, power, argmax, ws, win_state, window, hop, max_windows, window_power, window_argmax,
+                       latest_power, latest_argmax, (hipStream_t)stream);
+}
+
+/* status[0] = chunks contracted, [1] = frames contracted, [2] = carry fill, [3] = frames pushed (synchronises the stream) */
+int micloc_stream_complex_status(const void *state, int *status4, void *stream)
+{
+    if (!state || !status4) return MICLOC_ERR_INVALID;
+    int ctl[STREAM_CLK_T + 1];
+    HIP_TRY(hipMemcpyAsync(ctl, state, sizeof(ctl), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    status4[0] = ctl[0];
+    status4[1] = ctl[8];
+    status4[2] = ctl[2];
+    status4[3] = ctl[STREAM_CLK_T];
+    return MICLOC_OK;
+}
+
 // ---- stand-alone operators -------------------------------------------------------------------------------
 size_t micloc_rzcc_workspace_bytes(int B, int T, int C) { return micloc_rzcc_workspace_bytes_ex(B, T, C, 1, 0); }
 

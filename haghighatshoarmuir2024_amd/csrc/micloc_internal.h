@@ -148,6 +148,27 @@ hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp,
                                  int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
                                  double *latest_power, int32_t *latest_argmax, hipStream_t stream);
 
+// ---- streaming, complex Beamformer (stream_complex.hip) -------------------------------------------------------------------------
+// state: [256 B: 64 control ints][z: (n - 1) x nl DF2T words, word i of chain g at i nl + g][carry [nl][CH]][acc [B][2][G]], nl = B C
+struct StreamComplexLayout {
+    size_t z, carry, acc, total;
+};
+StreamComplexLayout stream_complex_layout(int B, int C, int G, int iir_n, int CH);
+int stream_complex_chunks(int max_tile, int CH);  // Ks: chunk rows of the staging array, ceil((max_tile + CH - 1) / CH)
+// h: the tile's first column of planar rows (row stride row_stride) -> staging [nl][S] columns [fill, fill + n), S = Ks CH
+hipError_t launch_stream_complex_bandpass(const IirCoef &co, const double *h, int nl, int n, size_t row_stride, double *staging, int S,
+                                          int CH, void *state, const StreamComplexLayout &L, hipStream_t stream);
+// partial [B][Ks][Gp] of launch_planar_beamform on the staging array: the new chunk rows onto the accumulators, running power / argmax
+hipError_t launch_stream_complex_accumulate(const double *partial, int B, int Ks, int Gp, int G, int CH, int final_tile, void *state,
+                                            const StreamComplexLayout &L, double *power, int32_t *argmax, hipStream_t stream);
+// launch_stream_windows for folded (Re | Im) rows; win_state as there (stream_window_state_bytes); between accumulate and slide
+hipError_t launch_stream_complex_windows(const double *partial, int B, int Ks, int Gp, int G, int CH, const void *state, int final_tile,
+                                         int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
+                                         double *latest_power, int32_t *latest_argmax, hipStream_t stream);
+// the frames behind the last contracted chunk -> carry, then the clock commit
+hipError_t launch_stream_complex_slide(const double *staging, int nl, int S, int CH, void *state, const StreamComplexLayout &L,
+                                       hipStream_t stream);
+
 // fp32-MFMA variant of LIF + beamforming + power (up to 64 channels, bf_mat must fit in LDS)
 hipError_t launch_lif_beamform_f32(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T,
                                    double *partial, hipStream_t stream, int *nchunks);

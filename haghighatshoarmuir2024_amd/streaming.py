@@ -31,6 +31,10 @@ that moves after a minute of audio.  With `window` the localizer also emits the 
 -- power and arg-max per window of the rule in include/micloc_hip.h ("streaming windows"), each window as soon as its last chunk is
 final, bit for bit the one-shot rows -- into a ring of `max_windows` rows: latest_window() / windows() / finish().  The state is
 2 x G doubles per trial and open window (ceil(window / hop) of them) whatever the length of the stream, and a tile is still one graph.
+
+THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
+the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
+the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
 """
 import ctypes
 
@@ -546,6 +550,241 @@ class WidebandStreamingLocalizer:
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
         out = dict(power=self.power, argmax=self.argmax, band_power=torch.stack([b.power for b in self.bands]))
+        if self.window is not None:
+            if self.T is not None:
+                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
+                if self.max_windows < nW:
+                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
+                                           "windows() while the stream runs)")
+            w = self.windows()
+            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
+        return out
+
+
+class ComplexStreamingLocalizer:
+    """The non-spiking complex Beamformer (beamformer.Beamformer; what the reference deploys live in micloc/localization_demo.py, restarting
+    the chain on every 0.25 s pack) as ONE stream that arrives in tiles, with the results of `Beamformer.localize_batch` on the whole
+    recording bit for bit, whatever the tiling (include/micloc_hip.h "streaming, complex Beamformer").
+
+    There are no spikes, no open clusters and no horizon: a frame is final once its tile has been band-passed, so tiles may have ANY
+    length (no multiple of 16) and status() has no lag failures.  One tile = STHT of [last L - 1 frames | tile], np.roll's wrap rows, the
+    band-pass tile (DF2T state on the device), the one-shot contraction kernel on [carry | tile], the accumulation of the new whole
+    chunks, (the window read-out,) the slide of the ragged remainder into the carry with the clock commit -- a chain of launches on one
+    stream, one graph per tile length in push_replay().  The state is 2M (CH + n_coef - 1) + 2G doubles per trial however long the stream.
+
+    The surface is StreamingLocalizer's: push, push_replay, status, latest_window, windows, finish."""
+
+    def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None):
+        """beamf: beamformer.Beamformer; bf_mat [M, G] complex; `batch` recordings are streamed in lock step.
+        total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
+                      final=True with the last tile.
+        wrap_tail     [batch, L // 2, M]: np.roll's wrap-around rows, np.roll(x, L // 2, axis=1)[:, : L // 2] -- the last L // 2 frames of a
+                      recording of at least that length (shorter ones: wrap_rows()) -- or None (zeros: a live source cannot know them).
+        max_tile      longest tile push() will be given.
+        window, hop, max_windows   the windowed read-out, as StreamingLocalizer's (multiples of the plan's window quantum, hop <= window)."""
+        if window is None and (hop is not None or max_windows is not None):
+            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+        torch = runtime._torch()
+        bf_mat = np.asarray(bf_mat)
+        if not np.iscomplexobj(bf_mat):
+            raise ValueError("ComplexStreamingLocalizer takes the complex bf_mat of a Beamformer (a real one belongs to StreamingLocalizer)")
+        self.beamf = beamf
+        b, a = beamf.bandpass_filter
+        self.plan = runtime.Plan(len(beamf.geometry), beamf.kernel, b, a, robust_width=1, bipolar=False, device=beamf.device)  # the stream's own
+        self.device = self.plan.device
+        self.B, self.M = int(batch), len(beamf.geometry)
+        if bf_mat.shape[0] != self.M:
+            raise ValueError(f"number of channels in the input siganl {bf_mat.shape[0]} should be the same as the number of microphones {self.M}!")
+        self.C = 2 * self.M
+        self.T = None if total_frames is None else int(total_frames)
+        self.L = len(beamf.kernel)
+        self.halo = -(-(self.L - 1) // 8) * 8
+        self.plan.set_bf_mat(bf_mat.astype(np.complex128))
+        self.lib = _lib.load()
+        self.G = self.plan.G
+        self.CH = self.plan.window_quantum()
+        self.window = self.hop = self.max_windows = None
+        if window is not None:
+            nW, self.window, self.hop = self.plan.window_count(self.T if self.T is not None else 1, window, hop)
+            if self.hop > self.window:
+                raise ValueError(f"the streaming read-out needs hop <= window (hop {self.hop}, window {self.window})")
+            self.max_windows = int(max_windows) if max_windows is not None else (nW if self.T is not None else 64)
+            if self.max_windows < 1:
+                raise ValueError("max_windows must be at least 1")
+        self.max_tile = int(max_tile)
+        if self.max_tile < 1:
+            raise ValueError("max_tile must be at least 1")
+        dev = self.device
+        self.nstate = int(self.lib.micloc_stream_complex_state_bytes(self.plan.handle, self.B))
+        self.nws = int(self.lib.micloc_stream_complex_workspace_bytes(self.plan.handle, self.B, self.max_tile))
+        if self.nstate == 0 or self.nws == 0:
+            raise _lib.MiclocError("micloc stream_complex_state_bytes: the plan, the batch or max_tile do not fit the complex stream's rule")
+        self.state = torch.empty(self.nstate, dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
+        self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (the FIR's zero state)
+        self.ext = torch.empty((self.B * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
+        self.h = torch.empty((self.B * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
+        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        st = runtime._stream(dev)
+        if self.window is not None:
+            self.nwst = int(self.lib.micloc_stream_complex_window_state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows))
+            if self.nwst == 0:
+                raise _lib.MiclocError("micloc stream_complex_window_state_bytes: the plan cannot serve the windowed read-out")
+            self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=dev)
+            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
+            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
+            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            _lib.check(self.lib.micloc_stream_complex_window_reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
+                                                                   self.max_windows, st), "stream_complex_window_reset")
+        self.wrap = None
+        if wrap_tail is not None:
+            wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
+            if tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
+                raise ValueError(f"wrap_tail must be [batch, {self.L // 2}, num_mic]")
+            self.wrap = wrap_tail
+        self.t = 0
+        self.done = False
+        self._seen, self._graphs = set(), {}
+        _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, st), "stream_complex_reset")
+
+    @staticmethod
+    def wrap_rows(x, L):
+        """wrap_tail of a recording x [B, T, M] (numpy) for an STHT kernel of L taps: np.roll(x, L // 2, axis=1)[:, : L // 2], zero-padded to
+        L // 2 rows when the recording is shorter -- the rows the one-shot call's np.roll puts in front of the in-phase channels."""
+        x = np.asarray(x, dtype=np.float64)
+        half = int(L) // 2
+        out = np.zeros((x.shape[0], half, x.shape[2]))
+        k = min(half, x.shape[1])
+        out[:, :k, :] = np.roll(x, half, axis=1)[:, :k, :]
+        return out
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _check_tile(self, B, n, M, final):
+        if self.done:
+            raise _lib.MiclocError("the stream has ended")
+        if B != self.B or M != self.M:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.M}!")
+        if final is None:
+            final = self.T is not None and self.t + n == self.T
+        if n < 1 or n > self.max_tile or (self.T is not None and (self.t + n > self.T or (final and self.t + n != self.T))):
+            raise ValueError("tiles must hold 1 .. max_tile frames and add up to total_frames")
+        if self.t + n > 0x7FFFFFFF:
+            raise ValueError("the stream's clock is a 32-bit frame counter")
+        return bool(final)
+
+    def _tile(self, x, n, final):
+        """The launches of one tile (nothing else: no allocation, no synchronisation, no absolute time by value), all on the current
+        stream one after the other, so that a tile of a given length is ONE replayable hipGraph without parallel branches."""
+        lib, plan, B, M = self.lib, self.plan, self.B, self.M
+        st = runtime._stream(self.device)
+        Text = self.halo + n
+        ext = self.ext[: B * Text * M].view(B, Text, M)  # contiguous [history | tile] of this tile length
+        ext[:, : self.halo, :].copy_(self.hist)
+        ext[:, self.halo :, :].copy_(x)
+        Ts = plan.padded_T(Text)
+        h = self.h[: B * self.C * Ts]
+        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), B, Text, runtime._ptr(h), Ts, st), "stht")
+        # np.roll's wrap-around rows while the clock (the state's frames-pushed word) is below L / 2; a no-op later
+        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(h), B, Ts, self.halo, n, runtime._ptr(self.wrap), st),
+                   "stream_wrap_rows")
+        _lib.check(lib.micloc_stream_complex_bandpass_tile_f64(plan.handle, runtime._ptr(h), B, n, Ts, self.halo, self.max_tile, runtime._ptr(self.state),
+                                                               self.nstate, runtime._ptr(self.ws), self.nws, st), "stream_complex_bandpass_tile")
+        if self.window is None:
+            _lib.check(lib.micloc_stream_complex_localize_tile_f64(plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
+                                                                   runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws, st),
+                       "stream_complex_localize_tile")
+        else:
+            _lib.check(lib.micloc_stream_complex_localize_tile_windows_f64(plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
+                                                                           runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws),
+                                                                           self.nws, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
+                                                                           self.max_windows, runtime._ptr(self.window_power),
+                                                                           runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
+                                                                           runtime._ptr(self.latest_argmax), st), "stream_complex_localize_tile_windows")
+        # history for the next tile's quadrature FIR: the last `halo` frames of [history | tile]
+        self.hist.copy_(ext[:, Text - self.halo :, :])
+
+    def _advance(self, n, final):
+        self.t += n
+        self.done = bool(final)
+
+    def push(self, x_tile, final=None):
+        """x_tile [batch, n, M] (numpy or device tensor), 1 <= n <= max_tile.  final: this is the last tile (default: inferred from
+        total_frames).  Returns the running (power, argmax) device tensors (overwritten by the next push; the mean over the whole chunks
+        contracted so far, zeros before the first one)."""
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        final = self._check_tile(B, n, M, final)
+        self._tile(x, n, final)
+        self._seen.add(n)
+        self._advance(n, final)
+        return self.power, self.argmax
+
+    def push_replay(self, x_tile):
+        """push() for the steady state of a live source: a non-final tile whose length has been pushed before is ONE hipGraph launch --
+        captured on its second occurrence, replayed from then on; the tile is copied into the graph's input buffer first.  Same results
+        as push()."""
+        torch = runtime._torch()
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        if n not in self._seen or (self.T is not None and self.t + n == self.T):
+            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
+        self._check_tile(B, n, M, False)
+        g = self._graphs.get(n)
+        if g is None:
+            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
+            graph = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
+                self._tile(x_in, n, False)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            g = self._graphs[n] = (graph, x_in)
+        g[1].copy_(x)
+        g[0].replay()
+        self._advance(n, False)
+        return self.power, self.argmax
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def status(self):
+        """dict(chunks, frames, carry, pushed): chunks and frames contracted, frames waiting in the carry, frames pushed (the device
+        clock).  Synchronises the stream."""
+        st4 = (ctypes.c_int * 4)()
+        _lib.check(self.lib.micloc_stream_complex_status(runtime._ptr(self.state), st4, runtime._stream(self.device)), "stream_complex_status")
+        return dict(chunks=int(st4[0]), frames=int(st4[1]), carry=int(st4[2]), pushed=int(st4[3]))
+
+    def _need_windows(self):
+        if self.window is None:
+            raise ValueError("the localizer was built without window=")
+
+    def latest_window(self):
+        """(power [B, G], argmax [B]) of the most recently emitted window: device tensors, zeros until the first one exists."""
+        self._need_windows()
+        return self.latest_power, self.latest_argmax
+
+    def windows(self):
+        """StreamingLocalizer.windows(): dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]).  Synchronises."""
+        self._need_windows()
+        torch = runtime._torch()
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.micloc_stream_window_count(runtime._ptr(self.wst), ctypes.byref(c), runtime._stream(self.device)), "stream_window_count")
+        count = int(c.value)
+        k = min(count, self.max_windows)
+        first = count - k
+        rows = torch.arange(first, count, device=self.device) % self.max_windows
+        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
+                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+
+    def finish(self):
+        """-> dict(power [B, G], argmax [B] int32) as device tensors; with window= also window_power [B, nW, G], window_argmax [B, nW] and
+        window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        if not self.done:
+            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+        s = self.status()
+        if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
+            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
+        out = dict(power=self.power, argmax=self.argmax)
         if self.window is not None:
             if self.T is not None:
                 nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)

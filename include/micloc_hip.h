@@ -308,6 +308,74 @@ int micloc_stream_window_count(const void *win_state, int *count, void *stream);
  * streaming" below); valid as long as win_state is */
 const int32_t *micloc_stream_window_count_ptr(const void *win_state);
 
+/* ---- streaming, complex Beamformer: tiles in, the one-shot bits out ------------------------------------------------- */
+/* The non-spiking complex Beamformer (micloc/beamformer.py; deployed live, restarting on every 0.25 s pack, by
+ * micloc/localization_demo.py) as ONE stream that arrives in tiles.  The entries above ("streaming", "streaming windows") keep
+ * returning MICLOC_ERR_SHAPE for a complex bf_mat; these are the complex chain's own.  The rule, for a plan with a complex bf_mat,
+ * any recording x [B][T][M] and any cut of T into tiles of n_1, n_2, ... frames (each n_i >= 1, no multiple of anything):
+ *   Results.
+ *   - After the final tile (final_tile = 1) power [B][G] and argmax [B] equal micloc_beamformer_pipeline_f64 on the whole recording
+ *     bit for bit.
+ *   - Before it they are the mean over the frames contracted so far: whole chunks of CH = micloc_window_quantum(plan) frames (256
+ *     up to 64 channels, 512 beyond).  power is 0 and argmax is 0 while no chunk is complete.  (Mid-stream values are those of the
+ *     one-shot call on the prefix only up to the prefix's own np.roll rows: see wrap_tail.)
+ *   - With window / hop (multiples of CH, 1 <= hop <= window) window n is emitted as soon as its last chunk has been contracted, in
+ *     ascending n; on the final tile every remaining window of micloc_window_count(T, window, hop, CH) is emitted, with T taken
+ *     from the device clock.  Each window has the bits of micloc_beamformer_pipeline_windows_f64 on the whole recording.  Bounds,
+ *     emission times, ring row n % max_windows, latest_* and "an emitted row never changes" are those of "streaming windows" above,
+ *     word for word; win_state has that section's layout and micloc_stream_window_count reads its count.
+ *   - Nothing allocates, synchronises with the host, uses atomics or takes an absolute time: the clock (frames pushed, chunks
+ *     contracted, carry fill) lives in device control words, every launch of a tile of n frames has the same arguments, and the
+ *     launches of a tile form ONE chain on the caller's stream with no parallel branches -- a tile is one capturable hipGraph.
+ *   How the bits follow.
+ *   - STHT: micloc_stht_f64 on [last L - 1 frames | tile] by the caller, then micloc_stream_wrap_rows_f64 with `state` as its
+ *     loc_state (it reads the frames-pushed word only, which sits at the same place): in-phase[t] = wrap_tail[t] for t < L/2, the rows
+ *     np.roll wraps around -- np.roll(x, L/2, axis = time)[: L/2], i.e. the last L/2 frames of a recording of at least L/2 frames.
+ *   - Band-pass: the DF2T steps of the one-shot launch in the same order on the planar rows, the n_coef - 1 state
+ *     words of every (trial, channel) chain loaded before the tile and stored after it; the ragged end of a tile is stepped frame by
+ *     frame, so a carried state never advances over padding.  Against the one-shot rows only the sign of a zero may differ.
+ *   - Contraction: the one-shot time reduction is per chunk of CH frames, the chunk rows added in ascending order inside blocks of
+ *     32 chunks and the blocks in ascending order onto the total, each chunk as s += Re; s += Im.  Tile borders fall anywhere, so
+ *     the band-passed frames behind the last whole chunk (fewer than CH) wait in a per-trial CARRY.  The band-pass writes carry and
+ *     tile into a chunk-aligned staging array [B][2M][Ks CH], Ks = ceil((max_tile + CH - 1) / CH), and zeros up to the next chunk
+ *     border; the one-shot contraction kernel runs on it unchanged as a recording of Ks whole chunks (its launch shape depends on
+ *     max_tile only; rows past the valid ones are computed and never read); the accumulate kernel adds the new whole chunk rows in
+ *     the order above; the slide kernel moves the frames behind them to the carry and commits the clock.  On the final tile the
+ *     ragged last chunk is contracted too: the one-shot kernels feed zeros for the frames past T - 1 of a ragged chunk and skip
+ *     nothing that would change a sum, so the zero-padded chunk row has the bits of the one-shot call's last row.
+ *   State and footprint.  state (micloc_stream_complex_state_bytes, 256-B aligned, zero-filled once by micloc_stream_complex_reset):
+ *     256 B of control words | (n_coef - 1) x B 2M DF2T words, word i of chain g = b 2M + c at i B 2M + g (the lanes of a wave touch
+ *     consecutive doubles per word) | carry [B][2M][CH] | accumulators [B][2][G] {total, open-block sum}, each part rounded up to
+ *     256 B.  Per trial: 2M (n_coef - 1 + CH) + 2G doubles -- 36 KB at M = 7, CH = 256, G = 449, n_coef = 5; 57 KB of carry at CH = 512.
+ *     ws (micloc_stream_complex_workspace_bytes; pure scratch, nothing in it survives a tile): the staging array and the chunk rows
+ *     partial [B][Ks][Gp].  The state does not grow with the stream.
+ *   One tile of n <= max_tile frames =
+ *     micloc_stht_f64, micloc_stream_wrap_rows_f64              by the caller, as above; the tile's frame i at column first_col + i
+ *     micloc_stream_complex_bandpass_tile_f64                   h [B][2M][row_stride] -> staging
+ *     micloc_stream_complex_localize_tile[_windows]_f64         contraction, accumulation, (windows,) slide and clock commit
+ *   with the same max_tile, state and ws in both calls.  power / argmax may be NULL.  micloc_stream_complex_status: {chunks contracted,
+ *   frames contracted, carry fill, frames pushed}; it synchronises the stream.  A stream is at most 2^31 - 1 frames.
+ *   Status, before any launch: MICLOC_ERR_INVALID for NULL or non-positive arguments; MICLOC_ERR_NOT_SET without a bf_mat;
+ *   MICLOC_ERR_SHAPE for a real bf_mat, a window or hop that is not a multiple of CH, hop > window, n > max_tile or
+ *   first_col + n > row_stride; MICLOC_ERR_WORKSPACE for a short or misaligned state, ws or win_state.  The size functions return 0
+ *   for such arguments. */
+size_t micloc_stream_complex_state_bytes(const micloc_plan *plan, int B);
+size_t micloc_stream_complex_workspace_bytes(const micloc_plan *plan, int B, int max_tile);
+int micloc_stream_complex_reset(const micloc_plan *plan, int B, void *state, size_t state_bytes, void *stream);
+int micloc_stream_complex_bandpass_tile_f64(const micloc_plan *plan, const double *h, int B, int n, int row_stride, int first_col,
+                                            int max_tile, void *state, size_t state_bytes, void *ws, size_t ws_bytes, void *stream);
+int micloc_stream_complex_localize_tile_f64(const micloc_plan *plan, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
+                                            double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
+size_t micloc_stream_complex_window_state_bytes(const micloc_plan *plan, int B, int window, int hop, int max_windows);
+int micloc_stream_complex_window_reset(const micloc_plan *plan, int B, void *win_state, size_t win_bytes, int window, int hop,
+                                       int max_windows, void *stream);
+int micloc_stream_complex_localize_tile_windows_f64(const micloc_plan *plan, void *state, size_t state_bytes, int B, int max_tile,
+                                                    int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                                    void *win_state, size_t win_bytes, int window, int hop, int max_windows,
+                                                    double *window_power, int32_t *window_argmax, double *latest_power,
+                                                    int32_t *latest_argmax, void *stream);
+int micloc_stream_complex_status(const void *state, int *status4, void *stream);
+
 /* ---- beamforming vectors from membrane covariances (design_from_template's decomposition step) ------ */
 /* Replaces the per-DoA np.linalg.svd calls of SNNBeamformer.design_from_template (snn_beamformer.py:183-203) and
  * _find_dc_removed_sing_vec (:372-422) by one batched kernel: column g0 + i of bf_mat [C][G] from cov[i] [C][C]
