@@ -185,6 +185,16 @@ int window_readout(const micloc_plan *p, const double *partial, int B, int T, in
     return MICLOC_OK;
 }
 
+// The one-shot power launch: the fixed-shape kernel of beamform_lean.hip where the plan and the call have its shape, the general kernels
+// otherwise (same bits in `partial` either way).  Windows, streaming, tracking and y stay with launch_lif_beamform.
+hipError_t lif_beamform_oneshot(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T, double *y, double *partial,
+                                hipStream_t stream, int *nchunks)
+{
+    hipError_t e = hipSuccess;
+    if (launch_lif_beamform_lean(W, nt, spikes, B, T, y, partial, stream, nchunks, &e)) return e;
+    return launch_lif_beamform(W, nt, spikes, B, T, y, partial, stream, nchunks);
+}
+
 }  // namespace
 
 extern "C" {
@@ -477,7 +487,7 @@ int micloc_lif_beamform_f64(const micloc_plan *p, const int8_t *spikes, int B, i
     if (want_power && bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, Gp))) return MICLOC_ERR_WORKSPACE;
     double *partial = want_power ? reinterpret_cast<double *>(ws) : nullptr;
     int nch = 0;
-    HIP_TRY(launch_lif_beamform(p->W, p->ntab, spikes, B, T, y, partial, (hipStream_t)stream, &nch));
+    HIP_TRY(lif_beamform_oneshot(p->W, p->ntab, spikes, B, T, y, partial, (hipStream_t)stream, &nch));
     if (want_power)
         HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 0, 0, power, argmax, (hipStream_t)stream));
     return MICLOC_OK;
@@ -538,7 +548,7 @@ int micloc_snn_pipeline_stages_f64(const micloc_plan *p, const double *x, int B,
         const bool want_power = power || argmax;
         double *partial = want_power ? reinterpret_cast<double *>(base + w.partial) : nullptr;
         int nch = 0;
-        HIP_TRY(launch_lif_beamform(p->W, p->ntab, spk, B, T, y, partial, st, &nch));
+        HIP_TRY(lif_beamform_oneshot(p->W, p->ntab, spk, B, T, y, partial, st, &nch));
         if (want_power) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 0, 0, power, argmax, st));
     }
     return MICLOC_OK;

@@ -16,6 +16,7 @@ constexpr bool VARIANT_WS_FOUR_KSTEPS = false;    // ws_k4: beamform_ws_kernel m
 constexpr bool VARIANT_STHT_VECTOR_FORM = false;  // stht_valu: stride-2 STHT kernels on the vector ALU instead of the matrix cores
 constexpr bool VARIANT_STHT_WIDE_TWO_TILES = false;  // stht_wide2: the 480-tap walking STHT (96 kHz) with two time tiles per wave and ONE workgroup per CU (98 KB) instead of one tile / two workgroups
 constexpr bool VARIANT_STHT_ONE_TILE = false;     // stht_one_tile: the matrix-core STHT with one time tile per workgroup (round 3's form) instead of the walk
+constexpr bool VARIANT_WS_GENERAL_ONLY = false;  // set in EVERY variant of the `beamform` unit (ws_k4, ws_sparse_lif): beamform_lean.hip's fixed-shape kernel declines, so the variant's beamform_ws_kernel serves the sweep's shape too
 
 // ---- XCD-aware workgroup order (speed only, never correctness) -------------------------------------------------------
 // Workgroup L of a launch runs on XCD L % 8, and every XCD has its own L2.  Kernels whose NEIGHBOURING work items read the same
@@ -120,6 +121,11 @@ size_t beamform_partial_bytes(int B, int T, int Gp);
 // *nchunks: number of partial-sum rows per trial the chosen kernel wrote (input of launch_power_argmax)
 hipError_t launch_lif_beamform(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T,
                                double *y, double *partial, hipStream_t stream, int *nchunks);
+// beamform_lean.hip, the fixed-shape form of the sweep's launch (real bf_mat, 14 channels, three DoA tiles per wave, an instantiated NK,
+// power only, no device-side chunk range): true = this launch was its to serve (*err, *nchunks as above, same bits in `partial`),
+// false = nothing was enqueued and the caller launches launch_lif_beamform
+bool launch_lif_beamform_lean(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T, double *y, double *partial,
+                              hipStream_t stream, int *nchunks, hipError_t *err);
 // *nchunks: partial-sum rows per trial the chosen kernel wrote
 hipError_t launch_planar_beamform(const BeamformW &W, const double *pre, int B, int T, int Ts, double *y,
                                   int y_complex, double *partial, hipStream_t stream, int *nchunks);

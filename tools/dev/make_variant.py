@@ -12,6 +12,8 @@
 The shipped library has no run-time switches: a variant is the same sources with ONE constant of csrc/micloc_internal.h flipped, or (an
 experiment that was rejected and moved out of the product) with a patch of tools/experiments/ applied to the copy.
 Only the translation unit that reads the constant is recompiled (in build_dev/variants/<name>/); the other objects are the product's.
+A variant of the `beamform` unit also recompiles csrc/beamform_lean.hip with VARIANT_WS_GENERAL_ONLY set: the fixed-shape kernel, which
+the product's api.o asks first at the sweep's shape, declines, so the variant's own beamform_ws_kernel is what runs and is measured there.
 A/B runs load it with `MICLOC_DEV_LIB=<path>` understood by the tools (never by the package), the stht_valu one is also what
 tests/test_hip_parity.py::test_stht_vector_form_still_exact loads."""
 import os
@@ -23,6 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 CS = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
 VARIANTS = {"stht_wide2": ("VARIANT_STHT_WIDE_TWO_TILES", "stht"), "stht_valu": ("VARIANT_STHT_VECTOR_FORM", "stht"), "ws_k4": ("VARIANT_WS_FOUR_KSTEPS", "beamform"), "stht_one_tile": ("VARIANT_STHT_ONE_TILE", "stht"),
             "ws_sparse_lif": (os.path.join(ROOT, "tools", "experiments", "ws_sparse_lif", "ws_sparse_lif.patch"), "beamform")}
+# further units of a variant: recompiled against the variant's header with the listed constant set as well
+COMPANIONS = {"beamform": (("beamform_lean", "VARIANT_WS_GENERAL_ONLY"),)}
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result".split()
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -30,10 +34,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 def build(name):
     const, unit = VARIANTS[name]
     out = os.path.join(ROOT, "tools", "_variants", f"libmicloc_hip_{name}.so")
-    srcs = [os.path.join(CS, f) for f in (unit + ".hip", "micloc_internal.h", "synth_dev.h")] + [os.path.join(ROOT, "include", "micloc_hip.h")]
+    extra = COMPANIONS.get(unit, ())
+    units = [unit] + [u for u, _ in extra]
+    srcs = [os.path.join(CS, f) for f in [u + ".hip" for u in units] + ["micloc_internal.h", "synth_dev.h"]] + [os.path.join(ROOT, "include", "micloc_hip.h")]
     if const.endswith(".patch"):
         srcs.append(const)
-    objs = [os.path.join(CS, f) for f in sorted(os.listdir(CS)) if f.endswith(".o") and f != unit + ".o"]
+    objs = [os.path.join(CS, f) for f in sorted(os.listdir(CS)) if f.endswith(".o") and f[:-2] not in units]
     newest = max(os.path.getmtime(p) for p in srcs + objs + [os.path.abspath(__file__)])
     if os.path.exists(out) and os.path.getmtime(out) >= newest:
         return out
@@ -42,9 +48,14 @@ def build(name):
     inc = os.path.join(ROOT, "build_dev", "variants", "include")
     os.makedirs(inc, exist_ok=True)
     shutil.copy(os.path.join(ROOT, "include", "micloc_hip.h"), inc)
-    for f in (unit + ".hip", "synth_dev.h"):
+    for f in [u + ".hip" for u in units] + ["synth_dev.h"]:
         shutil.copy(os.path.join(CS, f), work)
     hdr = open(os.path.join(CS, "micloc_internal.h")).read()
+    for _, c in extra:
+        needle = f"constexpr bool {c} = false;"
+        if hdr.count(needle) != 1:
+            raise SystemExit(f"make_variant: '{needle}' not found exactly once in micloc_internal.h")
+        hdr = hdr.replace(needle, f"constexpr bool {c} = true;")
     if const.endswith(".patch"):
         # an experiment kept outside the product: the patch touches the unit's translation unit only (no shared declaration changes)
         open(os.path.join(work, "micloc_internal.h"), "w").write(hdr)
@@ -54,10 +65,12 @@ def build(name):
         if hdr.count(needle) != 1:
             raise SystemExit(f"make_variant: '{needle}' not found exactly once in micloc_internal.h")
         open(os.path.join(work, "micloc_internal.h"), "w").write(hdr.replace(needle, f"constexpr bool {const} = true;"))
-    obj = os.path.join(work, unit + ".o")
-    subprocess.check_call([HIPCC] + FLAGS + ["-c", "-o", obj, os.path.join(work, unit + ".hip")])
+    new_objs = []
+    for u in units:
+        new_objs.append(os.path.join(work, u + ".o"))
+        subprocess.check_call([HIPCC] + FLAGS + ["-c", "-o", new_objs[-1], os.path.join(work, u + ".hip")])
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, obj] + objs)
+    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + new_objs + objs)
     return out
 
 
