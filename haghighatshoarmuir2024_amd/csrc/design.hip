@@ -135,7 +135,9 @@ __global__ __launch_bounds__(64) void design_vec_kernel(const double *__restrict
             th[lane] = s;
         }
         __syncthreads();
-        double u_min = Dv[order[1]], u_max = Dv[order[0]];
+        // (a zero eigenvalue of a rank-deficient covariance can leave the rotations as -1e-17: LAPACK's singular values are never
+        // negative, and with u_min < 0 the stopping rule below would hold before the first step)
+        double u_min = fmax(Dv[order[1]], 0.0), u_max = Dv[order[0]];
         for (int it = 0; it < 200; ++it) {  // :399-411
             if ((u_max - u_min) / u_min < rel_prec) break;
             const double u_mid = (u_min + u_max) / 2;
@@ -315,7 +317,8 @@ __global__ __launch_bounds__(256) void design_vec_wide_kernel(const double *__re
         for (int it = 0; it < 200; ++it) {  // :399-411 (one term per thread; every thread sees the same sum)
             if ((u_max - u_min) / u_min < rel_prec) break;
             const double u_mid = (u_min + u_max) / 2;
-            const double part = wave_sum(th2 / (dmine - u_mid));
+            // threads past n add exactly zero: dividing their 0 by (1.0 - u_mid) is NaN when a midpoint is exactly 1.0
+            const double part = wave_sum(tid < n ? th2 / (dmine - u_mid) : 0.0);
             if (lane == 0) psum[wv] = part;
             __syncthreads();
             const double val = (psum[0] + psum[1]) + (psum[2] + psum[3]);
