@@ -1162,18 +1162,60 @@ int micloc_stream_encode_tile_f64(const micloc_plan *p, const double *h, int B, 
     return MICLOC_OK;
 }
 
-int micloc_stream_localize_tile_f64(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window, int B,
-                                    int window_frames, int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
+// ---- the localize step of a tile, with or without the streaming windows: the time-resolved read-out of the same chunk rows, emitted
+// while the recording arrives ----------------------------------------------------------------------------------------------------
+// win_state: [256 B: int windows emitted][B][ceil(window / hop)][2][G] doubles (stream_windows.hip), for the SNN stream and the complex one
+namespace {
+
+// MICLOC_OK and *CH, or the status of a plan that cannot serve the SNN stream's localize step (p non-NULL)
+int stream_plan_args(const micloc_plan *p, int *CH)
 {
-    if (!p || !enc_state || !loc_state || !window || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
-    DeviceGuard guard(p->device);
+    *CH = 0;
     if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
     if (p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int CH = lif_beamform_chunk_frames(p->W, p->ntab);
+    *CH = lif_beamform_chunk_frames(p->W, p->ntab);
+    return MICLOC_OK;
+}
+
+// the window-argument rule of both streams; rc: the status of the stream's own plan check, which gave the chunk length *CH (read only
+// behind rc == MICLOC_OK, so the check may be an argument of the same call)
+int stream_window_args(int rc, int window, int hop, int max_windows, const int *CH)
+{
+    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
+    if (rc != MICLOC_OK) return rc;
+    if (window % *CH != 0 || hop % *CH != 0 || hop > window) return MICLOC_ERR_SHAPE;
+    return MICLOC_OK;
+}
+
+// the tail of both *_window_reset entries; rc: stream_window_args' status
+int stream_window_zero(int rc, const micloc_plan *p, int B, void *win_state, size_t win_bytes, int window, int hop, void *stream)
+{
+    if (rc != MICLOC_OK) return rc;
+    const size_t need = stream_window_state_bytes(B, p->G_out, window, hop);
+    if (bad_ws(win_state, win_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_zero_fill(win_state, need, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+// the launches of a tile behind the encoder: horizon, LIF + beamforming of the chunks that became final, accumulation, (the window
+// read-out in front of the commit,) commit, tick.  win_state == nullptr: no read-out; loc_state, power and argmax end with the same bits
+// either way.
+int stream_localize(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *raster, int B, int window_frames,
+                    int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window,
+                    int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power, int32_t *latest_argmax,
+                    void *stream)
+{
+    if (!p || !enc_state || !loc_state || !raster || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    int CH;
+    int rc = stream_plan_args(p, &CH);
+    if (win_state) rc = stream_window_args(rc, window, hop, max_windows, &CH);
+    if (rc != MICLOC_OK) return rc;
     if (window_frames % CH != 0) return MICLOC_ERR_SHAPE;
     const int G = p->G_out, Gp = 16 * p->W.GT;
     if (bad_ws(loc_state, loc_bytes, micloc_stream_localize_state_bytes(p, B))) return MICLOC_ERR_WORKSPACE;
     if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, window_frames, Gp))) return MICLOC_ERR_WORKSPACE;
+    if (win_state && bad_ws(win_state, win_bytes, stream_window_state_bytes(B, G, window, hop))) return MICLOC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     int *ctl = reinterpret_cast<int *>(loc_state);
     double *acc = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(loc_state) + 256);
@@ -1184,28 +1226,29 @@ int micloc_stream_localize_tile_f64(const micloc_plan *p, const void *enc_state,
     double *partial = reinterpret_cast<double *>(ws);
     int nch = 0;
     // the whole window as the launch shape; the kernel takes the frames that exist from the control words
-    HIP_TRY(launch_lif_beamform(W, p->ntab, window, B, window_frames, nullptr, partial, st, &nch));
+    HIP_TRY(launch_lif_beamform(W, p->ntab, raster, B, window_frames, nullptr, partial, st, &nch));
     HIP_TRY(launch_stream_accumulate(partial, B, nch, Gp, G, ctl + 4, ctl, acc, ctl + 8, power, argmax, st));
+    if (win_state)
+        HIP_TRY(launch_stream_windows(partial, B, nch, Gp, G, 0, 0, CH, ctl, final_tile ? 1 : 0, window, hop, max_windows, win_state, window_power,
+                                      window_argmax, latest_power, latest_argmax, st));
     HIP_TRY(launch_stream_commit(ctl, STREAM_BLOCK_CHUNKS, st));
     HIP_TRY(launch_stream_tick(ctl, st));
     return MICLOC_OK;
 }
 
-// ---- streaming windows: the time-resolved read-out of the same chunk rows, emitted while the recording arrives ----------------
-// win_state: [256 B: int windows emitted][B][ceil(window / hop)][2][G] doubles (stream_windows.hip)
-static int stream_window_args(const micloc_plan *p, int window, int hop, int max_windows)
+}  // namespace
+
+int micloc_stream_localize_tile_f64(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window, int B,
+                                    int window_frames, int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream)
 {
-    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int CH = lif_beamform_chunk_frames(p->W, p->ntab);
-    if (window % CH != 0 || hop % CH != 0 || hop > window) return MICLOC_ERR_SHAPE;
-    return MICLOC_OK;
+    return stream_localize(p, enc_state, loc_state, loc_bytes, window, B, window_frames, final_tile, power, argmax, ws, ws_bytes, nullptr, 0, 0, 0, 0,
+                           nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 size_t micloc_stream_window_state_bytes(const micloc_plan *p, int B, int window, int hop, int max_windows)
 {
-    if (!p || bad_batch(B) || p->G_out < 1 || stream_window_args(p, window, hop, max_windows) != MICLOC_OK) return 0;
+    int CH;
+    if (!p || bad_batch(B) || p->G_out < 1 || stream_window_args(stream_plan_args(p, &CH), window, hop, max_windows, &CH) != MICLOC_OK) return 0;
     return stream_window_state_bytes(B, p->G_out, window, hop);
 }
 
@@ -1213,12 +1256,9 @@ int micloc_stream_window_reset(const micloc_plan *p, int B, void *win_state, siz
 {
     if (!p || !win_state || bad_batch(B)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    const int rc = stream_window_args(p, window, hop, max_windows);
-    if (rc != MICLOC_OK) return rc;
-    const size_t need = stream_window_state_bytes(B, p->G_out, window, hop);
-    if (bad_ws(win_state, win_bytes, need)) return MICLOC_ERR_WORKSPACE;
-    HIP_TRY(launch_zero_fill(win_state, need, (hipStream_t)stream));
-    return MICLOC_OK;
+    int CH;
+    const int rc = stream_plan_args(p, &CH);
+    return stream_window_zero(stream_window_args(rc, window, hop, max_windows, &CH), p, B, win_state, win_bytes, window, hop, stream);
 }
 
 int micloc_stream_localize_tile_windows_f64(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
@@ -1226,34 +1266,9 @@ int micloc_stream_localize_tile_windows_f64(const micloc_plan *p, const void *en
                                             void *win_state, size_t win_bytes, int window, int hop, int max_windows, double *window_power,
                                             int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *stream)
 {
-    if (!p || !enc_state || !loc_state || !window_raster || !win_state || !window_argmax || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
-    DeviceGuard guard(p->device);
-    const int rc = stream_window_args(p, window, hop, max_windows);
-    if (rc != MICLOC_OK) return rc;
-    const int CH = lif_beamform_chunk_frames(p->W, p->ntab);
-    if (window_frames % CH != 0) return MICLOC_ERR_SHAPE;
-    const int G = p->G_out, Gp = 16 * p->W.GT;
-    if (bad_ws(loc_state, loc_bytes, micloc_stream_localize_state_bytes(p, B))) return MICLOC_ERR_WORKSPACE;
-    if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, window_frames, Gp))) return MICLOC_ERR_WORKSPACE;
-    if (bad_ws(win_state, win_bytes, stream_window_state_bytes(B, G, window, hop))) return MICLOC_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    int *ctl = reinterpret_cast<int *>(loc_state);
-    double *acc = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(loc_state) + 256);
-    const int nwin = window_frames / CH;
-    // the launches of micloc_stream_localize_tile_f64 with the window read-out in front of the commit: loc_state, power and argmax
-    // end with the bits of that call
-    HIP_TRY(launch_stream_horizon(enc_state, B * p->C, p->bipolar, 0, final_tile ? 1 : 0, CH, 0, nwin, ctl, st, 1));
-    BeamformW W = p->W;
-    W.chunk_range = ctl + 4;
-    double *partial = reinterpret_cast<double *>(ws);
-    int nch = 0;
-    HIP_TRY(launch_lif_beamform(W, p->ntab, window_raster, B, window_frames, nullptr, partial, st, &nch));
-    HIP_TRY(launch_stream_accumulate(partial, B, nch, Gp, G, ctl + 4, ctl, acc, ctl + 8, power, argmax, st));
-    HIP_TRY(launch_stream_windows(partial, B, nch, Gp, G, CH, ctl, final_tile ? 1 : 0, window, hop, max_windows, win_state, window_power,
-                                  window_argmax, latest_power, latest_argmax, st));
-    HIP_TRY(launch_stream_commit(ctl, STREAM_BLOCK_CHUNKS, st));
-    HIP_TRY(launch_stream_tick(ctl, st));
-    return MICLOC_OK;
+    if (!win_state || !window_argmax) return MICLOC_ERR_INVALID;
+    return stream_localize(p, enc_state, loc_state, loc_bytes, window_raster, B, window_frames, final_tile, power, argmax, ws, ws_bytes, win_state,
+                           win_bytes, window, hop, max_windows, window_power, window_argmax, latest_power, latest_argmax, stream);
 }
 
 /* windows emitted so far (synchronises the stream) */
@@ -1296,6 +1311,7 @@ struct ScArgs {
 // MICLOC_OK and *a, or the status of the rule's argument errors (p non-NULL, B checked)
 int sc_args(const micloc_plan *p, int B, int max_tile, ScArgs *a)
 {
+    *a = ScArgs{};
     if (!p->d_W) return MICLOC_ERR_NOT_SET;
     if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
     const int CH = window_quantum(p);
@@ -1303,8 +1319,6 @@ int sc_args(const micloc_plan *p, int B, int max_tile, ScArgs *a)
     a->CH = CH;
     a->Gp = 16 * p->W.GT;
     a->L = stream_complex_layout(B, p->C, p->G_out, p->iir.n, CH);
-    a->Ks = a->S = 0;
-    a->ws_partial = a->ws_total = 0;
     if (max_tile > 0) {
         if ((long long)max_tile + 2ll * CH > 0x7fffffffll) return MICLOC_ERR_SHAPE;
         a->Ks = stream_complex_chunks(max_tile, CH);
@@ -1312,13 +1326,6 @@ int sc_args(const micloc_plan *p, int B, int max_tile, ScArgs *a)
         a->ws_partial = align256((size_t)B * p->C * a->S * sizeof(double));
         a->ws_total = a->ws_partial + align256(beamform_partial_bytes(B, a->S, a->Gp));
     }
-    return MICLOC_OK;
-}
-
-int sc_window_args(int window, int hop, int max_windows, int CH)
-{
-    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
-    if (window % CH != 0 || hop % CH != 0 || hop > window) return MICLOC_ERR_SHAPE;
     return MICLOC_OK;
 }
 
@@ -1335,8 +1342,8 @@ int sc_localize(const micloc_plan *p, const ScArgs &a, void *state, int B, int f
     if (nch != a.Ks) return MICLOC_ERR_INVALID;  // the launch chose a kernel window_quantum() does not describe
     HIP_TRY(launch_stream_complex_accumulate(partial, B, a.Ks, a.Gp, p->G_out, a.CH, final_tile, state, a.L, power, argmax, st));
     if (win_state)
-        HIP_TRY(launch_stream_complex_windows(partial, B, a.Ks, a.Gp, p->G_out, a.CH, state, final_tile, window, hop, max_windows, win_state,
-                                              window_power, window_argmax, latest_power, latest_argmax, st));
+        HIP_TRY(launch_stream_windows(partial, B, a.Ks, a.Gp, p->G_out, 1, a.Gp / 2, a.CH, reinterpret_cast<const int *>(state), final_tile ? 1 : 0,
+                                      window, hop, max_windows, win_state, window_power, window_argmax, latest_power, latest_argmax, st));
     HIP_TRY(launch_stream_complex_slide(staging, B * p->C, a.S, a.CH, state, a.L, st));
     return MICLOC_OK;
 }
@@ -1401,7 +1408,7 @@ int micloc_stream_complex_localize_tile_f64(const micloc_plan *p, void *state, s
 size_t micloc_stream_complex_window_state_bytes(const micloc_plan *p, int B, int window, int hop, int max_windows)
 {
     ScArgs a;
-    if (!p || bad_batch(B) || sc_args(p, B, 0, &a) != MICLOC_OK || sc_window_args(window, hop, max_windows, a.CH) != MICLOC_OK) return 0;
+    if (!p || bad_batch(B) || stream_window_args(sc_args(p, B, 0, &a), window, hop, max_windows, &a.CH) != MICLOC_OK) return 0;
     return stream_window_state_bytes(B, p->G_out, window, hop);
 }
 
@@ -1410,15 +1417,9 @@ int micloc_stream_complex_window_reset(const micloc_plan *p, int B, void *win_st
 {
     if (!p || !win_state || bad_batch(B)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
     ScArgs a;
-    int rc = sc_args(p, B, 0, &a);
-    if (rc == MICLOC_OK) rc = sc_window_args(window, hop, max_windows, a.CH);
-    if (rc != MICLOC_OK) return rc;
-    const size_t need = stream_window_state_bytes(B, p->G_out, window, hop);
-    if (bad_ws(win_state, win_bytes, need)) return MICLOC_ERR_WORKSPACE;
-    HIP_TRY(launch_zero_fill(win_state, need, (hipStream_t)stream));
-    return MICLOC_OK;
+    const int rc = sc_args(p, B, 0, &a);
+    return stream_window_zero(stream_window_args(rc, window, hop, max_windows, &a.CH), p, B, win_state, win_bytes, window, hop, stream);
 }
 
 int micloc_stream_complex_localize_tile_windows_f64(const micloc_plan *p, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
@@ -1428,10 +1429,8 @@ int micloc_stream_complex_localize_tile_windows_f64(const micloc_plan *p, void *
 {
     if (!p || !state || !ws || !win_state || !window_argmax || bad_batch(B) || max_tile < 1) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (window < 1 || hop < 1 || max_windows < 1) return MICLOC_ERR_INVALID;
     ScArgs a;
-    int rc = sc_args(p, B, max_tile, &a);
-    if (rc == MICLOC_OK) rc = sc_window_args(window, hop, max_windows, a.CH);
+    const int rc = stream_window_args(sc_args(p, B, max_tile, &a), window, hop, max_windows, &a.CH);
     if (rc != MICLOC_OK) return rc;
     if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
     if (bad_ws(ws, ws_bytes, a.ws_total)) return MICLOC_ERR_WORKSPACE;

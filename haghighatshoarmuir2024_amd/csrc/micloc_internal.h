@@ -150,9 +150,11 @@ size_t stream_window_state_bytes(int B, int G, int window, int hop);
 // between launch_stream_accumulate and launch_stream_commit of a tile: ctl is the head of loc_state (chunks done, the chunk range of
 // this call, the clock); window n goes to row n % max_windows of power_w [B][max_windows][G] / argmax_w [B][max_windows], the newest
 // one also to latest_power [B][G] / latest_argmax [B] (each may be NULL).  hop <= window, both multiples of chunk_frames.
-hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp, int G, int chunk_frames, const int *ctl, int final_tile,
-                                 int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
-                                 double *latest_power, int32_t *latest_argmax, hipStream_t stream);
+// complex_pairs: the rows are folded, columns [0, Ghp) Re and [Ghp, Gp) Im (the complex stream, whose control words are its ctl,
+// between its accumulate and its slide); 0: real rows, Ghp is not read.
+hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp, int G, int complex_pairs, int Ghp, int chunk_frames,
+                                 const int *ctl, int final_tile, int window, int hop, int max_windows, void *win_state, double *power_w,
+                                 int32_t *argmax_w, double *latest_power, int32_t *latest_argmax, hipStream_t stream);
 
 // ---- streaming, complex Beamformer (stream_complex.hip) -------------------------------------------------------------------------
 // state: [256 B: 64 control ints][z: (n - 1) x nl DF2T words, word i of chain g at i nl + g][carry [nl][CH]][acc [B][2][G]], nl = B C
@@ -167,10 +169,6 @@ hipError_t launch_stream_complex_bandpass(const IirCoef &co, const double *h, in
 // partial [B][Ks][Gp] of launch_planar_beamform on the staging array: the new chunk rows onto the accumulators, running power / argmax
 hipError_t launch_stream_complex_accumulate(const double *partial, int B, int Ks, int Gp, int G, int CH, int final_tile, void *state,
                                             const StreamComplexLayout &L, double *power, int32_t *argmax, hipStream_t stream);
-// launch_stream_windows for folded (Re | Im) rows; win_state as there (stream_window_state_bytes); between accumulate and slide
-hipError_t launch_stream_complex_windows(const double *partial, int B, int Ks, int Gp, int G, int CH, const void *state, int final_tile,
-                                         int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
-                                         double *latest_power, int32_t *latest_argmax, hipStream_t stream);
 // the frames behind the last contracted chunk -> carry, then the clock commit
 hipError_t launch_stream_complex_slide(const double *staging, int nl, int S, int CH, void *state, const StreamComplexLayout &L,
                                        hipStream_t stream);

@@ -8,7 +8,7 @@
 //   launch_planar_beamform              (beamform.hip, unchanged) on staging [B][2M][Ks CH] as a recording of Ks whole chunks: the launch
 //                                       shape depends on max_tile only; rows past the valid ones are computed and never read
 //   stream_complex_accumulate_kernel    the new chunk rows onto {total, open-block sum} in the one-shot order, Re | Im folded
-//   stream_complex_window_kernel        (windowed) stream_window_kernel's rule on the folded rows
+//   stream_window_kernel<1>             (windowed; stream_windows.hip) the streaming read-out's one kernel, instantiated for folded rows
 //   stream_complex_slide_kernel         frames behind the last whole chunk -> carry; the one-thread clock commit
 // all on one stream, one after the other.
 //
@@ -245,88 +245,6 @@ __global__ __launch_bounds__(SA_COLS) void stream_complex_accumulate_kernel(cons
     }
 }
 
-// stream_window_kernel (stream_windows.hip) for folded rows: the same bookkeeping word for word -- windows open, emitted, cut at the
-// end of the recording, ring row, latest_* --, the same win_state layout, and per chunk the two additions s += Re; s += Im of
-// window_power_kernel with complex_pairs = 1 (windows.hip).
-__global__ __launch_bounds__(SA_COLS) void stream_complex_window_kernel(const double *__restrict__ partial, int nwin, int Gp, int G, int Ghp,
-                                                                         int CH, const int *__restrict__ ctl, int final_tile, int wchunks,
-                                                                         int hchunks, int K, int max_windows, double *__restrict__ state,
-                                                                         int *__restrict__ head, double *__restrict__ power_w,
-                                                                         int32_t *__restrict__ argmax_w, double *__restrict__ latest_power,
-                                                                         int32_t *__restrict__ latest_argmax)
-{
-    __shared__ double sv[SA_COLS];
-    __shared__ int si[SA_COLS];
-    const int b = blockIdx.x;
-    const int col = threadIdx.x;
-    const int done = ctl[0], lo = ctl[4], hi = ctl[5], ready = ctl[6];
-    const int T = ctl[STREAM_CLK_TEND];
-    const bool ended = final_tile && (long long)ready * CH >= T;
-    if (ready - done != hi - lo || hi < lo || lo < 0 || hi > nwin) return;  // (never: the accumulate kernel writes both)
-    const int n0 = done < wchunks ? 0 : (done - wchunks) / hchunks + 1;      // first window not emitted before this call
-    const int n_started = ready > 0 ? (ready - 1) / hchunks : -1;            // last window that holds a chunk
-    long long n_emit;                                                        // windows emitted after this call
-    if (ended)
-        n_emit = T <= (long long)wchunks * CH ? 1 : 1 + ((long long)T - (long long)wchunks * CH + (long long)hchunks * CH - 1) / ((long long)hchunks * CH);
-    else
-        n_emit = ready < wchunks ? 0 : (ready - wchunks) / hchunks + 1;
-    const double *pb = partial + (size_t)b * nwin * Gp;
-    for (int n = n0; n <= n_started; ++n) {
-        const int c0 = n * hchunks;
-        const int ca = done > c0 ? done : c0;
-        const int cb = ready - c0 < wchunks ? ready : c0 + wchunks;
-        const bool emit = n < n_emit;  // complete, or cut at the end of the recording
-        double *tot = state + (((size_t)b * K + n % K) * 2) * G, *blk = tot + G;
-        long long frames = (long long)T - (long long)c0 * CH;
-        if (!ended || frames > (long long)wchunks * CH) frames = (long long)wchunks * CH;
-        const size_t row = (size_t)b * max_windows + n % max_windows;
-        const bool newest = n == n_emit - 1;
-        double best = -1.0;
-        int bi = 0x7fffffff;
-        for (int g = col; g < G; g += SA_COLS) {
-            double total = 0.0, s = 0.0;
-            if (ca > c0) {  // the window opened in an earlier call
-                total = tot[g];
-                s = blk[g];
-            }
-            int open = (ca - c0) % STREAM_BLOCK_CHUNKS;
-            for (int ch = ca; ch < cb; ++ch) {
-                const double *pr = pb + (size_t)(lo + ch - done) * Gp;
-                s += pr[g];
-                s += pr[Ghp + g];
-                if (++open == STREAM_BLOCK_CHUNKS) {
-                    total += s;
-                    s = 0.0;
-                    open = 0;
-                }
-            }
-            if (!emit) {
-                tot[g] = total;
-                blk[g] = s;
-                continue;
-            }
-            if (open > 0) total += s;  // the last block of the window, if it holds any chunk
-            const double p = total / (double)frames;
-            if (power_w) power_w[row * G + g] = p;
-            if (newest && latest_power) latest_power[(size_t)b * G + g] = p;
-            if (p > best) {
-                best = p;
-                bi = g;
-            }
-            tot[g] = 0.0;
-            blk[g] = 0.0;
-        }
-        if (!emit) continue;  // (uniform over the workgroup)
-        const int a = sc_argmax(best, bi, sv, si);
-        if (col == 0) {
-            if (argmax_w) argmax_w[row] = a;
-            if (newest && latest_argmax) latest_argmax[b] = a;
-        }
-        __syncthreads();  // sv / si are rewritten by the next window
-    }
-    if (b == 0 && col == 0) head[0] = (int)(n_emit > 0x7fffffffll ? 0x7fffffffll : n_emit);
-}
-
 // One workgroup per (trial, channel) row: the frames behind the last contracted chunk go to the row's carry.  Source (staging, the
 // workspace) and destination (carry, the state) are different arrays: they never overlap, so there is no scratch pass.  Thread 0 of
 // workgroup 0 commits the clock; the words it writes are read by no thread of this launch.
@@ -404,19 +322,6 @@ hipError_t launch_stream_complex_accumulate(const double *partial, int B, int Ks
     unsigned char *base = reinterpret_cast<unsigned char *>(state);
     hipLaunchKernelGGL(stream_complex_accumulate_kernel, dim3(B), dim3(SA_COLS), 0, stream, partial, Ks, Gp, G, Gp / 2, CH, final_tile ? 1 : 0,
                        reinterpret_cast<int *>(base), reinterpret_cast<double *>(base + L.acc), power, argmax);
-    return hipGetLastError();
-}
-
-hipError_t launch_stream_complex_windows(const double *partial, int B, int Ks, int Gp, int G, int CH, const void *state, int final_tile,
-                                         int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
-                                         double *latest_power, int32_t *latest_argmax, hipStream_t stream)
-{
-    if (CH < 1 || window < 1 || hop < 1 || hop > window || window % CH != 0 || hop % CH != 0 || max_windows < 1) return hipErrorInvalidValue;
-    int *head = reinterpret_cast<int *>(win_state);
-    double *wst = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(win_state) + 256);
-    hipLaunchKernelGGL(stream_complex_window_kernel, dim3(B), dim3(SA_COLS), 0, stream, partial, Ks, Gp, G, Gp / 2, CH,
-                       reinterpret_cast<const int *>(state), final_tile ? 1 : 0, window / CH, hop / CH, stream_window_slots(window, hop),
-                       max_windows, wst, head, power_w, argmax_w, latest_power, latest_argmax);
     return hipGetLastError();
 }
 

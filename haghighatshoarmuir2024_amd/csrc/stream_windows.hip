@@ -18,6 +18,10 @@
 //
 // One workgroup per trial, the windows of a call in a loop inside the kernel: the grid depends on B only, no launch argument
 // on time, so the launch is part of the tile's graph.  No atomics, no host synchronisation.
+//
+// The complex Beamformer's stream (stream_complex.hip) emits its windows through the same kernel: its rows are folded, columns
+// [0, Ghp) Re and [Ghp, Gp) Im, and its control words carry the same meaning.  PAIRS = 1 adds both halves per chunk, s += Re; s += Im,
+// the additions of window_power_kernel with complex_pairs = 1 (windows.hip); PAIRS = 0 is the real read-out, which never reads Ghp.
 #include "micloc_internal.h"
 
 namespace micloc {
@@ -26,12 +30,13 @@ namespace {
 
 constexpr int SW_COLS = 256;
 
+template <int PAIRS>
 __global__ __launch_bounds__(SW_COLS) void stream_window_kernel(const double *__restrict__ partial, int nwin, int Gp, int G, int CH,
                                                                  const int *__restrict__ ctl, int final_tile, int wchunks, int hchunks,
                                                                  int K, int max_windows, double *__restrict__ state,
                                                                  int *__restrict__ head, double *__restrict__ power_w,
                                                                  int32_t *__restrict__ argmax_w, double *__restrict__ latest_power,
-                                                                 int32_t *__restrict__ latest_argmax)
+                                                                 int32_t *__restrict__ latest_argmax, int Ghp)
 {
     __shared__ double sv[SW_COLS];
     __shared__ int si[SW_COLS];
@@ -41,7 +46,7 @@ __global__ __launch_bounds__(SW_COLS) void stream_window_kernel(const double *__
     const int T = ctl[STREAM_CLK_TEND];
     // the recording is complete once the final tile's chunks cover its T frames (a lag failure leaves them short: no read-out)
     const bool ended = final_tile && (long long)ready * CH >= T;
-    if (ready - done != hi - lo || hi < lo || lo < 0 || hi > nwin) return;  // (never: the horizon kernel writes both)
+    if (ready - done != hi - lo || hi < lo || lo < 0 || hi > nwin) return;  // (never: the kernel in front writes both)
     const int n0 = done < wchunks ? 0 : (done - wchunks) / hchunks + 1;      // first window not emitted before this call
     const int n_started = ready > 0 ? (ready - 1) / hchunks : -1;            // last window that holds a chunk
     long long n_emit;                                                        // windows emitted after this call
@@ -71,6 +76,7 @@ __global__ __launch_bounds__(SW_COLS) void stream_window_kernel(const double *__
             int open = (ca - c0) % STREAM_BLOCK_CHUNKS;
             for (int ch = ca; ch < cb; ++ch) {
                 s += pb[(size_t)(lo + ch - done) * Gp + g];
+                if (PAIRS) s += pb[(size_t)(lo + ch - done) * Gp + Ghp + g];
                 if (++open == STREAM_BLOCK_CHUNKS) {
                     total += s;
                     s = 0.0;
@@ -127,17 +133,17 @@ size_t stream_window_state_bytes(int B, int G, int window, int hop)
     return 256 + (((size_t)B * stream_window_slots(window, hop) * 2 * G * sizeof(double) + 255) & ~(size_t)255);
 }
 
-hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp, int G, int chunk_frames, const int *ctl, int final_tile,
-                                 int window, int hop, int max_windows, void *win_state, double *power_w, int32_t *argmax_w,
-                                 double *latest_power, int32_t *latest_argmax, hipStream_t stream)
+hipError_t launch_stream_windows(const double *partial, int B, int nwin, int Gp, int G, int complex_pairs, int Ghp, int chunk_frames,
+                                 const int *ctl, int final_tile, int window, int hop, int max_windows, void *win_state, double *power_w,
+                                 int32_t *argmax_w, double *latest_power, int32_t *latest_argmax, hipStream_t stream)
 {
     if (chunk_frames < 1 || window < 1 || hop < 1 || hop > window || window % chunk_frames != 0 || hop % chunk_frames != 0 || max_windows < 1)
         return hipErrorInvalidValue;
     int *head = reinterpret_cast<int *>(win_state);
     double *state = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(win_state) + 256);
-    hipLaunchKernelGGL(stream_window_kernel, dim3(B), dim3(SW_COLS), 0, stream, partial, nwin, Gp, G, chunk_frames, ctl, final_tile ? 1 : 0,
-                       window / chunk_frames, hop / chunk_frames, stream_window_slots(window, hop), max_windows, state, head, power_w,
-                       argmax_w, latest_power, latest_argmax);
+    hipLaunchKernelGGL(complex_pairs ? stream_window_kernel<1> : stream_window_kernel<0>, dim3(B), dim3(SW_COLS), 0, stream, partial, nwin, Gp, G,
+                       chunk_frames, ctl, final_tile ? 1 : 0, window / chunk_frames, hop / chunk_frames, stream_window_slots(window, hop),
+                       max_windows, state, head, power_w, argmax_w, latest_power, latest_argmax, Ghp);
     return hipGetLastError();
 }
 

@@ -35,6 +35,12 @@ final, bit for bit the one-shot rows -- into a ring of `max_windows` rows: lates
 THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
+
+THE CLASSES: StreamingLocalizer (one SNNBeamformer chain), WidebandStreamingLocalizer (a filterbank and one StreamingLocalizer per band) and
+ComplexStreamingLocalizer share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
+_TileStream states once: what a window / hop / max_windows may be, which tiles are accepted, how a tile length becomes a captured graph, how
+the ring of windows is read, what finish() refuses about it.  A class adds its own state and scratch, the launches of its tile (_tile), the
+host mirror of its clock (_advance), status() and its own refusals in finish().
 """
 import ctypes
 
@@ -44,7 +50,210 @@ from . import _lib, runtime, utils
 from .snn_beamformer import neuron_impulse_response
 
 
-class StreamingLocalizer:
+class _TileStream:
+    """The tile protocol of the three localizers (module docstring, THE CLASSES).  A subclass supplies
+      _tile(x, n, final)   the launches of one tile and nothing else: no allocation, no synchronisation, no absolute time by value (the clock
+                           is a device word), so that a tile of a given length is ONE replayable hipGraph;
+      _advance(n, final)   the host mirror of the clock and the end-of-stream bookkeeping;
+      _before_slide(n)     (optional) host work that must see the state in front of the tile's launches;
+      _window_count()      (optional) windows emitted so far, where they are not counted in `wst`
+    and sets plan, device, lib, B, M, G, T and max_tile before it uses the helpers of the constructor below."""
+
+    TILE_MULTIPLE = 1  # a tile other than the last one holds a multiple of this many frames
+
+    # ---- the constructor's shared parts -----------------------------------------------------------------------------------
+    @staticmethod
+    def _check_window_given(window, hop, max_windows):
+        if window is None and (hop is not None or max_windows is not None):
+            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+
+    @staticmethod
+    def _check_hop(hop, window):
+        if hop > window:
+            raise ValueError(f"the streaming read-out needs hop <= window (hop {hop}, window {window})")
+
+    @staticmethod
+    def _check_ring(max_windows):
+        if max_windows < 1:
+            raise ValueError("max_windows must be at least 1")
+
+    def _set_windows(self, plan, window, hop, max_windows):
+        """self.window / hop / max_windows (None without window=): ValueError, naming the quantum, for a window or hop that does not fit
+        `plan`'s -- before any launch of the stream; the ring holds every window of the recording where total_frames is given, else 64."""
+        self.window = self.hop = self.max_windows = None
+        if window is not None:
+            nW, self.window, self.hop = plan.window_count(self.T if self.T is not None else 1, window, hop)
+            self._check_hop(self.hop, self.window)
+            self.max_windows = int(max_windows) if max_windows is not None else (nW if self.T is not None else 64)
+            self._check_ring(self.max_windows)
+
+    def _alloc_results(self):
+        """The running estimate and, with window=, the ring and the newest window; then the stream is at frame 0 with no graph."""
+        torch = runtime._torch()
+        dev = self.device
+        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self.window_power = self.window_argmax = self.latest_power = self.latest_argmax = None
+        if self.window is not None:
+            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
+            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
+            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self.t = 0
+        self.done = False
+        self._seen, self._graphs = set(), {}
+
+    def _reset_window_state(self, state_bytes, reset, name, hint=""):
+        """wst, the device state of the open windows (single-band classes): sized by `state_bytes`, zero-filled by `reset`."""
+        if self.window is None:
+            return
+        self.nwst = int(state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows))
+        if self.nwst == 0:
+            raise _lib.MiclocError(f"micloc {name}_state_bytes: the plan cannot serve the windowed read-out{hint}")
+        torch = runtime._torch()
+        self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=self.device)
+        _lib.check(reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
+                         runtime._stream(self.device)), f"{name}_reset")
+
+    def _set_wrap(self, wrap_tail):
+        """self.wrap: np.roll's wrap-around rows [batch, L // 2, M] on the device, or None (zeros)."""
+        self.wrap = None
+        if wrap_tail is not None:
+            wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
+            if tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
+                raise ValueError(f"wrap_tail must be [batch, {self.L // 2}, num_mic]")
+            self.wrap = wrap_tail
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _check_tile(self, B, n, M, final):
+        if self.done:
+            raise _lib.MiclocError("the stream has ended")
+        if B != self.B or M != self.M:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.M}!")
+        if final is None:
+            final = self.T is not None and self.t + n == self.T
+        if n < 1 or n > self.max_tile or (not final and n % self.TILE_MULTIPLE != 0) \
+                or (self.T is not None and (self.t + n > self.T or (final and self.t + n != self.T))):
+            raise ValueError("tiles must hold 1 .. max_tile frames and add up to total_frames" if self.TILE_MULTIPLE == 1 else
+                             f"tiles must be multiples of {self.TILE_MULTIPLE} frames (except the last), at most max_tile long, and add up to total_frames")
+        if self.t + n > 0x7FFFFFFF:
+            raise ValueError("the stream's clock is a 32-bit frame counter")
+        return bool(final)
+
+    def _stht_tile(self, x, n, clock, spare_rows=0):
+        """The front of a single-band tile: [history | tile] into `ext`, its STHT into the planar rows `h` (+ spare_rows rows), np.roll's
+        wrap-around rows while the frames-pushed word of `clock` is below L / 2.  -> (ext, h, Ts)"""
+        lib, plan, B, M = self.lib, self.plan, self.B, self.M
+        st = runtime._stream(self.device)
+        Text = self.halo + n
+        ext = self.ext[: B * Text * M].view(B, Text, M)  # contiguous [history | tile] of this tile length
+        ext[:, : self.halo, :].copy_(self.hist)
+        ext[:, self.halo :, :].copy_(x)
+        Ts = plan.padded_T(Text)
+        h = self.h[: (B * self.C + spare_rows) * Ts]
+        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), B, Text, runtime._ptr(h), Ts, st), "stht")
+        # in-phase[t] = x[T - L/2 + t] for t < L/2 (zeros if the caller could not know them); a no-op later
+        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(clock), runtime._ptr(h), B, Ts, self.halo, n, runtime._ptr(self.wrap), st),
+                   "stream_wrap_rows")
+        return ext, h, Ts
+
+    def _keep_history(self, ext):
+        """The back of a single-band tile: the last `halo` frames of [history | tile] for the next tile's quadrature FIR."""
+        self.hist.copy_(ext[:, ext.shape[1] - self.halo :, :])
+
+    def _before_slide(self, n):
+        pass
+
+    def push(self, x_tile, final=None):
+        """x_tile [batch, n, M] (numpy or device tensor); n <= max_tile and, except for the last tile, a multiple of TILE_MULTIPLE.
+        final: this is the last tile (default: inferred from total_frames).  Returns the running (power, argmax) device tensors
+        (overwritten by the next push; over the frames beamformed so far)."""
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        final = self._check_tile(B, n, M, final)
+        self._before_slide(n)
+        self._tile(x, n, final)
+        self._seen.add(n)
+        self._advance(n, final)
+        return self.power, self.argmax
+
+    def push_replay(self, x_tile):
+        """push() for the steady state of a live source (micloc/localization_demo_snn.py:125-193: one 0.25 s frame after the other):
+        a non-final tile whose length has been pushed before is ONE hipGraph launch -- every launch of the tile, captured on the length's
+        second occurrence, replayed from then on; the tile is copied into the graph's input buffer first.  Same results as push()."""
+        torch = runtime._torch()
+        x = self.plan.to_device(x_tile)
+        B, n, M = x.shape
+        if n not in self._seen or (self.T is not None and self.t + n == self.T):
+            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
+        self._check_tile(B, n, M, False)
+        g = self._graphs.get(n)
+        if g is None:
+            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
+            graph = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
+                self._tile(x_in, n, False)
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            g = self._graphs[n] = (graph, x_in)
+        self._before_slide(n)
+        g[1].copy_(x)
+        g[0].replay()
+        self._advance(n, False)
+        return self.power, self.argmax
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def _need_windows(self):
+        if self.window is None:
+            raise ValueError("the localizer was built without window=")
+
+    def _window_count(self):
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.micloc_stream_window_count(runtime._ptr(self.wst), ctypes.byref(c), runtime._stream(self.device)), "stream_window_count")
+        return int(c.value)
+
+    def latest_window(self):
+        """(power [B, G], argmax [B]) of the most recently emitted window: device tensors, overwritten when the next window is emitted,
+        zeros until the first one exists.  Does not synchronise."""
+        self._need_windows()
+        return self.latest_power, self.latest_argmax
+
+    def windows(self):
+        """dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]): `count` windows have been emitted so far
+        (utils.windows_complete of the frames beamformed); the k = min(count, max_windows) newest of them, windows first .. count - 1 in
+        ascending order, as device tensors (copies: later pushes do not change them); window_start: their first frames, host int64.
+        Synchronises the stream."""
+        self._need_windows()
+        torch = runtime._torch()
+        count = self._window_count()
+        k = min(count, self.max_windows)
+        first = count - k
+        rows = torch.arange(first, count, device=self.device) % self.max_windows
+        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
+                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+
+    def _need_done(self):
+        if not self.done:
+            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+
+    def _finish_windows(self, out):
+        """finish()'s windowed tail: `out` with window_power [B, nW, G], window_argmax [B, nW] and window_count = nW, every window of the
+        recording (a live source without total_frames: the max_windows newest, see windows())."""
+        if self.window is not None:
+            if self.T is not None:
+                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
+                if self.max_windows < nW:
+                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
+                                           "windows() while the stream runs)")
+            w = self.windows()
+            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
+        return out
+
+
+class StreamingLocalizer(_TileStream):
+    TILE_MULTIPLE = 16  # the encoder takes its frames sixteen at a time
+
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False,
                  window=None, hop=None, max_windows=None, _share=None):
         """beamf: SNNBeamformer; bf_mat [2M, G]; `batch` recordings are streamed in lock step.
@@ -63,8 +272,7 @@ class StreamingLocalizer:
         _share        (WidebandStreamingLocalizer) another StreamingLocalizer whose tile-sized scratch (`ext`, `h`, `ws`, the slide's staging
                       copy) this one uses instead of allocating its own, where it is large enough: for localizers whose tiles run one
                       after the other on one stream.  None: nothing changes."""
-        if window is None and (hop is not None or max_windows is not None):
-            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+        self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.beamf = beamf
         self.plan = beamf.new_plan()
@@ -82,15 +290,7 @@ class StreamingLocalizer:
         self.CH = self.lib.micloc_stream_chunk_frames(self.plan.handle)
         if self.CH <= 0:
             _lib.check(self.CH, "stream_chunk_frames")
-        self.window = self.hop = self.max_windows = None
-        if window is not None:
-            # ValueError, naming the quantum, for a window or hop that does not fit it -- before any launch of the stream
-            nW, self.window, self.hop = self.plan.window_count(self.T if self.T is not None else 1, window, hop)
-            if self.hop > self.window:
-                raise ValueError(f"the streaming read-out needs hop <= window (hop {self.hop}, window {self.window})")
-            self.max_windows = int(max_windows) if max_windows is not None else (nW if self.T is not None else 64)
-            if self.max_windows < 1:
-                raise ValueError("max_windows must be at least 1")
+        self._set_windows(self.plan, window, hop, max_windows)
         self.max_tile = -(-int(max_tile) // 16) * 16
         # window: the tile being encoded + the frames that may still be waiting for their spikes + one chunk of LIF history
         self.cap = -(-(self.max_tile + int(lag_frames) + 2 * self.CH) // self.CH) * self.CH
@@ -116,85 +316,40 @@ class StreamingLocalizer:
         self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (lfilter's zero state)
         self.ext = scratch("ext", (self.B * (self.halo + self.max_tile) * self.M,), torch.float64)
         self.h = scratch("h", ((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile),), torch.float64)
-        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        if self.window is not None:
-            self.nwst = self.lib.micloc_stream_window_state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows)
-            if self.nwst == 0:
-                raise _lib.MiclocError("micloc stream_window_state_bytes: the plan cannot serve the windowed read-out (a complex bf_mat?)")
-            self.wst = torch.empty(int(self.nwst), dtype=torch.uint8, device=dev)
-            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
-            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
-            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-            _lib.check(self.lib.micloc_stream_window_reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
-                                                           self.max_windows, runtime._stream(dev)), "stream_window_reset")
-        self.wrap = None
-        if wrap_tail is not None:
-            wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
-            if tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
-                raise ValueError(f"wrap_tail must be [batch, {self.L // 2}, num_mic]")
-            self.wrap = wrap_tail
+        self._alloc_results()
+        self._reset_window_state(self.lib.micloc_stream_window_state_bytes, self.lib.micloc_stream_window_reset, "stream_window", " (a complex bf_mat?)")
+        self._set_wrap(wrap_tail)
         self.raster = None
         if keep_raster:
             if self.T is None:
                 raise ValueError("keep_raster needs total_frames")
             self.raster = torch.zeros((self.B, self.T, self.C), dtype=torch.int8, device=dev)
-        self.t = 0
-        self.done = False
-        self._seen, self._graphs = set(), {}
         # the stream's clock (frames pushed, window base) lives on the device: zeroed here with the states and the window
         _lib.check(self.lib.micloc_stream_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, runtime._ptr(self.loc), self.nloc,
                                                 runtime._ptr(self.win), self.cap, runtime._stream(dev)), "stream_reset")
 
     # ---- one tile -------------------------------------------------------------------------------------------------------
-    def _check_tile(self, B, n, M, final):
-        if self.done:
-            raise _lib.MiclocError("the stream has ended")
-        if B != self.B or M != self.M:
-            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.M}!")
-        if final is None:
-            final = self.T is not None and self.t + n == self.T
-        if n < 1 or n > self.max_tile or (not final and n % 16 != 0) or (self.T is not None and (self.t + n > self.T or (final and self.t + n != self.T))):
-            raise ValueError("tiles must be multiples of 16 frames (except the last), at most max_tile long, and add up to total_frames")
-        if self.t + n > 0x7FFFFFFF:
-            raise ValueError("the stream's clock is a 32-bit frame counter")
-        return bool(final)
-
     def _tile(self, x, n, final):
-        """The launches of one tile (nothing else: no allocation, no synchronisation, no absolute time by value -- the clock is a
-        device word), so that a tile of a given length is ONE replayable hipGraph (push_replay)."""
-        lib, plan, B, M = self.lib, self.plan, self.B, self.M
+        lib, plan, B = self.lib, self.plan, self.B
         st = runtime._stream(self.device)
         # clock: t_end = t + n; the window slides forward (whole chunks) if it does not cover [.., t + n)
         _lib.check(lib.micloc_stream_begin_tile(plan.handle, runtime._ptr(self.loc), runtime._ptr(self.win), runtime._ptr(self.win_tmp), B, n, self.cap, st),
                    "stream_begin_tile")
-        ext = self.ext[: B * (self.halo + n) * M].view(B, self.halo + n, M)  # contiguous [history | tile] of this tile length
-        ext[:, : self.halo, :].copy_(self.hist)
-        ext[:, self.halo :, :].copy_(x)
-        Text = self.halo + n
-        Ts = plan.padded_T(Text)
-        h = self.h[: (B * self.C + 1) * Ts]  # one spare row: the encoder's loader may read up to `halo` elements past its last row
-        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), B, Text, runtime._ptr(h), Ts, st), "stht")
-        # np.roll's wrap-around: in-phase[t] = x[T - L/2 + t] for t < L/2 (zeros if the caller could not know them); a no-op later
-        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(self.loc), runtime._ptr(h), B, Ts, self.halo, n, runtime._ptr(self.wrap), st),
-                   "stream_wrap_rows")
+        # one spare row in h: the encoder's loader may read up to `halo` elements past its last row
+        ext, h, Ts = self._stht_tile(x, n, self.loc, spare_rows=1)
         h_tile = ctypes.c_void_p(h.data_ptr() + 8 * self.halo)
         _lib.check(lib.micloc_stream_encode_tile_f64(plan.handle, h_tile, B, n, Ts, int(final), runtime._ptr(self.win), self.cap, runtime._ptr(self.state),
                                                      self.nstate, runtime._ptr(self.loc), st), "stream_encode_tile")
+        tile = (plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B, self.cap, int(final),
+                runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         if self.window is None:
-            _lib.check(lib.micloc_stream_localize_tile_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B,
-                                                           self.cap, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws),
-                                                           self.nws, st), "stream_localize_tile")
+            _lib.check(lib.micloc_stream_localize_tile_f64(*tile, st), "stream_localize_tile")
         else:  # the same launches with the window read-out in front of the commit
-            _lib.check(lib.micloc_stream_localize_tile_windows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc,
-                                                                   runtime._ptr(self.win), B, self.cap, int(final), runtime._ptr(self.power),
-                                                                   runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws, runtime._ptr(self.wst),
-                                                                   self.nwst, self.window, self.hop, self.max_windows, runtime._ptr(self.window_power),
-                                                                   runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
-                                                                   runtime._ptr(self.latest_argmax), st), "stream_localize_tile_windows")
-        # history for the next tile's quadrature FIR: the last `halo` frames of [history | tile]
-        self.hist.copy_(ext[:, Text - self.halo :, :])
+            _lib.check(lib.micloc_stream_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
+                                                                   runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
+                                                                   runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st),
+                       "stream_localize_tile_windows")
+        self._keep_history(ext)
 
     def _advance(self, n, final):
         """Host mirror of the device clock (rz_stream_clock_begin_kernel's schedule) and the end-of-stream bookkeeping."""
@@ -206,45 +361,6 @@ class StreamingLocalizer:
     def _before_slide(self, n):
         if self.raster is not None and self.t + n > self.base + self.cap:
             self._save_window(self.t)  # (keep_raster) the rows about to leave the window
-
-    def push(self, x_tile, final=None):
-        """x_tile [batch, n, M] (numpy or device tensor); n a multiple of 16 except for the last tile, n <= max_tile.
-        final: this is the last tile (default: inferred from total_frames).  Returns the running (power, argmax) device
-        tensors (overwritten by the next push; over the frames beamformed so far)."""
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        final = self._check_tile(B, n, M, final)
-        self._before_slide(n)
-        self._tile(x, n, final)
-        self._seen.add(n)
-        self._advance(n, final)
-        return self.power, self.argmax
-
-    def push_replay(self, x_tile):
-        """push() for the steady state of a live source (micloc/localization_demo_snn.py:125-193: one 0.25 s frame after the other):
-        a non-final tile whose length has been pushed before is ONE hipGraph launch -- captured on its second occurrence, replayed from
-        then on; the tile is copied into the graph's input buffer first.  Same results as push()."""
-        torch = runtime._torch()
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        if n not in self._seen or (self.T is not None and self.t + n == self.T):
-            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
-        self._check_tile(B, n, M, False)
-        g = self._graphs.get(n)
-        if g is None:
-            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
-                self._tile(x_in, n, False)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            g = self._graphs[n] = (graph, x_in)
-        self._before_slide(n)
-        g[1].copy_(x)
-        g[0].replay()
-        self._advance(n, False)
-        return self.power, self.argmax
 
     def _save_window(self, t_end):
         """(keep_raster) copy the window's frames [base, t_end) into the full raster: later copies carry more final data."""
@@ -261,38 +377,11 @@ class StreamingLocalizer:
         _lib.check(self.lib.micloc_stream_overflow(runtime._ptr(self.state), ctypes.byref(lost), runtime._stream(self.device)), "stream_overflow")
         return dict(chunks=int(st4[0]), frames=int(st4[1]), lag_failures=int(st4[2]), overflow=int(lost.value))
 
-    def _need_windows(self):
-        if self.window is None:
-            raise ValueError("the localizer was built without window=")
-
-    def latest_window(self):
-        """(power [B, G], argmax [B]) of the most recently emitted window: device tensors, overwritten when the next window is emitted,
-        zeros until the first one exists.  Does not synchronise."""
-        self._need_windows()
-        return self.latest_power, self.latest_argmax
-
-    def windows(self):
-        """dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]): `count` windows have been emitted so far
-        (utils.windows_complete of the frames beamformed); the k = min(count, max_windows) newest of them, windows first .. count - 1 in
-        ascending order, as device tensors (copies: later pushes do not change them); window_start: their first frames, host int64.
-        Synchronises the stream."""
-        self._need_windows()
-        torch = runtime._torch()
-        c = ctypes.c_int(0)
-        _lib.check(self.lib.micloc_stream_window_count(runtime._ptr(self.wst), ctypes.byref(c), runtime._stream(self.device)), "stream_window_count")
-        count = int(c.value)
-        k = min(count, self.max_windows)
-        first = count - k
-        rows = torch.arange(first, count, device=self.device) % self.max_windows
-        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
-                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
-
     def finish(self, want_spikes=False):
         """-> dict(power [B, G], argmax [B] int32, spikes [B, T, 2M] int8 (keep_raster only) or None) as device tensors; with window=
         also window_power [B, nW, G], window_argmax [B, nW] and window_count = nW, every window of the recording (a live source
         without total_frames: the max_windows newest, see windows())."""
-        if not self.done:
-            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+        self._need_done()
         s = self.status()
         if s["overflow"]:
             raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
@@ -307,18 +396,10 @@ class StreamingLocalizer:
             self._save_window(self.t)
             spikes = self.raster
         out = dict(power=self.power, argmax=self.argmax, spikes=spikes)
-        if self.window is not None:
-            if self.T is not None:
-                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
-                if self.max_windows < nW:
-                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
-                                           "windows() while the stream runs)")
-            w = self.windows()
-            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
-        return out
+        return self._finish_windows(out)
 
 
-class WidebandStreamingLocalizer:
+class WidebandStreamingLocalizer(_TileStream):
     """The wideband chain (wideband.WidebandSNNLocalizer: a filterbank, one SNNBeamformer chain per band, the power patterns added, one
     arg-max -- what the reference deploys, micloc/localization_demo_snn.py:125-193) as ONE stream that arrives in tiles, with the results of
     `WidebandSNNLocalizer.localize_batch` on the whole recording bit for bit, whatever the tiling (include/micloc_hip.h "wideband
@@ -329,8 +410,6 @@ class WidebandStreamingLocalizer:
     launches (a StreamingLocalizer per band with its own plan, encoder and localize state, raster window, running power and window ring;
     the bands run one after the other on the one stream and share the tile-sized scratch), then the band sum
     (micloc_stream_band_sum_f64).  push_replay() captures that whole sequence as one graph per tile length.
-
-    The surface is StreamingLocalizer's: push, push_replay, status, latest_window, windows, finish.
 
     RING DEPTH of the bands (Kb).  Bands finish a window at different calls; a wideband window is emitted once every band has emitted
     it, so the windows [emitted, count_f) must still be in band f's ring when the band sum runs.  `emitted` is the smallest count after
@@ -346,8 +425,7 @@ class WidebandStreamingLocalizer:
         """loc: wideband.WidebandSNNLocalizer; the other arguments as StreamingLocalizer's, except
         wrap_tail  [F, batch, L // 2, M]: the last L // 2 frames of every band's FILTERED recording (np.roll's wrap-around happens after
                    the filterbank), or None (zeros, as for a live source)."""
-        if window is None and (hop is not None or max_windows is not None):
-            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+        self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
         F = self.F = len(loc.beamfs)
@@ -358,10 +436,10 @@ class WidebandStreamingLocalizer:
         L2 = len(loc.beamfs[0].kernel) // 2
         if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
             raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
-        if window is not None and hop is not None and int(hop) > int(window):
-            raise ValueError(f"the streaming read-out needs hop <= window (hop {int(hop)}, window {int(window)})")
-        if max_windows is not None and int(max_windows) < 1:
-            raise ValueError("max_windows must be at least 1")
+        if window is not None and hop is not None:
+            self._check_hop(int(hop), int(window))
+        if max_windows is not None:
+            self._check_ring(int(max_windows))
         self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
         if len(loc.filterbank.ba_list) != F:
             raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
@@ -380,16 +458,13 @@ class WidebandStreamingLocalizer:
                                                  _share=self.bands[0] if self.bands else None, **kw))
         b0 = self.bands[0]
         self.device, self.lib, self.plan = b0.device, b0.lib, b0.plan
-        self.window, self.hop, self.Kb = b0.window, b0.hop, Kb
+        self.Kb = Kb
+        self._set_windows(b0.plan, window, hop, max_windows)  # what every band has accepted
         if any(b.window != self.window or b.hop != self.hop or b.CH != b0.CH for b in self.bands):
             raise ValueError("window and hop must be multiples of every band's chunk length")
         if any(b.cap > self._cap_bound(lag_frames) for b in self.bands):
             raise _lib.MiclocError("a band's raster window is longer than the bound the ring depth was derived from")
         dev = self.device
-        self.max_windows = None
-        if self.window is not None:
-            nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T) if self.T is not None else None
-            self.max_windows = int(max_windows) if max_windows is not None else (nW if nW is not None else 64)
         self.nfb = int(self.lib.micloc_filterbank_stream_state_bytes(F, self.ncoef, self.B, self.M))
         if self.nfb == 0:
             raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
@@ -397,22 +472,13 @@ class WidebandStreamingLocalizer:
         self.nbs = int(self.lib.micloc_stream_bands_state_bytes())
         self.bands_state = torch.empty(self.nbs, dtype=torch.uint8, device=dev)
         self.xf = torch.empty(F * self.B * self.max_tile * self.M, dtype=torch.float64, device=dev)  # the filtered tile [F][B][n][M]
-        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self._alloc_results()
         vp = ctypes.c_void_p
         self._p_power = (vp * F)(*[b.power.data_ptr() for b in self.bands])
         self._p_rows = self._p_count = None
-        self.window_power = self.window_argmax = self.latest_power = self.latest_argmax = None
         if self.window is not None:
             self._p_rows = (vp * F)(*[b.window_power.data_ptr() for b in self.bands])
             self._p_count = (vp * F)(*[self.lib.micloc_stream_window_count_ptr(runtime._ptr(b.wst)) for b in self.bands])
-            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
-            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
-            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        self.t = 0
-        self.done = False
-        self._seen, self._graphs = set(), {}
         st = runtime._stream(dev)
         _lib.check(self.lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, st), "filterbank_stream_reset")
         _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, st), "stream_bands_reset")
@@ -435,10 +501,7 @@ class WidebandStreamingLocalizer:
 
     # ---- one tile -------------------------------------------------------------------------------------------------------
     def _check_tile(self, B, n, M, final):
-        if self.done:
-            raise _lib.MiclocError("the stream has ended")
-        final = self.bands[0]._check_tile(B, n, M, final)  # the bands advance in lock step: one check serves all
-        return final
+        return self.bands[0]._check_tile(B, n, M, final)  # the bands advance in lock step: one check serves all
 
     def _tile(self, x, n, final):
         """The launches of one tile, all on the current stream, in a fixed order: filterbank tile, the bands in ascending order, band
@@ -465,41 +528,6 @@ class WidebandStreamingLocalizer:
         self.t += n
         self.done = bool(final)
 
-    def push(self, x_tile, final=None):
-        """x_tile [batch, n, M] (numpy or device tensor), tiles as StreamingLocalizer.push's.  Returns the running (power, argmax) device
-        tensors of the band sum (overwritten by the next push; every band over the frames IT has beamformed so far)."""
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        final = self._check_tile(B, n, M, final)
-        self._tile(x, n, final)
-        self._seen.add(n)
-        self._advance(n, final)
-        return self.power, self.argmax
-
-    def push_replay(self, x_tile):
-        """push() as ONE graph launch per tile: a non-final tile whose length has been pushed before is captured on its second occurrence
-        (filterbank tile, every band's launches, band sum) and replayed from then on.  Same results as push()."""
-        torch = runtime._torch()
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        if n not in self._seen or (self.T is not None and self.t + n == self.T):
-            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
-        self._check_tile(B, n, M, False)
-        g = self._graphs.get(n)
-        if g is None:
-            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
-                self._tile(x_in, n, False)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            g = self._graphs[n] = (graph, x_in)
-        g[1].copy_(x)
-        g[0].replay()
-        self._advance(n, False)
-        return self.power, self.argmax
-
     # ---- results ----------------------------------------------------------------------------------------------------------
     def _bands_status(self):
         st2 = (ctypes.c_int * 2)()
@@ -513,33 +541,15 @@ class WidebandStreamingLocalizer:
         return dict(chunks=min(s["chunks"] for s in per), frames=min(s["frames"] for s in per), lag_failures=sum(s["lag_failures"] for s in per),
                     overflow=sum(s["overflow"] for s in per), bands=per, band_sum_failures=self._bands_status()[1])
 
-    def _need_windows(self):
-        if self.window is None:
-            raise ValueError("the localizer was built without window=")
-
-    def latest_window(self):
-        """(power [B, G], argmax [B]) of the most recently emitted wideband window: device tensors, zeros until the first one exists."""
-        self._need_windows()
-        return self.latest_power, self.latest_argmax
-
-    def windows(self):
-        """StreamingLocalizer.windows() of the band sum: dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]).
-        `count` is the smallest of the bands' counts at the last push.  Synchronises the stream."""
-        self._need_windows()
-        torch = runtime._torch()
-        count = self._bands_status()[0]
-        k = min(count, self.max_windows)
-        first = count - k
-        rows = torch.arange(first, count, device=self.device) % self.max_windows
-        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
-                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+    def _window_count(self):
+        """The smallest of the bands' counts at the last push."""
+        return self._bands_status()[0]
 
     def finish(self):
         """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
         window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
         torch = runtime._torch()
-        if not self.done:
-            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+        self._need_done()
         s = self.status()
         if s["overflow"]:
             raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
@@ -550,18 +560,10 @@ class WidebandStreamingLocalizer:
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
         out = dict(power=self.power, argmax=self.argmax, band_power=torch.stack([b.power for b in self.bands]))
-        if self.window is not None:
-            if self.T is not None:
-                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
-                if self.max_windows < nW:
-                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
-                                           "windows() while the stream runs)")
-            w = self.windows()
-            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
-        return out
+        return self._finish_windows(out)
 
 
-class ComplexStreamingLocalizer:
+class ComplexStreamingLocalizer(_TileStream):
     """The non-spiking complex Beamformer (beamformer.Beamformer; what the reference deploys live in micloc/localization_demo.py, restarting
     the chain on every 0.25 s pack) as ONE stream that arrives in tiles, with the results of `Beamformer.localize_batch` on the whole
     recording bit for bit, whatever the tiling (include/micloc_hip.h "streaming, complex Beamformer").
@@ -570,9 +572,7 @@ class ComplexStreamingLocalizer:
     length (no multiple of 16) and status() has no lag failures.  One tile = STHT of [last L - 1 frames | tile], np.roll's wrap rows, the
     band-pass tile (DF2T state on the device), the one-shot contraction kernel on [carry | tile], the accumulation of the new whole
     chunks, (the window read-out,) the slide of the ragged remainder into the carry with the clock commit -- a chain of launches on one
-    stream, one graph per tile length in push_replay().  The state is 2M (CH + n_coef - 1) + 2G doubles per trial however long the stream.
-
-    The surface is StreamingLocalizer's: push, push_replay, status, latest_window, windows, finish."""
+    stream, one graph per tile length in push_replay().  The state is 2M (CH + n_coef - 1) + 2G doubles per trial however long the stream."""
 
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None):
         """beamf: beamformer.Beamformer; bf_mat [M, G] complex; `batch` recordings are streamed in lock step.
@@ -582,8 +582,7 @@ class ComplexStreamingLocalizer:
                       recording of at least that length (shorter ones: wrap_rows()) -- or None (zeros: a live source cannot know them).
         max_tile      longest tile push() will be given.
         window, hop, max_windows   the windowed read-out, as StreamingLocalizer's (multiples of the plan's window quantum, hop <= window)."""
-        if window is None and (hop is not None or max_windows is not None):
-            raise ValueError("hop and max_windows belong to the windowed read-out: give window as well")
+        self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         bf_mat = np.asarray(bf_mat)
         if not np.iscomplexobj(bf_mat):
@@ -603,14 +602,7 @@ class ComplexStreamingLocalizer:
         self.lib = _lib.load()
         self.G = self.plan.G
         self.CH = self.plan.window_quantum()
-        self.window = self.hop = self.max_windows = None
-        if window is not None:
-            nW, self.window, self.hop = self.plan.window_count(self.T if self.T is not None else 1, window, hop)
-            if self.hop > self.window:
-                raise ValueError(f"the streaming read-out needs hop <= window (hop {self.hop}, window {self.window})")
-            self.max_windows = int(max_windows) if max_windows is not None else (nW if self.T is not None else 64)
-            if self.max_windows < 1:
-                raise ValueError("max_windows must be at least 1")
+        self._set_windows(self.plan, window, hop, max_windows)
         self.max_tile = int(max_tile)
         if self.max_tile < 1:
             raise ValueError("max_tile must be at least 1")
@@ -624,30 +616,11 @@ class ComplexStreamingLocalizer:
         self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (the FIR's zero state)
         self.ext = torch.empty((self.B * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
         self.h = torch.empty((self.B * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
-        self.power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-        self.argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-        st = runtime._stream(dev)
-        if self.window is not None:
-            self.nwst = int(self.lib.micloc_stream_complex_window_state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows))
-            if self.nwst == 0:
-                raise _lib.MiclocError("micloc stream_complex_window_state_bytes: the plan cannot serve the windowed read-out")
-            self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=dev)
-            self.window_power = torch.zeros((self.B, self.max_windows, self.G), dtype=torch.float64, device=dev)
-            self.window_argmax = torch.zeros((self.B, self.max_windows), dtype=torch.int32, device=dev)
-            self.latest_power = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
-            self.latest_argmax = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-            _lib.check(self.lib.micloc_stream_complex_window_reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
-                                                                   self.max_windows, st), "stream_complex_window_reset")
-        self.wrap = None
-        if wrap_tail is not None:
-            wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
-            if tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
-                raise ValueError(f"wrap_tail must be [batch, {self.L // 2}, num_mic]")
-            self.wrap = wrap_tail
-        self.t = 0
-        self.done = False
-        self._seen, self._graphs = set(), {}
-        _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, st), "stream_complex_reset")
+        self._alloc_results()
+        self._reset_window_state(self.lib.micloc_stream_complex_window_state_bytes, self.lib.micloc_stream_complex_window_reset, "stream_complex_window")
+        self._set_wrap(wrap_tail)
+        _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
+                   "stream_complex_reset")
 
     @staticmethod
     def wrap_rows(x, L):
@@ -661,90 +634,26 @@ class ComplexStreamingLocalizer:
         return out
 
     # ---- one tile -------------------------------------------------------------------------------------------------------
-    def _check_tile(self, B, n, M, final):
-        if self.done:
-            raise _lib.MiclocError("the stream has ended")
-        if B != self.B or M != self.M:
-            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.M}!")
-        if final is None:
-            final = self.T is not None and self.t + n == self.T
-        if n < 1 or n > self.max_tile or (self.T is not None and (self.t + n > self.T or (final and self.t + n != self.T))):
-            raise ValueError("tiles must hold 1 .. max_tile frames and add up to total_frames")
-        if self.t + n > 0x7FFFFFFF:
-            raise ValueError("the stream's clock is a 32-bit frame counter")
-        return bool(final)
-
     def _tile(self, x, n, final):
-        """The launches of one tile (nothing else: no allocation, no synchronisation, no absolute time by value), all on the current
-        stream one after the other, so that a tile of a given length is ONE replayable hipGraph without parallel branches."""
-        lib, plan, B, M = self.lib, self.plan, self.B, self.M
+        lib, plan, B = self.lib, self.plan, self.B
         st = runtime._stream(self.device)
-        Text = self.halo + n
-        ext = self.ext[: B * Text * M].view(B, Text, M)  # contiguous [history | tile] of this tile length
-        ext[:, : self.halo, :].copy_(self.hist)
-        ext[:, self.halo :, :].copy_(x)
-        Ts = plan.padded_T(Text)
-        h = self.h[: B * self.C * Ts]
-        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), B, Text, runtime._ptr(h), Ts, st), "stht")
-        # np.roll's wrap-around rows while the clock (the state's frames-pushed word) is below L / 2; a no-op later
-        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(h), B, Ts, self.halo, n, runtime._ptr(self.wrap), st),
-                   "stream_wrap_rows")
+        ext, h, Ts = self._stht_tile(x, n, self.state)
         _lib.check(lib.micloc_stream_complex_bandpass_tile_f64(plan.handle, runtime._ptr(h), B, n, Ts, self.halo, self.max_tile, runtime._ptr(self.state),
                                                                self.nstate, runtime._ptr(self.ws), self.nws, st), "stream_complex_bandpass_tile")
+        tile = (plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax),
+                runtime._ptr(self.ws), self.nws)
         if self.window is None:
-            _lib.check(lib.micloc_stream_complex_localize_tile_f64(plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
-                                                                   runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws, st),
-                       "stream_complex_localize_tile")
+            _lib.check(lib.micloc_stream_complex_localize_tile_f64(*tile, st), "stream_complex_localize_tile")
         else:
-            _lib.check(lib.micloc_stream_complex_localize_tile_windows_f64(plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
-                                                                           runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws),
-                                                                           self.nws, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
-                                                                           self.max_windows, runtime._ptr(self.window_power),
-                                                                           runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
-                                                                           runtime._ptr(self.latest_argmax), st), "stream_complex_localize_tile_windows")
-        # history for the next tile's quadrature FIR: the last `halo` frames of [history | tile]
-        self.hist.copy_(ext[:, Text - self.halo :, :])
+            _lib.check(lib.micloc_stream_complex_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
+                                                                           runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
+                                                                           runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st),
+                       "stream_complex_localize_tile_windows")
+        self._keep_history(ext)
 
     def _advance(self, n, final):
         self.t += n
         self.done = bool(final)
-
-    def push(self, x_tile, final=None):
-        """x_tile [batch, n, M] (numpy or device tensor), 1 <= n <= max_tile.  final: this is the last tile (default: inferred from
-        total_frames).  Returns the running (power, argmax) device tensors (overwritten by the next push; the mean over the whole chunks
-        contracted so far, zeros before the first one)."""
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        final = self._check_tile(B, n, M, final)
-        self._tile(x, n, final)
-        self._seen.add(n)
-        self._advance(n, final)
-        return self.power, self.argmax
-
-    def push_replay(self, x_tile):
-        """push() for the steady state of a live source: a non-final tile whose length has been pushed before is ONE hipGraph launch --
-        captured on its second occurrence, replayed from then on; the tile is copied into the graph's input buffer first.  Same results
-        as push()."""
-        torch = runtime._torch()
-        x = self.plan.to_device(x_tile)
-        B, n, M = x.shape
-        if n not in self._seen or (self.T is not None and self.t + n == self.T):
-            return self.push(x)  # first tile of this length (lazy kernel set-up must not happen inside a capture) / the final tile
-        self._check_tile(B, n, M, False)
-        g = self._graphs.get(n)
-        if g is None:
-            x_in = torch.empty((B, n, M), dtype=torch.float64, device=self.device)
-            graph = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.graph(graph, stream=s, capture_error_mode="thread_local"):
-                self._tile(x_in, n, False)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            g = self._graphs[n] = (graph, x_in)
-        g[1].copy_(x)
-        g[0].replay()
-        self._advance(n, False)
-        return self.power, self.argmax
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -754,43 +663,12 @@ class ComplexStreamingLocalizer:
         _lib.check(self.lib.micloc_stream_complex_status(runtime._ptr(self.state), st4, runtime._stream(self.device)), "stream_complex_status")
         return dict(chunks=int(st4[0]), frames=int(st4[1]), carry=int(st4[2]), pushed=int(st4[3]))
 
-    def _need_windows(self):
-        if self.window is None:
-            raise ValueError("the localizer was built without window=")
-
-    def latest_window(self):
-        """(power [B, G], argmax [B]) of the most recently emitted window: device tensors, zeros until the first one exists."""
-        self._need_windows()
-        return self.latest_power, self.latest_argmax
-
-    def windows(self):
-        """StreamingLocalizer.windows(): dict(count, first, window_power [B, k, G], window_argmax [B, k], window_start [k]).  Synchronises."""
-        self._need_windows()
-        torch = runtime._torch()
-        c = ctypes.c_int(0)
-        _lib.check(self.lib.micloc_stream_window_count(runtime._ptr(self.wst), ctypes.byref(c), runtime._stream(self.device)), "stream_window_count")
-        count = int(c.value)
-        k = min(count, self.max_windows)
-        first = count - k
-        rows = torch.arange(first, count, device=self.device) % self.max_windows
-        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
-                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
-
     def finish(self):
         """-> dict(power [B, G], argmax [B] int32) as device tensors; with window= also window_power [B, nW, G], window_argmax [B, nW] and
         window_count (a live source without total_frames: the max_windows newest, see windows())."""
-        if not self.done:
-            raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
+        self._need_done()
         s = self.status()
         if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
             raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
         out = dict(power=self.power, argmax=self.argmax)
-        if self.window is not None:
-            if self.T is not None:
-                nW = utils.windows_complete(self.T, self.window, self.hop, T=self.T)
-                if self.max_windows < nW:
-                    raise _lib.MiclocError(f"the recording has {nW} windows and the ring keeps {self.max_windows}: raise max_windows (or read "
-                                           "windows() while the stream runs)")
-            w = self.windows()
-            out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
-        return out
+        return self._finish_windows(out)

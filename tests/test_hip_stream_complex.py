@@ -269,6 +269,55 @@ def test_windows_not_in_the_count_are_not_emitted_and_the_ring_wraps(torch):
         assert torch.equal(loc.window_power[:, n % 2], ref["window_power"][:, n])
 
 
+@pytest.mark.parametrize("G", [57, 449])  # Ghp padded past G; two columns per thread
+def test_replayed_windows_on_folded_rows(G, torch):
+    """The window read-out on folded rows inside a captured graph: two windows open at once, the last one cut at the end of the recording,
+    a ring shorter than the recording -- push_replay against push after every tile, and every row against the one-shot call."""
+    from haghighatshoarmuir2024_amd import _lib
+    from haghighatshoarmuir2024_amd.streaming import ComplexStreamingLocalizer
+
+    bf = beamformer(7)
+    rng = np.random.default_rng(29)
+    W = random_bf_mat(rng, 7, G)
+    bf.plan().set_bf_mat(W)
+    CH = bf.plan().window_quantum()
+    B, T = 2, 3 * CH + 5
+    window, hop = 2 * CH, CH
+    x = rng.standard_normal((B, T, 7))
+    tiles = [160] * 4 + [T - 640]  # the first 160 eager, captured on the second and replayed for tiles 2, 3 and 4; the final tile is pushed eagerly
+    ref = bf.localize_batch(W, x, window=window, hop=hop)
+    nW = ref["window_power"].shape[1]
+    assert nW == 3
+    kw = dict(batch=B, total_frames=T, wrap_tail=ComplexStreamingLocalizer.wrap_rows(x, len(bf.kernel)), max_tile=160, window=window, hop=hop)
+    replayed = bf.streaming_localizer(W, max_windows=2, **kw)
+    eager = bf.streaming_localizer(W, max_windows=2, **kw)
+    t = 0
+    for n, s in zip(tiles, bookkeeping(tiles, CH, window, hop)):
+        pr, ar = replayed.push_replay(x[:, t : t + n, :])
+        pe, ae = eager.push(x[:, t : t + n, :])
+        t += n
+        assert torch.equal(pr, pe) and torch.equal(ar, ae)
+        wr, we = replayed.windows(), eager.windows()
+        assert wr["count"] == we["count"] == s["windows"] and wr["first"] == we["first"] == max(0, s["windows"] - 2)
+        assert torch.equal(wr["window_power"], we["window_power"]) and torch.equal(wr["window_argmax"], we["window_argmax"])
+        assert torch.equal(wr["window_power"], ref["window_power"][:, wr["first"] : wr["count"]])  # the rows in the ring: the one-shot bits
+        assert torch.equal(wr["window_argmax"], ref["window_argmax"][:, wr["first"] : wr["count"]])
+        for a, b in zip(replayed.latest_window(), eager.latest_window()):
+            assert torch.equal(a, b)
+        if wr["count"]:
+            assert torch.equal(replayed.latest_window()[0], ref["window_power"][:, wr["count"] - 1])
+    assert wr["count"] == nW
+    assert sorted(replayed._graphs) == [160] and not eager._graphs
+    for loc in (replayed, eager):
+        with pytest.raises(_lib.MiclocError, match="max_windows"):  # a ring of 2 rows for 3 windows
+            loc.finish()
+    # every row against the one-shot call: the same input once more with the default ring depth
+    loc, out = stream(bf, W, x, tiles, replay=True, window=window, hop=hop)
+    assert sorted(loc._graphs) == [160] and out["window_count"] == nW
+    assert torch.equal(out["window_power"], ref["window_power"]) and torch.equal(out["window_argmax"], ref["window_argmax"])
+    assert torch.equal(out["power"], ref["power"]) and torch.equal(out["argmax"], ref["argmax"])
+
+
 # ---- 5. the reference's fixture ------------------------------------------------------------------------------------------------------------
 def test_reference_trial_pushed_in_packs(torch):
     """The noisy trial of the reference's Beamformer (tests/golden/beamformer_c128_g449.npz, the tolerances of tests/test_hip_pins_r5.py for
