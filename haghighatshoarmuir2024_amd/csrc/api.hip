@@ -13,14 +13,17 @@ static thread_local int g_last_hip = 0;
 
 // (a failed runtime call also leaves its code in HIP's sticky "last error": clear it, or the next, unrelated launch
 // check -- hipGetLastError() after a successful launch -- would report it again)
-#define HIP_TRY(expr)                   \
-    do {                                \
-        hipError_t _e = (expr);         \
-        if (_e != hipSuccess) {         \
-            g_last_hip = (int)_e;       \
-            (void)hipGetLastError();    \
-            return MICLOC_ERR_HIP;      \
-        }                               \
+static int hip_failed(hipError_t e)
+{
+    g_last_hip = (int)e;
+    (void)hipGetLastError();
+    return MICLOC_ERR_HIP;
+}
+
+#define HIP_TRY(expr)                                \
+    do {                                             \
+        hipError_t _e = (expr);                      \
+        if (_e != hipSuccess) return hip_failed(_e); \
     } while (0)
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -105,8 +108,13 @@ int pad_ct(int C)
     return ct;
 }
 
-struct WsLayout {
-    size_t h, pre, scratch, spikes, partial, total;
+// where the front end of a pipeline entry (STHT, band-pass / RZCC) keeps its arrays in the caller's workspace
+struct FrontOffsets {
+    size_t h, pre, scratch, spikes;
+};
+
+struct WsLayout : FrontOffsets {
+    size_t partial, total;
 };
 
 WsLayout ws_layout(const micloc_plan *p, int B, int T)
@@ -142,6 +150,8 @@ bool bad_ws(const void *ws, size_t have, size_t need)
 {
     return ws == nullptr || have < need || (reinterpret_cast<uintptr_t>(ws) & 255) != 0;
 }
+
+double *ws_doubles(void *ws, size_t offset) { return reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + offset); }
 
 // ---- windowed read-out (windows.hip) ----------------------------------------------------------------------------------
 // Frames per row of partial sums of the kernel family beamform_nchunks_ct describes (the general kernel): the largest T that is one chunk.
@@ -193,6 +203,107 @@ hipError_t lif_beamform_oneshot(const BeamformW &W, const NeuronTab &nt, const i
     hipError_t e = hipSuccess;
     if (launch_lif_beamform_lean(W, nt, spikes, B, T, y, partial, stream, nchunks, &e)) return e;
     return launch_lif_beamform(W, nt, spikes, B, T, y, partial, stream, nchunks);
+}
+
+// MICLOC_OK when the plan holds what an entry for a complex / a real bf_mat reads: the matrix of that kind and, for a real one, the neuron kernel
+int plan_kind(const micloc_plan *p, bool cpx)
+{
+    if (!p->d_W || (!cpx && !p->d_ntab)) return MICLOC_ERR_NOT_SET;
+    return (p->W_is_complex != 0) == cpx ? MICLOC_OK : MICLOC_ERR_SHAPE;
+}
+
+// the kind check of a window entry, then the window rule: the plan's quantum (> 0), or the status (< 0) of the check that failed
+int window_check(const micloc_plan *p, bool cpx, int B, int T, int window, int hop)
+{
+    int rc = plan_kind(p, cpx), nW = 0;
+    if (rc != MICLOC_OK) return rc;
+    const int q = window_quantum(p);
+    rc = window_args(T, window, hop, q, B, &nW);
+    return rc == MICLOC_OK ? q : rc;
+}
+
+// The rule of the two covariance entries: the neuron kernel always, a real bf_mat only for the power, at most 128 channels.
+int cov_check(const micloc_plan *p, bool want_power)
+{
+    if (!p->d_ntab) return MICLOC_ERR_NOT_SET;
+    if (want_power && (!p->d_W || p->W_is_complex)) return p->d_W ? MICLOC_ERR_SHAPE : MICLOC_ERR_NOT_SET;
+    return pad_ct(p->C) > 8 ? MICLOC_ERR_SHAPE : MICLOC_OK;
+}
+
+// ---- the front end of the pipeline entries ---------------------------------------------------------------------------------------
+struct Front {
+    int rc;
+    const void *src;  // what the tails below read: the spike raster (real bf_mat) or the planar band-passed rows [B][C][Ts] (complex)
+    int Ts;
+};
+
+// STHT, then the band-pass stage, into the workspace regions at `o`.  Real bf_mat (cpx false): the raster, in `spikes` when the caller
+// wants it, with the plan's encoder chunking and only the launches that `stages` (MICLOC_STAGE_* bits) selects.  Complex: the planar rows.
+Front front_end(const micloc_plan *p, bool cpx, const double *x, int B, int T, void *ws, const FrontOffsets &o, int8_t *spikes, int stages,
+                hipStream_t st)
+{
+    Front f{MICLOC_OK, nullptr, micloc_padded_T(T)};
+    double *h = ws_doubles(ws, o.h);
+    // the in-phase channels are the rolled input frames: the band-pass kernel reads them from x directly
+    hipError_t e = (stages & MICLOC_STAGE_STHT) ? launch_stht(p->taps, x, h, B, T, p->M, f.Ts, st, false) : hipSuccess;
+    if (cpx) {
+        double *pre = ws_doubles(ws, o.pre);
+        f.src = pre;
+        if (e == hipSuccess)
+            e = launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, f.Ts, p->robust_width, p->bipolar, pre, nullptr, nullptr, st, x, p->M,
+                                     p->taps.shift);
+    } else {
+        int8_t *spk = spikes ? spikes : static_cast<int8_t *>(ws) + o.spikes;
+        f.src = spk;
+        const int phases = (stages & MICLOC_STAGE_ENCODE) ? RZ_PHASE_ALL
+                                                          : ((stages & MICLOC_STAGE_ENCODE_SCAN) ? RZ_PHASE_SCAN : 0) |
+                                                                ((stages & MICLOC_STAGE_ENCODE_REST) ? RZ_PHASE_ENCODE : 0);
+        if (e == hipSuccess && phases)
+            e = launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, f.Ts, p->robust_width, p->bipolar, nullptr, spk,
+                                     static_cast<char *>(ws) + o.scratch, st, x, p->M, p->taps.shift, p->chunk_frames, phases);
+    }
+    if (e != hipSuccess) f.rc = hip_failed(e);
+    return f;
+}
+
+// ---- the tails: from Front::src (or a caller's array of that kind) to one read-out; the fourth, track_run, is further down ----------------
+// y and / or power and arg-max; `partial` (the chunk sums) is read only when one of the latter two is wanted
+int power_tail(const micloc_plan *p, const void *src, int B, int T, int Ts, double *y, double *power, int32_t *argmax, double *partial,
+               hipStream_t st)
+{
+    const int Gp = 16 * p->W.GT, cpx = p->W_is_complex ? 1 : 0;
+    if (!power && !argmax) partial = nullptr;
+    int nch = 0;
+    if (cpx)
+        HIP_TRY(launch_planar_beamform(p->W, static_cast<const double *>(src), B, T, Ts, y, 1, partial, st, &nch));
+    else
+        HIP_TRY(lif_beamform_oneshot(p->W, p->ntab, static_cast<const int8_t *>(src), B, T, y, partial, st, &nch));
+    if (partial) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, cpx, cpx ? Gp / 2 : 0, power, argmax, st));
+    return MICLOC_OK;
+}
+
+// the power-only launch, then both read-outs of its partial sums
+int window_tail(const micloc_plan *p, const void *src, int B, int T, int Ts, int quantum, int window, int hop, double *power_w,
+                int32_t *argmax_w, double *power, int32_t *argmax, double *partial, hipStream_t st)
+{
+    int nch = 0;
+    if (p->W_is_complex)
+        HIP_TRY(launch_planar_beamform(p->W, static_cast<const double *>(src), B, T, Ts, nullptr, 1, partial, st, &nch));
+    else
+        HIP_TRY(launch_lif_beamform(p->W, p->ntab, static_cast<const int8_t *>(src), B, T, nullptr, partial, st, &nch));
+    return window_readout(p, partial, B, T, nch, quantum, window, hop, power_w, argmax_w, power, argmax, st);
+}
+
+// membrane covariance of the frames t >= t_start and, on request, the power in its covariance form
+int cov_tail(const micloc_plan *p, const int8_t *spikes, int B, int T, int t_start, double *cov, double *power, int32_t *argmax, double *partial,
+             hipStream_t st)
+{
+    const int CT = pad_ct(p->C);
+    const bool want_power = power || argmax;
+    HIP_TRY(launch_lif_cov(p->ntab, spikes, B, T, p->C, CT, t_start, partial, st));
+    HIP_TRY(launch_cov_power(partial, B, T, CT, p->C, T - t_start, want_power ? p->W.Wp : nullptr, want_power ? 16 * p->W.GT : 16,
+                             want_power ? p->G_out : 0, cov, power, argmax, st));
+    return MICLOC_OK;
 }
 
 }  // namespace
@@ -480,17 +591,10 @@ int micloc_lif_beamform_f64(const micloc_plan *p, const int8_t *spikes, int B, i
 {
     if (!p || !spikes || bad_batch(B) || T < 1 || (!y && !power && !argmax)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int Gp = 16 * p->W.GT;
-    const bool want_power = power || argmax;
-    if (want_power && bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, Gp))) return MICLOC_ERR_WORKSPACE;
-    double *partial = want_power ? reinterpret_cast<double *>(ws) : nullptr;
-    int nch = 0;
-    HIP_TRY(lif_beamform_oneshot(p->W, p->ntab, spikes, B, T, y, partial, (hipStream_t)stream, &nch));
-    if (want_power)
-        HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 0, 0, power, argmax, (hipStream_t)stream));
-    return MICLOC_OK;
+    const int rc = plan_kind(p, false);
+    if (rc != MICLOC_OK) return rc;
+    if ((power || argmax) && bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
+    return power_tail(p, spikes, B, T, 0, y, power, argmax, ws_doubles(ws, 0), (hipStream_t)stream);
 }
 
 int micloc_beamform_c128_f64(const micloc_plan *p, const double *pre, int B, int T, int Ts, double *y, double *power,
@@ -499,17 +603,10 @@ int micloc_beamform_c128_f64(const micloc_plan *p, const double *pre, int B, int
     if (!p || !pre || bad_batch(B) || T < 1 || (!y && !power && !argmax)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
     if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int Gp = 16 * p->W.GT;
-    const bool want_power = power || argmax;
-    if (want_power && bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, Gp))) return MICLOC_ERR_WORKSPACE;
-    double *partial = want_power ? reinterpret_cast<double *>(ws) : nullptr;
-    int nch = 0;
-    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, y, 1, partial, (hipStream_t)stream, &nch));
-    if (want_power)
-        HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 1, Gp / 2, power, argmax, (hipStream_t)stream));
-    return MICLOC_OK;
+    const int rc = plan_kind(p, true);
+    if (rc != MICLOC_OK) return rc;
+    if ((power || argmax) && bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
+    return power_tail(p, pre, B, T, Ts, y, power, argmax, ws_doubles(ws, 0), (hipStream_t)stream);
 }
 
 // ---- pipelines -------------------------------------------------------------------------------------------
@@ -525,33 +622,15 @@ int micloc_snn_pipeline_stages_f64(const micloc_plan *p, const double *x, int B,
     if (!p || !x || bad_batch(B) || T < 1 || (!spikes && !y && !power && !argmax)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
     if (stages <= 0 || (stages & ~(MICLOC_STAGE_ALL | MICLOC_STAGE_ENCODE_SCAN | MICLOC_STAGE_ENCODE_REST))) return MICLOC_ERR_INVALID;
-    const bool want_bf = y || power || argmax;
-    if (want_bf && (!p->d_ntab || !p->d_W)) return MICLOC_ERR_NOT_SET;
-    if (want_bf && p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int phases = (stages & MICLOC_STAGE_ENCODE) ? RZ_PHASE_ALL
-                                                      : ((stages & MICLOC_STAGE_ENCODE_SCAN) ? RZ_PHASE_SCAN : 0) |
-                                                            ((stages & MICLOC_STAGE_ENCODE_REST) ? RZ_PHASE_ENCODE : 0);
+    const bool want_bf = y || power || argmax;  // a call for the raster alone needs no table
+    const int rc = want_bf ? plan_kind(p, false) : MICLOC_OK;
+    if (rc != MICLOC_OK) return rc;
     const WsLayout w = ws_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + w.h);
-    int8_t *spk = spikes ? spikes : reinterpret_cast<int8_t *>(base + w.spikes);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    // the in-phase channels are the rolled input frames: the band-pass kernel reads them from x directly
-    if (stages & MICLOC_STAGE_STHT) HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    if (phases)
-        HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, nullptr, spk,
-                                     base + w.scratch, st, x, p->M, p->taps.shift, p->chunk_frames, phases));
-    if (want_bf && (stages & MICLOC_STAGE_BEAMFORM)) {
-        const int Gp = 16 * p->W.GT;
-        const bool want_power = power || argmax;
-        double *partial = want_power ? reinterpret_cast<double *>(base + w.partial) : nullptr;
-        int nch = 0;
-        HIP_TRY(lif_beamform_oneshot(p->W, p->ntab, spk, B, T, y, partial, st, &nch));
-        if (want_power) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 0, 0, power, argmax, st));
-    }
-    return MICLOC_OK;
+    const Front f = front_end(p, false, x, B, T, ws, w, spikes, stages, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    if (!want_bf || !(stages & MICLOC_STAGE_BEAMFORM)) return MICLOC_OK;
+    return power_tail(p, f.src, B, T, f.Ts, y, power, argmax, ws_doubles(ws, w.partial), (hipStream_t)stream);
 }
 
 int micloc_beamformer_pipeline_f64(const micloc_plan *p, const double *x, int B, int T, double *y, double *power,
@@ -559,32 +638,20 @@ int micloc_beamformer_pipeline_f64(const micloc_plan *p, const double *x, int B,
 {
     if (!p || !x || bad_batch(B) || T < 1 || (!y && !power && !argmax)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    const int rc = plan_kind(p, true);
+    if (rc != MICLOC_OK) return rc;
     const WsLayout w = ws_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + w.h);
-    double *pre = reinterpret_cast<double *>(base + w.pre);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, pre, nullptr,
-                                 nullptr, st, x, p->M, p->taps.shift));
-    const int Gp = 16 * p->W.GT;
-    const bool want_power = power || argmax;
-    double *partial = want_power ? reinterpret_cast<double *>(base + w.partial) : nullptr;
-    int nch = 0;
-    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, y, 1, partial, st, &nch));
-    if (want_power) HIP_TRY(launch_power_argmax(partial, B, T, nch, Gp, p->G_out, 1, Gp / 2, power, argmax, st));
-    return MICLOC_OK;
+    const Front f = front_end(p, true, x, B, T, ws, w, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return power_tail(p, f.src, B, T, f.Ts, y, power, argmax, ws_doubles(ws, w.partial), (hipStream_t)stream);
 }
 
 // ---- time-resolved DoA: power and arg-max per window ------------------------------------------------------------------
 int micloc_window_quantum(const micloc_plan *p)
 {
     if (!p) return MICLOC_ERR_INVALID;
-    if (!p->d_W || (!p->W_is_complex && !p->d_ntab)) return MICLOC_ERR_NOT_SET;
+    if (plan_kind(p, p->W_is_complex) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
     const int q = window_quantum(p);
     return q > 0 ? q : MICLOC_ERR_INVALID;
 }
@@ -609,17 +676,10 @@ int micloc_lif_beamform_windows_f64(const micloc_plan *p, const int8_t *spikes, 
 {
     if (!p || !spikes || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int q = window_quantum(p);
-    int nW = 0;
-    const int rc = window_args(T, window, hop, q, B, &nW);
-    if (rc != MICLOC_OK) return rc;
+    const int q = window_check(p, false, B, T, window, hop);
+    if (q < 0) return q;
     if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
-    double *partial = reinterpret_cast<double *>(ws);
-    int nch = 0;
-    HIP_TRY(launch_lif_beamform(p->W, p->ntab, spikes, B, T, nullptr, partial, (hipStream_t)stream, &nch));
-    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, (hipStream_t)stream);
+    return window_tail(p, spikes, B, T, 0, q, window, hop, power_w, argmax_w, power, argmax, ws_doubles(ws, 0), (hipStream_t)stream);
 }
 
 int micloc_beamform_c128_windows_f64(const micloc_plan *p, const double *pre, int B, int T, int Ts, int window, int hop, double *power_w,
@@ -628,46 +688,26 @@ int micloc_beamform_c128_windows_f64(const micloc_plan *p, const double *pre, in
     if (!p || !pre || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
     if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int q = window_quantum(p);
-    int nW = 0;
-    const int rc = window_args(T, window, hop, q, B, &nW);
-    if (rc != MICLOC_OK) return rc;
+    const int q = window_check(p, true, B, T, window, hop);
+    if (q < 0) return q;
     if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, 16 * p->W.GT))) return MICLOC_ERR_WORKSPACE;
-    double *partial = reinterpret_cast<double *>(ws);
-    int nch = 0;
-    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, nullptr, 1, partial, (hipStream_t)stream, &nch));
-    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, (hipStream_t)stream);
+    return window_tail(p, pre, B, T, Ts, q, window, hop, power_w, argmax_w, power, argmax, ws_doubles(ws, 0), (hipStream_t)stream);
 }
 
+// the launches of micloc_snn_pipeline_f64 up to the raster, then both read-outs of the partial sums
 int micloc_snn_pipeline_windows_f64(const micloc_plan *p, const double *x, int B, int T, int window, int hop, int8_t *spikes,
                                     double *power_w, int32_t *argmax_w, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
                                     void *stream)
 {
     if (!p || !x || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int q = window_quantum(p);
-    int nW = 0;
-    const int rc = window_args(T, window, hop, q, B, &nW);
-    if (rc != MICLOC_OK) return rc;
+    const int q = window_check(p, false, B, T, window, hop);
+    if (q < 0) return q;
     const WsLayout w = ws_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + w.h);
-    int8_t *spk = spikes ? spikes : reinterpret_cast<int8_t *>(base + w.spikes);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    // the launches of micloc_snn_pipeline_f64, then both read-outs of its partial sums
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, nullptr, spk, base + w.scratch, st, x,
-                                 p->M, p->taps.shift, p->chunk_frames, RZ_PHASE_ALL));
-    double *partial = reinterpret_cast<double *>(base + w.partial);
-    int nch = 0;
-    HIP_TRY(launch_lif_beamform(p->W, p->ntab, spk, B, T, nullptr, partial, st, &nch));
-    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, st);
+    const Front f = front_end(p, false, x, B, T, ws, w, spikes, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return window_tail(p, f.src, B, T, f.Ts, q, window, hop, power_w, argmax_w, power, argmax, ws_doubles(ws, w.partial), (hipStream_t)stream);
 }
 
 int micloc_beamformer_pipeline_windows_f64(const micloc_plan *p, const double *x, int B, int T, int window, int hop, double *power_w,
@@ -675,26 +715,13 @@ int micloc_beamformer_pipeline_windows_f64(const micloc_plan *p, const double *x
 {
     if (!p || !x || bad_batch(B) || T < 1 || (!power_w && !argmax_w)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
-    const int q = window_quantum(p);
-    int nW = 0;
-    const int rc = window_args(T, window, hop, q, B, &nW);
-    if (rc != MICLOC_OK) return rc;
+    const int q = window_check(p, true, B, T, window, hop);
+    if (q < 0) return q;
     const WsLayout w = ws_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + w.h);
-    double *pre = reinterpret_cast<double *>(base + w.pre);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, pre, nullptr, nullptr, st, x, p->M,
-                                 p->taps.shift));
-    double *partial = reinterpret_cast<double *>(base + w.partial);
-    int nch = 0;
-    HIP_TRY(launch_planar_beamform(p->W, pre, B, T, Ts, nullptr, 1, partial, st, &nch));
-    return window_readout(p, partial, B, T, nch, q, window, hop, power_w, argmax_w, power, argmax, st);
+    const Front f = front_end(p, true, x, B, T, ws, w, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return window_tail(p, f.src, B, T, f.Ts, q, window, hop, power_w, argmax_w, power, argmax, ws_doubles(ws, w.partial), (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -913,8 +940,7 @@ namespace {
 // encoder scratch and the raster (real bf_mat) or the band-passed rows (complex); not the pipeline's per-chunk sums, not the
 // planar array the plan's kind never writes.  Tracking region of fused plans: the (value, index) pairs.  Other plans (the two-step
 // route): y and its envelope for as many trials at a time as the caller's buffer holds, one at least.
-struct TrackLayout {
-    size_t h, pre, scratch, spikes;
+struct TrackLayout : FrontOffsets {
     size_t base, per_trial, min_total;  // per_trial == 0: fused
 };
 
@@ -945,19 +971,20 @@ TrackLayout track_layout(const micloc_plan *p, int B, int T)
     return t;
 }
 
-int track_args(const micloc_plan *p, int B, int T, const int32_t *index)
+// the argument checks of a tracking entry; in: its input array
+int track_args(const micloc_plan *p, const void *in, int B, int T, const int32_t *index)
 {
     if (!p || !index || bad_batch(B)) return MICLOC_ERR_INVALID;
     if (T < 1 || (long long)B * T > 0x7fffffffll) return MICLOC_ERR_SHAPE;
-    return MICLOC_OK;
+    return in ? MICLOC_OK : MICLOC_ERR_INVALID;
 }
 
 // src: the spike raster (real bf_mat) or the planar band-passed rows [B][C][Ts] (complex)
 int track_run(const micloc_plan *p, const void *src, int B, int T, int Ts, double a_rise, double i_rise, double a_fall, int32_t *index,
-              double *peak_env, double *env_last, unsigned char *ws, size_t ws_bytes, const TrackLayout &lay, hipStream_t st)
+              double *peak_env, double *env_last, void *ws, size_t ws_bytes, const TrackLayout &lay, hipStream_t st)
 {
     const int G = p->G_out, cpx = p->W_is_complex;
-    unsigned char *reg = ws + lay.base;
+    unsigned char *reg = static_cast<unsigned char *>(ws) + lay.base;
     if (lay.per_trial == 0) {
         HIP_TRY(launch_track_fused(p->W, p->ntab, cpx, src, B, T, Ts, G, a_rise, i_rise, a_fall, index, peak_env, env_last, reg, st));
         return MICLOC_OK;
@@ -988,91 +1015,73 @@ extern "C" {
 
 size_t micloc_track_workspace_bytes(const micloc_plan *p, int B, int T)
 {
-    if (!p || bad_batch(B) || T < 1 || (long long)B * T > 0x7fffffffll || !p->d_W || (!p->W_is_complex && !p->d_ntab)) return 0;
+    if (!p || bad_batch(B) || T < 1 || (long long)B * T > 0x7fffffffll || plan_kind(p, p->W_is_complex) != MICLOC_OK) return 0;
     return track_layout(p, B, T).min_total;
 }
 
 int micloc_track_is_fused(const micloc_plan *p)
 {
     if (!p) return MICLOC_ERR_INVALID;
-    if (!p->d_W || (!p->W_is_complex && !p->d_ntab)) return MICLOC_ERR_NOT_SET;
+    if (plan_kind(p, p->W_is_complex) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
     return track_fused_eligible(p->W, p->ntab, p->W_is_complex) ? 1 : 0;
 }
 
 int micloc_lif_beamform_track_f64(const micloc_plan *p, const int8_t *spikes, int B, int T, double a_rise, double i_rise, double a_fall,
                                   int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    const int rc = track_args(p, B, T, index);
+    int rc = track_args(p, spikes, B, T, index);
     if (rc != MICLOC_OK) return rc;
-    if (!spikes) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
+    rc = plan_kind(p, false);
+    if (rc != MICLOC_OK) return rc;
     const TrackLayout lay = track_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    return track_run(p, spikes, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, reinterpret_cast<unsigned char *>(ws), ws_bytes, lay,
-                     (hipStream_t)stream);
+    return track_run(p, spikes, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
 }
 
 int micloc_beamform_c128_track_f64(const micloc_plan *p, const double *pre, int B, int T, int Ts, double a_rise, double i_rise, double a_fall,
                                    int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    const int rc = track_args(p, B, T, index);
+    int rc = track_args(p, pre, B, T, index);
     if (rc != MICLOC_OK) return rc;
-    if (!pre) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
     if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    rc = plan_kind(p, true);
+    if (rc != MICLOC_OK) return rc;
     const TrackLayout lay = track_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    return track_run(p, pre, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, reinterpret_cast<unsigned char *>(ws), ws_bytes, lay,
-                     (hipStream_t)stream);
+    return track_run(p, pre, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
 }
 
+// the first two launches of micloc_snn_pipeline_f64, then the tracking read-out of their raster
 int micloc_snn_pipeline_track_f64(const micloc_plan *p, const double *x, int B, int T, double a_rise, double i_rise, double a_fall,
                                   int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    const int rc = track_args(p, B, T, index);
+    int rc = track_args(p, x, B, T, index);
     if (rc != MICLOC_OK) return rc;
-    if (!x) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex) return MICLOC_ERR_SHAPE;
+    rc = plan_kind(p, false);
+    if (rc != MICLOC_OK) return rc;
     const TrackLayout lay = track_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + lay.h);
-    int8_t *spk = reinterpret_cast<int8_t *>(base + lay.spikes);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    // the first two launches of micloc_snn_pipeline_f64, then the tracking read-out of their raster
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, nullptr, spk, base + lay.scratch, st, x,
-                                 p->M, p->taps.shift, p->chunk_frames, RZ_PHASE_ALL));
-    return track_run(p, spk, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, base, ws_bytes, lay, st);
+    const Front f = front_end(p, false, x, B, T, ws, lay, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return track_run(p, f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
 }
 
 int micloc_beamformer_pipeline_track_f64(const micloc_plan *p, const double *x, int B, int T, double a_rise, double i_rise, double a_fall,
                                          int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    const int rc = track_args(p, B, T, index);
+    int rc = track_args(p, x, B, T, index);
     if (rc != MICLOC_OK) return rc;
-    if (!x) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
-    if (!p->d_W) return MICLOC_ERR_NOT_SET;
-    if (!p->W_is_complex) return MICLOC_ERR_SHAPE;
+    rc = plan_kind(p, true);
+    if (rc != MICLOC_OK) return rc;
     const TrackLayout lay = track_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + lay.h);
-    double *pre = reinterpret_cast<double *>(base + lay.pre);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, pre, nullptr, nullptr, st, x, p->M,
-                                 p->taps.shift));
-    return track_run(p, pre, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, base, ws_bytes, lay, st);
+    const Front f = front_end(p, true, x, B, T, ws, lay, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return track_run(p, f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
 }
 
 // ---- streaming: the band-pass / RZCC stage tile by tile, exact state hand-off -----------------------------------
@@ -1528,8 +1537,9 @@ int micloc_lif_beamform_f32(const micloc_plan *p, const int8_t *spikes, int B, i
 {
     if (!p || !spikes || bad_batch(B) || T < 1 || (!power && !argmax)) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
-    if (!p->d_ntab || !p->d_W) return MICLOC_ERR_NOT_SET;
-    if (p->W_is_complex || p->W.CT > 4) return MICLOC_ERR_SHAPE;
+    const int rc = plan_kind(p, false);
+    if (rc != MICLOC_OK) return rc;
+    if (p->W.CT > 4) return MICLOC_ERR_SHAPE;
     const int Gp = 16 * p->W.GT;
     if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, T, Gp))) return MICLOC_ERR_WORKSPACE;
     double *partial = reinterpret_cast<double *>(ws);
@@ -1546,18 +1556,10 @@ int micloc_lif_covariance_f64(const micloc_plan *p, const int8_t *spikes, int B,
     if (!p || !spikes || bad_batch(B) || T < 1 || t_start < 0 || t_start >= T || (!cov && !power && !argmax))
         return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
-    if (!p->d_ntab) return MICLOC_ERR_NOT_SET;
-    const bool want_power = power || argmax;
-    if (want_power && (!p->d_W || p->W_is_complex)) return p->d_W ? MICLOC_ERR_SHAPE : MICLOC_ERR_NOT_SET;
-    const int CT = pad_ct(p->C);
-    if (CT > 8) return MICLOC_ERR_SHAPE;
-    if (bad_ws(ws, ws_bytes, cov_partial_bytes(B, T, CT))) return MICLOC_ERR_WORKSPACE;
-    double *partial = reinterpret_cast<double *>(ws);
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(launch_lif_cov(p->ntab, spikes, B, T, p->C, CT, t_start, partial, st));
-    HIP_TRY(launch_cov_power(partial, B, T, CT, p->C, T - t_start, want_power ? p->W.Wp : nullptr,
-                             want_power ? 16 * p->W.GT : 16, want_power ? p->G_out : 0, cov, power, argmax, st));
-    return MICLOC_OK;
+    const int rc = cov_check(p, power || argmax);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(ws, ws_bytes, cov_partial_bytes(B, T, pad_ct(p->C)))) return MICLOC_ERR_WORKSPACE;
+    return cov_tail(p, spikes, B, T, t_start, cov, power, argmax, ws_doubles(ws, 0), (hipStream_t)stream);
 }
 
 int micloc_snn_pipeline_cov_f64(const micloc_plan *p, const double *x, int B, int T, int t_start, int8_t *spikes,
@@ -1566,27 +1568,13 @@ int micloc_snn_pipeline_cov_f64(const micloc_plan *p, const double *x, int B, in
     if (!p || !x || bad_batch(B) || T < 1 || t_start < 0 || t_start >= T || (!cov && !power && !argmax))
         return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);  // launches and stream belong to the plan's device, whatever the caller's current one
-    if (!p->d_ntab) return MICLOC_ERR_NOT_SET;
-    const bool want_power = power || argmax;
-    if (want_power && (!p->d_W || p->W_is_complex)) return p->d_W ? MICLOC_ERR_SHAPE : MICLOC_ERR_NOT_SET;
-    const int CT = pad_ct(p->C);
-    if (CT > 8) return MICLOC_ERR_SHAPE;
+    const int rc = cov_check(p, power || argmax);
+    if (rc != MICLOC_OK) return rc;
     const WsLayout w = ws_layout(p, B, T);
     if (bad_ws(ws, ws_bytes, w.total)) return MICLOC_ERR_WORKSPACE;
-    unsigned char *base = reinterpret_cast<unsigned char *>(ws);
-    double *h = reinterpret_cast<double *>(base + w.h);
-    int8_t *spk = spikes ? spikes : reinterpret_cast<int8_t *>(base + w.spikes);
-    const int Ts = micloc_padded_T(T);
-    hipStream_t st = (hipStream_t)stream;
-    // the in-phase channels are the rolled input frames: the band-pass kernel reads them from x directly
-    HIP_TRY(launch_stht(p->taps, x, h, B, T, p->M, Ts, st, false));
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, Ts, p->robust_width, p->bipolar, nullptr, spk,
-                                 base + w.scratch, st, x, p->M, p->taps.shift, p->chunk_frames));
-    double *partial = reinterpret_cast<double *>(base + w.partial);
-    HIP_TRY(launch_lif_cov(p->ntab, spk, B, T, p->C, CT, t_start, partial, st));
-    HIP_TRY(launch_cov_power(partial, B, T, CT, p->C, T - t_start, want_power ? p->W.Wp : nullptr,
-                             want_power ? 16 * p->W.GT : 16, want_power ? p->G_out : 0, cov, power, argmax, st));
-    return MICLOC_OK;
+    const Front f = front_end(p, false, x, B, T, ws, w, spikes, MICLOC_STAGE_ALL, (hipStream_t)stream);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return cov_tail(p, static_cast<const int8_t *>(f.src), B, T, t_start, cov, power, argmax, ws_doubles(ws, w.partial), (hipStream_t)stream);
 }
 
 // ---- Gram matrix of a planar signal (complex covariance of Beamformer.design_from_template) ------------------------------

@@ -202,7 +202,23 @@ class Plan:
             raise ValueError("out holds window tensors of another shape")
         return window, hop
 
+    def _windowed(self, fn, what, src, B, T, window, hop, out, ws, nbytes, Ts=(), spikes=()):
+        """The windowed form of a read-out into `out`: fn(plan, src, B, T, [Ts], window, hop, [spikes], window tensors, power, argmax, workspace, stream)."""
+        if out["y"] is not None:
+            raise ValueError("the windowed read-out has no T x G output (want_y=False)")
+        window, hop = self._window_out(B, T, window, hop, out)
+        _lib.check(fn(self.handle, _ptr(src), B, T, *Ts, window, hop, *spikes, _ptr(out["window_power"]), _ptr(out["window_argmax"]), _ptr(out["power"]),
+                      _ptr(out["argmax"]), _ptr(ws), nbytes, _stream(self.device)), what)
+        return out
+
     # ---- helpers -----------------------------------------------------------------------------------
+    def _beamform_out(self, B, T, want_y, want_power, y_dtype="float64"):
+        """The result tensors of a beamforming read-out, None where not wanted: y [B, T, G], power [B, G], argmax [B]."""
+        torch = _torch()
+        return dict(y=torch.empty((B, T, self.G), dtype=getattr(torch, y_dtype), device=self.device) if want_y else None,
+                    power=torch.empty((B, self.G), dtype=torch.float64, device=self.device) if want_power else None,
+                    argmax=torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None)
+
     def to_device(self, x):
         """numpy / torch [B, T, M] float64 -> contiguous device tensor."""
         torch = _torch()
@@ -226,24 +242,15 @@ class Plan:
         B, T, M = x.shape
         if M != self.num_mic:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
-        G = self.G
         if out is None:
             out = dict(spikes=torch.empty((B, T, self.C), dtype=torch.int8, device=self.device) if want_spikes else None,
-                       y=torch.empty((B, T, G), dtype=torch.float64, device=self.device) if want_y else None,
-                       power=torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None,
-                       argmax=torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None)
+                       **self._beamform_out(B, T, want_y, want_power))
         ws, nbytes = self.workspace(B, T)
         if window is not None:
             if out["y"] is not None or int(stages) != 7:
                 raise ValueError("the windowed read-out runs the whole pipeline and has no T x G output (want_y=False, stages=7)")
-            window, hop = self._window_out(B, T, window, hop, out)
-            _lib.check(
-                self.lib.micloc_snn_pipeline_windows_f64(self.handle, _ptr(x), B, T, window, hop, _ptr(out["spikes"]), _ptr(out["window_power"]),
-                                                          _ptr(out["window_argmax"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws), nbytes,
-                                                          _stream(self.device)),
-                "snn_pipeline_windows",
-            )
-            return out
+            return self._windowed(self.lib.micloc_snn_pipeline_windows_f64, "snn_pipeline_windows", x, B, T, window, hop, out, ws, nbytes,
+                                  spikes=(_ptr(out["spikes"]),))
         _lib.check(
             self.lib.micloc_snn_pipeline_stages_f64(self.handle, _ptr(x), B, T, _ptr(out["spikes"]), _ptr(out["y"]), _ptr(out["power"]),
                                                      _ptr(out["argmax"]), _ptr(ws), nbytes, _stream(self.device), int(stages)),
@@ -298,55 +305,31 @@ class Plan:
 
     def beamformer_pipeline(self, x, want_y=False, want_power=True, window=None, hop=None):
         """The complex Beamformer's pipeline; `window` / `hop` as in snn_pipeline (power per window = mean |y|^2 over its frames)."""
-        torch = _torch()
         B, T, M = x.shape
         if M != self.num_mic:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
-        G = self.G
-        y = torch.empty((B, T, G), dtype=torch.complex128, device=self.device) if want_y else None
-        power = torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None
-        argmax = torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None
+        out = self._beamform_out(B, T, want_y, want_power, "complex128")
         ws, nbytes = self.workspace(B, T)
         if window is not None:
-            if want_y:
-                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
-            out = dict(y=None, power=power, argmax=argmax)
-            window, hop = self._window_out(B, T, window, hop, out)
-            _lib.check(
-                self.lib.micloc_beamformer_pipeline_windows_f64(self.handle, _ptr(x), B, T, window, hop, _ptr(out["window_power"]),
-                                                                 _ptr(out["window_argmax"]), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
-                                                                 _stream(self.device)),
-                "beamformer_pipeline_windows",
-            )
-            return out
+            return self._windowed(self.lib.micloc_beamformer_pipeline_windows_f64, "beamformer_pipeline_windows", x, B, T, window, hop, out, ws, nbytes)
         _lib.check(
-            self.lib.micloc_beamformer_pipeline_f64(self.handle, _ptr(x), B, T, _ptr(y), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
+            self.lib.micloc_beamformer_pipeline_f64(self.handle, _ptr(x), B, T, _ptr(out["y"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws), nbytes,
                                                      _stream(self.device)),
             "beamformer_pipeline",
         )
-        return dict(y=y, power=power, argmax=argmax)
+        return out
 
     def beamform_c128(self, pre, T, want_y=False, want_power=True, out=None, window=None, hop=None):
         """The contraction stage of the complex Beamformer alone (micloc_beamform_c128_f64): planar band-passed rows
         pre [B, 2M, Ts] -> y [B, T, G] complex128 and / or power [B, G], argmax [B].  `out` reuses a previous result dict.
         `window` / `hop`: also window_power / window_argmax (micloc_beamform_c128_windows_f64; no y)."""
-        torch = _torch()
         B, C, Ts = pre.shape
-        G = self.G
         if out is None:
-            out = dict(y=torch.empty((B, T, G), dtype=torch.complex128, device=self.device) if want_y else None,
-                       power=torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None,
-                       argmax=torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None)
+            out = self._beamform_out(B, T, want_y, want_power, "complex128")
         nbytes = self.lib.micloc_lif_beamform_workspace_bytes(self.handle, B, T)
         ws = self.ws.get(nbytes)
         if window is not None:
-            if out["y"] is not None:
-                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
-            window, hop = self._window_out(B, T, window, hop, out)
-            _lib.check(self.lib.micloc_beamform_c128_windows_f64(self.handle, _ptr(pre), B, T, Ts, window, hop, _ptr(out["window_power"]),
-                                                                 _ptr(out["window_argmax"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws),
-                                                                 nbytes, _stream(self.device)), "beamform_c128_windows")
-            return out
+            return self._windowed(self.lib.micloc_beamform_c128_windows_f64, "beamform_c128_windows", pre, B, T, window, hop, out, ws, nbytes, Ts=(Ts,))
         _lib.check(self.lib.micloc_beamform_c128_f64(self.handle, _ptr(pre), B, T, Ts, _ptr(out["y"]), _ptr(out["power"]), _ptr(out["argmax"]),
                                                      _ptr(ws), nbytes, _stream(self.device)), "beamform_c128")
         return out
@@ -424,25 +407,14 @@ class Plan:
         return pre, spikes
 
     def lif_beamform(self, spikes, want_y=False, want_power=True, window=None, hop=None):
-        torch = _torch()
         B, T, C = spikes.shape
-        G = self.G
-        y = torch.empty((B, T, G), dtype=torch.float64, device=self.device) if want_y else None
-        power = torch.empty((B, G), dtype=torch.float64, device=self.device) if want_power else None
-        argmax = torch.empty((B,), dtype=torch.int32, device=self.device) if want_power else None
+        out = self._beamform_out(B, T, want_y, want_power)
         ws, nbytes = self.workspace(B, T)
         if window is not None:
-            if want_y:
-                raise ValueError("the windowed read-out has no T x G output (want_y=False)")
-            out = dict(y=None, power=power, argmax=argmax)
-            window, hop = self._window_out(B, T, window, hop, out)
-            _lib.check(self.lib.micloc_lif_beamform_windows_f64(self.handle, _ptr(spikes), B, T, window, hop, _ptr(out["window_power"]),
-                                                                _ptr(out["window_argmax"]), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
-                                                                _stream(self.device)), "lif_beamform_windows")
-            return out
-        _lib.check(self.lib.micloc_lif_beamform_f64(self.handle, _ptr(spikes), B, T, _ptr(y), _ptr(power), _ptr(argmax), _ptr(ws), nbytes,
-                                                    _stream(self.device)), "lif_beamform")
-        return dict(y=y, power=power, argmax=argmax)
+            return self._windowed(self.lib.micloc_lif_beamform_windows_f64, "lif_beamform_windows", spikes, B, T, window, hop, out, ws, nbytes)
+        _lib.check(self.lib.micloc_lif_beamform_f64(self.handle, _ptr(spikes), B, T, _ptr(out["y"]), _ptr(out["power"]), _ptr(out["argmax"]), _ptr(ws),
+                                                    nbytes, _stream(self.device)), "lif_beamform")
+        return out
 
 
 # ---- plan-less operators -------------------------------------------------------------------------------
