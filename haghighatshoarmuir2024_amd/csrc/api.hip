@@ -195,6 +195,20 @@ int window_readout(const micloc_plan *p, const double *partial, int B, int T, in
     return MICLOC_OK;
 }
 
+// The spikes-only encoder launch: the three-slot form of rzcc_sweep.hip where the launch has its shape, rzcc.hip's kernels otherwise
+// (same spikes, same scratch either way).
+static hipError_t bandpass_rzcc_spikes(const IirCoef &coef, const double *h, int nlanes, int C, int T, int Ts, int robust_width, int bipolar,
+                                       int8_t *spikes, void *scratch, hipStream_t stream, const double *xin, int M, int shift,
+                                       int chunk_frames, int phases)
+{
+    hipError_t e = hipSuccess;
+    if (launch_bandpass_rzcc_sweep(coef, h, nlanes, C, T, Ts, robust_width, bipolar, spikes, scratch, stream, xin, M, shift, chunk_frames,
+                                   phases, &e))
+        return e;
+    return launch_bandpass_rzcc(coef, h, nlanes, C, T, Ts, robust_width, bipolar, nullptr, spikes, scratch, stream, xin, M, shift,
+                                chunk_frames, phases);
+}
+
 // The one-shot power launch: the fixed-shape kernel of beamform_lean.hip where the plan and the call have its shape, the general kernels
 // otherwise (same bits in `partial` either way).  Windows, streaming, tracking and y stay with launch_lif_beamform.
 hipError_t lif_beamform_oneshot(const BeamformW &W, const NeuronTab &nt, const int8_t *spikes, int B, int T, double *y, double *partial,
@@ -259,7 +273,7 @@ Front front_end(const micloc_plan *p, bool cpx, const double *x, int B, int T, v
                                                           : ((stages & MICLOC_STAGE_ENCODE_SCAN) ? RZ_PHASE_SCAN : 0) |
                                                                 ((stages & MICLOC_STAGE_ENCODE_REST) ? RZ_PHASE_ENCODE : 0);
         if (e == hipSuccess && phases)
-            e = launch_bandpass_rzcc(p->iir, h, B * p->C, p->C, T, f.Ts, p->robust_width, p->bipolar, nullptr, spk,
+            e = bandpass_rzcc_spikes(p->iir, h, B * p->C, p->C, T, f.Ts, p->robust_width, p->bipolar, spk,
                                      static_cast<char *>(ws) + o.scratch, st, x, p->M, p->taps.shift, p->chunk_frames, phases);
     }
     if (e != hipSuccess) f.rc = hip_failed(e);
@@ -581,8 +595,12 @@ int micloc_bandpass_rzcc_f64(const micloc_plan *p, const double *h, int B, int T
     if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
     const int nl = B * p->C;
     if (spikes && bad_ws(ws, ws_bytes, rzcc_scratch_bytes(nl, T, p->robust_width, p->chunk_frames))) return MICLOC_ERR_WORKSPACE;
-    HIP_TRY(launch_bandpass_rzcc(p->iir, h, nl, p->C, T, Ts, p->robust_width, p->bipolar, pre, spikes, ws,
-                                 (hipStream_t)stream, nullptr, 0, 0, p->chunk_frames));
+    if (spikes && !pre)
+        HIP_TRY(bandpass_rzcc_spikes(p->iir, h, nl, p->C, T, Ts, p->robust_width, p->bipolar, spikes, ws, (hipStream_t)stream, nullptr, 0, 0,
+                                     p->chunk_frames, RZ_PHASE_ALL));
+    else
+        HIP_TRY(launch_bandpass_rzcc(p->iir, h, nl, p->C, T, Ts, p->robust_width, p->bipolar, pre, spikes, ws,
+                                     (hipStream_t)stream, nullptr, 0, 0, p->chunk_frames));
     return MICLOC_OK;
 }
 

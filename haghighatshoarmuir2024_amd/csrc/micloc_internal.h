@@ -17,6 +17,7 @@ constexpr bool VARIANT_STHT_VECTOR_FORM = false;  // stht_valu: stride-2 STHT ke
 constexpr bool VARIANT_STHT_WIDE_TWO_TILES = false;  // stht_wide2: the 480-tap walking STHT (96 kHz) with two time tiles per wave and ONE workgroup per CU (98 KB) instead of one tile / two workgroups
 constexpr bool VARIANT_STHT_ONE_TILE = false;     // stht_one_tile: the matrix-core STHT with one time tile per workgroup (round 3's form) instead of the walk
 constexpr bool VARIANT_WS_GENERAL_ONLY = false;  // set in EVERY variant of the `beamform` unit (ws_k4, ws_sparse_lif): beamform_lean.hip's fixed-shape kernel declines, so the variant's beamform_ws_kernel serves the sweep's shape too
+constexpr bool VARIANT_RZ_TWO_SLOTS = false;  // rz_two_slots: rzcc_sweep.hip's three-slot encoder declines, so the sweep's encoder launch is rzcc.hip's 64-entry ring form (two workgroups per CU)
 
 // ---- XCD-aware workgroup order (speed only, never correctness) -------------------------------------------------------
 // Workgroup L of a launch runs on XCD L % 8, and every XCD has its own L2.  Kernels whose NEIGHBOURING work items read the same
@@ -66,6 +67,12 @@ hipError_t launch_bandpass_rzcc(const IirCoef &coef, const double *h, int nlanes
                                 int robust_width, int bipolar, double *pre, int8_t *spikes, void *scratch,
                                 hipStream_t stream, const double *xin = nullptr, int M = 0, int shift = 0,
                                 int chunk_frames = 0, int phases = RZ_PHASE_ALL);
+// rzcc_sweep.hip, the three-workgroups-per-CU form of the sweep's launch (spikes only, one chunk, five filter coefficients): true = this
+// launch was its to serve (*err: the status; same spikes, same scratch layout), false = nothing was enqueued and the caller launches
+// launch_bandpass_rzcc
+bool launch_bandpass_rzcc_sweep(const IirCoef &coef, const double *h, int nlanes, int C, int T, int Ts, int robust_width, int bipolar,
+                                int8_t *spikes, void *scratch, hipStream_t stream, const double *xin, int M, int shift, int chunk_frames,
+                                int phases, hipError_t *err);
 // streaming: one tile per launch, exact state hand-off (rzcc.hip "streaming")
 size_t rzcc_stream_state_bytes(int nlanes);
 hipError_t launch_stream_encode(const IirCoef &coef, const double *h, int nlanes, int C, int T, int Ts, int robust_width,

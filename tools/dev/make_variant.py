@@ -5,6 +5,7 @@
     python tools/dev/make_variant.py ws_k4          beamform_ws_kernel with four k-steps whatever the channel count (VARIANT_WS_FOUR_KSTEPS)
     python tools/dev/make_variant.py stht_one_tile  the matrix-core STHT with one time tile per workgroup instead of the walk (VARIANT_STHT_ONE_TILE)
     python tools/dev/make_variant.py stht_wide2     the 480-tap walking STHT with two time tiles per wave, one workgroup per CU (VARIANT_STHT_WIDE_TWO_TILES)
+    python tools/dev/make_variant.py rz_two_slots   the sweep's encoder launch by rzcc.hip's 64-entry ring form, two workgroups per CU (VARIANT_RZ_TWO_SLOTS: rzcc_sweep.hip declines)
     python tools/dev/make_variant.py ws_sparse_lif  beamform_ws_kernel's LIF stage event by event on the vector ALU instead of the dense Toeplitz product
                                                     (round 5's rejected experiment: NOT in the product sources -- tools/experiments/ws_sparse_lif/ws_sparse_lif.patch
                                                     is applied to a copy of csrc/beamform.hip)
@@ -24,6 +25,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CS = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
 VARIANTS = {"stht_wide2": ("VARIANT_STHT_WIDE_TWO_TILES", "stht"), "stht_valu": ("VARIANT_STHT_VECTOR_FORM", "stht"), "ws_k4": ("VARIANT_WS_FOUR_KSTEPS", "beamform"), "stht_one_tile": ("VARIANT_STHT_ONE_TILE", "stht"),
+            "rz_two_slots": ("VARIANT_RZ_TWO_SLOTS", "rzcc_sweep"),
             "ws_sparse_lif": (os.path.join(ROOT, "tools", "experiments", "ws_sparse_lif", "ws_sparse_lif.patch"), "beamform")}
 # further units of a variant: recompiled against the variant's header with the listed constant set as well
 COMPANIONS = {"beamform": (("beamform_lean", "VARIANT_WS_GENERAL_ONLY"),)}
