@@ -284,6 +284,13 @@ hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, i
 // band_power [F][R][G] -> power [R][G] (ascending band order, from p_0), argmax [R] (first maximum; either may be NULL)
 hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, double *power, int32_t *argmax, hipStream_t stream);
 
+// ---- wideband, complex Beamformer: the band-pass of all bands' analytic signals in one launch (bands_complex.hip) ---------------------
+// xf [F][B][T][M] (in-phase rows, through the roll by `shift`) and h [F B][2M][Ts] (quadrature rows c >= M) -> pre [F B][2M][Ts]; band f
+// filters with row f of `co` (the plans' band-pass coefficients, divided by a[0]); the bits of launch_bandpass_rzcc's `pre` band by band
+hipError_t launch_bands_bandpass(const FilterbankCoef &co, const double *xf, const double *h, int F, int B, int T, int M, int Ts, int shift,
+                                 double *pre, hipStream_t stream);
+int bands_bandpass_chains(int nl);  // chains per workgroup the launcher takes for nl chains
+
 // ---- wideband streaming: the resumable filterbank (filterbank.hip) and the band sum of a stream (stream_bands.hip) ----------------
 // fb_state: [B][n - 1][F][M] doubles (at least 256 B), zero-filled once; one tile x [B][T][M] -> xf [F][B][T][M]
 size_t filterbank_stream_state_bytes(int F, int n, int B, int M);

@@ -576,6 +576,87 @@ def snn_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power
     return out
 
 
+def _band_handles(plans):
+    """The checks every band entry shares -> (F, the C array of plan handles)."""
+    F = len(plans)
+    if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+        raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+    p0 = plans[0]
+    if any(p.num_mic != p0.num_mic for p in plans):
+        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
+    return F, (ctypes.c_void_p * F)(*[p.handle.value for p in plans])
+
+
+def beamformer_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
+    """micloc_beamformer_pipeline_bands_f64: the filterbank `ba_list`, then the complex Beamformer chains of ALL bands as one batch (one
+    STHT launch, one band-pass launch, plans[f]'s complex bf_mat per band, one time reduction), the band sum -- x [B, T, M] on the plans'
+    device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults to it), dict(window_power [B, nW, G],
+    window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G], band by band the bits of
+    plans[f].beamformer_pipeline on that band's filterbank output.  `ws`: a runtime.Workspace to take the scratch from (default: the
+    first plan's)."""
+    torch = _torch()
+    lib = _lib.load()
+    F, handles = _band_handles(plans)
+    if len(ba_list) != F:
+        raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
+    bb, aa, n = pad_ba_list(ba_list)
+    p0 = plans[0]
+    if any(p.G != p0.G for p in plans):
+        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
+    B, T, M = x.shape
+    if M != p0.num_mic:
+        raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {p0.num_mic}!")
+    G, dev = p0.G, p0.device
+    if window is None:
+        nW, win, hp = None, 0, 0
+    else:
+        nW, win, hp = p0.window_count(T, window, hop)
+        for p in plans[1:]:
+            p.window_count(T, window, hop)  # ValueError naming that band's quantum
+        if F * B * nW > 0x7FFFFFFF:
+            raise ValueError(f"{F} bands x {B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
+    rows = (B,) if nW is None else (B, nW)
+    power = torch.empty(rows + (G,), dtype=torch.float64, device=dev)
+    argmax = torch.empty(rows, dtype=torch.int32, device=dev)
+    bp = torch.empty((F,) + rows + (G,), dtype=torch.float64, device=dev) if want_band_power else None
+    nbytes = lib.micloc_beamformer_bands_workspace_bytes(handles, F, B, T, win, hp)
+    if nbytes == 0:
+        raise ValueError("micloc beamformer_bands_workspace_bytes: the plans, the batch or the windows do not fit the band pipeline's rule")
+    buf = (ws or p0.ws).get(nbytes)
+    _lib.check(lib.micloc_beamformer_pipeline_bands_f64(handles, F, _dptr(bb), _dptr(aa), n, _ptr(x), B, T, win, hp, _ptr(bp), _ptr(power),
+                                                        _ptr(argmax), _ptr(buf), nbytes, _stream(dev)), "beamformer_pipeline_bands")
+    out = dict(power=power, argmax=argmax) if nW is None else dict(window_power=power, window_argmax=argmax)
+    if want_band_power:
+        out["band_power"] = bp
+    return out
+
+
+def beamformer_bands_bandpass(plans, xf, one_launch=True, pre=None, h=None):
+    """Stages (2) and (3) of the complex band pipeline alone (micloc_beamformer_bands_bandpass_f64): xf [F, B, T, M] on the plans' device
+    -> (h, pre), planar [F * B, 2M, Ts] each; the in-phase rows of h are not written.  one_launch=False takes the one-shot band-pass
+    launch per band instead of bands_bandpass_kernel.  `pre`: a contiguous float64 device tensor of that shape to write into.  `h`: the
+    STHT rows of an earlier call, in which case the STHT launch is skipped."""
+    torch = _torch()
+    lib = _lib.load()
+    F, handles = _band_handles(plans)
+    p0 = plans[0]
+    if xf.dim() != 4 or xf.shape[0] != F or xf.shape[3] != p0.num_mic or xf.dtype != torch.float64 or not xf.is_contiguous():
+        raise ValueError(f"xf must be a contiguous float64 device tensor [{F}, B, T, {p0.num_mic}]")
+    _, B, T, M = xf.shape
+    Ts = p0.padded_T(T)
+    with_stht = h is None
+    if with_stht:
+        h = torch.empty((F * B, 2 * M, Ts), dtype=torch.float64, device=p0.device)
+    if pre is None:
+        pre = torch.empty_like(h)
+    for t in (h, pre):
+        if tuple(t.shape) != (F * B, 2 * M, Ts) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != xf.device:
+            raise ValueError("h and pre must be contiguous float64 device tensors [F * B, 2M, Ts]")
+    _lib.check(lib.micloc_beamformer_bands_bandpass_f64(handles, F, _ptr(xf), B, T, _ptr(h), _ptr(pre), Ts, 1 if with_stht else 0,
+                                                        1 if one_launch else 0, _stream(p0.device)), "beamformer_bands_bandpass")
+    return h, pre
+
+
 def synth_delay(time_in, sig_in, delays, fs, device=None):
     """Device synthesis of noise-free array signals: time_in/sig_in numpy [T] (already on the fs grid), delays numpy
     [B, M] (min-shifted) -> device tensor [B, T, M], bit-exact with np.interp (see csrc/synth.hip)."""

@@ -545,7 +545,8 @@ def speech_target_sweep(beamf, bf_mat, doa_list, source, snr_db_vec=None, num_si
 
 def wideband_localizer(loc, max_batch=25):
     """Localizer of the wideband sweeps: wideband.WidebandSNNLocalizer.localize_batch (filterbank, one SNN chain per band, band sum
-    and arg-max on the device) in device batches of at most `max_batch` trials.  The neuron kernels are built on the live demo's own
+    and arg-max on the device) -- or WidebandBeamformerLocalizer's, the complex chains of all bands as one batch -- in device batches of
+    at most `max_batch` trials.  The neuron kernels are built on the live demo's own
     time axis, np.arange(T) / fs (micloc/localization_demo_snn.py:149; Demo.power_grid), not on the sweep's: the results are those of
     Demo.power_grid trial by trial, bit for bit."""
 
@@ -570,7 +571,8 @@ def _wideband_store_key(loc):
         for k, v in _method_key(beamf).items():
             if k != "method":
                 key[f"band{f}_{k}"] = v
-        key[f"band{f}_bf_mat_sha256"] = hashlib.sha256(np.ascontiguousarray(W, dtype=np.float64).tobytes()).hexdigest()
+        W = np.asarray(W)  # (a complex matrix is hashed as complex128: its imaginary part is half of it)
+        key[f"band{f}_bf_mat_sha256"] = hashlib.sha256(np.ascontiguousarray(W, dtype=np.complex128 if np.iscomplexobj(W) else np.float64).tobytes()).hexdigest()
     return key
 
 
@@ -578,7 +580,8 @@ def wideband_speech_sweep(loc, doa_list, source, snr_db_vec=None, num_sim=20, se
                           localizer=None, batch_trials=None, out_dir=None):
     """The speech accuracy sweep (speech_target_sweep: paper_plots/target_snn_localization.py:213-245, 11 SNRs x 20 trials, no bandwidth
     correction) read out by the WIDEBAND localizer `loc` (wideband.WidebandSNNLocalizer: the live demo's filterbank + per-band chains +
-    band sum, micloc/localization_demo_snn.py:125-193) instead of one band.  One batch at a time (the band pipeline runs on one
+    band sum, micloc/localization_demo_snn.py:125-193; or wideband.WidebandBeamformerLocalizer, the complex Beamformer's form of it,
+    micloc/localization_demo.py:158-182) instead of one band.  One batch at a time (the band pipeline runs on one
     stream).  `localizer`: another read-out with wideband_localizer's signature (tests).  out_dir: resume as in noisy_target_sweep; the
     store key carries the band edges, the filterbank coefficients and every band's parameters and bf_mat hash."""
     if batch_trials is None:
@@ -1089,7 +1092,7 @@ def main(argv=None):
                     help="wideband-speech: the bands as low:high pairs in Hz, comma separated (at most 16)")
     ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
-    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy, moving-noisy (snn | beamformer): the localizer")
+    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy, moving-noisy and wideband-speech (snn | beamformer): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
@@ -1133,7 +1136,10 @@ def main(argv=None):
     elif args.sweep == "multi-noisy":
         res = _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world)
     elif args.sweep == "wideband-speech":
-        from .wideband import WidebandSNNLocalizer
+        from .wideband import WidebandBeamformerLocalizer, WidebandSNNLocalizer
+
+        if args.method == "music":
+            ap.error("--sweep wideband-speech takes --method snn or beamformer")
 
         if args.pcm_npz:
             z = np.load(args.pcm_npz)
@@ -1143,8 +1149,11 @@ def main(argv=None):
         else:
             ap.error("--sweep wideband-speech needs --flac or --pcm-npz")
         # the live demo's set-up per band (micloc/localization_demo_snn.py:40-93): 0.25 s design sines, 10 ms Hilbert kernel, bipolar
-        loc = WidebandSNNLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3,
-                                              bipolar_spikes=True, fs=fs)
+        if args.method == "beamformer":  # (micloc/localization_demo.py:43-89: complex Beamformers behind the order-2 filterbank)
+            loc = WidebandBeamformerLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3, fs=fs)
+        else:
+            loc = WidebandSNNLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3,
+                                                  bipolar_spikes=True, fs=fs)
         res = wideband_speech_sweep(loc, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
     elif args.sweep.startswith("music"):
         # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048

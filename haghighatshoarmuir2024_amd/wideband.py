@@ -1,14 +1,23 @@
-"""Wideband SNN localisation for batches: the form the reference deploys in its live demo (micloc/localization_demo_snn.py:125-193) --
+"""Wideband localisation for batches, SNN and complex.
+
+WidebandSNNLocalizer: wideband SNN localisation for batches: the form the reference deploys in its live demo (micloc/localization_demo_snn.py:125-193) --
 a filterbank, one SNNBeamformer chain per band (own band-pass, neuron kernel and bf_mat), the angular power patterns added, one
 arg-max (:166-190) -- as ONE library call for B recordings (micloc_snn_pipeline_bands_f64): the filterbank kernel for all bands
 together, every band's fused pipeline on its slice, the band sum and its arg-max on the device.
 
 `localization_demo_snn.Demo.power_grid` is the same computation one pack and one band at a time; `localize_batch` returns its
 numbers (tests/test_hip_wideband.py).  There is no CPU fallback.
+
+WidebandBeamformerLocalizer: the same for the non-spiking complex `Beamformer`, the chain of the reference's other live demo
+(micloc/localization_demo.py:43-89,158-182): an order-2 Butterworth filterbank, one Beamformer per band designed on a sine at the band
+centre, mean_t |y|^2 per band, the patterns added, one arg-max -- as ONE library call (micloc_beamformer_pipeline_bands_f64) in which the
+band dimension is folded into the batch: one STHT launch and one band-pass launch for all bands' chains.  `localization_demo.Demo.power_grid`
+is the same computation one pack and one band at a time; `localize_batch` returns its numbers (tests/test_hip_wideband_complex.py).
 """
 import numpy as np
 
 from . import runtime
+from .beamformer import Beamformer
 from .filterbank import ButterworthFilterbank
 from .snn_beamformer import SNNBeamformer, neuron_impulse_response
 
@@ -84,6 +93,104 @@ class WidebandSNNLocalizer:
         plans = self.plans(time_vec)
         x = plans[0].to_device(sig_batch)
         out = runtime.snn_pipeline_bands(plans, self.filterbank.ba_list, x, window=window, hop=hop, want_band_power=return_band_power)
+        if doa_list is None:
+            doa_list = getattr(self, "doa_list", None)
+        if window is not None:
+            out["window_start"] = window_bounds(T, window, hop)[0]
+            return _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+        return _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+
+
+class WidebandBeamformerLocalizer:
+    def __init__(self, beamfs, bf_mats, filterbank):
+        """beamfs: one Beamformer per band; bf_mats: their complex [M, G] matrices; filterbank: a Filterbank with one (b, a) section per
+        band.  ValueError for bands with different microphone or DoA counts, more than 16 bands, or a bf_mat that is not complex [M, G]."""
+        from . import _lib
+
+        self.beamfs, self.filterbank = list(beamfs), filterbank
+        self.bf_mats = [np.asarray(W) for W in bf_mats]
+        F = len(self.beamfs)
+        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+            raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+        if len(self.bf_mats) != F or len(filterbank.ba_list) != F:
+            raise ValueError(f"{F} beamformers need {F} bf_mats and {F} filterbank sections (got {len(self.bf_mats)}, {len(filterbank.ba_list)})")
+        M = len(self.beamfs[0].geometry)
+        if any(len(b.geometry) != M for b in self.beamfs):
+            raise ValueError(f"every band needs the same {M} microphones")
+        if any(not np.iscomplexobj(W) or W.ndim != 2 or W.shape[0] != M for W in self.bf_mats):
+            raise ValueError(f"every band needs a complex bf_mat with {M} rows ([M, G]; a real [2M, G] matrix belongs to WidebandSNNLocalizer)")
+        self.bf_mats = [W.astype(np.complex128, copy=False) for W in self.bf_mats]
+        G = self.bf_mats[0].shape[1]
+        if any(W.shape[1] != G for W in self.bf_mats):
+            raise ValueError(f"every band's bf_mat needs the same DoA grid ({[W.shape[1] for W in self.bf_mats]} columns)")
+        self.num_mic, self.num_grid = M, G
+        self.fs = self.beamfs[0].fs
+        self.geometry = self.beamfs[0].geometry
+
+    @classmethod
+    def from_bands(cls, geometry, freq_bands, doa_list, recording_duration, kernel_duration, fs, device=None):
+        """What localization_demo.Demo.__init__ builds (reference micloc/localization_demo.py:43-89): per band a Beamformer designed on a
+        sine at the band's centre, and the order-2 Butterworth filterbank."""
+        freq_bands = np.asarray(freq_bands)
+        if freq_bands.ndim == 1:
+            freq_bands = freq_bands.reshape(1, -1)
+        beamfs, bf_mats = [], []
+        for freq_range in freq_bands:
+            freq_mid = np.mean(freq_range)
+            beamf = Beamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, fs=fs, device=device)
+            beamfs.append(beamf)
+            time_temp = np.arange(0, recording_duration, step=1 / fs)
+            sig_temp = np.sin(2 * np.pi * freq_mid * time_temp)
+            bf_vecs, _ = beamf.design_from_template(template=(time_temp, sig_temp), doa_list=doa_list)
+            bf_mats.append(bf_vecs)
+        loc = cls(beamfs, bf_mats, ButterworthFilterbank(freq_bands=freq_bands, order=2, fs=fs, device=device))
+        loc.doa_list = np.asarray(doa_list)
+        return loc
+
+    def plans(self):
+        """The bands' device plans with their matrices set."""
+        plans = []
+        for beamf, W in zip(self.beamfs, self.bf_mats):
+            plan = beamf.plan()
+            plan.set_bf_mat(W)
+            plans.append(plan)
+        return plans
+
+    def trials_per_call(self, plans, B, T, window, hop, budget_bytes):
+        """The largest sub-batch of B whose workspace stays inside budget_bytes (one trial at least)."""
+        import ctypes
+
+        from . import _lib
+
+        lib = _lib.load()
+        handles = (ctypes.c_void_p * len(plans))(*[p.handle.value for p in plans])
+        one = lib.micloc_beamformer_bands_workspace_bytes(handles, len(plans), 1, T, window or 0, hop or 0)
+        if one == 0 or budget_bytes is None:
+            return B  # (bad arguments: the call itself names them)
+        return int(max(1, min(B, int(budget_bytes) // one)))
+
+    def localize_batch(self, sig_batch, return_band_power=False, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0,
+                       window=None, hop=None, budget_bytes=8 << 30):
+        """sig_batch [B, T, M] (numpy or device tensor, on the fs grid) -> dict of device tensors: power [B, G] = the bands' powers
+        added in ascending band order, argmax [B] int32; return_band_power: band_power [F, B, G] (with `window`: [F, B, nW, G]).
+        window=N frames (hop defaults to it; multiples of every band's window quantum): window_power [B, nW, G], window_argmax [B, nW]
+        and window_start [nW] (frames, host) INSTEAD of power / argmax.  num_sources=K (with doa_list): the K strongest peaks of the
+        summed pattern -- peaks / peak_power [B, K], with `window` window_peaks / window_peak_power [B, nW, K].
+        budget_bytes: B is split into sub-batches whose workspace (the filterbank output and two planar copies of every band: 35 doubles
+        per frame, band and 7 microphones) stays inside it, so a speech-length sweep batch fits; the results do not depend on the split."""
+        import torch
+
+        from .utils import _add_peaks, _add_window_peaks, window_bounds
+
+        B, T, M = sig_batch.shape
+        if M != self.num_mic:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
+        plans = self.plans()
+        x = plans[0].to_device(sig_batch)
+        step = self.trials_per_call(plans, B, T, window, hop, budget_bytes)
+        parts = [runtime.beamformer_pipeline_bands(plans, self.filterbank.ba_list, x[lo : lo + step], window=window, hop=hop,
+                                                   want_band_power=return_band_power) for lo in range(0, B, step)]
+        out = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts], dim=1 if k == "band_power" else 0) for k in parts[0]}
         if doa_list is None:
             doa_list = getattr(self, "doa_list", None)
         if window is not None:

@@ -676,6 +676,45 @@ int micloc_snn_pipeline_bands_f64(const micloc_plan *const *plans, int F, const 
                                   double *band_power /* [F][R][G] or NULL */, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
                                   void *stream);
 
+/* ---- wideband localisation, complex Beamformer: every band's chain in one batch ------------------ */
+/* The non-spiking form the reference deploys (micloc/localization_demo.py:43-89,158-182): a filterbank, one complex Beamformer per
+ * band (own band-pass, own complex bf_mat), mean_t |y|^2 per band, the patterns added, ONE arg-max.  The chains have no encoder
+ * state, so the band dimension folds into the batch dimension.  The rule:
+ *   - xf = the filterbank of "wideband localisation" above: x [B][T][M] -> xf [F][B][T][M], one launch.
+ *   - Band f's rows of band_power [F][R][G] are bit for bit the `power` of micloc_beamformer_pipeline_f64(plans[f], xf[f], B, T)
+ *     (window == 0) or the power_w of micloc_beamformer_pipeline_windows_f64(plans[f], xf[f], B, T, window, hop) (window > 0, the
+ *     window rule of "time-resolved DoA" above; R = B * nW, row r = b * nW + n).  band_power may be NULL: the rows stay in the workspace.
+ *   - power[r][g] = ((p_0[r][g] + p_1[r][g]) + p_2[r][g]) + ... in ascending band order, starting FROM p_0, every addition rounded
+ *     to nearest.  argmax[r] is the first maximum of the row; a NaN never wins; a row of NaN only gives 0.  power or argmax may be NULL.
+ *   Launches, all on the one stream, in this order: (1) the filterbank; (2) ONE STHT launch over the F * B trials of xf (the plans
+ *   share the Hilbert kernel); (3) ONE band-pass launch over the F * B * 2M chains of the analytic signal, band f with plans[f]'s
+ *   coefficients -- in-phase rows from xf through the roll by L / 2, quadrature rows from the STHT, the DF2T arithmetic of
+ *   micloc_lfilter_f64 from zero state, every term computed: against the rows the one-shot pipeline of band f forms only the sign of a
+ *   zero may differ; (4) per band in ascending order the contraction of that band's own pipeline call (its bf_mat) on its B
+ *   trials, into one array of chunk sums [F * B][chunks][Gp]; (5) ONE time reduction (window == 0) or window read-out (window > 0)
+ *   over the F * B trials; (6) the band sum.  5 + F launches; no atomics, no host synchronisation, no allocation: re-entrant per
+ *   stream with workspaces of their own and capturable in a hipGraph (a straight chain: nothing runs side by side).
+ *   Workspace (micloc_beamformer_bands_workspace_bytes, 256-B aligned): xf, the STHT rows and the band-passed rows [F * B][2M][Ts]
+ *   each, the chunk sums, and band_power when the caller passes NULL.
+ *   Status, before any launch and in this order: MICLOC_ERR_INVALID for NULL (plans, a plan, coefficients, x, both of power /
+ *   argmax), F outside 1..MICLOC_MAX_BANDS, fb_n outside 1..MICLOC_MAX_IIR, a_f[0] == 0, B or F * B outside 1..65535, T < 1, window
+ *   or hop < 0; MICLOC_ERR_NOT_SET for a plan without bf_mat; MICLOC_ERR_SHAPE for a real bf_mat, plans on different devices, with
+ *   different M or G, a different Hilbert kernel or band-pass length, T * M >= 2^32, or (window > 0) a window or hop that is not a
+ *   positive multiple of EVERY plan's micloc_window_quantum, or F * B * nW > INT32_MAX; MICLOC_ERR_WORKSPACE for a short or
+ *   misaligned ws.  hop == 0 means hop = window.
+ * micloc_beamformer_bands_bandpass_f64 is stages (2) and (3) alone, for tests and measurements: xf [F][B][T][M] -> h, pre
+ * [F * B][2M][Ts] (Ts = micloc_padded_T(T); the in-phase rows of h are not written; frames [T, Ts) of pre are zero with
+ * one_launch != 0 and unspecified with one_launch == 0, which takes the one-shot band-pass launch per band instead of (3)).
+ * with_stht == 0 skips (2): the quadrature rows of h are the caller's.  The plans need no bf_mat; the checks are those above that
+ * do not concern it. */
+size_t micloc_beamformer_bands_workspace_bytes(const micloc_plan *const *plans, int F, int B, int T, int window, int hop); /* 0 on bad arguments */
+int micloc_beamformer_pipeline_bands_f64(const micloc_plan *const *plans, int F, const double *fb_b, const double *fb_a, int fb_n,
+                                         const double *x, int B, int T, int window, int hop, /* window 0: whole recording */
+                                         double *band_power /* [F][R][G] or NULL */, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                         void *stream);
+int micloc_beamformer_bands_bandpass_f64(const micloc_plan *const *plans, int F, const double *xf, int B, int T, double *h, double *pre, int Ts,
+                                         int with_stht, int one_launch, void *stream);
+
 /* ---- wideband streaming: filterbank state carry, band sum per tile ------------------------------ */
 /* The wideband chain above for ONE stream that arrives in tiles: the results after the last tile are bit for bit those of
  * micloc_snn_pipeline_bands_f64 on the whole recording, for any tiling.  One tile of n frames, every launch on the caller's one
