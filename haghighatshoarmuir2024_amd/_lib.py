@@ -181,7 +181,21 @@ SYMBOLS = {
                                            ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
     "micloc_stream_bands_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_music_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "micloc_stream_complex_bands_state_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int]),
+    "micloc_stream_complex_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
+    "micloc_stream_complex_bands_reset": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_complex_bands_bandpass_tile_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                              c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_complex_bands_localize_tile_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
+                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_complex_bands_window_state_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
+    "micloc_stream_complex_bands_window_reset": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int,
+                                                         c_void_p]),
+    "micloc_stream_complex_bands_localize_tile_windows_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_int,
+                                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int,
+                                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "micloc_stream_complex_bands_status": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "micloc_music_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_abi_version": (c_int, []),

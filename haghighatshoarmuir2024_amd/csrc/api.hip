@@ -1646,6 +1646,223 @@ int micloc_stream_complex_status(const void *state, int *status4, void *stream)
     return MICLOC_OK;
 }
 
+// ---- wideband streaming, complex Beamformer (stream_bands_complex.hip; the rule: include/micloc_hip.h) ----------------------------------
+// The complex stream above for F * B rows.  state: stream_complex_layout(F * B); ws: [staging [F B][2M][Ks CH]][partial [F B][Ks][Gp]]
+// [running band power [F B][G]]; win_state: [the window state of F * B rows, the band sum's words at byte SCB_BANDS_WORDS of its 256-B head][band ring [F B][Kb][G]]
+}  // extern "C"
+
+namespace {
+
+struct ScbArgs {
+    ScArgs a;  // the complex stream's arguments for F * B rows
+    int FB;
+    size_t ws_band_power, ws_total;
+    // windows (scb_window_args)
+    int Kb;
+    size_t win_ring, win_total;
+};
+
+// the window kernel keeps its count in int word 0 of win_state's 256-B head and touches no other word of it: the band sum's four words
+// {emitted, given up, pending emitted, pending given up} live further on in the same head, zero-filled with it
+constexpr size_t SCB_BANDS_WORDS = 64;
+
+// argument checks of the wideband complex stream in the header's order (max_tile == 0: the state's layout only)
+int scb_args(const micloc_plan *const *plans, int F, int B, int max_tile, ScbArgs *s)
+{
+    *s = ScbArgs{};
+    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || bad_batch(F * B) || max_tile < 0) return MICLOC_ERR_INVALID;
+    for (int f = 0; f < F; ++f)
+        if (!plans[f]) return MICLOC_ERR_INVALID;
+    for (int f = 0; f < F; ++f)
+        if (!plans[f]->d_W) return MICLOC_ERR_NOT_SET;
+    const micloc_plan *p0 = plans[0];
+    for (int f = 0; f < F; ++f) {
+        const micloc_plan *p = plans[f];
+        if (!p->W_is_complex || p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out || p->W.GT != p0->W.GT || p->W.CT != p0->W.CT ||
+            p->L != p0->L || p->taps_host != p0->taps_host || p->iir.n != p0->iir.n)
+            return MICLOC_ERR_SHAPE;
+    }
+    s->FB = F * B;
+    const int rc = sc_args(p0, s->FB, max_tile, &s->a);  // (one chunk length: it depends on CT and GT only, which the plans share)
+    if (rc != MICLOC_OK) return rc;
+    s->ws_band_power = s->a.ws_total;
+    s->ws_total = s->a.ws_total + align256((size_t)s->FB * p0->G_out * sizeof(double));
+    return MICLOC_OK;
+}
+
+// the window rule of the streams, then the layout of win_state; rc: scb_args' status with max_tile >= 1
+int scb_window_args(int rc, const micloc_plan *const *plans, int window, int hop, int max_windows, ScbArgs *s)
+{
+    rc = stream_window_args(rc, window, hop, max_windows, &s->a.CH);
+    if (rc != MICLOC_OK) return rc;
+    s->Kb = stream_bands_ring_depth(s->a.Ks, hop / s->a.CH);
+    s->win_ring = stream_window_state_bytes(s->FB, plans[0]->G_out, window, hop);
+    s->win_total = s->win_ring + align256((size_t)s->FB * s->Kb * plans[0]->G_out * sizeof(double));
+    return MICLOC_OK;
+}
+
+// the launches behind the band-pass of a tile: contraction per band, accumulation, (windows,) slide + commit over the F * B rows, band sum
+int scb_localize(const micloc_plan *const *plans, int F, int B, const ScbArgs &s, void *state, int final_tile, double *band_power, double *power,
+                 int32_t *argmax, void *ws, void *win_state, int window, int hop, int max_windows, double *window_power, int32_t *window_argmax,
+                 double *latest_power, int32_t *latest_argmax, hipStream_t st)
+{
+    const micloc_plan *p0 = plans[0];
+    const ScArgs &a = s.a;
+    const int G = p0->G_out;
+    double *staging = ws_doubles(ws, 0), *partial = ws_doubles(ws, a.ws_partial);
+    double *bp = band_power ? band_power : ws_doubles(ws, s.ws_band_power);
+    // per band the contraction of 4.16's tile (that band's bf_mat) on its B rows of the one staging array, into one array of chunk rows
+    const size_t band_rows = (size_t)B * p0->C * a.S, band_partial = (size_t)B * a.Ks * a.Gp;
+    for (int f = 0; f < F; ++f) {
+        int nch = 0;
+        HIP_TRY(launch_planar_beamform(plans[f]->W, staging + f * band_rows, B, a.S, a.S, nullptr, 1, partial + f * band_partial, st, &nch));
+        if (nch != a.Ks) return MICLOC_ERR_INVALID;  // the launch chose a kernel window_quantum() does not describe
+    }
+    HIP_TRY(launch_stream_complex_accumulate(partial, s.FB, a.Ks, a.Gp, G, a.CH, final_tile, state, a.L, bp, nullptr, st));
+    unsigned char *wbase = reinterpret_cast<unsigned char *>(win_state);
+    double *ring = win_state ? reinterpret_cast<double *>(wbase + s.win_ring) : nullptr;
+    if (win_state)  // every band's windows into its rows of the ring, window n in row n % Kb; the one count word serves all bands
+        HIP_TRY(launch_stream_windows(partial, s.FB, a.Ks, a.Gp, G, 1, a.Gp / 2, a.CH, reinterpret_cast<const int *>(state), final_tile ? 1 : 0, window,
+                                      hop, s.Kb, win_state, ring, nullptr, nullptr, nullptr, st));
+    HIP_TRY(launch_stream_complex_slide(staging, s.FB * p0->C, a.S, a.CH, state, a.L, st));
+    StreamBandsArgs args{};
+    for (int f = 0; f < F; ++f) {
+        args.power[f] = bp + (size_t)f * B * G;
+        if (win_state) {
+            args.rows[f] = ring + (size_t)f * B * s.Kb * G;
+            args.count[f] = reinterpret_cast<const int32_t *>(win_state);
+        }
+    }
+    // (without windows the band sum reads no word of its state: the stream's own stands in for the non-NULL pointer the launcher wants)
+    HIP_TRY(launch_stream_band_sum(args, F, B, G, win_state != nullptr, s.Kb, max_windows, win_state ? (void *)(wbase + SCB_BANDS_WORDS) : state, power,
+                                   argmax, window_power, window_argmax, latest_power, latest_argmax, st));
+    return MICLOC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t micloc_stream_complex_bands_state_bytes(const micloc_plan *const *plans, int F, int B)
+{
+    ScbArgs s;
+    return scb_args(plans, F, B, 0, &s) == MICLOC_OK ? s.a.L.total : 0;
+}
+
+size_t micloc_stream_complex_bands_workspace_bytes(const micloc_plan *const *plans, int F, int B, int max_tile)
+{
+    ScbArgs s;
+    if (max_tile < 1 || scb_args(plans, F, B, max_tile, &s) != MICLOC_OK) return 0;
+    return s.ws_total;
+}
+
+int micloc_stream_complex_bands_reset(const micloc_plan *const *plans, int F, int B, void *state, size_t state_bytes, void *stream)
+{
+    if (!plans || !state) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    const int rc = scb_args(plans, F, B, 0, &s);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, s.a.L.total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    HIP_TRY(launch_zero_fill(state, s.a.L.total, (hipStream_t)stream));  // clock, zero DF2T state, empty carry, accumulators
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_bands_bandpass_tile_f64(const micloc_plan *const *plans, int F, const double *h, int B, int n, int row_stride,
+                                                  int first_col, int max_tile, int chains_per_workgroup, void *state, size_t state_bytes, void *ws,
+                                                  size_t ws_bytes, void *stream)
+{
+    if (!plans || !h || !state || !ws || n < 1 || max_tile < 1 || first_col < 0 || row_stride < 1) return MICLOC_ERR_INVALID;
+    if (chains_per_workgroup != 0 && chains_per_workgroup != 16 && chains_per_workgroup != 32 && chains_per_workgroup != 64) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    const int rc = scb_args(plans, F, B, max_tile, &s);
+    if (rc != MICLOC_OK) return rc;
+    if (n > max_tile || (long long)first_col + n > row_stride) return MICLOC_ERR_SHAPE;
+    if (bad_ws(state, state_bytes, s.a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, s.ws_total)) return MICLOC_ERR_WORKSPACE;
+    const micloc_plan *p0 = plans[0];
+    DeviceGuard guard(p0->device);
+    FilterbankCoef pc;
+    cbands_coef(plans, F, &pc);
+    HIP_TRY(launch_stream_bands_bandpass(pc, h + first_col, F, B * p0->C, n, (size_t)row_stride, ws_doubles(ws, 0), s.a.S, s.a.CH, state, s.a.L,
+                                         chains_per_workgroup, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_bands_localize_tile_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B, int max_tile,
+                                                  int final_tile, double *band_power, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                                  void *stream)
+{
+    if (!plans || !state || !ws || max_tile < 1) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    const int rc = scb_args(plans, F, B, max_tile, &s);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, s.a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, s.ws_total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    return scb_localize(plans, F, B, s, state, final_tile, band_power, power, argmax, ws, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                        (hipStream_t)stream);
+}
+
+size_t micloc_stream_complex_bands_window_state_bytes(const micloc_plan *const *plans, int F, int B, int max_tile, int window, int hop,
+                                                      int max_windows)
+{
+    ScbArgs s;
+    if (max_tile < 1 || scb_window_args(scb_args(plans, F, B, max_tile, &s), plans, window, hop, max_windows, &s) != MICLOC_OK) return 0;
+    return s.win_total;
+}
+
+int micloc_stream_complex_bands_window_reset(const micloc_plan *const *plans, int F, int B, int max_tile, void *win_state, size_t win_bytes,
+                                             int window, int hop, int max_windows, void *stream)
+{
+    if (!plans || !win_state || max_tile < 1) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    const int rc = scb_window_args(scb_args(plans, F, B, max_tile, &s), plans, window, hop, max_windows, &s);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(win_state, win_bytes, s.win_total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    HIP_TRY(launch_zero_fill(win_state, s.win_total, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_bands_localize_tile_windows_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B,
+                                                          int max_tile, int final_tile, double *band_power, double *power, int32_t *argmax,
+                                                          void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop,
+                                                          int max_windows, double *window_power, int32_t *window_argmax, double *latest_power,
+                                                          int32_t *latest_argmax, void *stream)
+{
+    if (!plans || !state || !ws || !win_state || !window_argmax || max_tile < 1) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    const int rc = scb_window_args(scb_args(plans, F, B, max_tile, &s), plans, window, hop, max_windows, &s);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, s.a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, s.ws_total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(win_state, win_bytes, s.win_total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    return scb_localize(plans, F, B, s, state, final_tile, band_power, power, argmax, ws, win_state, window, hop, max_windows, window_power,
+                        window_argmax, latest_power, latest_argmax, (hipStream_t)stream);
+}
+
+/* status[0 .. 3] = micloc_stream_complex_status' words of the F * B rows; [4] = wideband windows emitted or given up, [5] = given up
+ * (0 and 0 with win_state == NULL) (synchronises the stream) */
+int micloc_stream_complex_bands_status(const void *state, const void *win_state, int *status6, void *stream)
+{
+    if (!state || !status6) return MICLOC_ERR_INVALID;
+    int ctl[STREAM_CLK_T + 1], w[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(ctl, state, sizeof(ctl), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    if (win_state)
+        HIP_TRY(hipMemcpyAsync(w, reinterpret_cast<const unsigned char *>(win_state) + SCB_BANDS_WORDS, sizeof(w), hipMemcpyDeviceToHost,
+                               (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    status6[0] = ctl[0];
+    status6[1] = ctl[8];
+    status6[2] = ctl[2];
+    status6[3] = ctl[STREAM_CLK_T];
+    status6[4] = w[0];
+    status6[5] = w[1];
+    return MICLOC_OK;
+}
+
 // ---- stand-alone operators -------------------------------------------------------------------------------
 size_t micloc_rzcc_workspace_bytes(int B, int T, int C) { return micloc_rzcc_workspace_bytes_ex(B, T, C, 1, 0); }
 

@@ -308,6 +308,15 @@ hipError_t launch_stream_band_sum(const StreamBandsArgs &args, int F, int B, int
                                   double *power, int32_t *argmax, double *power_w, int32_t *argmax_w, double *latest_power,
                                   int32_t *latest_argmax, hipStream_t stream);
 
+// ---- wideband streaming, complex Beamformer: the band-pass tile of all bands' chains in one launch (stream_bands_complex.hip) --------
+// the complex stream's band-pass tile (launch_stream_complex_bandpass) over F * band_chains chains, band_chains = B 2M, state and staging
+// laid out by stream_complex_layout for F * B rows; band f filters with row f of `co`; chains: 0 (the launcher's choice) or 16 / 32 / 64
+hipError_t launch_stream_bands_bandpass(const FilterbankCoef &co, const double *h, int F, int band_chains, int n, size_t row_stride,
+                                        double *staging, int S, int chunk, void *state, const StreamComplexLayout &L, int chains,
+                                        hipStream_t stream);
+int stream_bands_bandpass_chains(int nl);                    // chains per workgroup the launcher takes for nl chains
+int stream_bands_ring_depth(int Ks, int hop_chunks);         // windows one tile of Ks chunk rows can complete, plus the one cut at the end
+
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------
 struct MusicDims {
     int B, T, M;     // trials, samples per trial, microphones

@@ -36,8 +36,8 @@ THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as 
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
 
-THE CLASSES: StreamingLocalizer (one SNNBeamformer chain), WidebandStreamingLocalizer (a filterbank and one StreamingLocalizer per band) and
-ComplexStreamingLocalizer share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
+THE CLASSES: StreamingLocalizer (one SNNBeamformer chain), WidebandStreamingLocalizer (a filterbank and one StreamingLocalizer per band),
+ComplexStreamingLocalizer and WidebandComplexStreamingLocalizer (a filterbank and ONE complex stream of bands x batch rows) share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
 _TileStream states once: what a window / hop / max_windows may be, which tiles are accepted, how a tile length becomes a captured graph, how
 the ring of windows is read, what finish() refuses about it.  A class adds its own state and scratch, the launches of its tile (_tile), the
 host mirror of its clock (_advance), status() and its own refusals in finish().
@@ -51,7 +51,7 @@ from .snn_beamformer import neuron_impulse_response
 
 
 class _TileStream:
-    """The tile protocol of the three localizers (module docstring, THE CLASSES).  A subclass supplies
+    """The tile protocol of the localizers (module docstring, THE CLASSES).  A subclass supplies
       _tile(x, n, final)   the launches of one tile and nothing else: no allocation, no synchronisation, no absolute time by value (the clock
                            is a device word), so that a tile of a given length is ONE replayable hipGraph;
       _advance(n, final)   the host mirror of the clock and the end-of-stream bookkeeping;
@@ -671,4 +671,161 @@ class ComplexStreamingLocalizer(_TileStream):
         if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
             raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
         out = dict(power=self.power, argmax=self.argmax)
+        return self._finish_windows(out)
+
+
+class WidebandComplexStreamingLocalizer(_TileStream):
+    """The wideband complex chain (wideband.WidebandBeamformerLocalizer: an order-2 filterbank, one complex Beamformer per band, the
+    patterns added, one arg-max -- what the reference deploys live in micloc/localization_demo.py, restarting on every 0.25 s pack) as ONE
+    stream that arrives in tiles, with the results of `WidebandBeamformerLocalizer.localize_batch` on the whole recording bit for bit,
+    whatever the tiling (include/micloc_hip.h "wideband streaming, complex Beamformer").
+
+    The complex chain has no encoder state and no horizon, so the bands advance in lock step: the stream is ONE ComplexStreamingLocalizer
+    of F * batch rows with per-band coefficients and per-band bf_mat, behind WidebandStreamingLocalizer's filterbank state carry.  One tile
+    = the filterbank tile, ONE STHT launch over the F * batch trials of [last L - 1 filtered frames | filtered tile], np.roll's wrap rows,
+    ONE band-pass tile launch over all F * batch * 2M chains, the contraction per band, ONE accumulate / window read-out / slide over the
+    F * batch rows, the band sum -- a chain of launches on one stream, one graph per tile length in push_replay().  Tiles may have any
+    length.  The bands complete every window in the same tile, so the bands' ring (inside the window state) is as deep as the number of
+    windows one tile can complete plus the one cut at the end of the recording, and no window is ever given up."""
+
+    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None):
+        """loc: wideband.WidebandBeamformerLocalizer; `batch` recordings are streamed in lock step.
+        total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
+                      final=True with the last tile.
+        wrap_tail     [F, batch, L // 2, M]: np.roll's wrap-around rows of every band's FILTERED recording (the roll happens after the
+                      filterbank; ComplexStreamingLocalizer.wrap_rows of each band's filterbank output), or None (zeros: a live source).
+        max_tile      longest tile push() will be given.
+        window, hop, max_windows   the windowed read-out, as ComplexStreamingLocalizer's."""
+        self._check_window_given(window, hop, max_windows)
+        torch = runtime._torch()
+        self.loc_def = loc
+        F = self.F = len(loc.beamfs)
+        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+            raise ValueError(f"a wideband stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+        self.B, self.M, self.G = int(batch), loc.num_mic, loc.num_grid
+        self.C = 2 * self.M
+        if not 1 <= F * self.B <= 65535:
+            raise ValueError(f"bands x batch must be 1 .. 65535, got {F} x {self.B}")
+        self.T = None if total_frames is None else int(total_frames)
+        self.L = len(loc.beamfs[0].kernel)
+        self.halo = -(-(self.L - 1) // 8) * 8
+        L2 = self.L // 2
+        if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
+            raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
+        if len(loc.filterbank.ba_list) != F:
+            raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
+        self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
+        self.max_tile = int(max_tile)
+        if self.max_tile < 1:
+            raise ValueError("max_tile must be at least 1")
+        # the stream's own plans, one per band (the band-pass coefficients and the bf_mat of that band)
+        self.plans = []
+        for beamf, W in zip(loc.beamfs, loc.bf_mats):
+            b, a = beamf.bandpass_filter
+            plan = runtime.Plan(self.M, beamf.kernel, b, a, robust_width=1, bipolar=False, device=beamf.device)
+            plan.set_bf_mat(np.asarray(W).astype(np.complex128))
+            self.plans.append(plan)
+        self.plan = self.plans[0]
+        self.device = dev = self.plan.device
+        self.lib = _lib.load()
+        self.handles = (ctypes.c_void_p * F)(*[p.handle.value for p in self.plans])
+        self.CH = self.plan.window_quantum()
+        self._set_windows(self.plan, window, hop, max_windows)
+        lib, FB = self.lib, F * self.B
+        self.nstate = int(lib.micloc_stream_complex_bands_state_bytes(self.handles, F, self.B))
+        self.nws = int(lib.micloc_stream_complex_bands_workspace_bytes(self.handles, F, self.B, self.max_tile))
+        if self.nstate == 0 or self.nws == 0:
+            raise ValueError("micloc stream_complex_bands_state_bytes: the bands do not share the device, the microphones, the DoA grid, the Hilbert "
+                             "kernel and the band-pass length, or max_tile does not fit the stream's rule")
+        self.nfb = int(lib.micloc_filterbank_stream_state_bytes(F, self.ncoef, self.B, self.M))
+        if self.nfb == 0:
+            raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
+        self.state = torch.empty(self.nstate, dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
+        self.fb_state = torch.empty(self.nfb, dtype=torch.uint8, device=dev)
+        self.xf = torch.empty(FB * self.max_tile * self.M, dtype=torch.float64, device=dev)  # the filtered tile [F][B][n][M]
+        self.hist = torch.zeros((FB, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (the FIR's zero state)
+        self.ext = torch.empty((FB * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
+        self.h = torch.empty((FB * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
+        self.band_power = torch.zeros((F, self.B, self.G), dtype=torch.float64, device=dev)
+        self._alloc_results()
+        st = runtime._stream(dev)
+        self.wst, self.nwst = None, 0
+        if self.window is not None:
+            wargs = (self.window, self.hop, self.max_windows)
+            self.nwst = int(lib.micloc_stream_complex_bands_window_state_bytes(self.handles, F, self.B, self.max_tile, *wargs))
+            if self.nwst == 0:
+                raise _lib.MiclocError("micloc stream_complex_bands_window_state_bytes: the plans cannot serve the windowed read-out")
+            self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=dev)
+            _lib.check(lib.micloc_stream_complex_bands_window_reset(self.handles, F, self.B, self.max_tile, runtime._ptr(self.wst), self.nwst, *wargs, st),
+                       "stream_complex_bands_window_reset")
+        self.wrap = None
+        if wrap_tail is not None:
+            wrap = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
+            self.wrap = wrap.reshape(FB, L2, self.M).contiguous()
+        _lib.check(lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, st), "filterbank_stream_reset")
+        _lib.check(lib.micloc_stream_complex_bands_reset(self.handles, F, self.B, runtime._ptr(self.state), self.nstate, st), "stream_complex_bands_reset")
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _tile(self, x, n, final):
+        """The launches of one tile, all on the current stream, in a fixed order.  Nothing else (no allocation, no synchronisation, no
+        absolute time), so a tile of a given length is one replayable graph."""
+        lib, plan, F, B, M = self.lib, self.plan, self.F, self.B, self.M
+        FB = F * B
+        st = runtime._stream(self.device)
+        xf = self.xf[: FB * n * M].view(FB, n, M)
+        _lib.check(lib.micloc_filterbank_tile_f64(runtime._dptr(self.bb), runtime._dptr(self.aa), F, self.ncoef, runtime._ptr(x), B, n, M,
+                                                  runtime._ptr(self.fb_state), self.nfb, runtime._ptr(xf), st), "filterbank_tile")
+        # [history | filtered tile] of all bands' trials, ONE STHT launch, the wrap rows of every band's filtered recording
+        Text = self.halo + n
+        ext = self.ext[: FB * Text * M].view(FB, Text, M)
+        ext[:, : self.halo, :].copy_(self.hist)
+        ext[:, self.halo :, :].copy_(xf)
+        Ts = plan.padded_T(Text)
+        h = self.h[: FB * self.C * Ts]
+        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), FB, Text, runtime._ptr(h), Ts, st), "stht")
+        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(h), FB, Ts, self.halo, n, runtime._ptr(self.wrap), st),
+                   "stream_wrap_rows")
+        _lib.check(lib.micloc_stream_complex_bands_bandpass_tile_f64(self.handles, F, runtime._ptr(h), B, n, Ts, self.halo, self.max_tile, 0,
+                                                                     runtime._ptr(self.state), self.nstate, runtime._ptr(self.ws), self.nws, st),
+                   "stream_complex_bands_bandpass_tile")
+        tile = (self.handles, F, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final), runtime._ptr(self.band_power),
+                runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
+        if self.window is None:
+            _lib.check(lib.micloc_stream_complex_bands_localize_tile_f64(*tile, st), "stream_complex_bands_localize_tile")
+        else:
+            _lib.check(lib.micloc_stream_complex_bands_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
+                                                                                 self.max_windows, runtime._ptr(self.window_power),
+                                                                                 runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
+                                                                                 runtime._ptr(self.latest_argmax), st),
+                       "stream_complex_bands_localize_tile_windows")
+        self.hist.copy_(ext[:, Text - self.halo :, :])
+
+    def _advance(self, n, final):
+        self.t += n
+        self.done = bool(final)
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def status(self):
+        """dict(chunks, frames, carry, pushed, windows, band_sum_failures): chunks and frames contracted (the same for every band), frames
+        waiting in the carry, frames pushed (the device clock), wideband windows emitted, windows given up (always 0: the ring depth
+        covers what one tile can complete).  Synchronises the stream."""
+        s6 = (ctypes.c_int * 6)()
+        _lib.check(self.lib.micloc_stream_complex_bands_status(runtime._ptr(self.state), runtime._ptr(self.wst), s6, runtime._stream(self.device)),
+                   "stream_complex_bands_status")
+        return dict(chunks=int(s6[0]), frames=int(s6[1]), carry=int(s6[2]), pushed=int(s6[3]), windows=int(s6[4]), band_sum_failures=int(s6[5]))
+
+    def _window_count(self):
+        return self.status()["windows"]
+
+    def finish(self):
+        """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
+        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        self._need_done()
+        s = self.status()
+        if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
+            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
+        if s["band_sum_failures"]:
+            raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up by the band sum")
+        out = dict(power=self.power, argmax=self.argmax, band_power=self.band_power)
         return self._finish_windows(out)

@@ -156,6 +156,14 @@ class WidebandBeamformerLocalizer:
             plans.append(plan)
         return plans
 
+    def streaming_localizer(self, batch=1, **kw):
+        """localize_batch for recordings that arrive tile by tile: a streaming.WidebandComplexStreamingLocalizer (push / push_replay /
+        finish; total_frames, wrap_tail, max_tile, window, hop, max_windows as there) whose results after the last tile are localize_batch's
+        on the whole recording bit for bit."""
+        from .streaming import WidebandComplexStreamingLocalizer
+
+        return WidebandComplexStreamingLocalizer(self, batch, **kw)
+
     def trials_per_call(self, plans, B, T, window, hop, budget_bytes):
         """The largest sub-batch of B whose workspace stays inside budget_bytes (one trial at least)."""
         import ctypes

@@ -776,6 +776,81 @@ int micloc_stream_band_sum_f64(int F, int B, int G, const double *const *band_po
                                int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *stream);
 int micloc_stream_bands_status(const void *bands_state, int *status2, void *stream);
 
+/* ---- wideband streaming, complex Beamformer: all bands' tiles in one batch ----------------------- */
+/* The chain of "wideband localisation, complex Beamformer" for ONE stream that arrives in tiles.  The complex chain has no encoder
+ * state and no horizon, so all bands advance in lock step: a stream of F bands x B recordings is one complex stream ("streaming, complex
+ * Beamformer" above) of F * B rows -- row f B + b is band f of recording b -- with per-band band-pass coefficients and per-band bf_mat.
+ * The rule, for F plans (1 <= F <= MICLOC_MAX_BANDS) with complex bf_mats that agree in device, M, G, Hilbert kernel and band-pass length,
+ * filterbank coefficients [F][n], a recording x [B][T][M] and any cut of T into tiles of any lengths >= 1:
+ *   Results.
+ *   - After the final tile band_power [F][B][G], power [B][G] and argmax [B] equal micloc_beamformer_pipeline_bands_f64 on the whole
+ *     recording bit for bit.
+ *   - With window / hop (multiples of CH = micloc_window_quantum, 1 <= hop <= window) every emitted wideband window has the bits of that
+ *     entry's windows form.  Emission time, ring row n % max_windows, latest_* and "an emitted row never changes" are those of "streaming
+ *     windows" above.  power = ((p_0 + p_1) + p_2) + ... in ascending band order from p_0, every addition rounded to nearest; the
+ *     arg-max is the first maximum, a NaN never wins, a row of NaN gives 0.
+ *   - Before the final tile band f's power is the running read-out of "streaming, complex Beamformer" (the mean over the whole chunks
+ *     contracted so far; the same frames for every band) and power is their band sum.
+ *   - Nothing allocates, synchronises with the host, uses atomics or takes an absolute time.  A tile of n frames is ONE chain of launches
+ *     on the caller's stream with no parallel branches: one capturable hipGraph per tile length.
+ *   One tile of n <= max_tile frames, in this order:
+ *     micloc_filterbank_tile_f64                         x_tile [B][n][M] -> xf_tile [F][B][n][M] ("wideband streaming" above)
+ *     micloc_stht_f64, micloc_stream_wrap_rows_f64       by the caller with plans[0] over the F * B trials of [last L - 1 FILTERED frames |
+ *                                                        xf_tile]; the wrap rows are those of every band's filtered recording,
+ *                                                        [F][B][L/2][M]; `state` serves as loc_state
+ *     micloc_stream_complex_bands_bandpass_tile_f64      h [F B][2M][row_stride] -> staging: ONE launch over the F * B * 2M chains, band
+ *                                                        g / (B 2M) of chain g with plans[f]'s coefficients; the DF2T steps, the state
+ *                                                        words (word i of chain g at i F B 2M + g), the carry and the zero padding of
+ *                                                        micloc_stream_complex_bandpass_tile_f64.  Against the rows of
+ *                                                        micloc_beamformer_bands_bandpass_f64 on the whole recording only the sign of a
+ *                                                        zero may differ.  chains_per_workgroup: 0 (the launcher's choice by chain
+ *                                                        count) or 16 / 32 / 64 (tests, measurements): the bits do not depend on it
+ *     micloc_stream_complex_bands_localize_tile[_windows]_f64
+ *                                                        per band in ascending order the contraction of that band's bf_mat on its B rows
+ *                                                        of the staging array into one array of chunk rows [F B][Ks][Gp]; then ONE
+ *                                                        accumulate, (ONE window read-out,) ONE slide + clock commit over the F * B rows
+ *                                                        -- the kernels of the complex stream, unchanged; then the band sum of "wideband
+ *                                                        streaming" (followed, with windows, by its one-thread commit)
+ *   with the same max_tile, state and ws in both calls: 6 + F launches, 8 + F with windows.  band_power, power and argmax may be NULL.
+ *   Windows.  The bands complete every window in the same tile.  Band f's windows go to a ring [B][Kb][G] inside win_state, window n in row
+ *   n % Kb, all bands counted by the one count word of the window state; the band sum then emits the windows [emitted, count).  Kb =
+ *   ceil(Ks / (hop / CH)) + 1: a tile contracts at most Ks = ceil((max_tile + CH - 1) / CH) chunk rows, r chunk rows complete at most
+ *   ceil(r / (hop / CH)) windows, and on the final tile at most ONE more window is cut at the end of the recording.  So count - emitted
+ *   <= Kb always and no window is ever given up.  micloc_stream_window_count(win_state) is the number of wideband windows emitted.
+ *   State and footprint.  state (micloc_stream_complex_bands_state_bytes; zero-filled once by _reset): the complex stream's layout for
+ *   F * B rows.  ws (_workspace_bytes; pure scratch): staging [F B][2M][Ks CH], chunk rows [F B][Ks][Gp], running band power [F B][G].
+ *   win_state (_window_state_bytes; zero-filled once by _window_reset): the window state of F * B rows, whose 256-B head also holds the
+ *   band sum's counts, and the band ring [F B][Kb][G].  All 256-B aligned; none grows with the stream.  The filterbank state is the
+ *   caller's (micloc_filterbank_stream_state_bytes).
+ *   micloc_stream_complex_bands_status: {chunks contracted, frames contracted, carry fill, frames pushed, wideband windows emitted or
+ *   given up, windows given up}; win_state may be NULL (the last two are then 0); it synchronises the stream.
+ *   Status, before any launch and in this order: MICLOC_ERR_INVALID for NULL (plans, a plan, h, state, ws, win_state, window_argmax),
+ *   F outside 1..MICLOC_MAX_BANDS, B or F * B outside 1..65535, n, max_tile or row_stride < 1, first_col < 0, a chains_per_workgroup other
+ *   than 0, 16, 32, 64, window, hop or max_windows < 1; MICLOC_ERR_NOT_SET for a plan without bf_mat; MICLOC_ERR_SHAPE for a real bf_mat,
+ *   plans on different devices, with different M or G, a different Hilbert kernel or band-pass length, a window or hop that is not a
+ *   multiple of CH, hop > window, n > max_tile or first_col + n > row_stride; MICLOC_ERR_WORKSPACE for a short or misaligned state, ws
+ *   or win_state.  The size functions return 0 for such arguments. */
+size_t micloc_stream_complex_bands_state_bytes(const micloc_plan *const *plans, int F, int B);
+size_t micloc_stream_complex_bands_workspace_bytes(const micloc_plan *const *plans, int F, int B, int max_tile);
+int micloc_stream_complex_bands_reset(const micloc_plan *const *plans, int F, int B, void *state, size_t state_bytes, void *stream);
+int micloc_stream_complex_bands_bandpass_tile_f64(const micloc_plan *const *plans, int F, const double *h, int B, int n, int row_stride,
+                                                  int first_col, int max_tile, int chains_per_workgroup, void *state, size_t state_bytes,
+                                                  void *ws, size_t ws_bytes, void *stream);
+int micloc_stream_complex_bands_localize_tile_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B,
+                                                  int max_tile, int final_tile, double *band_power, double *power, int32_t *argmax,
+                                                  void *ws, size_t ws_bytes, void *stream);
+size_t micloc_stream_complex_bands_window_state_bytes(const micloc_plan *const *plans, int F, int B, int max_tile, int window, int hop,
+                                                      int max_windows);
+int micloc_stream_complex_bands_window_reset(const micloc_plan *const *plans, int F, int B, int max_tile, void *win_state, size_t win_bytes,
+                                             int window, int hop, int max_windows, void *stream);
+int micloc_stream_complex_bands_localize_tile_windows_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B,
+                                                          int max_tile, int final_tile, double *band_power, double *power,
+                                                          int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes,
+                                                          int window, int hop, int max_windows, double *window_power,
+                                                          int32_t *window_argmax, double *latest_power, int32_t *latest_argmax,
+                                                          void *stream);
+int micloc_stream_complex_bands_status(const void *state, const void *win_state, int *status6, void *stream);
+
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
  * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
