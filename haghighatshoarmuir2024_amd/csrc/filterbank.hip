@@ -2,10 +2,9 @@
 // micloc/filterbank.py:25-46: scipy.signal.lfilter per band) as ONE launch for all bands of a batch, and the sum of the per-band
 // angular power patterns with its arg-max (:166-190).
 //
-// filterbank_kernel: x [B][T][M] -> xf [F][B][T][M].  The arithmetic is the project's DF2T contract from zero state, the step of
-// rzcc.hip's Iir restated (that file is pinned by the profile manifest): y = fma(b0, x, z0); z_i = fma(-a_{i+1}, y, fma(b_{i+1}, x,
-// z_{i+1})); z_{n-2} = fma(-a_{n-1}, y, b_{n-1} * x) -- every term, no zero-coefficient skipping, so the results are those of
-// micloc_lfilter_f64 band by band.  Time is serial per (band, trial, microphone) chain: one lane owns one chain.
+// filterbank_kernel: x [B][T][M] -> xf [F][B][T][M].  The arithmetic is the project's DF2T contract from zero state, Df2tChain<N>
+// (bandpass_rows.h) -- every term, no zero-coefficient skipping, so the results are those of micloc_lfilter_f64 band by band.  Time is
+// serial per (band, trial, microphone) chain: one lane owns one chain.
 //   * A workgroup owns one trial (and a group of `mg` microphones: all of them unless (1 + F) * M > FB_MAX_ROWS) with ALL its
 //     bands: an input tile of FB_TT frames comes from HBM once and every band reads it from LDS (lanes of different bands read the
 //     same address: a broadcast).
@@ -25,7 +24,7 @@
 // band_sum_kernel: band_power [F][R][G] -> power [R][G] = ((p_0 + p_1) + p_2) + ... in ascending band order (__dadd_rn, starting
 // from p_0: the additions of Demo.power_grid) and argmax [R] with power_argmax_kernel's rule (first maximum, a NaN never wins, a
 // row of NaN only gives 0).  One workgroup per row, no atomics.
-#include "micloc_internal.h"
+#include "bandpass_rows.h"
 
 namespace micloc {
 
@@ -36,45 +35,13 @@ constexpr int FB_MAX_MG = 16;     // microphones per workgroup (FB_XREG register
 constexpr int FB_XREG = FB_TT * FB_MAX_MG / FB_THREADS;
 constexpr int FB_GROUP = 8;       // steps per register group of the recurrence
 
-template <int N>
-struct FbChain {
-    double b[N], a[N];
-    double z[N > 1 ? N - 1 : 1];
-
-    __device__ __forceinline__ void init(const FilterbankCoef &co, int f)
-    {
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            b[i] = co.b[f][i];
-            a[i] = co.a[f][i];
-        }
-#pragma unroll
-        for (int i = 0; i < (N > 1 ? N - 1 : 1); ++i) z[i] = 0.0;
-    }
-
-    // the DF2T step of the contract, operation for operation rzcc.hip's Iir<N>::step
-    __device__ __forceinline__ double step(double xin)
-    {
-        double y;
-        if (N == 1) {
-            y = __builtin_fma(b[0], xin, 0.0);
-        } else {
-            y = __builtin_fma(b[0], xin, z[0]);
-#pragma unroll
-            for (int i = 0; i < N - 2; ++i) z[i] = __builtin_fma(-a[i + 1], y, __builtin_fma(b[i + 1], xin, z[i + 1]));
-            z[N - 2] = __builtin_fma(-a[N - 1], y, b[N - 1] * xin);
-        }
-        return y;
-    }
-};
-
 // LDS: [2][xin: mg rows... ] as time-major tiles.  xin[buf][t * mg + j]; yout[buf][f][t * mg + j] with a band stride of
 // (FB_TT + 1) * mg doubles: lanes (f, j) of one step then write F * mg different banks (up to 16 doubles) instead of F-way conflicts.
 //
 // fb_tiles<N, Resume> is the tile loop of both kernels.  Resume = false: the one-shot filterbank_kernel, zero state, exactly the code it
 // always was (`state` is not touched and every `if (Resume)` below is a compile-time false).  Resume = true: filterbank_tile_kernel,
 // one tile of a stream -- each chain lane loads its n - 1 DF2T states from `state` before the first LDS tile and stores them after the
-// last; the steps are the same FbChain<N>::step calls in the same order, so a stream cut into tiles at any frames gives the bits of one
+// last; the steps are the same Df2tChain<N>::step calls in the same order, so a stream cut into tiles at any frames gives the bits of one
 // call on the whole recording.  The only difference in the loop: the one-shot kernel may run the recurrence over the zero frames that
 // pad its last group of 8 (nothing of them is stored); the stream's state must not see them, so its ragged last group is stepped
 // frame by frame.  state layout: [B][n - 1][F][M] doubles -- element i of chain (f, b, m) at ((b (n - 1) + i) F + f) M + m -- so the
@@ -98,7 +65,7 @@ __device__ __forceinline__ void fb_tiles(double *fb_lds, const FilterbankCoef &c
     // chain lanes: lane c = f * mw + j
     const bool chain = tid < F * mw;
     const int cf = chain ? tid / mw : 0, cj = chain ? tid - (tid / mw) * mw : 0;
-    FbChain<N> ch;
+    Df2tChain<N> ch;
     ch.init(co, cf);
     // the chain's state word i (Resume only); all indices size_t
     auto sidx = [&](int i) -> size_t { return (((size_t)b * (N - 1) + i) * F + cf) * M + m0 + cj; };
@@ -213,18 +180,7 @@ static hipError_t fb_launch(const FilterbankCoef &co, const double *x, int F, in
 hipError_t launch_filterbank(const FilterbankCoef &co, const double *x, int F, int B, int T, int M, double *xf, hipStream_t stream)
 {
     if (F < 1 || F > MICLOC_MAX_BANDS || B < 1 || T < 1 || M < 1) return hipErrorInvalidValue;
-    switch (co.n) {
-        case 1: return fb_launch<1>(co, x, F, B, T, M, xf, stream);
-        case 2: return fb_launch<2>(co, x, F, B, T, M, xf, stream);
-        case 3: return fb_launch<3>(co, x, F, B, T, M, xf, stream);
-        case 4: return fb_launch<4>(co, x, F, B, T, M, xf, stream);
-        case 5: return fb_launch<5>(co, x, F, B, T, M, xf, stream);
-        case 6: return fb_launch<6>(co, x, F, B, T, M, xf, stream);
-        case 7: return fb_launch<7>(co, x, F, B, T, M, xf, stream);
-        case 8: return fb_launch<8>(co, x, F, B, T, M, xf, stream);
-        case 9: return fb_launch<9>(co, x, F, B, T, M, xf, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_iir_order(co.n, [&](auto N) { return fb_launch<decltype(N)::value>(co, x, F, B, T, M, xf, stream); });
 }
 
 // ---- the resumable form ----------------------------------------------------------------------------------------------------------
@@ -251,18 +207,7 @@ hipError_t launch_filterbank_tile(const FilterbankCoef &co, const double *x, int
                                   hipStream_t stream)
 {
     if (F < 1 || F > MICLOC_MAX_BANDS || B < 1 || T < 1 || M < 1 || !state) return hipErrorInvalidValue;
-    switch (co.n) {
-        case 1: return fb_tile_launch<1>(co, x, F, B, T, M, xf, state, stream);
-        case 2: return fb_tile_launch<2>(co, x, F, B, T, M, xf, state, stream);
-        case 3: return fb_tile_launch<3>(co, x, F, B, T, M, xf, state, stream);
-        case 4: return fb_tile_launch<4>(co, x, F, B, T, M, xf, state, stream);
-        case 5: return fb_tile_launch<5>(co, x, F, B, T, M, xf, state, stream);
-        case 6: return fb_tile_launch<6>(co, x, F, B, T, M, xf, state, stream);
-        case 7: return fb_tile_launch<7>(co, x, F, B, T, M, xf, state, stream);
-        case 8: return fb_tile_launch<8>(co, x, F, B, T, M, xf, state, stream);
-        case 9: return fb_tile_launch<9>(co, x, F, B, T, M, xf, state, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_iir_order(co.n, [&](auto N) { return fb_tile_launch<decltype(N)::value>(co, x, F, B, T, M, xf, state, stream); });
 }
 
 // ---- band sum + arg-max ---------------------------------------------------------------------------------------------------------

@@ -289,7 +289,17 @@ hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, 
 // filters with row f of `co` (the plans' band-pass coefficients, divided by a[0]); the bits of launch_bandpass_rzcc's `pre` band by band
 hipError_t launch_bands_bandpass(const FilterbankCoef &co, const double *xf, const double *h, int F, int B, int T, int M, int Ts, int shift,
                                  double *pre, hipStream_t stream);
-int bands_bandpass_chains(int nl);  // chains per workgroup the launcher takes for nl chains
+// Chains per workgroup the band-pass launchers of the complex bands (batch and stream) take for nl chains.  256 CUs; a workgroup is four
+// waves, one per SIMD, and 8.4 KB (16 chains) or 16.9 KB (32) of LDS; every instantiation with <= 32 chains runs at least four waves per
+// SIMD (DESIGN 4.17 and 4.18 have the registers), so four workgroups are resident per CU: up to 1024 workgroups run as one round.  Past
+// that the 64-chain form (33.8 KB) keeps the number of rounds down.
+inline int bands_bandpass_chains(int nl)
+{
+    constexpr int ROUND = 1024;
+    if (nl <= 16 * ROUND) return 16;
+    if (nl <= 32 * ROUND) return 32;
+    return 64;
+}
 
 // ---- wideband streaming: the resumable filterbank (filterbank.hip) and the band sum of a stream (stream_bands.hip) ----------------
 // fb_state: [B][n - 1][F][M] doubles (at least 256 B), zero-filled once; one tile x [B][T][M] -> xf [F][B][T][M]
@@ -310,11 +320,10 @@ hipError_t launch_stream_band_sum(const StreamBandsArgs &args, int F, int B, int
 
 // ---- wideband streaming, complex Beamformer: the band-pass tile of all bands' chains in one launch (stream_bands_complex.hip) --------
 // the complex stream's band-pass tile (launch_stream_complex_bandpass) over F * band_chains chains, band_chains = B 2M, state and staging
-// laid out by stream_complex_layout for F * B rows; band f filters with row f of `co`; chains: 0 (the launcher's choice) or 16 / 32 / 64
+// laid out by stream_complex_layout for F * B rows; band f filters with row f of `co`; chains: 0 (bands_bandpass_chains) or 16 / 32 / 64
 hipError_t launch_stream_bands_bandpass(const FilterbankCoef &co, const double *h, int F, int band_chains, int n, size_t row_stride,
                                         double *staging, int S, int chunk, void *state, const StreamComplexLayout &L, int chains,
                                         hipStream_t stream);
-int stream_bands_bandpass_chains(int nl);                    // chains per workgroup the launcher takes for nl chains
 int stream_bands_ring_depth(int Ks, int hop_chunks);         // windows one tile of Ks chunk rows can complete, plus the one cut at the end
 
 // ---- MUSIC (music.hip) ------------------------------------------------------------------------------------------------

@@ -32,6 +32,27 @@ def test_header_declares_and_lib_binds_the_symbols():
     assert "bands_complex.hip" in open(os.path.join(csrc, "Makefile")).read()
 
 
+def test_the_df2t_step_and_the_row_tile_pipeline_are_written_once():
+    """csrc/bandpass_rows.h holds the one DF2T step outside the encoder files (rzcc.hip and rzcc_sweep.hip are pinned by profile rounds and
+    keep theirs) and the tile pipeline of the complex chains' band-pass kernels, barrier included; what the source checks above ask of
+    bands_complex.hip and stream_bands_complex.hip holds for the header their kernels now come from."""
+    import glob
+
+    csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
+    strip = lambda path: re.sub(r"//[^\n]*", "", open(path).read())  # noqa: E731
+    files = [p for p in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+             if os.path.basename(p) not in ("rzcc.hip", "rzcc_sweep.hip")]
+    assert len(files) > 20 and os.path.join(csrc, "bandpass_rows.h") in files
+    hits = {os.path.basename(p): strip(p).count("z[N - 2] =") for p in files}
+    assert {k: v for k, v in hits.items() if v} == {"bandpass_rows.h": 1}, hits
+    for name in ("bands_complex.hip", "stream_bands_complex.hip"):
+        assert strip(os.path.join(csrc, name)).count("__syncthreads") == 0, name
+    code = strip(os.path.join(csrc, "bandpass_rows.h"))
+    assert "__syncthreads" in code
+    assert "atomic" not in code.lower() and "hipStreamSynchronize" not in code and "hipDeviceSynchronize" not in code and "hipMalloc" not in code
+    assert "bandpass_rows.h" in open(os.path.join(csrc, "Makefile")).read()  # an edit to the header rebuilds its objects
+
+
 def test_invalid_arguments_before_any_launch():
     """MICLOC_ERR_INVALID of the new entries, returned before any device call (the codes that need a plan -- NOT_SET, SHAPE, WORKSPACE --
     are in tests/test_hip_wideband_complex.py::test_status_codes)."""
