@@ -1,4 +1,4 @@
-"""The contract of the one-shot plan entries of csrc/api.hip, entry by entry: which status code each refusal gives and in which order the
+"""The contract of the one-shot plan entries of csrc/api_plan.hip and csrc/api_track.hip, entry by entry: which status code each refusal gives and in which order the
 checks run (nothing is launched by a refused call), and that every pipeline entry computes, bit for bit, what the chain
 micloc_stht_f64 -> micloc_bandpass_rzcc_f64 -> the stage entry of the same read-out computes.
 

@@ -107,7 +107,7 @@ try:
 finally:
     if "--keep" not in sys.argv:
         os.remove(tmp)
-objs = [os.path.join(CS, o) for o in "api.o stht.o beamform.o xylo.o synth.o covariance.o beamform_f32.o sweep.o rng.o design.o".split()]
+objs = [os.path.join(CS, o) for o in "api_plan.o api_track.o api_bands.o api_stream.o api_ops.o stht.o beamform.o xylo.o synth.o covariance.o beamform_f32.o sweep.o rng.o design.o".split()]
 os.makedirs(os.path.join(ROOT, "tools", "_variants"), exist_ok=True)
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(ROOT, "tools", "_variants", "libmicloc_hip_prof%s.so" % (("_" + abl) if abl else "")), obj] + objs)
 print("built variant", abl or "(plain)")

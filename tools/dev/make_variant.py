@@ -14,7 +14,7 @@ The shipped library has no run-time switches: a variant is the same sources with
 experiment that was rejected and moved out of the product) with a patch of tools/experiments/ applied to the copy.
 Only the translation unit that reads the constant is recompiled (in build_dev/variants/<name>/); the other objects are the product's.
 A variant of the `beamform` unit also recompiles csrc/beamform_lean.hip with VARIANT_WS_GENERAL_ONLY set: the fixed-shape kernel, which
-the product's api.o asks first at the sweep's shape, declines, so the variant's own beamform_ws_kernel is what runs and is measured there.
+the product's api_plan.o asks first at the sweep's shape, declines, so the variant's own beamform_ws_kernel is what runs and is measured there.
 A/B runs load it with `MICLOC_DEV_LIB=<path>` understood by the tools (never by the package), the stht_valu one is also what
 tests/test_hip_parity.py::test_stht_vector_form_still_exact loads."""
 import os

@@ -28,7 +28,7 @@ if ROOT not in sys.path:
 from tools.wideband_time import timed  # noqa: E402
 
 FS, M, G = 48_000, 7, 449
-SOURCES = ["haghighatshoarmuir2024_amd/csrc/stream_complex.hip", "haghighatshoarmuir2024_amd/csrc/api.hip", "haghighatshoarmuir2024_amd/csrc/rzcc.hip",
+SOURCES = ["haghighatshoarmuir2024_amd/csrc/stream_complex.hip", "haghighatshoarmuir2024_amd/csrc/api_stream.hip", "haghighatshoarmuir2024_amd/csrc/api_plan.hip", "haghighatshoarmuir2024_amd/csrc/api_internal.h", "haghighatshoarmuir2024_amd/csrc/rzcc.hip",
            "haghighatshoarmuir2024_amd/csrc/beamform.hip", "haghighatshoarmuir2024_amd/csrc/stht.hip", "haghighatshoarmuir2024_amd/streaming.py",
            "haghighatshoarmuir2024_amd/runtime.py", "haghighatshoarmuir2024_amd/beamformer.py", "tools/wideband_time.py", "tools/stream_complex_time.py"]
 

@@ -34,7 +34,7 @@ from tools.wideband_complex_time import BANDS, FS, G, M, build  # noqa: E402
 from tools.wideband_time import timed  # noqa: E402
 
 SOURCES = ["haghighatshoarmuir2024_amd/csrc/stream_bands_complex.hip", "haghighatshoarmuir2024_amd/csrc/stream_complex.hip",
-           "haghighatshoarmuir2024_amd/csrc/stream_bands.hip", "haghighatshoarmuir2024_amd/csrc/filterbank.hip", "haghighatshoarmuir2024_amd/csrc/api.hip",
+           "haghighatshoarmuir2024_amd/csrc/stream_bands.hip", "haghighatshoarmuir2024_amd/csrc/filterbank.hip", "haghighatshoarmuir2024_amd/csrc/api_stream.hip", "haghighatshoarmuir2024_amd/csrc/api_bands.hip", "haghighatshoarmuir2024_amd/csrc/api_plan.hip", "haghighatshoarmuir2024_amd/csrc/api_internal.h",
            "haghighatshoarmuir2024_amd/csrc/beamform.hip", "haghighatshoarmuir2024_amd/csrc/stht.hip", "haghighatshoarmuir2024_amd/streaming.py",
            "haghighatshoarmuir2024_amd/runtime.py", "tools/wideband_time.py", "tools/wideband_complex_time.py", "tools/wideband_complex_stream_time.py"]
 

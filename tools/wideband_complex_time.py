@@ -30,7 +30,7 @@ from tools.wideband_time import timed  # noqa: E402
 
 FS, M, G = 48_000, 7, 112
 BANDS = [[1000.0, 1600.0], [1600.0, 2400.0], [2400.0, 3400.0]]
-SOURCES = ["haghighatshoarmuir2024_amd/csrc/bands_complex.hip", "haghighatshoarmuir2024_amd/csrc/filterbank.hip", "haghighatshoarmuir2024_amd/csrc/api.hip",
+SOURCES = ["haghighatshoarmuir2024_amd/csrc/bands_complex.hip", "haghighatshoarmuir2024_amd/csrc/filterbank.hip", "haghighatshoarmuir2024_amd/csrc/api_bands.hip", "haghighatshoarmuir2024_amd/csrc/api_plan.hip", "haghighatshoarmuir2024_amd/csrc/api_internal.h",
            "haghighatshoarmuir2024_amd/csrc/rzcc.hip", "haghighatshoarmuir2024_amd/csrc/beamform.hip", "haghighatshoarmuir2024_amd/csrc/stht.hip",
            "haghighatshoarmuir2024_amd/wideband.py", "haghighatshoarmuir2024_amd/runtime.py", "tools/wideband_time.py", "tools/wideband_complex_time.py"]
 

@@ -27,7 +27,7 @@ if ROOT not in sys.path:
 from tools.wideband_time import BANDS, FS, G, M, build, timed  # noqa: E402
 
 SOURCES = ["haghighatshoarmuir2024_amd/csrc/filterbank.hip", "haghighatshoarmuir2024_amd/csrc/stream_bands.hip", "haghighatshoarmuir2024_amd/csrc/stream_windows.hip",
-           "haghighatshoarmuir2024_amd/csrc/api.hip", "haghighatshoarmuir2024_amd/csrc/rzcc.hip", "haghighatshoarmuir2024_amd/csrc/beamform.hip",
+           "haghighatshoarmuir2024_amd/csrc/api_stream.hip", "haghighatshoarmuir2024_amd/csrc/api_bands.hip", "haghighatshoarmuir2024_amd/csrc/api_plan.hip", "haghighatshoarmuir2024_amd/csrc/api_internal.h", "haghighatshoarmuir2024_amd/csrc/rzcc.hip", "haghighatshoarmuir2024_amd/csrc/beamform.hip",
            "haghighatshoarmuir2024_amd/csrc/stht.hip", "haghighatshoarmuir2024_amd/streaming.py", "haghighatshoarmuir2024_amd/runtime.py",
            "haghighatshoarmuir2024_amd/localization_demo_snn.py", "tools/wideband_time.py", "tools/wideband_stream_time.py"]
 
