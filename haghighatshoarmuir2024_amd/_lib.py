@@ -198,6 +198,12 @@ SYMBOLS = {
     "micloc_music_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                  c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_music_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "micloc_stream_music_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "micloc_stream_music_tile_f64": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
+    "micloc_stream_music_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_abi_version": (c_int, []),
     "micloc_status_string": (ctypes.c_char_p, [c_int]),
     "micloc_last_hip_error": (c_int, []),

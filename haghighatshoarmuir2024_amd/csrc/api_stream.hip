@@ -1,6 +1,7 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations): recordings that arrive tile by tile --
-// the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream, and the complex stream of F bands.
+// the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream, the complex stream of F bands, and the MUSIC stream.
 #include "api_internal.h"
+#include "stream_music.h"
 
 using namespace micloc;
 
@@ -676,6 +677,82 @@ int micloc_stream_complex_bands_status(const void *state, const void *win_state,
     status6[3] = ctl[STREAM_CLK_T];
     status6[4] = w[0];
     status6[5] = w[1];
+    return MICLOC_OK;
+}
+
+}  // extern "C"
+
+// ---- streaming, MUSIC (stream_music.hip; the rule: include/micloc_hip.h) ------------------------------------------------------------------
+namespace {
+
+// MICLOC_OK and *d, or the status of the rule's argument errors
+int sm_args(int B, int M, int L, int hop, int N, int nbin, int G, int k, int max_slices, MusicStreamDims *d)
+{
+    if (bad_batch(B) || M < 1 || L < 1 || hop < 1 || N < 2 || nbin < 1 || G < 1 || k < 0 || max_slices < 1) return MICLOC_ERR_INVALID;
+    return music_stream_dims(B, M, L, hop, N, nbin, G, k, max_slices, d) ? MICLOC_OK : MICLOC_ERR_SHAPE;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t micloc_stream_music_state_bytes(int B, int M, int L, int hop, int N, int nbin, int G, int k, int max_slices)
+{
+    MusicStreamDims d{};
+    if (sm_args(B, M, L, hop, N, nbin, G, k, max_slices, &d) != MICLOC_OK) return 0;
+    return music_stream_layout(d).total;
+}
+
+int micloc_stream_music_reset(void *state, size_t state_bytes, int B, int M, int L, int hop, int N, int nbin, int G, int k, int max_slices,
+                              void *stream)
+{
+    if (!state) return MICLOC_ERR_INVALID;
+    MusicStreamDims d{};
+    const int rc = sm_args(B, M, L, hop, N, nbin, G, k, max_slices, &d);
+    if (rc != MICLOC_OK) return rc;
+    const size_t total = music_stream_layout(d).total;
+    if (bad_ws(state, state_bytes, total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(state));
+    // clock 0, lfilter's zero state, no slice emitted, sum 0, and the zero padding of the frame rows (columns N .. Np, rows R .. Rp)
+    HIP_TRY(launch_zero_fill(state, total, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_music_tile_f64(void *state, size_t state_bytes, const double *x_tile, int B, int n, int M, int final_tile, const double *b,
+                                 const double *a, int ncoef, int L, int hop, int N, const double *W, int nbin, const double *steer_re,
+                                 const double *steer_im, int G, int k, int max_slices, double *power, int32_t *argmax, double *latest_spec,
+                                 int32_t *latest_argmax, double *slice_spec, int32_t *slice_sel, int32_t *slice_argmax, void *stream)
+{
+    if (!state || !x_tile || !b || !a || !W || !steer_re || !steer_im || n < 1 || ncoef < 1 || ncoef > MICLOC_MAX_IIR || a[0] == 0.0)
+        return MICLOC_ERR_INVALID;
+    MusicStreamDims d{};
+    const int rc = sm_args(B, M, L, hop, N, nbin, G, k, max_slices, &d);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, music_stream_layout(d).total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(state));
+    IirCoef co{};
+    co.n = ncoef;
+    for (int i = 0; i < ncoef; ++i) {
+        co.b[i] = b[i] / a[0];
+        co.a[i] = a[i] / a[0];
+    }
+    HIP_TRY(launch_music_stream_tile(d, co, x_tile, n, final_tile ? 1 : 0, state, W, steer_re, steer_im, power, argmax, latest_spec, latest_argmax,
+                                     slice_spec, slice_sel, slice_argmax, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+/* status[0] = samples pushed, [1] = slices emitted, [2] = open slices, [3] = 1 when the final tile left a leftover slice shorter than N
+ * (synchronises the stream) */
+int micloc_stream_music_status(const void *state, int *status4, void *stream)
+{
+    if (!state || !status4) return MICLOC_ERR_INVALID;
+    int clk[4];
+    HIP_TRY(hipMemcpyAsync(clk, state, sizeof(clk), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    status4[0] = clk[0];
+    status4[1] = clk[1];
+    status4[2] = clk[3];
+    status4[3] = clk[2];
     return MICLOC_OK;
 }
 

@@ -18,18 +18,15 @@
 //   4. music_steer_kernel    P[g] = sum over the selected bins, in that order, of mean_f |a(bin, g)^H X[:, f, bin]|^2, with the
 //                            steering table a = exp(-1j 2 pi freq_vec[bin] delays) computed by NumPy (the reference's own expression).
 //   5. music_readout_kernel  optional: power[b][g] = mean_s P[b][s][g]^2 and its first arg-max.
-#include "micloc_internal.h"
+// The arithmetic of every stage is music_rows.h's, which the stream (stream_music.hip) runs as well.
+#include "music_rows.h"
 
 namespace micloc {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int MU_FILT_STREAMS = 64;  // streams per filter tile
 constexpr int MU_FILT_CHUNK = 32;    // samples per stream and tile (Np is a multiple of it)
-constexpr int MU_KC = 32;            // k rows of W staged in LDS per step of the DFT
 
 __device__ __forceinline__ int slice_frames(const MusicDims &d, int s)
 {
@@ -69,12 +66,7 @@ __global__ __launch_bounds__(64) void music_filter_kernel(const double *__restri
             for (int i = 0; i < MU_FILT_CHUNK; ++i) {
                 double v = 0.0;
                 if (f < F && c0 + i < d.N) {
-                    const double xv = cur[i];
-                    // DF2T: y = fma(b0, x, z0); z_i = fma(-a_{i+1}, y, fma(b_{i+1}, x, z_{i+1}))
-                    const double y = NC > 1 ? __builtin_fma(co.b[0], xv, z[0]) : co.b[0] * xv;
-#pragma unroll
-                    for (int k = 0; k < NC - 1; ++k) z[k] = __builtin_fma(-co.a[k + 1], y, __builtin_fma(co.b[k + 1], xv, k + 1 < NC - 1 ? z[k + 1] : 0.0));
-                    v = y;
+                    v = music_df2t_step<NC>(co, cur[i], z);
                 }
                 tile[lane][i] = v;
             }
@@ -92,10 +84,8 @@ __global__ __launch_bounds__(64) void music_filter_kernel(const double *__restri
     }
 }
 
-// One workgroup: 4 waves x 16 frame rows, CT column tiles of 16 (one 16 x 16 accumulator each).  Per step of 32 k: the W rows
-// [k0, k0 + 32) x the workgroup's columns go to LDS; every lane holds 8 consecutive samples of its row (k = k0 + 8 (lane >> 4) + j in
-// k-step j), so the A operand is read as 64 contiguous bytes per lane and the B operand of k-step j is W row k0 + 8 (lane >> 4) + j.
-// Rows beyond R are padding of the frame buffer: computed, never stored (rows are independent in the product).
+// One workgroup: 64 frame rows x CT column tiles of 16 (music_dft_rows).  Rows beyond R are padding of the frame buffer: computed, never
+// stored (rows are independent in the product).
 template <int CT>
 __global__ __launch_bounds__(256) void music_dft_kernel(const double *__restrict__ xf, const double *__restrict__ W, double *__restrict__ X,
                                                         int Np, int Cp, long long R)
@@ -107,33 +97,8 @@ __global__ __launch_bounds__(256) void music_dft_kernel(const double *__restrict
     const int col0 = blockIdx.y * WC;
     const int ncol = min(WC, Cp - col0);
     const size_t row0 = (size_t)blockIdx.x * 64 + (size_t)w * 16;
-    const double *arow = xf + (row0 + c) * (size_t)Np + 8 * q;
     double4_t acc[CT];
-#pragma unroll
-    for (int t = 0; t < CT; ++t) acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-    double2_t a[4], an[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const double2_t *>(arow + 2 * i);
-    for (int k0 = 0; k0 < Np; k0 += MU_KC) {
-        __syncthreads();
-        for (int e = threadIdx.x; e < MU_KC * WC; e += 256) {
-            const int r = e / WC, cc = e - r * WC;
-            Ws[e] = cc < ncol ? W[(size_t)(k0 + r) * Cp + col0 + cc] : 0.0;
-        }
-        __syncthreads();
-        const bool more = k0 + MU_KC < Np;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) an[i] = more ? *reinterpret_cast<const double2_t *>(arow + k0 + MU_KC + 2 * i) : a[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const double av = a[j >> 1][j & 1];
-            const double *wr = Ws + (8 * q + j) * WC + c;
-#pragma unroll
-            for (int t = 0; t < CT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, wr[16 * t], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = an[i];
-    }
+    music_dft_rows<CT>(xf + (row0 + c) * (size_t)Np + 8 * q, W, Np, Cp, col0, ncol, Ws, acc);
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
         if (16 * t >= ncol) break;
@@ -151,28 +116,11 @@ __global__ __launch_bounds__(256) void music_select_kernel(const double *__restr
     extern __shared__ double pw[];
     const int bs = blockIdx.x;
     const int F = slice_frames(d, bs % d.S);
-    const double inv = (double)(d.M * F);
-    for (int j = threadIdx.x; j < d.nbin; j += blockDim.x) {
-        double sum = 0.0;
-        for (int m = 0; m < d.M; ++m) {
-            const double *xr = X + ((size_t)(bs * d.M + m) * d.Fmax) * d.Cp + 2 * j;
-            for (int f = 0; f < F; ++f) {
-                const double re = xr[(size_t)f * d.Cp], im = xr[(size_t)f * d.Cp + 1];
-                sum = sum + (re * re + im * im);
-            }
-        }
-        pw[j] = sum / inv;
-    }
+    for (int j = threadIdx.x; j < d.nbin; j += blockDim.x) pw[j] = music_bin_power(X, (size_t)bs, d.M, d.Fmax, F, d.Cp, j);
     __syncthreads();
-    // position of bin j in a stable ascending sort; the last ksel positions are the selection, in that order
+    // the last ksel positions of the stable ascending sort are the selection, in that order
     for (int j = threadIdx.x; j < d.nbin; j += blockDim.x) {
-        const double p = pw[j];
-        int rank = 0;
-        for (int i = 0; i < d.nbin; ++i) {
-            const double pi = pw[i];
-            rank += (pi < p) || (pi == p && i < j);
-        }
-        const int pos = rank - (d.nbin - d.ksel);
+        const int pos = music_bin_rank(pw, d.nbin, j) - (d.nbin - d.ksel);
         if (pos >= 0) sel[(size_t)bs * d.ksel + pos] = j;
     }
 }
@@ -185,25 +133,7 @@ __global__ __launch_bounds__(128) void music_steer_kernel(const double *__restri
     const int g = blockIdx.y * blockDim.x + threadIdx.x;
     if (g >= d.G) return;
     const int F = slice_frames(d, bs % d.S);
-    double P = 0.0;
-    for (int i = 0; i < d.ksel; ++i) {
-        const int j = sel[(size_t)bs * d.ksel + i];
-        double acc = 0.0;
-        for (int f = 0; f < F; ++f) {
-            double zr = 0.0, zi = 0.0;
-            for (int m = 0; m < d.M; ++m) {
-                const size_t ai = ((size_t)j * d.M + m) * d.G + g;
-                const double ar = sre[ai], aim = sim[ai];
-                const double *xr = X + ((size_t)(bs * d.M + m) * d.Fmax + f) * d.Cp + 2 * j;
-                const double re = xr[0], im = xr[1];
-                // conj(a) x = (ar re + ai im) + 1j (ar im - ai re)
-                zr = zr + (ar * re + aim * im);
-                zi = zi + (ar * im - aim * re);
-            }
-            acc = acc + (zr * zr + zi * zi);
-        }
-        P = P + acc / (double)F;
-    }
+    const double P = music_steer_sum(X, (size_t)bs, d.M, d.Fmax, F, d.Cp, sel + (size_t)bs * d.ksel, d.ksel, sre, sim, d.G, g);
     spec[(size_t)bs * d.G + g] = P;
 }
 
@@ -218,32 +148,14 @@ __global__ __launch_bounds__(256) void music_readout_kernel(const double *__rest
     for (int g = threadIdx.x; g < G; g += 256) {
         double p = 0.0;
         for (int s = 0; s < S; ++s) {
-            const double v = spec[((size_t)b * S + s) * G + g];
-            p = p + v * v;
+            p = music_power_add(p, spec[((size_t)b * S + s) * G + g]);
         }
         p = p / (double)S;
         if (power) power[(size_t)b * G + g] = p;
-        if (besti < 0 || p > best) {
-            best = p;
-            besti = g;
-        }
+        music_first_max(p, g, best, besti);
     }
-    bv[threadIdx.x] = best;
-    bi[threadIdx.x] = besti;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            const double ov = bv[threadIdx.x + h];
-            const int oi = bi[threadIdx.x + h];
-            // first maximum (np.argmax): the larger value, on equal values the smaller index
-            if (oi >= 0 && (bi[threadIdx.x] < 0 || ov > bv[threadIdx.x] || (ov == bv[threadIdx.x] && oi < bi[threadIdx.x]))) {
-                bv[threadIdx.x] = ov;
-                bi[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && argmax) argmax[b] = bi[0];
+    const int first = music_first_argmax(best, besti, bv, bi);  // np.argmax: the larger value, on equal values the smaller index
+    if (threadIdx.x == 0 && argmax) argmax[b] = first;
 }
 
 template <int CT>
@@ -283,29 +195,9 @@ hipError_t launch_music(const MusicDims &d, const IirCoef &co, const double *x, 
 {
     const MusicBuffers L = music_layout(d);
     hipError_t e = hipSuccess;
-    switch (co.n) {
-    case 1: e = launch_filter<1>(x, xf, d, co, st); break;
-    case 2: e = launch_filter<2>(x, xf, d, co, st); break;
-    case 3: e = launch_filter<3>(x, xf, d, co, st); break;
-    case 4: e = launch_filter<4>(x, xf, d, co, st); break;
-    case 5: e = launch_filter<5>(x, xf, d, co, st); break;
-    case 6: e = launch_filter<6>(x, xf, d, co, st); break;
-    case 7: e = launch_filter<7>(x, xf, d, co, st); break;
-    case 8: e = launch_filter<8>(x, xf, d, co, st); break;
-    default: e = launch_filter<MICLOC_MAX_IIR>(x, xf, d, co, st); break;
-    }
+    e = music_dispatch_order(co.n, [&](auto NC) { return launch_filter<decltype(NC)::value>(x, xf, d, co, st); });
     if (e != hipSuccess) return e;
-    const int tiles = d.Cp / 16;
-    switch (tiles < 8 ? tiles : 8) {
-    case 1: e = launch_dft<1>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 2: e = launch_dft<2>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 3: e = launch_dft<3>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 4: e = launch_dft<4>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 5: e = launch_dft<5>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 6: e = launch_dft<6>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    case 7: e = launch_dft<7>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    default: e = launch_dft<8>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); break;
-    }
+    e = music_dispatch_tiles(d.Cp, [&](auto CT) { return launch_dft<decltype(CT)::value>(xf, W, X, d.Np, d.Cp, L.R, L.Rp, st); });
     if (e != hipSuccess) return e;
     const unsigned BS = (unsigned)(d.B * d.S);
     hipLaunchKernelGGL(music_select_kernel, dim3(BS), dim3(256), (size_t)d.nbin * sizeof(double), st, X, sel, d);

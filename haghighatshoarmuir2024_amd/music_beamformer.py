@@ -7,8 +7,9 @@ reference method                         -> what runs here
                                             cores, bin power + top-k, steering power (csrc/music.hip)
   apply_to_signal     :178-247           -> the same kernels on all slices at once
   apply_to_template   :249-316           -> host synthesis (same draws from np.random) + the above
-plus a batched entry point the reference does not have:
+plus two entry points the reference does not have:
   localize_batch(sig[B,T,M], ...)        -> spectrum [B,S,G], the scripts' read-out power = mean_s P^2 [B,G] and arg-max [B]
+  streaming_localizer(batch, ...)        -> the same for recordings that arrive in tiles (streaming.MusicStreamingLocalizer)
 
 Parity contract: the in-band bins are those of `np.linspace(0, fs, N)` (labels k fs / (N - 1), the reference's quirk, used by the
 steering too); the steering table is `exp(-1j 2 pi freq delays)` computed by NumPy for every in-band bin, once per plan; exact ties of
@@ -47,6 +48,14 @@ class MusicPlan:
         self.sre = torch.from_numpy(np.ascontiguousarray(steer.real)).to(self.device)
         self.sim = torch.from_numpy(np.ascontiguousarray(steer.imag)).to(self.device)
         self.G = steer.shape[2]
+
+    def to_device(self, x):
+        """numpy / torch [B, T, M] -> contiguous float64 tensor on the plan's device (the streams' tiles)."""
+        import torch
+
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        return x.to(device=self.device, dtype=torch.float64).contiguous()
 
 
 class MUSIC:
@@ -208,6 +217,14 @@ class MUSIC:
         out = self._run(sig_batch, L, hop, len(starts), num_active_freq, num_fft_bin, want_spec=want_spectrum, want_readout=True,
                         want_sel=want_sel)
         return _add_peaks(out, self.doa_list, num_sources, min_separation, rel_threshold)
+
+    def streaming_localizer(self, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None):
+        """localize_batch for recordings that arrive in tiles (streaming.MusicStreamingLocalizer): push / push_replay tiles of any
+        length, the same bits after the last one.  The ValueErrors of localize_batch are raised here, before any device work."""
+        from .streaming import MusicStreamingLocalizer
+
+        return MusicStreamingLocalizer(self, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=total_frames,
+                                       max_tile=max_tile, max_slices=max_slices)
 
     def synthesize_batch(self, template, doas, device_delays=False):
         """Noise-free array signals of a batch of trials on the device (as SNNBeamformer.synthesize_batch)."""

@@ -829,3 +829,132 @@ class WidebandComplexStreamingLocalizer(_TileStream):
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up by the band sum")
         out = dict(power=self.power, argmax=self.argmax, band_power=self.band_power)
         return self._finish_windows(out)
+
+
+class MusicStreamingLocalizer(_TileStream):
+    """MUSIC (music_beamformer.MUSIC; what the reference deploys live in micloc/localization_demo_MUSIC.py, one `beamforming` call per
+    0.25 s pack) as ONE stream that arrives in tiles, with the results of `MUSIC.localize_batch` on the whole recording bit for bit,
+    whatever the tiling (include/micloc_hip.h "streaming, MUSIC").
+
+    A slice of apply_to_signal is this stream's window: window = L = fs * frame_duration samples, hop = L - overlap.  Every slice is
+    band-passed from zero state, every FFT frame is transformed on its own and the read-out mean_s P^2 is a left-to-right sum, so the
+    stream filters as the samples arrive, transforms a frame when its last sample arrives and closes a slice when its last sample
+    arrives; the final tile also closes the reference's leftover slice.  Tiles may have any length; one tile is one C call whose launches
+    depend on the tile's length only (the clock is a device word): one graph per tile length in push_replay().
+
+    latest_window() and windows() return slices: a slice's "power" row is its angular spectrum P [G], the row `beamforming` returns, and
+    its arg-max the row's first maximum; windows() adds `spectrum` (the same rows) and `sel` (the selected in-band bins)."""
+
+    def __init__(self, music, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None):
+        """music: music_beamformer.MUSIC; `batch` recordings are streamed in lock step.
+        num_active_freq, duration_overlap, num_fft_bin   as MUSIC.localize_batch's; the ValueErrors of that call are raised here.
+        total_frames  length of the recordings if known (the last tile is then recognised by itself, and a recording whose leftover slice
+                      is shorter than num_fft_bin is refused here); None: a live source -- pass final=True with the last tile.
+        max_tile      longest tile push() will be given.
+        max_slices    rows of the ring the slices are kept in (slice s in row s % max_slices); default: every slice of the recording
+                      when total_frames is given, else 64."""
+        self.music = music
+        self.B, self.M = int(batch), len(music.geometry)
+        self.T = None if total_frames is None else int(total_frames)
+        self.N, self.k = int(num_fft_bin), int(num_active_freq)
+        _, _, self.L, self.slice_hop = music.slice_plan(self.T if self.T is not None else 0, duration_overlap)  # (its ValueError: overlap >= L)
+        music._check([self.L], self.M, self.k, self.N)
+        if self.T is not None:
+            full, left = self.slices_of(self.T, self.L, self.slice_hop)
+            if left is not None:
+                music._check([left[1]], self.M, self.k, self.N)
+        self.max_tile = int(max_tile)
+        if self.max_tile < 1:
+            raise ValueError("max_tile must be at least 1")
+        if self.B < 1:
+            raise ValueError("batch must be at least 1")
+        # the stream's windows are the slices
+        self.window, self.hop = self.L, self.slice_hop
+        if max_slices is not None:
+            self.max_windows = int(max_slices)
+        else:
+            self.max_windows = 64 if self.T is None else max(1, self.slice_count(self.T, self.L, self.slice_hop))
+        self._check_ring(self.max_windows)
+        # ---- device ----
+        torch = runtime._torch()
+        self.plan = music.plan(self.N)
+        self.device = dev = self.plan.device
+        self.lib = _lib.load()
+        self.G, self.nbin = self.plan.G, self.plan.nbin
+        self.ksel = self.nbin if (self.k == 0 or self.k > self.nbin) else self.k
+        self.bb, self.aa, self.ncoef = runtime.pad_ba(*music.filterbank.ba_list[0])
+        self._dims = (self.B, self.M, self.L, self.slice_hop, self.N, self.nbin, self.G, self.ksel, self.max_windows)
+        self.nstate = int(self.lib.micloc_stream_music_state_bytes(*self._dims))
+        if self.nstate == 0:
+            raise _lib.MiclocError("micloc stream_music_state_bytes: the slices, the FFT length or the band do not fit the MUSIC stream's rule")
+        self.state = torch.empty(self.nstate, dtype=torch.uint8, device=dev)
+        self._alloc_results()
+        self.window_sel = torch.zeros((self.B, self.max_windows, self.ksel), dtype=torch.int32, device=dev)
+        _lib.check(self.lib.micloc_stream_music_reset(runtime._ptr(self.state), self.nstate, *self._dims, runtime._stream(dev)), "stream_music_reset")
+
+    # ---- the host mirror of the device's slice rule (stream_music.hip: ms_leftover) ---------------------------------------------
+    @staticmethod
+    def slices_of(T, L, hop):
+        """(full, leftover) of a recording of T samples: `full` slices [s hop, s hop + L) and the leftover slice (start, length), or None --
+        MUSIC.slice_plan's slices in integers."""
+        full = (T - L) // hop + 1 if T >= L else 0
+        rest = T - full * hop
+        return full, ((full * hop, rest) if 2 * rest > L else None)
+
+    @classmethod
+    def slice_count(cls, T, L, hop):
+        full, left = cls.slices_of(T, L, hop)
+        return full + (left is not None)
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _tile(self, x, n, final):
+        pl = self.plan
+        B, M, L, hop, N, nbin, G, ksel, ring = self._dims
+        _lib.check(self.lib.micloc_stream_music_tile_f64(runtime._ptr(self.state), self.nstate, runtime._ptr(x), B, n, M, int(final),
+                                                         runtime._dptr(self.bb), runtime._dptr(self.aa), self.ncoef, L, hop, N, runtime._ptr(pl.W), nbin,
+                                                         runtime._ptr(pl.sre), runtime._ptr(pl.sim), G, ksel, ring, runtime._ptr(self.power),
+                                                         runtime._ptr(self.argmax), runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax),
+                                                         runtime._ptr(self.window_power), runtime._ptr(self.window_sel), runtime._ptr(self.window_argmax),
+                                                         runtime._stream(self.device)), "stream_music_tile")
+
+    def _advance(self, n, final):
+        self.t += n
+        self.done = bool(final)
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def status(self):
+        """dict(pushed, slices, open, short_leftover): samples pushed (the device clock), slices emitted, slices begun and not yet emitted,
+        1 after a final tile whose leftover slice was shorter than num_fft_bin.  Synchronises the stream."""
+        st4 = (ctypes.c_int * 4)()
+        _lib.check(self.lib.micloc_stream_music_status(runtime._ptr(self.state), st4, runtime._stream(self.device)), "stream_music_status")
+        return dict(pushed=int(st4[0]), slices=int(st4[1]), open=int(st4[2]), short_leftover=int(st4[3]))
+
+    def _window_count(self):
+        return self.status()["slices"]
+
+    def windows(self):
+        """_TileStream.windows() over the slices, plus spectrum [B, k, G] (the rows of window_power under the name localize_batch gives
+        them) and sel [B, k, ksel], the selected in-band bins of every slice."""
+        w = super().windows()
+        rows = runtime._torch().arange(w["first"], w["count"], device=self.device) % self.max_windows
+        w.update(spectrum=w["window_power"], sel=self.window_sel.index_select(1, rows))
+        return w
+
+    def finish(self):
+        """-> dict(spectrum [B, S, G], power [B, G], argmax [B] int32, slice_argmax [B, S] int32, sel [B, S, ksel]) as device tensors: every
+        slice of the recording (a live source without total_frames: the max_slices newest, see windows())."""
+        self._need_done()
+        s = self.status()
+        if s["pushed"] != self.t:
+            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} samples")
+        if s["short_leftover"]:
+            full, left = self.slices_of(self.t, self.L, self.slice_hop)
+            self.music._check([left[1]], self.M, self.k, self.N)  # localize_batch's ValueError
+        if s["slices"] == 0:
+            raise ValueError(f"a signal of {self.t} samples has no slice of at least half a frame ({self.L} samples)")
+        if self.T is not None and self.max_windows < s["slices"]:
+            raise _lib.MiclocError(f"the recording has {s['slices']} slices and the ring keeps {self.max_windows}: raise max_slices (or read "
+                                   "windows() while the stream runs)")
+        w = self.windows()
+        return dict(spectrum=w["spectrum"], power=self.power, argmax=self.argmax, slice_argmax=w["window_argmax"], sel=w["sel"],
+                    slice_count=w["count"])

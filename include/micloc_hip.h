@@ -868,6 +868,41 @@ int micloc_music_f64(const double *x, int B, int T, int M, const double *b, cons
                      const double *W, int nbin, const double *steer_re, const double *steer_im, int G, int k, int32_t *sel, double *spec,
                      double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- streaming, MUSIC ---------------------------------------------------------------------------- */
+/* "MUSIC baseline beamformer" above for ONE stream of B recordings that arrive in tiles x_tile [B][n][M] of any lengths n >= 1.  A stream
+ * is fixed at reset by B, M, L, hop (1 <= hop <= L), N (2 <= N <= L), nbin (<= 4096), G, k (0 or 1 .. nbin) and max_slices; W, the steering
+ * table and the filter are those of micloc_music_f64 and are passed with every tile.
+ *   Results.  Full slice s = samples [s hop, s hop + L) is emitted by the tile that delivers sample s hop + L - 1; the final tile
+ *   (final_tile != 0) also emits the reference's leftover slice, start = (number of full slices) hop, when T - start > L / 2, with its
+ *   (T - start) / N frames.  An emitted slice writes its spectrum row [G], its selected bins [ksel] and its first arg-max into row
+ *   s % max_slices of slice_spec [B][max_slices][G], slice_sel [B][max_slices][ksel], slice_argmax [B][max_slices], and the newest one of
+ *   a tile into latest_spec [B][G], latest_argmax [B]; power [B][G] = (sum over the emitted slices, in ascending order, of spec^2) / their
+ *   number and argmax [B] its first maximum, after every tile that emits a slice.  All of them equal micloc_music_f64 on the samples
+ *   pushed so far, bit for bit, for every cut into tiles: the band-pass of a slice runs from zero state as the samples arrive, a frame
+ *   of N samples is transformed by the tile that completes it, the read-out is a left-to-right sum.  Every output may be NULL.
+ *   A leftover slice shorter than N (micloc_music_f64: MICLOC_ERR_SHAPE) is not emitted; status[3] reports it.
+ *   Launches.  A tile is cut into pieces of at most hop samples; a piece is four launches (filter, DFT of the completed frames, slice,
+ *   read-out + clock) on the caller's stream with no parallel branches.  The sequence depends on n only -- the clock is a device word --
+ *   so a tile length is ONE capturable hipGraph (not the final tile: final_tile is an argument).  Nothing allocates, synchronises with
+ *   the host or uses atomics; two streams with their own state may run on two HIP streams at once.
+ *   State (micloc_stream_music_state_bytes, 256-B aligned, zero-filled by _reset): the clock, 8 DF2T words per (trial, slot, mic), the
+ *   frame rows [.. ][Np] and DFT rows [..][Cp] of K = ceil(L / hop) + 1 slots per trial (slice s in slot s % K; one slot more than
+ *   slices can be open, so that a slot rests while the kernels behind the filter still read it), sum_s spec^2 [B][G], the slots' spectra
+ *   [B][K][G].  It does not grow with the stream.
+ *   micloc_stream_music_status: {samples pushed, slices emitted, slices open, 1 after a leftover slice shorter than N}; it synchronises.
+ *   Status, before any launch: MICLOC_ERR_INVALID for NULL (state, x_tile, b, a, W, steer_re, steer_im, status), B outside 1..65535, M, L,
+ *   hop, nbin, G, max_slices or n < 1, N < 2, k < 0, ncoef outside 1..MICLOC_MAX_IIR, a[0] == 0; MICLOC_ERR_SHAPE for hop > L, N > L,
+ *   k > nbin, nbin > N or > 4096, L > 2^28 or more than 2^31 frame rows; MICLOC_ERR_WORKSPACE for a short or misaligned state.  The size
+ *   function returns 0 for such arguments. */
+size_t micloc_stream_music_state_bytes(int B, int M, int L, int hop, int N, int nbin, int G, int k, int max_slices);
+int micloc_stream_music_reset(void *state, size_t state_bytes, int B, int M, int L, int hop, int N, int nbin, int G, int k, int max_slices,
+                              void *stream);
+int micloc_stream_music_tile_f64(void *state, size_t state_bytes, const double *x_tile, int B, int n, int M, int final_tile, const double *b,
+                                 const double *a, int ncoef, int L, int hop, int N, const double *W, int nbin, const double *steer_re,
+                                 const double *steer_im, int G, int k, int max_slices, double *power, int32_t *argmax, double *latest_spec,
+                                 int32_t *latest_argmax, double *slice_spec, int32_t *slice_sel, int32_t *slice_argmax, void *stream);
+int micloc_stream_music_status(const void *state, int *status4, void *stream);
+
 /* ---- misc ------------------------------------------------------------------------------------- */
 int micloc_abi_version(void);
 const char *micloc_status_string(int status);
