@@ -48,9 +48,14 @@ class Beamformer:
         b, a = self.bandpass_filter
         key = (len(self.geometry), np.asarray(self.kernel).tobytes(), np.asarray(b).tobytes(), np.asarray(a).tobytes())
         if self._plan is None or key != self._plan_key:
-            self._plan = runtime.Plan(len(self.geometry), self.kernel, b, a, robust_width=1, bipolar=False, device=self.device)
+            self._plan = self.new_plan()
             self._plan_key = key
         return self._plan
+
+    def new_plan(self):
+        """A fresh, un-cached device plan (own coefficient tables and workspace), as SNNBeamformer.new_plan: one per stream of tiles."""
+        b, a = self.bandpass_filter
+        return runtime.Plan(len(self.geometry), self.kernel, b, a, robust_width=1, bipolar=False, device=self.device)
 
     def apply_to_signal(self, bf_mat, sig_in, to_host=True):
         """Reference :260-292.  to_host=False (not in the reference): the complex T x G result stays on the device (a complex128 torch

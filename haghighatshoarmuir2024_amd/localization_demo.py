@@ -10,26 +10,14 @@ T x G product the reference materialises is never formed), `localizer()` all ban
 """
 import numpy as np
 
-from .beamformer import Beamformer
-from .filterbank import ButterworthFilterbank
+from .utils import active_packs
+from .wideband import WidebandBeamformerLocalizer, complex_band, design_bands
 
 
 class Demo:
     def __init__(self, geometry, freq_bands, doa_list, recording_duration, kernel_duration, fs, device=None):
-        freq_bands = np.asarray(freq_bands)
-        if freq_bands.ndim == 1:
-            freq_bands = freq_bands.reshape(1, -1)
-        self.beamfs, self.bf_mats = [], []
-        for freq_range in freq_bands:
-            freq_mid = np.mean(freq_range)
-            beamf = Beamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, fs=fs, device=device)
-            self.beamfs.append(beamf)
-            time_temp = np.arange(0, recording_duration, step=1 / fs)
-            sig_temp = np.sin(2 * np.pi * freq_mid * time_temp)
-            bf_vecs, _ = beamf.design_from_template(template=(time_temp, sig_temp), doa_list=doa_list)
-            self.bf_mats.append(bf_vecs)
-        order = 2
-        self.filterbank = ButterworthFilterbank(freq_bands=freq_bands, order=order, fs=fs, device=device)
+        self.beamfs, self.bf_mats, self.filterbank = design_bands(freq_bands, recording_duration, fs, complex_band(geometry, doa_list, kernel_duration, fs, device),
+                                                                  order=2, device=device)
         self.doa_list = np.asarray(doa_list)
         self.recording_duration = recording_duration
         self.kernel_duration = kernel_duration
@@ -48,19 +36,14 @@ class Demo:
     def process_frame(self, data, rel_threshold=0.0001):
         """One recorded pack (integer samples, last channel unused as on the devkit, reference :127-137) ->
         DoA in degrees, or NaN when the pack is below the activity threshold."""
-        data = np.asarray(data)
-        max_value = np.iinfo(data.dtype).max if np.issubdtype(data.dtype, np.integer) else 1.0
-        threshold = rel_threshold * max_value
-        sig = np.asarray(data[:, :-1], dtype=np.float64)
-        if np.sqrt(np.mean(sig**2)) < threshold:
+        sig, active = active_packs(np.asarray(data)[None], rel_threshold)
+        if not active[0]:
             return np.nan
-        return self.doa_list[int(np.argmax(self.power_grid(sig)))] * 180 / np.pi
+        return self.doa_list[int(np.argmax(self.power_grid(sig[0])))] * 180 / np.pi
 
     def localizer(self):
         """The batched form of this demo's chain (wideband.WidebandBeamformerLocalizer over the same beamformers, matrices and
         filterbank): B packs per call, every band's chain in one batch, the band sum and its arg-max on the device."""
-        from .wideband import WidebandBeamformerLocalizer
-
         loc = WidebandBeamformerLocalizer(self.beamfs, self.bf_mats, self.filterbank)
         loc.doa_list = self.doa_list
         return loc
@@ -69,11 +52,8 @@ class Demo:
         """`process_frame` for a batch of recorded packs [B, T, num_mic + 1] of one length: DoA in degrees per pack [B], NaN for the
         packs below the activity threshold (tested per pack, on the host, as in the loop); the others go through ONE
         localizer().localize_batch call."""
-        packs = np.asarray(packs)
-        max_value = np.iinfo(packs.dtype).max if np.issubdtype(packs.dtype, np.integer) else 1.0
-        sig = np.asarray(packs[:, :, :-1], dtype=np.float64)
-        active = np.asarray([np.sqrt(np.mean(s**2)) >= rel_threshold * max_value for s in sig], dtype=bool)  # process_frame's test, pack by pack
-        doa = np.full(len(packs), np.nan)
+        sig, active = active_packs(packs, rel_threshold)  # process_frame's test, pack by pack
+        doa = np.full(len(sig), np.nan)
         if active.any():
             idx = self.localizer().localize_batch(np.ascontiguousarray(sig[active]))["argmax"].cpu().numpy()
             doa[active] = self.doa_list[idx] * 180 / np.pi

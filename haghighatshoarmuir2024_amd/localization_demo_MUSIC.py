@@ -13,6 +13,7 @@ which allows int(800 / 23.4375) = 34; this Demo fails the same way, on the first
 import numpy as np
 
 from .music_beamformer import MUSIC
+from .utils import active_packs
 
 METHODS = ["peak", "periodic_ml", "trimmed_periodic_ml"]
 
@@ -44,15 +45,6 @@ class Demo:
         idx = np.arange(-half // 2, half // 2 + 1) - np.argmax(spec)
         return np.angle(np.mean(spec[idx] * np.exp(1j * doa_list[idx])))
 
-    @staticmethod
-    def _active(packs, rel_threshold):
-        """packs [B, T, num_mic + 1] -> (float signals [B, T, num_mic] without the devkit's empty last channel, active [B] bool): the
-        loop's activity test (reference :142-165), pack by pack."""
-        packs = np.asarray(packs)
-        max_value = np.iinfo(packs.dtype).max if np.issubdtype(packs.dtype, np.integer) else 1.0
-        sig = np.asarray(packs[:, :, :-1], dtype=np.float64)
-        return sig, np.asarray([np.sqrt(np.mean(s**2)) >= rel_threshold * max_value for s in sig], dtype=bool)
-
     def power_grid(self, data):
         """float [T, num_mic] -> angular power spectrum [G] of the pack (numpy): MUSIC.beamforming, ValueErrors included."""
         return self.music.beamforming(np.ascontiguousarray(data, dtype=np.float64), num_active_freq=self.num_active_freq, num_fft_bin=self.num_fft_bin)
@@ -60,7 +52,7 @@ class Demo:
     def process_frame(self, data, rel_threshold=0.0001, method="peak"):
         """One recorded pack (integer samples, last channel unused as on the devkit) -> DoA in degrees, or NaN when the pack is below the
         activity threshold."""
-        sig, active = self._active(np.asarray(data)[None], rel_threshold)
+        sig, active = active_packs(np.asarray(data)[None], rel_threshold)
         if not active[0]:
             return np.nan
         return self.estimate_doa(self.power_grid(sig[0]), method) / np.pi * 180
@@ -69,7 +61,7 @@ class Demo:
         """`process_frame` for a batch of recorded packs [B, T, num_mic + 1] of one length: DoA in degrees per pack [B], NaN for the packs
         below the activity threshold; the others go through ONE MUSIC.localize_batch call (a pack is one slice: frame_duration is its
         length), the estimator runs on the host per pack."""
-        sig, active = self._active(packs, rel_threshold)
+        sig, active = active_packs(packs, rel_threshold)
         doa = np.full(len(sig), np.nan)
         if active.any():
             music = self.music

@@ -531,51 +531,6 @@ def band_sum(band_power, want_power=True, want_argmax=True):
     return power, argmax
 
 
-def snn_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
-    """micloc_snn_pipeline_bands_f64: the filterbank `ba_list`, per band the SNN pipeline of plans[f] (neuron kernel and bf_mat set) on its
-    slice, the band sum -- x [B, T, M] on the plans' device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults
-    to it), dict(window_power [B, nW, G], window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G].
-    `ws`: a runtime.Workspace to take the scratch from (default: the first plan's)."""
-    torch = _torch()
-    lib = _lib.load()
-    F = len(plans)
-    if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
-        raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
-    if len(ba_list) != F:
-        raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
-    bb, aa, n = pad_ba_list(ba_list)
-    p0 = plans[0]
-    if any(p.num_mic != p0.num_mic for p in plans) or any(p.G != p0.G for p in plans):
-        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
-    B, T, M = x.shape
-    if M != p0.num_mic:
-        raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {p0.num_mic}!")
-    G, dev = p0.G, p0.device
-    handles = (ctypes.c_void_p * F)(*[p.handle.value for p in plans])
-    if window is None:
-        nW, win, hp = None, 0, 0
-    else:
-        nW, win, hp = p0.window_count(T, window, hop)
-        for p in plans[1:]:
-            p.window_count(T, window, hop)  # ValueError naming that band's quantum
-        if B * nW > 0x7FFFFFFF:
-            raise ValueError(f"{B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
-    rows = (B,) if nW is None else (B, nW)
-    power = torch.empty(rows + (G,), dtype=torch.float64, device=dev)
-    argmax = torch.empty(rows, dtype=torch.int32, device=dev)
-    bp = torch.empty((F,) + rows + (G,), dtype=torch.float64, device=dev) if want_band_power else None
-    nbytes = lib.micloc_snn_bands_workspace_bytes(handles, F, B, T, win, hp)
-    if nbytes == 0:
-        raise ValueError("micloc snn_bands_workspace_bytes: the plans, the batch or the windows do not fit the band pipeline's rule")
-    buf = (ws or p0.ws).get(nbytes)
-    _lib.check(lib.micloc_snn_pipeline_bands_f64(handles, F, _dptr(bb), _dptr(aa), n, _ptr(x), B, T, win, hp, _ptr(bp), _ptr(power), _ptr(argmax),
-                                                 _ptr(buf), nbytes, _stream(dev)), "snn_pipeline_bands")
-    out = dict(power=power, argmax=argmax) if nW is None else dict(window_power=power, window_argmax=argmax)
-    if want_band_power:
-        out["band_power"] = bp
-    return out
-
-
 def _band_handles(plans):
     """The checks every band entry shares -> (F, the C array of plan handles)."""
     F = len(plans)
@@ -587,13 +542,10 @@ def _band_handles(plans):
     return F, (ctypes.c_void_p * F)(*[p.handle.value for p in plans])
 
 
-def beamformer_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
-    """micloc_beamformer_pipeline_bands_f64: the filterbank `ba_list`, then the complex Beamformer chains of ALL bands as one batch (one
-    STHT launch, one band-pass launch, plans[f]'s complex bf_mat per band, one time reduction), the band sum -- x [B, T, M] on the plans'
-    device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults to it), dict(window_power [B, nW, G],
-    window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G], band by band the bits of
-    plans[f].beamformer_pipeline on that band's filterbank output.  `ws`: a runtime.Workspace to take the scratch from (default: the
-    first plan's)."""
+def _pipeline_bands(name, row_limit, plans, ba_list, x, window, hop, want_band_power, ws):
+    """The caller of a band pipeline entry: the checks, the result tensors, the scratch, the call.  name: "snn" (micloc_snn_pipeline_bands_f64
+    with micloc_snn_bands_workspace_bytes) or "beamformer" (micloc_beamformer_pipeline_bands_f64 with micloc_beamformer_bands_workspace_bytes);
+    row_limit(F, B, nW) -> (rows of one windowed call, how the message names them)."""
     torch = _torch()
     lib = _lib.load()
     F, handles = _band_handles(plans)
@@ -613,22 +565,42 @@ def beamformer_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_ban
         nW, win, hp = p0.window_count(T, window, hop)
         for p in plans[1:]:
             p.window_count(T, window, hop)  # ValueError naming that band's quantum
-        if F * B * nW > 0x7FFFFFFF:
-            raise ValueError(f"{F} bands x {B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
+        rows, factors = row_limit(F, B, nW)
+        if rows > 0x7FFFFFFF:
+            raise ValueError(f"{factors} exceed the 2^31 - 1 rows of one call")
     rows = (B,) if nW is None else (B, nW)
     power = torch.empty(rows + (G,), dtype=torch.float64, device=dev)
     argmax = torch.empty(rows, dtype=torch.int32, device=dev)
     bp = torch.empty((F,) + rows + (G,), dtype=torch.float64, device=dev) if want_band_power else None
-    nbytes = lib.micloc_beamformer_bands_workspace_bytes(handles, F, B, T, win, hp)
+    nbytes = getattr(lib, f"micloc_{name}_bands_workspace_bytes")(handles, F, B, T, win, hp)
     if nbytes == 0:
-        raise ValueError("micloc beamformer_bands_workspace_bytes: the plans, the batch or the windows do not fit the band pipeline's rule")
+        raise ValueError(f"micloc {name}_bands_workspace_bytes: the plans, the batch or the windows do not fit the band pipeline's rule")
     buf = (ws or p0.ws).get(nbytes)
-    _lib.check(lib.micloc_beamformer_pipeline_bands_f64(handles, F, _dptr(bb), _dptr(aa), n, _ptr(x), B, T, win, hp, _ptr(bp), _ptr(power),
-                                                        _ptr(argmax), _ptr(buf), nbytes, _stream(dev)), "beamformer_pipeline_bands")
+    _lib.check(getattr(lib, f"micloc_{name}_pipeline_bands_f64")(handles, F, _dptr(bb), _dptr(aa), n, _ptr(x), B, T, win, hp, _ptr(bp), _ptr(power),
+                                                                 _ptr(argmax), _ptr(buf), nbytes, _stream(dev)), f"{name}_pipeline_bands")
     out = dict(power=power, argmax=argmax) if nW is None else dict(window_power=power, window_argmax=argmax)
     if want_band_power:
         out["band_power"] = bp
     return out
+
+
+def snn_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
+    """micloc_snn_pipeline_bands_f64: the filterbank `ba_list`, per band the SNN pipeline of plans[f] (neuron kernel and bf_mat set) on its
+    slice, the band sum -- x [B, T, M] on the plans' device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults
+    to it), dict(window_power [B, nW, G], window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G].
+    `ws`: a runtime.Workspace to take the scratch from (default: the first plan's)."""
+    return _pipeline_bands("snn", lambda F, B, nW: (B * nW, f"{B} trials x {nW} windows"), plans, ba_list, x, window, hop, want_band_power, ws)
+
+
+def beamformer_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_band_power=False, ws=None):
+    """micloc_beamformer_pipeline_bands_f64: the filterbank `ba_list`, then the complex Beamformer chains of ALL bands as one batch (one
+    STHT launch, one band-pass launch, plans[f]'s complex bf_mat per band, one time reduction), the band sum -- x [B, T, M] on the plans'
+    device -> dict(power [B, G], argmax [B]) or, with `window` (frames; `hop` defaults to it), dict(window_power [B, nW, G],
+    window_argmax [B, nW]); want_band_power: also band_power [F, B, G] / [F, B, nW, G], band by band the bits of
+    plans[f].beamformer_pipeline on that band's filterbank output.  `ws`: a runtime.Workspace to take the scratch from (default: the
+    first plan's)."""
+    return _pipeline_bands("beamformer", lambda F, B, nW: (F * B * nW, f"{F} bands x {B} trials x {nW} windows"), plans, ba_list, x, window, hop,
+                           want_band_power, ws)
 
 
 def beamformer_bands_bandpass(plans, xf, one_launch=True, pre=None, h=None):

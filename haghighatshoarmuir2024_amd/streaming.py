@@ -37,10 +37,15 @@ the frames behind the last whole chunk and the accumulators on the device, tiles
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
 
 THE CLASSES: StreamingLocalizer (one SNNBeamformer chain), WidebandStreamingLocalizer (a filterbank and one StreamingLocalizer per band),
-ComplexStreamingLocalizer and WidebandComplexStreamingLocalizer (a filterbank and ONE complex stream of bands x batch rows) share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
+ComplexStreamingLocalizer, WidebandComplexStreamingLocalizer (a filterbank and ONE complex stream of bands x batch rows) and
+MusicStreamingLocalizer share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
 _TileStream states once: what a window / hop / max_windows may be, which tiles are accepted, how a tile length becomes a captured graph, how
-the ring of windows is read, what finish() refuses about it.  A class adds its own state and scratch, the launches of its tile (_tile), the
-host mirror of its clock (_advance), status() and its own refusals in finish().
+the ring of windows is read, what finish() refuses about it.  It also holds the pieces more than one class launches: the STHT front of a tile
+for any number of rows (_stht_tile / _keep_history, with _set_stht, _alloc_stht and _set_wrap in the constructor), the read-out entry in its
+plain or its windowed form (_localize_tile, with _reset_window_state), the host clock (_advance) and the refusals of finish() that the SNN
+streams share (_need_spikes_final) and that the complex streams share (_need_clock).  _FilterbankFront is the filterbank of the two wideband
+classes: the rules for the bands and wrap_tail, the state, the launch.  A class adds its own state and scratch, the launches of its tile
+(_tile), what its clock mirrors beyond the frame count (StreamingLocalizer's window base), status() and its own refusals in finish().
 """
 import ctypes
 
@@ -54,7 +59,7 @@ class _TileStream:
     """The tile protocol of the localizers (module docstring, THE CLASSES).  A subclass supplies
       _tile(x, n, final)   the launches of one tile and nothing else: no allocation, no synchronisation, no absolute time by value (the clock
                            is a device word), so that a tile of a given length is ONE replayable hipGraph;
-      _advance(n, final)   the host mirror of the clock and the end-of-stream bookkeeping;
+      _advance(n, final)   (optional) what the host mirrors of the device clock beyond the frame count and the end of the stream;
       _before_slide(n)     (optional) host work that must see the state in front of the tile's launches;
       _window_count()      (optional) windows emitted so far, where they are not counted in `wst`
     and sets plan, device, lib, B, M, G, T and max_tile before it uses the helpers of the constructor below."""
@@ -103,26 +108,45 @@ class _TileStream:
         self.done = False
         self._seen, self._graphs = set(), {}
 
-    def _reset_window_state(self, state_bytes, reset, name, hint=""):
-        """wst, the device state of the open windows (single-band classes): sized by `state_bytes`, zero-filled by `reset`."""
+    def _reset_window_state(self, name, lead=None, who="the plan", hint=""):
+        """wst / nwst, the device state of the open windows (None / 0 without window=): sized by micloc_<name>_state_bytes, zero-filled by
+        micloc_<name>_reset.  lead: the leading arguments of both entries (default: this stream's plan and batch)."""
+        self.wst, self.nwst = None, 0
         if self.window is None:
             return
-        self.nwst = int(state_bytes(self.plan.handle, self.B, self.window, self.hop, self.max_windows))
+        lead = (self.plan.handle, self.B) if lead is None else lead
+        wargs = (self.window, self.hop, self.max_windows)
+        self.nwst = int(getattr(self.lib, f"micloc_{name}_state_bytes")(*lead, *wargs))
         if self.nwst == 0:
-            raise _lib.MiclocError(f"micloc {name}_state_bytes: the plan cannot serve the windowed read-out{hint}")
+            raise _lib.MiclocError(f"micloc {name}_state_bytes: {who} cannot serve the windowed read-out{hint}")
         torch = runtime._torch()
         self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=self.device)
-        _lib.check(reset(self.plan.handle, self.B, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
-                         runtime._stream(self.device)), f"{name}_reset")
+        _lib.check(getattr(self.lib, f"micloc_{name}_reset")(*lead, runtime._ptr(self.wst), self.nwst, *wargs, runtime._stream(self.device)),
+                   f"{name}_reset")
 
-    def _set_wrap(self, wrap_tail):
-        """self.wrap: np.roll's wrap-around rows [batch, L // 2, M] on the device, or None (zeros)."""
+    def _set_stht(self, kernel):
+        """L, halo and C of the STHT front: the taps, the frames of history in front of a tile (L - 1, rounded up to 8), the planar rows."""
+        self.L = len(kernel)
+        self.halo = -(-(self.L - 1) // 8) * 8
+        self.C = 2 * self.M
+
+    def _alloc_stht(self, rows):
+        """The tile workspace of _stht_tile for `rows` trials, allocated once: the history (zero: the FIR's zero state), [history | tile]
+        frames and their planar STHT output."""
+        torch = runtime._torch()
+        self.hist = torch.zeros((rows, self.halo, self.M), dtype=torch.float64, device=self.device)
+        self.ext = torch.empty((rows * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=self.device)
+        self.h = torch.empty((rows * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=self.device)
+
+    def _set_wrap(self, wrap_tail, bands=False):
+        """self.wrap: np.roll's wrap-around rows [batch, L // 2, M] on the device, or None (zeros).  bands: [F, batch, L // 2, M], already
+        checked (_FilterbankFront), as the F * batch trials of one stream."""
         self.wrap = None
         if wrap_tail is not None:
             wrap_tail = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
-            if tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
+            if not bands and tuple(wrap_tail.shape) != (self.B, self.L // 2, self.M):
                 raise ValueError(f"wrap_tail must be [batch, {self.L // 2}, num_mic]")
-            self.wrap = wrap_tail
+            self.wrap = wrap_tail.reshape(-1, self.L // 2, self.M)
 
     # ---- one tile -------------------------------------------------------------------------------------------------------
     def _check_tile(self, B, n, M, final):
@@ -140,29 +164,47 @@ class _TileStream:
             raise ValueError("the stream's clock is a 32-bit frame counter")
         return bool(final)
 
-    def _stht_tile(self, x, n, clock, spare_rows=0):
-        """The front of a single-band tile: [history | tile] into `ext`, its STHT into the planar rows `h` (+ spare_rows rows), np.roll's
-        wrap-around rows while the frames-pushed word of `clock` is below L / 2.  -> (ext, h, Ts)"""
-        lib, plan, B, M = self.lib, self.plan, self.B, self.M
+    def _stht_tile(self, x, n, clock, rows=None, spare_rows=0):
+        """The front of a tile of `rows` trials (default: the batch; a stream of bands: F * batch, ONE STHT launch for all of them):
+        [history | tile] into `ext`, its STHT into the planar rows `h` (+ spare_rows rows), np.roll's wrap-around rows while the
+        frames-pushed word of `clock` is below L / 2.  -> (ext, h, Ts)"""
+        lib, plan, M = self.lib, self.plan, self.M
+        R = self.B if rows is None else rows
         st = runtime._stream(self.device)
         Text = self.halo + n
-        ext = self.ext[: B * Text * M].view(B, Text, M)  # contiguous [history | tile] of this tile length
+        ext = self.ext[: R * Text * M].view(R, Text, M)  # contiguous [history | tile] of this tile length
         ext[:, : self.halo, :].copy_(self.hist)
         ext[:, self.halo :, :].copy_(x)
         Ts = plan.padded_T(Text)
-        h = self.h[: (B * self.C + spare_rows) * Ts]
-        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), B, Text, runtime._ptr(h), Ts, st), "stht")
+        h = self.h[: (R * self.C + spare_rows) * Ts]
+        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), R, Text, runtime._ptr(h), Ts, st), "stht")
         # in-phase[t] = x[T - L/2 + t] for t < L/2 (zeros if the caller could not know them); a no-op later
-        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(clock), runtime._ptr(h), B, Ts, self.halo, n, runtime._ptr(self.wrap), st),
+        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(clock), runtime._ptr(h), R, Ts, self.halo, n, runtime._ptr(self.wrap), st),
                    "stream_wrap_rows")
         return ext, h, Ts
 
     def _keep_history(self, ext):
-        """The back of a single-band tile: the last `halo` frames of [history | tile] for the next tile's quadrature FIR."""
+        """The back of a tile: the last `halo` frames of [history | tile] for the next tile's quadrature FIR."""
         self.hist.copy_(ext[:, ext.shape[1] - self.halo :, :])
+
+    def _localize_tile(self, name, *tile):
+        """The read-out launches of a tile: micloc_<name>_f64(*tile, stream) or, with window=, micloc_<name>_windows_f64 -- the same
+        launches with the window read-out in front of the commit -- which takes the window state, the rule and the ring behind `tile`."""
+        st = runtime._stream(self.device)
+        if self.window is None:
+            _lib.check(getattr(self.lib, f"micloc_{name}_f64")(*tile, st), name)
+        else:
+            _lib.check(getattr(self.lib, f"micloc_{name}_windows_f64")(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
+                                                                       runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
+                                                                       runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st),
+                       f"{name}_windows")
 
     def _before_slide(self, n):
         pass
+
+    def _advance(self, n, final):
+        self.t += n
+        self.done = bool(final)
 
     def push(self, x_tile, final=None):
         """x_tile [batch, n, M] (numpy or device tensor); n <= max_tile and, except for the last tile, a multiple of TILE_MULTIPLE.
@@ -237,6 +279,20 @@ class _TileStream:
         if not self.done:
             raise _lib.MiclocError(f"the stream is incomplete: {self.t} frames pushed and no final tile")
 
+    def _need_spikes_final(self, s, cap, whose="the", by=""):
+        """finish()'s refusals of the SNN streams, from status(): an overflowed encoder, frames the raster window (`cap` frames) left behind."""
+        if s["overflow"]:
+            raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
+                                   "one-shot call, which redoes such streams exactly")
+        if s["lag_failures"] or s["frames"] != self.t:
+            raise _lib.MiclocError(f"{whose} raster window ({cap} frames) slid past frames whose spikes were not final yet "
+                                   f"({s['frames']} of {self.t} frames beamformed{by}): raise lag_frames")
+
+    def _need_clock(self, s):
+        """finish()'s refusal of the complex streams, from status(): every frame pushed has been contracted and none waits in the carry."""
+        if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
+            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
+
     def _finish_windows(self, out):
         """finish()'s windowed tail: `out` with window_power [B, nW, G], window_argmax [B, nW] and window_count = nW, every window of the
         recording (a live source without total_frames: the max_windows newest, see windows())."""
@@ -249,6 +305,44 @@ class _TileStream:
             w = self.windows()
             out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
         return out
+
+
+class _FilterbankFront:
+    """The filterbank in front of a wideband stream (mixed into the two wideband classes): what the bands and `wrap_tail` must look like,
+    the DF2T states of every band's section on the device, and the launch that filters a tile into xf [F][B][n][M]."""
+
+    def _check_bands(self, loc, batch, wrap_tail):
+        """F, B, M, G and the filterbank's host tables from `loc` (a wideband.WidebandSNNLocalizer / WidebandBeamformerLocalizer); ValueError
+        for a band count, a wrap_tail shape or a section count that does not fit -- host work only, in front of any plan."""
+        F = self.F = len(loc.beamfs)
+        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+            raise ValueError(f"a wideband stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+        self.B, self.M, self.G = int(batch), loc.num_mic, loc.num_grid
+        L2 = len(loc.beamfs[0].kernel) // 2
+        if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
+            raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
+        if len(loc.filterbank.ba_list) != F:
+            raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
+        self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
+
+    def _alloc_filterbank(self):
+        """fb_state (sized by the library, zeroed on the stream) and xf, the filtered tile; needs device, lib and max_tile."""
+        torch = runtime._torch()
+        self.nfb = int(self.lib.micloc_filterbank_stream_state_bytes(self.F, self.ncoef, self.B, self.M))
+        if self.nfb == 0:
+            raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
+        self.fb_state = torch.empty(self.nfb, dtype=torch.uint8, device=self.device)
+        self.xf = torch.empty(self.F * self.B * self.max_tile * self.M, dtype=torch.float64, device=self.device)  # the filtered tile [F][B][n][M]
+        _lib.check(self.lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, runtime._stream(self.device)), "filterbank_stream_reset")
+
+    def _filterbank_tile(self, x, n):
+        """The first launch of a tile: every band's section over x [B, n, M] -> xf [F, B, n, M], the states carried in fb_state."""
+        F, B, M = self.F, self.B, self.M
+        xf = self.xf[: F * B * n * M].view(F, B, n, M)
+        _lib.check(self.lib.micloc_filterbank_tile_f64(runtime._dptr(self.bb), runtime._dptr(self.aa), F, self.ncoef, runtime._ptr(x), B, n, M,
+                                                       runtime._ptr(self.fb_state), self.nfb, runtime._ptr(xf), runtime._stream(self.device)),
+                   "filterbank_tile")
+        return xf
 
 
 class StreamingLocalizer(_TileStream):
@@ -278,10 +372,8 @@ class StreamingLocalizer(_TileStream):
         self.plan = beamf.new_plan()
         self.device = self.plan.device
         self.B, self.M = int(batch), len(beamf.geometry)
-        self.C = 2 * self.M
         self.T = None if total_frames is None else int(total_frames)
-        self.L = len(beamf.kernel)
-        self.halo = -(-(self.L - 1) // 8) * 8
+        self._set_stht(beamf.kernel)
         nir_frames = self.T if self.T is not None else int(beamf.fs)
         self.plan.set_neuron_kernel(neuron_impulse_response(np.arange(nir_frames) / beamf.fs, beamf.tau_vec))
         self.plan.set_bf_mat(np.asarray(bf_mat, dtype=np.float64))
@@ -317,7 +409,7 @@ class StreamingLocalizer(_TileStream):
         self.ext = scratch("ext", (self.B * (self.halo + self.max_tile) * self.M,), torch.float64)
         self.h = scratch("h", ((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile),), torch.float64)
         self._alloc_results()
-        self._reset_window_state(self.lib.micloc_stream_window_state_bytes, self.lib.micloc_stream_window_reset, "stream_window", " (a complex bf_mat?)")
+        self._reset_window_state("stream_window", hint=" (a complex bf_mat?)")
         self._set_wrap(wrap_tail)
         self.raster = None
         if keep_raster:
@@ -340,23 +432,15 @@ class StreamingLocalizer(_TileStream):
         h_tile = ctypes.c_void_p(h.data_ptr() + 8 * self.halo)
         _lib.check(lib.micloc_stream_encode_tile_f64(plan.handle, h_tile, B, n, Ts, int(final), runtime._ptr(self.win), self.cap, runtime._ptr(self.state),
                                                      self.nstate, runtime._ptr(self.loc), st), "stream_encode_tile")
-        tile = (plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B, self.cap, int(final),
-                runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
-        if self.window is None:
-            _lib.check(lib.micloc_stream_localize_tile_f64(*tile, st), "stream_localize_tile")
-        else:  # the same launches with the window read-out in front of the commit
-            _lib.check(lib.micloc_stream_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
-                                                                   runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
-                                                                   runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st),
-                       "stream_localize_tile_windows")
+        self._localize_tile("stream_localize_tile", plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B,
+                            self.cap, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         self._keep_history(ext)
 
     def _advance(self, n, final):
         """Host mirror of the device clock (rz_stream_clock_begin_kernel's schedule) and the end-of-stream bookkeeping."""
         if self.t + n > self.base + self.cap:
             self.base = -(-(self.t + n - self.cap) // self.CH) * self.CH
-        self.t += n
-        self.done = bool(final)
+        super()._advance(n, final)
 
     def _before_slide(self, n):
         if self.raster is not None and self.t + n > self.base + self.cap:
@@ -382,13 +466,7 @@ class StreamingLocalizer(_TileStream):
         also window_power [B, nW, G], window_argmax [B, nW] and window_count = nW, every window of the recording (a live source
         without total_frames: the max_windows newest, see windows())."""
         self._need_done()
-        s = self.status()
-        if s["overflow"]:
-            raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
-                                   "one-shot call, which redoes such streams exactly")
-        if s["lag_failures"] or s["frames"] != self.t:
-            raise _lib.MiclocError(f"the raster window ({self.cap} frames) slid past frames whose spikes were not final yet "
-                                   f"({s['frames']} of {self.t} frames beamformed): raise lag_frames")
+        self._need_spikes_final(self.status(), self.cap)
         spikes = None
         if want_spikes:
             if self.raster is None:
@@ -399,7 +477,7 @@ class StreamingLocalizer(_TileStream):
         return self._finish_windows(out)
 
 
-class WidebandStreamingLocalizer(_TileStream):
+class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
     """The wideband chain (wideband.WidebandSNNLocalizer: a filterbank, one SNNBeamformer chain per band, the power patterns added, one
     arg-max -- what the reference deploys, micloc/localization_demo_snn.py:125-193) as ONE stream that arrives in tiles, with the results of
     `WidebandSNNLocalizer.localize_batch` on the whole recording bit for bit, whatever the tiling (include/micloc_hip.h "wideband
@@ -428,21 +506,13 @@ class WidebandStreamingLocalizer(_TileStream):
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
-        F = self.F = len(loc.beamfs)
-        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
-            raise ValueError(f"a wideband stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
-        self.B, self.M, self.G = int(batch), loc.num_mic, loc.num_grid
+        self._check_bands(loc, batch, wrap_tail)
+        F = self.F
         self.T = None if total_frames is None else int(total_frames)
-        L2 = len(loc.beamfs[0].kernel) // 2
-        if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
-            raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
         if window is not None and hop is not None:
             self._check_hop(int(hop), int(window))
         if max_windows is not None:
             self._check_ring(int(max_windows))
-        self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
-        if len(loc.filterbank.ba_list) != F:
-            raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
         # the bands: band 0 checks window / hop against the quantum (ValueError) before anything is launched
         self.max_tile = -(-int(max_tile) // 16) * 16
         self.bands = []
@@ -464,14 +534,9 @@ class WidebandStreamingLocalizer(_TileStream):
             raise ValueError("window and hop must be multiples of every band's chunk length")
         if any(b.cap > self._cap_bound(lag_frames) for b in self.bands):
             raise _lib.MiclocError("a band's raster window is longer than the bound the ring depth was derived from")
-        dev = self.device
-        self.nfb = int(self.lib.micloc_filterbank_stream_state_bytes(F, self.ncoef, self.B, self.M))
-        if self.nfb == 0:
-            raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
-        self.fb_state = torch.empty(self.nfb, dtype=torch.uint8, device=dev)
+        self._alloc_filterbank()
         self.nbs = int(self.lib.micloc_stream_bands_state_bytes())
-        self.bands_state = torch.empty(self.nbs, dtype=torch.uint8, device=dev)
-        self.xf = torch.empty(F * self.B * self.max_tile * self.M, dtype=torch.float64, device=dev)  # the filtered tile [F][B][n][M]
+        self.bands_state = torch.empty(self.nbs, dtype=torch.uint8, device=self.device)
         self._alloc_results()
         vp = ctypes.c_void_p
         self._p_power = (vp * F)(*[b.power.data_ptr() for b in self.bands])
@@ -479,9 +544,7 @@ class WidebandStreamingLocalizer(_TileStream):
         if self.window is not None:
             self._p_rows = (vp * F)(*[b.window_power.data_ptr() for b in self.bands])
             self._p_count = (vp * F)(*[self.lib.micloc_stream_window_count_ptr(runtime._ptr(b.wst)) for b in self.bands])
-        st = runtime._stream(dev)
-        _lib.check(self.lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, st), "filterbank_stream_reset")
-        _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, st), "stream_bands_reset")
+        _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, runtime._stream(self.device)), "stream_bands_reset")
 
     MAX_CHUNK = 512  # the longest chunk of the beamforming kernels (include/micloc_hip.h: 256 frames up to 64 channels, 512 beyond)
 
@@ -506,27 +569,21 @@ class WidebandStreamingLocalizer(_TileStream):
     def _tile(self, x, n, final):
         """The launches of one tile, all on the current stream, in a fixed order: filterbank tile, the bands in ascending order, band
         sum.  Nothing else (no allocation, no synchronisation, no absolute time), so a tile of a given length is one replayable graph."""
-        lib, F, B, M = self.lib, self.F, self.B, self.M
+        lib, F, B = self.lib, self.F, self.B
         st = runtime._stream(self.device)
-        xf = self.xf[: F * B * n * M].view(F, B, n, M)
-        _lib.check(lib.micloc_filterbank_tile_f64(runtime._dptr(self.bb), runtime._dptr(self.aa), F, self.ncoef, runtime._ptr(x), B, n, M,
-                                                  runtime._ptr(self.fb_state), self.nfb, runtime._ptr(xf), st), "filterbank_tile")
+        xf = self._filterbank_tile(x, n)
         for f, band in enumerate(self.bands):
             band._tile(xf[f], n, final)
-        if self.window is None:
-            _lib.check(lib.micloc_stream_band_sum_f64(F, B, self.G, self._p_power, 0, 0, 0, None, None, runtime._ptr(self.bands_state), self.nbs,
-                                                      runtime._ptr(self.power), runtime._ptr(self.argmax), None, None, None, None, st), "stream_band_sum")
-        else:
-            _lib.check(lib.micloc_stream_band_sum_f64(F, B, self.G, self._p_power, self.window, self.Kb, self.max_windows, self._p_rows, self._p_count,
-                                                      runtime._ptr(self.bands_state), self.nbs, runtime._ptr(self.power), runtime._ptr(self.argmax),
-                                                      runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
-                                                      runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st), "stream_band_sum")
+        # without window=: window, ring depths, rows, counts and the window tensors are 0 / NULL, and the entry sums the running powers only
+        _lib.check(lib.micloc_stream_band_sum_f64(F, B, self.G, self._p_power, self.window or 0, self.Kb or 0, self.max_windows or 0, self._p_rows,
+                                                  self._p_count, runtime._ptr(self.bands_state), self.nbs, runtime._ptr(self.power), runtime._ptr(self.argmax),
+                                                  runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
+                                                  runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st), "stream_band_sum")
 
     def _advance(self, n, final):
         for band in self.bands:
             band._advance(n, final)
-        self.t += n
-        self.done = bool(final)
+        super()._advance(n, final)
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def _bands_status(self):
@@ -551,12 +608,7 @@ class WidebandStreamingLocalizer(_TileStream):
         torch = runtime._torch()
         self._need_done()
         s = self.status()
-        if s["overflow"]:
-            raise _lib.MiclocError(f"{s['overflow']} stream(s) overflowed the candidate ring or the raster window (out-of-band input): use the "
-                                   "one-shot call, which redoes such streams exactly")
-        if s["lag_failures"] or s["frames"] != self.t:
-            raise _lib.MiclocError(f"a band's raster window ({self.bands[0].cap} frames) slid past frames whose spikes were not final yet "
-                                   f"({s['frames']} of {self.t} frames beamformed by the slowest band): raise lag_frames")
+        self._need_spikes_final(s, self.bands[0].cap, whose="a band's", by=" by the slowest band")
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
         out = dict(power=self.power, argmax=self.argmax, band_power=torch.stack([b.power for b in self.bands]))
@@ -588,16 +640,13 @@ class ComplexStreamingLocalizer(_TileStream):
         if not np.iscomplexobj(bf_mat):
             raise ValueError("ComplexStreamingLocalizer takes the complex bf_mat of a Beamformer (a real one belongs to StreamingLocalizer)")
         self.beamf = beamf
-        b, a = beamf.bandpass_filter
-        self.plan = runtime.Plan(len(beamf.geometry), beamf.kernel, b, a, robust_width=1, bipolar=False, device=beamf.device)  # the stream's own
+        self.plan = beamf.new_plan()  # the stream's own
         self.device = self.plan.device
         self.B, self.M = int(batch), len(beamf.geometry)
         if bf_mat.shape[0] != self.M:
             raise ValueError(f"number of channels in the input siganl {bf_mat.shape[0]} should be the same as the number of microphones {self.M}!")
-        self.C = 2 * self.M
         self.T = None if total_frames is None else int(total_frames)
-        self.L = len(beamf.kernel)
-        self.halo = -(-(self.L - 1) // 8) * 8
+        self._set_stht(beamf.kernel)
         self.plan.set_bf_mat(bf_mat.astype(np.complex128))
         self.lib = _lib.load()
         self.G = self.plan.G
@@ -613,11 +662,9 @@ class ComplexStreamingLocalizer(_TileStream):
             raise _lib.MiclocError("micloc stream_complex_state_bytes: the plan, the batch or max_tile do not fit the complex stream's rule")
         self.state = torch.empty(self.nstate, dtype=torch.uint8, device=dev)
         self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
-        self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (the FIR's zero state)
-        self.ext = torch.empty((self.B * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
-        self.h = torch.empty((self.B * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
+        self._alloc_stht(self.B)
         self._alloc_results()
-        self._reset_window_state(self.lib.micloc_stream_complex_window_state_bytes, self.lib.micloc_stream_complex_window_reset, "stream_complex_window")
+        self._reset_window_state("stream_complex_window")
         self._set_wrap(wrap_tail)
         _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
                    "stream_complex_reset")
@@ -640,20 +687,9 @@ class ComplexStreamingLocalizer(_TileStream):
         ext, h, Ts = self._stht_tile(x, n, self.state)
         _lib.check(lib.micloc_stream_complex_bandpass_tile_f64(plan.handle, runtime._ptr(h), B, n, Ts, self.halo, self.max_tile, runtime._ptr(self.state),
                                                                self.nstate, runtime._ptr(self.ws), self.nws, st), "stream_complex_bandpass_tile")
-        tile = (plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax),
-                runtime._ptr(self.ws), self.nws)
-        if self.window is None:
-            _lib.check(lib.micloc_stream_complex_localize_tile_f64(*tile, st), "stream_complex_localize_tile")
-        else:
-            _lib.check(lib.micloc_stream_complex_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
-                                                                           runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
-                                                                           runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st),
-                       "stream_complex_localize_tile_windows")
+        self._localize_tile("stream_complex_localize_tile", plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
+                            runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         self._keep_history(ext)
-
-    def _advance(self, n, final):
-        self.t += n
-        self.done = bool(final)
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -667,14 +703,12 @@ class ComplexStreamingLocalizer(_TileStream):
         """-> dict(power [B, G], argmax [B] int32) as device tensors; with window= also window_power [B, nW, G], window_argmax [B, nW] and
         window_count (a live source without total_frames: the max_windows newest, see windows())."""
         self._need_done()
-        s = self.status()
-        if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
-            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
+        self._need_clock(self.status())
         out = dict(power=self.power, argmax=self.argmax)
         return self._finish_windows(out)
 
 
-class WidebandComplexStreamingLocalizer(_TileStream):
+class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
     """The wideband complex chain (wideband.WidebandBeamformerLocalizer: an order-2 filterbank, one complex Beamformer per band, the
     patterns added, one arg-max -- what the reference deploys live in micloc/localization_demo.py, restarting on every 0.25 s pack) as ONE
     stream that arrives in tiles, with the results of `WidebandBeamformerLocalizer.localize_batch` on the whole recording bit for bit,
@@ -699,30 +733,19 @@ class WidebandComplexStreamingLocalizer(_TileStream):
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
-        F = self.F = len(loc.beamfs)
-        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
-            raise ValueError(f"a wideband stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
-        self.B, self.M, self.G = int(batch), loc.num_mic, loc.num_grid
-        self.C = 2 * self.M
+        self._check_bands(loc, batch, wrap_tail)
+        F = self.F
         if not 1 <= F * self.B <= 65535:
             raise ValueError(f"bands x batch must be 1 .. 65535, got {F} x {self.B}")
         self.T = None if total_frames is None else int(total_frames)
-        self.L = len(loc.beamfs[0].kernel)
-        self.halo = -(-(self.L - 1) // 8) * 8
-        L2 = self.L // 2
-        if wrap_tail is not None and tuple(wrap_tail.shape) != (F, self.B, L2, self.M):
-            raise ValueError(f"wrap_tail must be [bands, batch, {L2}, num_mic] = {(F, self.B, L2, self.M)}")
-        if len(loc.filterbank.ba_list) != F:
-            raise ValueError(f"{len(loc.filterbank.ba_list)} filterbank sections for {F} bands")
-        self.bb, self.aa, self.ncoef = runtime.pad_ba_list(loc.filterbank.ba_list)
+        self._set_stht(loc.beamfs[0].kernel)
         self.max_tile = int(max_tile)
         if self.max_tile < 1:
             raise ValueError("max_tile must be at least 1")
         # the stream's own plans, one per band (the band-pass coefficients and the bf_mat of that band)
         self.plans = []
         for beamf, W in zip(loc.beamfs, loc.bf_mats):
-            b, a = beamf.bandpass_filter
-            plan = runtime.Plan(self.M, beamf.kernel, b, a, robust_width=1, bipolar=False, device=beamf.device)
+            plan = beamf.new_plan()
             plan.set_bf_mat(np.asarray(W).astype(np.complex128))
             self.plans.append(plan)
         self.plan = self.plans[0]
@@ -731,79 +754,37 @@ class WidebandComplexStreamingLocalizer(_TileStream):
         self.handles = (ctypes.c_void_p * F)(*[p.handle.value for p in self.plans])
         self.CH = self.plan.window_quantum()
         self._set_windows(self.plan, window, hop, max_windows)
-        lib, FB = self.lib, F * self.B
-        self.nstate = int(lib.micloc_stream_complex_bands_state_bytes(self.handles, F, self.B))
-        self.nws = int(lib.micloc_stream_complex_bands_workspace_bytes(self.handles, F, self.B, self.max_tile))
+        self.nstate = int(self.lib.micloc_stream_complex_bands_state_bytes(self.handles, F, self.B))
+        self.nws = int(self.lib.micloc_stream_complex_bands_workspace_bytes(self.handles, F, self.B, self.max_tile))
         if self.nstate == 0 or self.nws == 0:
             raise ValueError("micloc stream_complex_bands_state_bytes: the bands do not share the device, the microphones, the DoA grid, the Hilbert "
                              "kernel and the band-pass length, or max_tile does not fit the stream's rule")
-        self.nfb = int(lib.micloc_filterbank_stream_state_bytes(F, self.ncoef, self.B, self.M))
-        if self.nfb == 0:
-            raise ValueError("micloc filterbank_stream_state_bytes: the bands, the batch or the filters do not fit the filterbank's rule")
+        self._alloc_filterbank()
         self.state = torch.empty(self.nstate, dtype=torch.uint8, device=dev)
         self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev)
-        self.fb_state = torch.empty(self.nfb, dtype=torch.uint8, device=dev)
-        self.xf = torch.empty(FB * self.max_tile * self.M, dtype=torch.float64, device=dev)  # the filtered tile [F][B][n][M]
-        self.hist = torch.zeros((FB, self.halo, self.M), dtype=torch.float64, device=dev)  # zero history (the FIR's zero state)
-        self.ext = torch.empty((FB * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
-        self.h = torch.empty((FB * self.C * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
+        self._alloc_stht(F * self.B)
         self.band_power = torch.zeros((F, self.B, self.G), dtype=torch.float64, device=dev)
         self._alloc_results()
-        st = runtime._stream(dev)
-        self.wst, self.nwst = None, 0
-        if self.window is not None:
-            wargs = (self.window, self.hop, self.max_windows)
-            self.nwst = int(lib.micloc_stream_complex_bands_window_state_bytes(self.handles, F, self.B, self.max_tile, *wargs))
-            if self.nwst == 0:
-                raise _lib.MiclocError("micloc stream_complex_bands_window_state_bytes: the plans cannot serve the windowed read-out")
-            self.wst = torch.empty(self.nwst, dtype=torch.uint8, device=dev)
-            _lib.check(lib.micloc_stream_complex_bands_window_reset(self.handles, F, self.B, self.max_tile, runtime._ptr(self.wst), self.nwst, *wargs, st),
-                       "stream_complex_bands_window_reset")
-        self.wrap = None
-        if wrap_tail is not None:
-            wrap = self.plan.to_device(np.asarray(wrap_tail, dtype=np.float64) if isinstance(wrap_tail, np.ndarray) else wrap_tail)
-            self.wrap = wrap.reshape(FB, L2, self.M).contiguous()
-        _lib.check(lib.micloc_filterbank_stream_reset(runtime._ptr(self.fb_state), self.nfb, st), "filterbank_stream_reset")
-        _lib.check(lib.micloc_stream_complex_bands_reset(self.handles, F, self.B, runtime._ptr(self.state), self.nstate, st), "stream_complex_bands_reset")
+        self._reset_window_state("stream_complex_bands_window", lead=(self.handles, F, self.B, self.max_tile), who="the plans")
+        self._set_wrap(wrap_tail, bands=True)
+        _lib.check(self.lib.micloc_stream_complex_bands_reset(self.handles, F, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
+                   "stream_complex_bands_reset")
 
     # ---- one tile -------------------------------------------------------------------------------------------------------
     def _tile(self, x, n, final):
         """The launches of one tile, all on the current stream, in a fixed order.  Nothing else (no allocation, no synchronisation, no
         absolute time), so a tile of a given length is one replayable graph."""
-        lib, plan, F, B, M = self.lib, self.plan, self.F, self.B, self.M
-        FB = F * B
+        lib, F, B = self.lib, self.F, self.B
         st = runtime._stream(self.device)
-        xf = self.xf[: FB * n * M].view(FB, n, M)
-        _lib.check(lib.micloc_filterbank_tile_f64(runtime._dptr(self.bb), runtime._dptr(self.aa), F, self.ncoef, runtime._ptr(x), B, n, M,
-                                                  runtime._ptr(self.fb_state), self.nfb, runtime._ptr(xf), st), "filterbank_tile")
+        xf = self._filterbank_tile(x, n).view(F * B, n, self.M)
         # [history | filtered tile] of all bands' trials, ONE STHT launch, the wrap rows of every band's filtered recording
-        Text = self.halo + n
-        ext = self.ext[: FB * Text * M].view(FB, Text, M)
-        ext[:, : self.halo, :].copy_(self.hist)
-        ext[:, self.halo :, :].copy_(xf)
-        Ts = plan.padded_T(Text)
-        h = self.h[: FB * self.C * Ts]
-        _lib.check(lib.micloc_stht_f64(plan.handle, runtime._ptr(ext), FB, Text, runtime._ptr(h), Ts, st), "stht")
-        _lib.check(lib.micloc_stream_wrap_rows_f64(plan.handle, runtime._ptr(self.state), runtime._ptr(h), FB, Ts, self.halo, n, runtime._ptr(self.wrap), st),
-                   "stream_wrap_rows")
+        ext, h, Ts = self._stht_tile(xf, n, self.state, rows=F * B)
         _lib.check(lib.micloc_stream_complex_bands_bandpass_tile_f64(self.handles, F, runtime._ptr(h), B, n, Ts, self.halo, self.max_tile, 0,
                                                                      runtime._ptr(self.state), self.nstate, runtime._ptr(self.ws), self.nws, st),
                    "stream_complex_bands_bandpass_tile")
-        tile = (self.handles, F, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final), runtime._ptr(self.band_power),
-                runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
-        if self.window is None:
-            _lib.check(lib.micloc_stream_complex_bands_localize_tile_f64(*tile, st), "stream_complex_bands_localize_tile")
-        else:
-            _lib.check(lib.micloc_stream_complex_bands_localize_tile_windows_f64(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop,
-                                                                                 self.max_windows, runtime._ptr(self.window_power),
-                                                                                 runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power),
-                                                                                 runtime._ptr(self.latest_argmax), st),
-                       "stream_complex_bands_localize_tile_windows")
-        self.hist.copy_(ext[:, Text - self.halo :, :])
-
-    def _advance(self, n, final):
-        self.t += n
-        self.done = bool(final)
+        self._localize_tile("stream_complex_bands_localize_tile", self.handles, F, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
+                            runtime._ptr(self.band_power), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
+        self._keep_history(ext)
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -823,8 +804,7 @@ class WidebandComplexStreamingLocalizer(_TileStream):
         window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
         self._need_done()
         s = self.status()
-        if s["frames"] != self.t or s["pushed"] != self.t or s["carry"] != 0:
-            raise _lib.MiclocError(f"the device clock disagrees with the host's: {s} after {self.t} frames")
+        self._need_clock(s)
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up by the band sum")
         out = dict(power=self.power, argmax=self.argmax, band_power=self.band_power)
@@ -916,10 +896,6 @@ class MusicStreamingLocalizer(_TileStream):
                                                          runtime._ptr(self.argmax), runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax),
                                                          runtime._ptr(self.window_power), runtime._ptr(self.window_sel), runtime._ptr(self.window_argmax),
                                                          runtime._stream(self.device)), "stream_music_tile")
-
-    def _advance(self, n, final):
-        self.t += n
-        self.done = bool(final)
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):

@@ -201,3 +201,14 @@ def _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold):
         raise ValueError("num_sources needs the DoA grid of bf_mat's columns (doa_list=)")
     out["peaks"], out["peak_power"] = find_doa_peaks(out["power"], doa_list, num_sources, min_separation=min_separation, rel_threshold=rel_threshold)
     return out
+
+
+def active_packs(packs, rel_threshold):
+    """The live demos' activity test (reference micloc/localization_demo.py:127-137, localization_demo_snn.py:141-150,
+    localization_demo_MUSIC.py:142-165), pack by pack: packs [B, T, num_mic + 1], integer samples (full scale: the type's maximum) or float
+    ones (full scale 1) -> (float signals [B, T, num_mic] without the devkit's empty last channel, active [B] bool: the pack's RMS is at
+    least rel_threshold x full scale)."""
+    packs = np.asarray(packs)
+    max_value = np.iinfo(packs.dtype).max if np.issubdtype(packs.dtype, np.integer) else 1.0
+    sig = np.asarray(packs[:, :, :-1], dtype=np.float64)
+    return sig, np.asarray([np.sqrt(np.mean(s**2)) >= rel_threshold * max_value for s in sig], dtype=bool)

@@ -13,6 +13,8 @@ WidebandBeamformerLocalizer: the same for the non-spiking complex `Beamformer`, 
 centre, mean_t |y|^2 per band, the patterns added, one arg-max -- as ONE library call (micloc_beamformer_pipeline_bands_f64) in which the
 band dimension is folded into the batch: one STHT launch and one band-pass launch for all bands' chains.  `localization_demo.Demo.power_grid`
 is the same computation one pack and one band at a time; `localize_batch` returns its numbers (tests/test_hip_wideband_complex.py).
+
+What a set of bands must share (_WidebandLocalizer) and how the reference's demos design one (design_bands) are stated once for both forms.
 """
 import numpy as np
 
@@ -22,22 +24,65 @@ from .filterbank import ButterworthFilterbank
 from .snn_beamformer import SNNBeamformer, neuron_impulse_response
 
 
-class WidebandSNNLocalizer:
+def design_bands(freq_bands, recording_duration, fs, band, order, device=None):
+    """What both of the reference's demos build in __init__ (micloc/localization_demo_snn.py:40-93, micloc/localization_demo.py:43-89): per
+    band a beamformer designed on a sine at the band's centre over `recording_duration`, and the Butterworth filterbank of `order`.
+    freq_bands: [F, 2], or a single pair; band(freq_range, template) -> (beamformer, bf_mat) builds and designs one band (snn_band /
+    complex_band).  -> (beamfs, bf_mats, filterbank)"""
+    freq_bands = np.asarray(freq_bands)
+    if freq_bands.ndim == 1:
+        freq_bands = freq_bands.reshape(1, -1)
+    beamfs, bf_mats = [], []
+    for freq_range in freq_bands:
+        time_temp = np.arange(0, recording_duration, step=1 / fs)
+        sig_temp = np.sin(2 * np.pi * np.mean(freq_range) * time_temp)
+        beamf, bf_mat = band(freq_range, (time_temp, sig_temp))
+        beamfs.append(beamf)
+        bf_mats.append(bf_mat)
+    return beamfs, bf_mats, ButterworthFilterbank(freq_bands=freq_bands, order=order, fs=fs, device=device)
+
+
+def snn_band(geometry, doa_list, kernel_duration, bipolar_spikes, fs, device=None):
+    """design_bands' `band` for the SNN form: an SNNBeamformer with tau = 1 / (2 pi f_mid) and its real [2M, G] matrix."""
+    def band(freq_range, template):
+        tau = 1 / (2 * np.pi * np.mean(freq_range))
+        beamf = SNNBeamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, tau_vec=[tau, tau],
+                              bipolar_spikes=bipolar_spikes, fs=fs, device=device)
+        return beamf, beamf.design_from_template(template=template, doa_list=doa_list)
+
+    return band
+
+
+def complex_band(geometry, doa_list, kernel_duration, fs, device=None):
+    """design_bands' `band` for the complex form: a Beamformer and its complex [M, G] matrix (the design also returns the covariances)."""
+    def band(freq_range, template):
+        beamf = Beamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, fs=fs, device=device)
+        bf_vecs, _ = beamf.design_from_template(template=template, doa_list=doa_list)
+        return beamf, bf_vecs
+
+    return band
+
+
+class _WidebandLocalizer:
+    """What a set of bands must share -- 1 .. MICLOC_MAX_BANDS of them, a matrix and a filterbank section each, one microphone count, one
+    DoA grid -- and the read-out tail of localize_batch.  A subclass states its rule for ONE bf_mat (_as_bf_mat) and the two messages."""
+
     def __init__(self, beamfs, bf_mats, filterbank):
-        """beamfs: one SNNBeamformer per band; bf_mats: their real [2M, G] matrices; filterbank: a Filterbank with one (b, a) section per
-        band.  ValueError for bands with different microphone or DoA counts, or more than 16 bands."""
         from . import _lib
 
         self.beamfs, self.filterbank = list(beamfs), filterbank
-        self.bf_mats = [np.asarray(W, dtype=np.float64) for W in bf_mats]
+        bf_mats = list(bf_mats)
         F = len(self.beamfs)
         if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
             raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
-        if len(self.bf_mats) != F or len(filterbank.ba_list) != F:
-            raise ValueError(f"{F} beamformers need {F} bf_mats and {F} filterbank sections (got {len(self.bf_mats)}, {len(filterbank.ba_list)})")
+        if len(bf_mats) != F or len(filterbank.ba_list) != F:
+            raise ValueError(f"{F} beamformers need {F} bf_mats and {F} filterbank sections (got {len(bf_mats)}, {len(filterbank.ba_list)})")
         M = len(self.beamfs[0].geometry)
-        if any(len(b.geometry) != M for b in self.beamfs) or any(W.ndim != 2 or W.shape[0] != 2 * M for W in self.bf_mats):
-            raise ValueError(f"every band needs the same {M} microphones and a real bf_mat with {2 * M} rows")
+        if any(len(b.geometry) != M for b in self.beamfs):
+            raise ValueError(self.MICROPHONES.format(M=M, C=2 * M))
+        self.bf_mats = [self._as_bf_mat(W, M) for W in bf_mats]
+        if any(W is None for W in self.bf_mats):
+            raise ValueError(self.BF_MAT.format(M=M, C=2 * M))
         G = self.bf_mats[0].shape[1]
         if any(W.shape[1] != G for W in self.bf_mats):
             raise ValueError(f"every band's bf_mat needs the same DoA grid ({[W.shape[1] for W in self.bf_mats]} columns)")
@@ -45,24 +90,35 @@ class WidebandSNNLocalizer:
         self.fs = self.beamfs[0].fs
         self.geometry = self.beamfs[0].geometry
 
+    def _read_out(self, out, T, window, hop, doa_list, num_sources, min_separation, rel_threshold):
+        """localize_batch's tail: `out` of the band pipeline with window_start (windowed) and the peaks of num_sources."""
+        from .utils import _add_peaks, _add_window_peaks, window_bounds
+
+        if doa_list is None:
+            doa_list = getattr(self, "doa_list", None)
+        if window is not None:
+            out["window_start"] = window_bounds(T, window, hop)[0]
+            return _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+        return _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+
+
+class WidebandSNNLocalizer(_WidebandLocalizer):
+    """beamfs: one SNNBeamformer per band; bf_mats: their real [2M, G] matrices; filterbank: a Filterbank with one (b, a) section per
+    band.  ValueError for bands with different microphone or DoA counts, or more than 16 bands."""
+
+    MICROPHONES = BF_MAT = "every band needs the same {M} microphones and a real bf_mat with {C} rows"
+
+    @staticmethod
+    def _as_bf_mat(W, M):
+        W = np.asarray(W, dtype=np.float64)
+        return W if W.ndim == 2 and W.shape[0] == 2 * M else None
+
     @classmethod
     def from_bands(cls, geometry, freq_bands, doa_list, recording_duration, kernel_duration, bipolar_spikes, fs, device=None):
         """What localization_demo_snn.Demo.__init__ builds (reference :40-93): per band an SNNBeamformer with tau = 1 / (2 pi f_mid)
         designed on a sine at the band's centre, and the order-1 Butterworth filterbank."""
-        freq_bands = np.asarray(freq_bands)
-        if freq_bands.ndim == 1:
-            freq_bands = freq_bands.reshape(1, -1)
-        beamfs, bf_mats = [], []
-        for freq_range in freq_bands:
-            freq_mid = np.mean(freq_range)
-            tau = 1 / (2 * np.pi * freq_mid)
-            beamf = SNNBeamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, tau_vec=[tau, tau],
-                                  bipolar_spikes=bipolar_spikes, fs=fs, device=device)
-            beamfs.append(beamf)
-            time_temp = np.arange(0, recording_duration, step=1 / fs)
-            sig_temp = np.sin(2 * np.pi * freq_mid * time_temp)
-            bf_mats.append(beamf.design_from_template(template=(time_temp, sig_temp), doa_list=doa_list))
-        loc = cls(beamfs, bf_mats, ButterworthFilterbank(freq_bands=freq_bands, order=1, fs=fs, device=device))
+        loc = cls(*design_bands(freq_bands, recording_duration, fs, snn_band(geometry, doa_list, kernel_duration, bipolar_spikes, fs, device),
+                                order=1, device=device))
         loc.doa_list = np.asarray(doa_list)
         return loc
 
@@ -83,8 +139,6 @@ class WidebandSNNLocalizer:
         window=N frames (hop defaults to it; multiples of every band's window quantum): window_power [B, nW, G], window_argmax [B, nW]
         and window_start [nW] (frames, host) INSTEAD of power / argmax.  num_sources=K (with doa_list): the K strongest peaks of the
         summed pattern -- peaks / peak_power [B, K], with `window` window_peaks / window_peak_power [B, nW, K]."""
-        from .utils import _add_peaks, _add_window_peaks, window_bounds
-
         B, T, M = sig_batch.shape
         if M != self.num_mic:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
@@ -93,57 +147,27 @@ class WidebandSNNLocalizer:
         plans = self.plans(time_vec)
         x = plans[0].to_device(sig_batch)
         out = runtime.snn_pipeline_bands(plans, self.filterbank.ba_list, x, window=window, hop=hop, want_band_power=return_band_power)
-        if doa_list is None:
-            doa_list = getattr(self, "doa_list", None)
-        if window is not None:
-            out["window_start"] = window_bounds(T, window, hop)[0]
-            return _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
-        return _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+        return self._read_out(out, T, window, hop, doa_list, num_sources, min_separation, rel_threshold)
 
 
-class WidebandBeamformerLocalizer:
-    def __init__(self, beamfs, bf_mats, filterbank):
-        """beamfs: one Beamformer per band; bf_mats: their complex [M, G] matrices; filterbank: a Filterbank with one (b, a) section per
-        band.  ValueError for bands with different microphone or DoA counts, more than 16 bands, or a bf_mat that is not complex [M, G]."""
-        from . import _lib
+class WidebandBeamformerLocalizer(_WidebandLocalizer):
+    """beamfs: one Beamformer per band; bf_mats: their complex [M, G] matrices; filterbank: a Filterbank with one (b, a) section per
+    band.  ValueError for bands with different microphone or DoA counts, more than 16 bands, or a bf_mat that is not complex [M, G]."""
 
-        self.beamfs, self.filterbank = list(beamfs), filterbank
-        self.bf_mats = [np.asarray(W) for W in bf_mats]
-        F = len(self.beamfs)
-        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
-            raise ValueError(f"a wideband localizer has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
-        if len(self.bf_mats) != F or len(filterbank.ba_list) != F:
-            raise ValueError(f"{F} beamformers need {F} bf_mats and {F} filterbank sections (got {len(self.bf_mats)}, {len(filterbank.ba_list)})")
-        M = len(self.beamfs[0].geometry)
-        if any(len(b.geometry) != M for b in self.beamfs):
-            raise ValueError(f"every band needs the same {M} microphones")
-        if any(not np.iscomplexobj(W) or W.ndim != 2 or W.shape[0] != M for W in self.bf_mats):
-            raise ValueError(f"every band needs a complex bf_mat with {M} rows ([M, G]; a real [2M, G] matrix belongs to WidebandSNNLocalizer)")
-        self.bf_mats = [W.astype(np.complex128, copy=False) for W in self.bf_mats]
-        G = self.bf_mats[0].shape[1]
-        if any(W.shape[1] != G for W in self.bf_mats):
-            raise ValueError(f"every band's bf_mat needs the same DoA grid ({[W.shape[1] for W in self.bf_mats]} columns)")
-        self.num_mic, self.num_grid = M, G
-        self.fs = self.beamfs[0].fs
-        self.geometry = self.beamfs[0].geometry
+    MICROPHONES = "every band needs the same {M} microphones"
+    BF_MAT = "every band needs a complex bf_mat with {M} rows ([M, G]; a real [2M, G] matrix belongs to WidebandSNNLocalizer)"
+
+    @staticmethod
+    def _as_bf_mat(W, M):
+        W = np.asarray(W)
+        return W.astype(np.complex128, copy=False) if np.iscomplexobj(W) and W.ndim == 2 and W.shape[0] == M else None
 
     @classmethod
     def from_bands(cls, geometry, freq_bands, doa_list, recording_duration, kernel_duration, fs, device=None):
         """What localization_demo.Demo.__init__ builds (reference micloc/localization_demo.py:43-89): per band a Beamformer designed on a
         sine at the band's centre, and the order-2 Butterworth filterbank."""
-        freq_bands = np.asarray(freq_bands)
-        if freq_bands.ndim == 1:
-            freq_bands = freq_bands.reshape(1, -1)
-        beamfs, bf_mats = [], []
-        for freq_range in freq_bands:
-            freq_mid = np.mean(freq_range)
-            beamf = Beamformer(geometry=geometry, kernel_duration=kernel_duration, freq_range=freq_range, fs=fs, device=device)
-            beamfs.append(beamf)
-            time_temp = np.arange(0, recording_duration, step=1 / fs)
-            sig_temp = np.sin(2 * np.pi * freq_mid * time_temp)
-            bf_vecs, _ = beamf.design_from_template(template=(time_temp, sig_temp), doa_list=doa_list)
-            bf_mats.append(bf_vecs)
-        loc = cls(beamfs, bf_mats, ButterworthFilterbank(freq_bands=freq_bands, order=2, fs=fs, device=device))
+        loc = cls(*design_bands(freq_bands, recording_duration, fs, complex_band(geometry, doa_list, kernel_duration, fs, device), order=2,
+                                device=device))
         loc.doa_list = np.asarray(doa_list)
         return loc
 
@@ -188,8 +212,6 @@ class WidebandBeamformerLocalizer:
         per frame, band and 7 microphones) stays inside it, so a speech-length sweep batch fits; the results do not depend on the split."""
         import torch
 
-        from .utils import _add_peaks, _add_window_peaks, window_bounds
-
         B, T, M = sig_batch.shape
         if M != self.num_mic:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
@@ -199,9 +221,4 @@ class WidebandBeamformerLocalizer:
         parts = [runtime.beamformer_pipeline_bands(plans, self.filterbank.ba_list, x[lo : lo + step], window=window, hop=hop,
                                                    want_band_power=return_band_power) for lo in range(0, B, step)]
         out = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts], dim=1 if k == "band_power" else 0) for k in parts[0]}
-        if doa_list is None:
-            doa_list = getattr(self, "doa_list", None)
-        if window is not None:
-            out["window_start"] = window_bounds(T, window, hop)[0]
-            return _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
-        return _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
+        return self._read_out(out, T, window, hop, doa_list, num_sources, min_separation, rel_threshold)
