@@ -204,6 +204,29 @@ SYMBOLS = {
                                              c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p]),
     "micloc_stream_music_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "micloc_xylo_stream_state_bytes": (c_size_t, [c_int, c_int]),
+    "micloc_xylo_stream_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "micloc_xylo_lif_resume_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_xylo_state_bytes": (c_size_t, []),
+    "micloc_stream_xylo_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "micloc_stream_xylo_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t,
+                                         c_void_p, c_void_p]),
+    "micloc_stream_xylo_begin_tile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "micloc_stream_xylo_tile_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_xylo_window_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "micloc_stream_xylo_window_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "micloc_stream_xylo_tile_windows_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                    c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
+                                                    c_int, c_void_p]),
+    "micloc_stream_xylo_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "micloc_stream_xylo_readout_state_bytes": (c_size_t, []),
+    "micloc_stream_xylo_readout_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_xylo_readout": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int,
+                                           c_int, c_int, c_int, ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "micloc_stream_xylo_readout_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
     "micloc_abi_version": (c_int, []),
     "micloc_status_string": (ctypes.c_char_p, [c_int]),
     "micloc_last_hip_error": (c_int, []),

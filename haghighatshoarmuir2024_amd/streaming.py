@@ -37,8 +37,9 @@ the frames behind the last whole chunk and the accumulators on the device, tiles
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
 
 THE CLASSES: StreamingLocalizer (one SNNBeamformer chain), WidebandStreamingLocalizer (a filterbank and one StreamingLocalizer per band),
-ComplexStreamingLocalizer, WidebandComplexStreamingLocalizer (a filterbank and ONE complex stream of bands x batch rows) and
-MusicStreamingLocalizer share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
+ComplexStreamingLocalizer, WidebandComplexStreamingLocalizer (a filterbank and ONE complex stream of bands x batch rows),
+MusicStreamingLocalizer and XyloStreamingLocalizer (one STHT, per band an encoder stream and the Xylo integer LIF resumed across tiles, the
+rate / peak read-out over the bands; LIF parity unpinned) share one surface -- push, push_replay, status, latest_window, windows, finish -- and one tile protocol, which
 _TileStream states once: what a window / hop / max_windows may be, which tiles are accepted, how a tile length becomes a captured graph, how
 the ring of windows is read, what finish() refuses about it.  It also holds the pieces more than one class launches: the STHT front of a tile
 for any number of rows (_stht_tile / _keep_history, with _set_stht, _alloc_stht and _set_wrap in the constructor), the read-out entry in its
@@ -304,6 +305,8 @@ class _TileStream:
                                            "windows() while the stream runs)")
             w = self.windows()
             out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
+            if "window_counts" in w:  # (XyloStreamingLocalizer)
+                out["window_counts"] = w["window_counts"]
         return out
 
 
@@ -934,3 +937,247 @@ class MusicStreamingLocalizer(_TileStream):
         w = self.windows()
         return dict(spectrum=w["spectrum"], power=self.power, argmax=self.argmax, slice_argmax=w["window_argmax"], sel=w["sel"],
                     slice_count=w["count"])
+
+
+class XyloStreamingLocalizer(_TileStream):
+    """The Xylo chain (xylo_snn_localization.Demo: per band STHT -> order-1 band-pass -> RZCC spikes -> the Xylo integer LIF layer, then
+    rate and peak -- the reference's live loop micloc/xylo_snn_localization.py:446-542, which restarts the chain on every 0.25 s pack) as
+    ONE stream that arrives in tiles, with the results of `Demo.counts_batch`, `rate_batch` and `peak_batch` on the whole recording bit
+    for bit, whatever the tiling (include/micloc_hip.h "streaming, Xylo").  PARITY UNPINNED like Demo.xylo_process: the LIF equals the
+    oracle's restatement of the published update rule, which is not checked against XyloSim (rockpool is absent).
+
+    The Xylo chain has no filterbank in front of the STHT -- the band filter is the plan's band-pass -- so ONE STHT launch per tile
+    serves every band.  Behind it, for f ascending, band f's tile launches: its clock and window slide, its encoder tile (band-pass and
+    RZCC state on the device), the horizon, the resumable LIF over the chunks of 256 frames that became final, (the band's window
+    read-out,) commit and tick; the bands run one after the other on the one stream and share the tile-sized scratch.  Then the
+    read-out over the bands.  The network is block diagonal (band f's channels feed band f's neurons only), so each band integrates its
+    own block W_in[f C:(f + 1) C, f G:(f + 1) G] of the ALREADY quantised specification: the quantisation stays the global one.
+
+    LIMITS: w_rec == 0 (a recurrent weight couples all bands per step; the paper's -0.1 / N quantises to 0), bipolar spikes, at most 16
+    microphones (Cin = 4 M <= 64), at most MICLOC_MAX_BANDS bands.
+
+    Result slots: `power` holds the rate [B, G] (float64), `argmax` the peak index for `win_size`, `counts` the counts [B, F G] (int32).
+    Mid-stream each band is read over the frames IT has integrated so far (the bands' horizons differ); after the final tile every band
+    has integrated all of them.
+
+    WINDOWS (window=, hop=: multiples of 256 frames): per window the counts, the rate (counts / frames of that window x fs, band mean) and
+    the peak, by the window rule of the other streams, the window cut by the end of the recording included.  The network state is NOT
+    reset between windows: one stream is one continuous run of the network.  EMISSION RULE: the ring-depth one of
+    WidebandStreamingLocalizer -- every band emits its windows into a ring of Kb rows as its own horizon passes them, a window of the
+    stream is emitted by the read-out once every band has emitted it; Kb is WidebandStreamingLocalizer._ring_depth's bound with the
+    256-frame chunk, and the read-out counts a failure instead of reading an overwritten row (finish() then raises)."""
+
+    TILE_MULTIPLE = 16  # the encoder takes its frames sixteen at a time
+    CHUNK = 256         # frames per chunk of the LIF's stream: the quantum of window and hop
+
+    def __init__(self, demo, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, win_size=1, window=None, hop=None,
+                 max_windows=None, max_spikes=31):
+        """demo: xylo_snn_localization.Demo; `batch` recordings are streamed in lock step.  total_frames, wrap_tail [batch, L // 2, M],
+        max_tile, lag_frames, window, hop, max_windows: as StreamingLocalizer's (the window quantum is 256 frames); win_size: the
+        box-car of peak_batch (odd, at most G / 2)."""
+        # ---- the refusals, in front of any device work ----
+        self._check_window_given(window, hop, max_windows)
+        spec = demo.spec
+        if int(spec["w_rec"]) != 0:
+            raise ValueError(f"the Xylo stream integrates the bands independently and needs w_rec == 0, got {int(spec['w_rec'])} (the paper's "
+                             "-0.1 / N quantises to 0 at 8 bits; a non-zero recurrent weight couples all bands per step: use the one-shot calls)")
+        if not demo.bipolar_spikes:
+            raise ValueError("the Xylo stream needs bipolar_spikes=True (the LIF kernel splits the ternary raster)")
+        self.M = len(demo.beamfs[0].geometry)
+        if self.M > 16:
+            raise ValueError(f"the Xylo stream serves at most 16 microphones (Cin = 4 M <= 64), got {self.M}")
+        F = self.F = len(demo.beamfs)
+        if not 1 <= F <= _lib.MICLOC_MAX_BANDS:
+            raise ValueError(f"a Xylo stream has 1 .. {_lib.MICLOC_MAX_BANDS} bands, got {F}")
+        self.B = int(batch)
+        self.G = len(demo.doa_list)
+        self.T = None if total_frames is None else int(total_frames)
+        self.win_size = int(win_size)
+        if self.win_size < 1 or self.win_size % 2 != 1 or self.win_size > self.G // 2:
+            raise ValueError(f"win_size must be odd and at most G / 2 = {self.G // 2}, got {win_size}")
+        self.max_tile = -(-int(max_tile) // 16) * 16
+        self.lag_frames = int(lag_frames)
+        self._set_windows(None, window, hop, max_windows)
+        W = np.asarray(spec["W_in"])
+        C = 2 * self.M
+        if W.shape != (2 * F * C, F * self.G):
+            raise ValueError(f"the specification's W_in {W.shape} is not [2 x {F} x {C}, {F} x {self.G}]")
+        # ---- device work from here on ----
+        torch = runtime._torch()
+        self.demo = demo
+        self.fs = float(demo.fs)
+        self.max_spikes = int(max_spikes)
+        enc = demo.beamfs[0].spk_encoder
+        self.plans = [runtime.Plan(self.M, demo.beamfs[0].kernel, b, a, enc.robust_width, enc.bipolar, device=demo.device)
+                      for (b, a) in demo.filterbank.ba_list]  # the stream's own, as Demo._plans() builds them
+        self.plan = self.plans[0]
+        self.device = dev = self.plan.device
+        self.lib = lib = _lib.load()
+        self._set_stht(demo.beamfs[0].kernel)
+        CH = self.CHUNK
+        self.cap = -(-(self.max_tile + self.lag_frames + 2 * CH) // CH) * CH
+        self.Kb = self._ring_depth() if self.window is not None else 0
+        from .xylo_snn_localization import XyloNetwork
+
+        self.nloc = int(lib.micloc_stream_xylo_state_bytes())
+        self.nws = int(lib.micloc_stream_xylo_workspace_bytes(self.B, self.G, self.cap)) if self.window is not None else 0
+        self.ws = torch.empty(self.nws, dtype=torch.uint8, device=dev) if self.nws else None  # the per-chunk counts of a band's tile
+        self.win_tmp = torch.empty((self.B, self.cap, self.C), dtype=torch.int8, device=dev)  # the slide's staging copy
+        self.bands = []
+        st = runtime._stream(dev)
+        for f, plan in enumerate(self.plans):
+            band = dict(plan=plan)
+            band["net"] = XyloNetwork(self.band_spec(spec, f, F, C, self.G), device=dev)
+            band["nstate"] = int(lib.micloc_stream_state_bytes(plan.handle, self.B))
+            band["state"] = torch.empty(band["nstate"], dtype=torch.uint8, device=dev)
+            band["loc"] = torch.empty(self.nloc, dtype=torch.uint8, device=dev)
+            band["win"] = torch.empty((self.B, self.cap, self.C), dtype=torch.int8, device=dev)
+            band["nlif"] = int(lib.micloc_xylo_stream_state_bytes(self.B, self.G))
+            band["lif"] = torch.empty(band["nlif"], dtype=torch.uint8, device=dev)
+            band["counts"] = torch.empty((self.B, self.G), dtype=torch.int32, device=dev)
+            band["wst"], band["nwst"] = None, 0
+            _lib.check(lib.micloc_stream_xylo_reset(plan.handle, self.B, runtime._ptr(band["state"]), band["nstate"], runtime._ptr(band["loc"]), self.nloc,
+                                                    runtime._ptr(band["win"]), self.cap, self.G, runtime._ptr(band["lif"]), band["nlif"],
+                                                    runtime._ptr(band["counts"]), st), "stream_xylo_reset")
+            if self.window is not None:
+                band["nwst"] = int(lib.micloc_stream_xylo_window_state_bytes(self.B, self.G, self.window, self.hop, self.Kb))
+                band["wst"] = torch.empty(band["nwst"], dtype=torch.uint8, device=dev)
+                _lib.check(lib.micloc_stream_xylo_window_reset(runtime._ptr(band["wst"]), band["nwst"], self.B, self.G, self.window, self.hop, self.Kb, st),
+                           "stream_xylo_window_reset")
+            self.bands.append(band)
+        # the tile workspace of _stht_tile, shared by the bands: zero history (the FIR's zero state), [history | tile] frames and their planar
+        # STHT output, with one spare row in h: the encoder's loader may read up to `halo` elements past its last row
+        self.hist = torch.zeros((self.B, self.halo, self.M), dtype=torch.float64, device=dev)
+        self.ext = torch.empty((self.B * (self.halo + self.max_tile) * self.M,), dtype=torch.float64, device=dev)
+        self.h = torch.empty(((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile),), dtype=torch.float64, device=dev)
+        self._alloc_results()
+        self.counts = torch.zeros((self.B, F * self.G), dtype=torch.int32, device=dev)
+        self.window_counts = self.latest_counts = None
+        if self.window is not None:
+            self.window_counts = torch.zeros((self.B, self.max_windows, F * self.G), dtype=torch.int32, device=dev)
+            self.latest_counts = torch.zeros((self.B, F * self.G), dtype=torch.int32, device=dev)
+        self._set_wrap(wrap_tail)
+        vp = ctypes.c_void_p
+        self._p_counts = (vp * F)(*[b["counts"].data_ptr() for b in self.bands])
+        self._p_loc = (vp * F)(*[b["loc"].data_ptr() for b in self.bands])
+        self._p_wst = (vp * F)(*[b["wst"].data_ptr() for b in self.bands]) if self.window is not None else None
+        self.nro = int(lib.micloc_stream_xylo_readout_state_bytes())
+        self.ro = torch.empty(self.nro, dtype=torch.uint8, device=dev)
+        _lib.check(lib.micloc_stream_xylo_readout_reset(runtime._ptr(self.ro), self.nro, st), "stream_xylo_readout_reset")
+
+    @staticmethod
+    def band_spec(spec, f, F, C, G):
+        """Band f's block of the quantised specification of F bands with C ternary channels and G neurons each: the rows of its +1 and its
+        -1 events (W_in is [W; -W], xylo_specification) and its columns; dash_* and threshold sliced alike.  Exact: the network is block
+        diagonal and the quantisation happened before the slicing."""
+        W = np.asarray(spec["W_in"])
+        rows = np.r_[f * C : (f + 1) * C, F * C + f * C : F * C + (f + 1) * C]
+        cols = slice(f * G, (f + 1) * G)
+        return dict(W_in=np.ascontiguousarray(W[rows][:, cols]), w_rec=0, dash_syn=np.asarray(spec["dash_syn"])[cols],
+                    dash_mem=np.asarray(spec["dash_mem"])[cols], threshold=np.asarray(spec["threshold"])[cols])
+
+    def _set_windows(self, plan, window, hop, max_windows):
+        """_TileStream's rule with the Xylo stream's own quantum, 256 frames, on the host alone (no plan has been built yet)."""
+        self.window = self.hop = self.max_windows = None
+        if window is None:
+            return
+        window = int(window)
+        hop = window if hop is None else int(hop)
+        q = self.CHUNK
+        if window < 1 or hop < 1 or window % q or hop % q:
+            raise ValueError(f"window ({window}) and hop ({hop}) must be positive multiples of the Xylo stream's window quantum, {q} frames")
+        self._check_hop(hop, window)
+        self.window, self.hop = window, hop
+        nW = utils.windows_complete(self.T, window, hop, T=self.T) if self.T is not None else 64
+        self.max_windows = int(max_windows) if max_windows is not None else nW
+        self._check_ring(self.max_windows)
+
+    def _ring_depth(self):
+        """Kb: WidebandStreamingLocalizer._ring_depth's bound (its docstring) with this stream's `cap`."""
+        Kb = -(-(self.cap + self.max_tile) // self.hop) + 2
+        if self.T is not None and self.T >= 1:
+            Kb = min(Kb, utils.windows_complete(self.T, self.window, self.hop, T=self.T))
+        return max(1, Kb)
+
+    # ---- one tile -------------------------------------------------------------------------------------------------------
+    def _tile(self, x, n, final):
+        """The launches of one tile, all on the current stream, in a fixed order: the STHT of [history | tile] once, the bands in
+        ascending order, the read-out.  Nothing else (no allocation, no synchronisation, no absolute time)."""
+        lib, B = self.lib, self.B
+        st = runtime._stream(self.device)
+        # the wrap rows read the frames-pushed word, which every band ticks behind its own tile: band 0's is still this tile's start
+        ext, h, Ts = self._stht_tile(x, n, self.bands[0]["loc"], spare_rows=1)
+        h_tile = ctypes.c_void_p(h.data_ptr() + 8 * self.halo)
+        for band in self.bands:
+            plan = band["plan"]
+            loc, win = runtime._ptr(band["loc"]), runtime._ptr(band["win"])
+            _lib.check(lib.micloc_stream_xylo_begin_tile(plan.handle, loc, win, runtime._ptr(self.win_tmp), B, n, self.cap, st), "stream_xylo_begin_tile")
+            _lib.check(lib.micloc_stream_encode_tile_f64(plan.handle, h_tile, B, n, Ts, int(final), win, self.cap, runtime._ptr(band["state"]),
+                                                         band["nstate"], loc, st), "stream_encode_tile")
+            net = band["net"]
+            tile = (plan.handle, runtime._ptr(band["state"]), loc, self.nloc, win, B, self.cap, int(final), self.G, self.max_spikes,
+                    runtime._ptr(band["counts"]), runtime._ptr(band["lif"]), band["nlif"], runtime._ptr(net.ws), net.nbytes)
+            if self.window is None:
+                _lib.check(lib.micloc_stream_xylo_tile_i16(*tile, st), "stream_xylo_tile")
+            else:
+                _lib.check(lib.micloc_stream_xylo_tile_windows_i16(*tile, runtime._ptr(self.ws), self.nws, runtime._ptr(band["wst"]), band["nwst"],
+                                                                   self.window, self.hop, self.Kb, st), "stream_xylo_tile_windows")
+        _lib.check(lib.micloc_stream_xylo_readout(self.F, B, self.G, self.fs, self.win_size, self._p_counts, self._p_loc, self.window or 0, self.hop or 0,
+                                                  self.Kb, self.max_windows or 0, self._p_wst, runtime._ptr(self.ro), self.nro, runtime._ptr(self.counts),
+                                                  runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.window_counts),
+                                                  runtime._ptr(self.window_power), runtime._ptr(self.window_argmax), runtime._ptr(self.latest_counts),
+                                                  runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st), "stream_xylo_readout")
+        self._keep_history(ext)
+
+    # ---- results ----------------------------------------------------------------------------------------------------------
+    def _readout_status(self):
+        st2 = (ctypes.c_int * 2)()
+        _lib.check(self.lib.micloc_stream_xylo_readout_status(runtime._ptr(self.ro), st2, runtime._stream(self.device)), "stream_xylo_readout_status")
+        return int(st2[0]), int(st2[1])
+
+    def status(self):
+        """dict(chunks, frames, lag_failures, overflow, bands, readout_failures): chunks / frames integrated by the slowest band,
+        lag failures and overflowed encoder streams summed over the bands, the per-band dicts, and the windows the read-out gave up
+        because a band's ring had overwritten them.  Synchronises the stream."""
+        per = []
+        for band in self.bands:
+            st4 = (ctypes.c_int * 4)()
+            _lib.check(self.lib.micloc_stream_xylo_status(runtime._ptr(band["loc"]), st4, runtime._stream(self.device)), "stream_xylo_status")
+            lost = ctypes.c_int(0)
+            _lib.check(self.lib.micloc_stream_overflow(runtime._ptr(band["state"]), ctypes.byref(lost), runtime._stream(self.device)), "stream_overflow")
+            per.append(dict(chunks=int(st4[0]), frames=int(st4[1]), lag_failures=int(st4[2]), pushed=int(st4[3]), overflow=int(lost.value)))
+        return dict(chunks=min(s["chunks"] for s in per), frames=min(s["frames"] for s in per), lag_failures=sum(s["lag_failures"] for s in per),
+                    overflow=sum(s["overflow"] for s in per), bands=per, readout_failures=self._readout_status()[1] if self.window is not None else 0)
+
+    def _window_count(self):
+        return self._readout_status()[0]
+
+    def latest_window(self):
+        """(rate [B, G], peak [B], counts [B, F G]) of the most recently emitted window: device tensors, overwritten when the next window
+        is emitted, zeros until the first one exists.  Does not synchronise."""
+        self._need_windows()
+        return self.latest_power, self.latest_argmax, self.latest_counts
+
+    def windows(self):
+        """_TileStream.windows() -- window_power holds the rate, window_argmax the peak -- plus window_counts [B, k, F G]."""
+        w = super().windows()
+        torch = runtime._torch()
+        rows = torch.arange(w["first"], w["count"], device=self.device) % self.max_windows
+        w["window_counts"] = self.window_counts.index_select(1, rows)
+        w["window_rate"], w["window_peak"] = w["window_power"], w["window_argmax"]
+        return w
+
+    def finish(self):
+        """-> dict(counts [B, F G] int32, rate [B, G] float64, peak [B] int32; power and argmax name the same rate and peak) as device
+        tensors; with window= also window_counts [B, nW, F G], window_rate / window_power [B, nW, G], window_peak / window_argmax [B, nW]
+        and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        self._need_done()
+        s = self.status()
+        self._need_spikes_final(s, self.cap, whose="a band's", by=" by the slowest band")
+        if s["readout_failures"]:
+            raise _lib.MiclocError(f"{s['readout_failures']} window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
+        out = dict(counts=self.counts, rate=self.power, peak=self.argmax, power=self.power, argmax=self.argmax)
+        if self.window is not None:
+            self._finish_windows(out)
+            out.update(window_rate=out["window_power"], window_peak=out["window_argmax"])
+        return out

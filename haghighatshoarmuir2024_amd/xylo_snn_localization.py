@@ -11,7 +11,11 @@ reference                                   -> here
                                                tests/golden/filterbank.npz comes from the reference's own classes)
   Demo.xylo_process             :358-377    -> micloc_xylo_lif_i16 (integer LIF kernel)                   (UNPINNED)
   Demo.extract_rate / estimate_doa_from_rate :379-444 -> same formulas (host)
-  live demo / power measurement :446-682    -> out of scope (needs the physical Xylo board and microphone array)
+  Demo.run_demo (live loop)     :446-542    -> here, minus recorder and visualiser: `process_frame` is the body of the loop for one
+                                               recorded pack, `process_frames` a batch of packs, `run` drives it from any iterable;
+                                               `streaming_localizer` serves audio that arrives in tiles WITHOUT restarting the chain
+                                               (streaming.XyloStreamingLocalizer: w_rec == 0, bipolar spikes, at most 16 microphones)
+  recorder / visualiser / power measurement :543-682 -> out of scope (needs the physical Xylo board and microphone array)
 
 PARITY UNPINNED for xylo_process and the quantiser: in the reference both are rockpool code
 (`mapper`, `global_quantize`, `config_from_specification`, `XyloSim`), an un-vendored, un-pinned third-party
@@ -27,6 +31,7 @@ import numpy as np
 from . import _lib, runtime
 from .filterbank import ButterworthFilterbank
 from .snn_beamformer import SNNBeamformer
+from .utils import active_packs
 
 
 def signal_from_template(geometry, template):
@@ -157,6 +162,49 @@ class XyloNetwork:
                                                          runtime._stream(self.device)), "xylo_lif_resident")
         return out, rate
 
+    # ---- resumable across launches (micloc_xylo_lif_resume_i16; PARITY UNPINNED like run) ------------------------------------------
+    def new_state(self, B):
+        """A zeroed LIF state for `B` trials (micloc_xylo_stream_reset): dict(state, counts int32 [B, N], B).  Zero synaptic current,
+        membrane and counts come from here; run_resume only ever continues a state."""
+        import torch
+
+        if self.w_rec != 0:
+            raise ValueError("the resumable LIF is the w_rec == 0 form (a recurrent weight couples all neurons per step)")
+        nb = int(self.lib.micloc_xylo_stream_state_bytes(int(B), self.N))
+        if nb == 0:
+            raise ValueError(f"micloc xylo_stream_state_bytes: {B} trials x {self.N} neurons do not fit the rule")
+        state = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.micloc_xylo_stream_reset(runtime._ptr(state), nb, runtime._stream(self.device)), "xylo_stream_reset")
+        return dict(state=state, nbytes=nb, counts=torch.zeros((int(B), self.N), dtype=torch.int32, device=self.device), B=int(B))
+
+    def run_resume(self, raster, t0, n, state, want_spikes=False, max_spikes=31, spikes_out=None):
+        """Integrate the frames [t0, t0 + n) of the encoder's int8 raster [B, T, Cin / 2] from `state` (new_state) and leave the state
+        behind them; t0 is a multiple of 16, n may be 0 (nothing is rewritten).  Returns (spikes_out uint8 [B, T, N] or None -- only the
+        rows of this range are written; pass the tensor of an earlier call as spikes_out= to assemble a recording -- and the running
+        counts int32 [B, N], which are state["counts"]).  Consecutive ranges from a new state give XyloNetwork.run's bits for every cut.
+        No host access, no synchronisation."""
+        import torch
+
+        if self.w_rec != 0:
+            raise ValueError("the resumable LIF is the w_rec == 0 form (a recurrent weight couples all neurons per step)")
+        if getattr(raster, "dtype", None) != torch.int8 or raster.dim() != 3 or not raster.is_contiguous():
+            raise ValueError("raster must be a contiguous int8 device tensor [B, T, Cin / 2] (the encoder's ternary raster)")
+        t0, n = int(t0), int(n)
+        if t0 % 16 != 0:
+            raise ValueError(f"t0 ({t0}) must be a multiple of 16 frames")
+        B, T, C = raster.shape
+        if 2 * C != self.Cin:
+            raise ValueError(f"number of input spike channels {2 * C} should match the weight matrix {self.Cin}")
+        if B != state["B"] or t0 < 0 or n < 0 or t0 + n > T:
+            raise ValueError(f"the range [{t0}, {t0 + n}) or the batch {B} does not fit the raster [{B}, {T}] and the state of {state['B']} trials")
+        out = spikes_out
+        if want_spikes and out is None:
+            out = torch.zeros((B, T, self.N), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.micloc_xylo_lif_resume_i16(runtime._ptr(raster), C, T, B, t0, n, self.Cin, self.N, int(max_spikes), runtime._ptr(out),
+                                                       T if out is not None else 0, runtime._ptr(state["counts"]), runtime._ptr(state["state"]),
+                                                       state["nbytes"], runtime._ptr(self.ws), self.nbytes, runtime._stream(self.device)),
+                   "xylo_lif_resume")
+        return out, state["counts"]
 
     def queue_status(self):
         """dict(tickets, gave_up) of the last ticket-queue launch (micloc_xylo_sweep_status; synchronises): gave_up must be 0."""
@@ -288,6 +336,35 @@ class Demo:
         the estimator of paper_plots/target_xylo_localization.py:594-604."""
         counts = self.counts_batch(sig_batch)
         return runtime.peak_location(counts, len(self.doa_list), win_size)
+
+    # ---- the live loop (reference :446-542), minus recorder and visualiser -------------------------------------------------------
+    def process_frame(self, data, rel_threshold=1e-4, method="peak"):
+        """The body of run_demo for one recorded pack [T, num_mic + 1] (integer samples, last channel unused as on the devkit) -> DoA in
+        degrees, or NaN when the pack is below the activity threshold: spike_encoding -> xylo_process -> extract_rate (rate_batch: the
+        same chain without the T x N arrays) -> estimate_doa_from_rate."""
+        return self.process_frames(np.asarray(data)[None], rel_threshold, method)[0]
+
+    def process_frames(self, packs, rel_threshold=1e-4, method="peak"):
+        """`process_frame` for a batch of recorded packs [B, T, num_mic + 1] of one length: DoA in degrees per pack [B], NaN for the
+        packs below the activity threshold; the others go through ONE rate_batch call, the estimator runs on the host per pack."""
+        sig, active = active_packs(packs, rel_threshold)
+        doa = np.full(len(sig), np.nan)
+        if active.any():
+            rate = self.rate_batch(np.ascontiguousarray(sig[active])).cpu().numpy()
+            doa[active] = [self.estimate_doa_from_rate(r, method) / np.pi * 180 for r in rate]
+        return doa
+
+    def run(self, source, sink=print):
+        """`source`: iterable of recorded packs ([T, num_mic + 1] integer arrays); `sink(doa_deg)` replaces the visualiser."""
+        for data in source:
+            sink(self.process_frame(data))
+
+    def streaming_localizer(self, batch=1, **kw):
+        """The demo's chain for audio that arrives in tiles (streaming.XyloStreamingLocalizer): encoder and network carry their state
+        across the tiles instead of restarting on every pack.  PARITY UNPINNED like xylo_process."""
+        from .streaming import XyloStreamingLocalizer
+
+        return XyloStreamingLocalizer(self, batch, **kw)
 
     def extract_rate(self, spikes_in):
         rate_channels = np.mean(spikes_in, axis=0) * self.fs

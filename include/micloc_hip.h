@@ -903,6 +903,76 @@ int micloc_stream_music_tile_f64(void *state, size_t state_bytes, const double *
                                  int32_t *latest_argmax, double *slice_spec, int32_t *slice_sel, int32_t *slice_argmax, void *stream);
 int micloc_stream_music_status(const void *state, int *status4, void *stream);
 
+/* ---- streaming, Xylo ----------------------------------------------------------------------------- */
+/* The Xylo chain ("Xylo-A2 hidden-layer integer LIF" above: RZCC spikes into the integer LIF layer, rate, peak) for ONE stream of B
+ * recordings that arrive in tiles -- the reference's live loop micloc/xylo_snn_localization.py:446-542 without restarting the chain on
+ * every pack.  PARITY UNPINNED like every Xylo entry: the LIF equals oracle_xylo_lif bit for bit, the oracle is not checked against XyloSim.
+ *   Limits.  The stream is the w_rec == 0 packed form: no recurrent weight (it would couple all bands per step), a bipolar encoder
+ *   (ternary raster, Cin = 2 x ternary_channels), Cin <= 64 (at most 16 microphones), any N.
+ *   The resumable LIF by value.  state (micloc_xylo_stream_state_bytes, 256-B aligned) holds {isyn, vmem, count0, count1} of every lane
+ *   pair, 16 bytes per two neurons, [B][N rounded up to 512 / 2]; micloc_xylo_stream_reset zero-fills it -- zero state and zero counts come
+ *   from there, never from the kernel.  micloc_xylo_lif_resume_i16 integrates the frames [t0, t0 + n) of raster int8
+ *   [B][trial_stride_frames][ternary_channels] (16-byte aligned) from the state and leaves the state behind them: the counts accumulate
+ *   in the state and counts [B][N] is rewritten by every call; n == 0 returns MICLOC_OK and rewrites nothing.  t0 is a multiple of 16,
+ *   t0 + n <= trial_stride_frames.  spikes_out (may be NULL) uint8 [B][T_out][N] receives the rows t0 .. t0 + n - 1 (t0 + n <= T_out).
+ *   ws / ws_bytes: micloc_xylo_upload's.  Calls over consecutive ranges from a reset state equal micloc_xylo_lif_resident_i16 on the whole
+ *   raster bit for bit, for every cut.  No host access, no synchronisation.
+ *   One band's stream.  Per band: the plan of its band-pass (no bf_mat, no neuron kernel), the encoder state (micloc_stream_state_bytes),
+ *   loc_state (micloc_stream_xylo_state_bytes: the control words and the clock), the raster window int8 [B][window_frames][2M]
+ *   (window_frames a multiple of 256), the network (micloc_xylo_upload), lif_state and counts [B][N]; micloc_stream_xylo_reset zeroes all
+ *   but the network.  One tile = micloc_stream_xylo_begin_tile (clock, window slide) -> micloc_stht_f64 of [history | tile] ->
+ *   micloc_stream_wrap_rows_f64 -> micloc_stream_encode_tile_f64 -> micloc_stream_xylo_tile_i16: the horizon in chunks of 256 frames, the
+ *   resumable LIF over the chunks that became final (everything up to the end on the final tile), (the window read-out,) the commit, the
+ *   clock's tick.  No call carries an absolute time: a tile length is ONE capturable hipGraph.
+ *   micloc_stream_xylo_status: {chunks integrated, frames integrated, window-lag failures, frames pushed}; it synchronises.
+ *   Windows (micloc_stream_xylo_tile_windows_i16): window and hop are multiples of 256 frames, hop <= window; the rule of "streaming
+ *   windows" above -- window n = frames [n hop, n hop + window), emitted when its last chunk is integrated, on the final tile also the
+ *   windows of micloc_window_count that the end of the recording cuts.  The band's emitted windows (per-neuron counts, exact integers) go
+ *   to row n % ring_depth of a ring inside win_state (micloc_stream_xylo_window_state_bytes; _window_reset zero-fills it); ws
+ *   (micloc_stream_xylo_workspace_bytes) holds the per-chunk counts of a tile and may be shared by bands that run one after the other.  The
+ *   network state is NOT reset between windows: one stream is one continuous run of the network.
+ *   Read-out over the bands (micloc_stream_xylo_readout, behind the tiles of all F bands): counts [B][F G] (band f's neurons at f G ..),
+ *   rate[b][g] = mean over the bands of counts_f[b][g] / frames_f * fs -- micloc_rate_from_counts_f64's expression and band order, frames_f
+ *   the frames band f has integrated so far -- and peak[b] as micloc_peak_location_i32 computes it (win_size odd, <= G / 2).  Mid-stream
+ *   each band is read over the frames IT has integrated; after the final tile every frames_f is T and rate / peak equal the one-shot
+ *   calls on the one-shot counts bit for bit.  window > 0: a window is emitted once every band has emitted it, from the bands' rings:
+ *   window n in row n % max_windows of window_counts [B][max_windows][F G], window_rate [B][max_windows][G] (over the frames the window
+ *   holds) and window_peak [B][max_windows], the newest one also in latest_* (each may be NULL); a window that a band's ring has
+ *   overwritten by then is counted as given up instead.  micloc_stream_xylo_readout_status: {windows emitted or given up, given up}.
+ *   Status, before any launch: MICLOC_ERR_INVALID for NULL or out-of-range arguments (B outside 1..65535, N, n, window_frames, max_spikes,
+ *   ring_depth, max_windows < 1, t0 or n < 0, F outside 1..MICLOC_MAX_BANDS, fs <= 0, a win_size micloc_peak_location_i32 refuses);
+ *   MICLOC_ERR_SHAPE for t0 % 16 != 0, Cin != 2 * ternary_channels, Cin > 64, a range past trial_stride_frames or T_out, a raster that is
+ *   not 16-byte aligned, a unipolar plan, window_frames, window or hop that is no multiple of 256, hop > window, n > window_frames, G > 4096
+ *   in the read-out; MICLOC_ERR_WORKSPACE for a short or misaligned buffer.  The size functions return 0 for such arguments. */
+size_t micloc_xylo_stream_state_bytes(int B, int N);
+int micloc_xylo_stream_reset(void *state, size_t state_bytes, void *stream);
+int micloc_xylo_lif_resume_i16(const int8_t *raster, int ternary_channels, int trial_stride_frames, int B, int t0, int n, int Cin, int N,
+                               int max_spikes, uint8_t *spikes_out, int T_out, int32_t *counts, void *state, size_t state_bytes, void *ws,
+                               size_t ws_bytes, void *stream);
+size_t micloc_stream_xylo_state_bytes(void);
+size_t micloc_stream_xylo_workspace_bytes(int B, int N, int window_frames);
+int micloc_stream_xylo_reset(const micloc_plan *p, int B, void *enc_state, size_t enc_bytes, void *loc_state, size_t loc_bytes, int8_t *window,
+                             int window_frames, int N, void *lif_state, size_t lif_bytes, int32_t *counts, void *stream);
+int micloc_stream_xylo_begin_tile(const micloc_plan *p, void *loc_state, int8_t *window, int8_t *scratch_window, int B, int n, int window_frames,
+                                  void *stream);
+int micloc_stream_xylo_tile_i16(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window, int B,
+                                int window_frames, int final_tile, int N, int max_spikes, int32_t *counts, void *lif_state, size_t lif_bytes,
+                                void *net_ws, size_t net_ws_bytes, void *stream);
+size_t micloc_stream_xylo_window_state_bytes(int B, int N, int window, int hop, int ring_depth);
+int micloc_stream_xylo_window_reset(void *win_state, size_t win_bytes, int B, int N, int window, int hop, int ring_depth, void *stream);
+int micloc_stream_xylo_tile_windows_i16(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
+                                        int B, int window_frames, int final_tile, int N, int max_spikes, int32_t *counts, void *lif_state,
+                                        size_t lif_bytes, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *win_state,
+                                        size_t win_bytes, int window, int hop, int ring_depth, void *stream);
+int micloc_stream_xylo_status(const void *loc_state, int *status4, void *stream);
+size_t micloc_stream_xylo_readout_state_bytes(void);
+int micloc_stream_xylo_readout_reset(void *ro_state, size_t ro_bytes, void *stream);
+int micloc_stream_xylo_readout(int F, int B, int G, double fs, int win_size, const int32_t *const *band_counts, const void *const *band_loc_state,
+                               int window, int hop, int ring_depth, int max_windows, void *const *band_win_state, void *ro_state, size_t ro_bytes,
+                               int32_t *counts, double *rate, int32_t *peak, int32_t *window_counts, double *window_rate, int32_t *window_peak,
+                               int32_t *latest_counts, double *latest_rate, int32_t *latest_peak, void *stream);
+int micloc_stream_xylo_readout_status(const void *ro_state, int *status2, void *stream);
+
 /* ---- misc ------------------------------------------------------------------------------------- */
 int micloc_abi_version(void);
 const char *micloc_status_string(int status);
