@@ -162,6 +162,17 @@ SYMBOLS = {
     "micloc_beamform_c128_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_snn_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_beamformer_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_track_state_bytes": (c_size_t, [c_void_p, c_int]),
+    "micloc_stream_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "micloc_stream_track_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_localize_tile_track_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                      c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_complex_localize_tile_track_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                              c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                              c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_filterbank_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "micloc_band_sum_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "micloc_snn_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),

@@ -1,7 +1,9 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations): recordings that arrive tile by tile --
-// the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream, the complex stream of F bands, and the MUSIC stream.
+// the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream (each with or without the window read-out and the tracked read-out), the complex stream of F bands, and
+// the MUSIC stream.
 #include "api_internal.h"
 #include "stream_music.h"
+#include "stream_track.h"
 
 using namespace micloc;
 
@@ -207,13 +209,44 @@ int stream_window_zero(int rc, const micloc_plan *p, int B, void *win_state, siz
     return MICLOC_OK;
 }
 
+// the tracked read-out of a tile ("streaming, tracking"): the envelope state, the rule's constants, the ring and the pair scratch
+struct TrackArgs {
+    void *state;
+    size_t state_bytes;
+    double a_rise, i_rise, a_fall;
+    int R;
+    int32_t *index;
+    double *peak;
+    int32_t *latest_index;
+    double *latest_peak;
+    void *ws;
+    size_t ws_bytes;
+};
+
+// the argument rule of both tracked entries behind the stream's own plan check: `most` frames can become final in one tile
+int stream_track_args(const micloc_plan *p, const TrackArgs &t, int B, int most, int cap)
+{
+    if (!t.state || !t.index || !t.peak || !t.latest_index || !t.latest_peak || t.R < 1) return MICLOC_ERR_INVALID;
+    if (!track_fused_eligible(p->W, p->ntab, p->W_is_complex) || t.R < most) return MICLOC_ERR_SHAPE;
+    if (bad_ws(t.state, t.state_bytes, stream_track_state_bytes(B, p->G_out))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(t.ws, t.ws_bytes, stream_track_pairs_bytes(B, cap, p->G_out))) return MICLOC_ERR_WORKSPACE;
+    return MICLOC_OK;
+}
+
+int stream_track_launch(const micloc_plan *p, const TrackArgs &t, const void *src, const int *ctl, int B, int cap, int CH, hipStream_t st)
+{
+    HIP_TRY(launch_stream_track(p->W, p->ntab, p->W_is_complex, src, ctl, B, cap, CH, p->G_out, t.a_rise, t.i_rise, t.a_fall,
+                                reinterpret_cast<double *>(t.state), t.R, t.index, t.peak, t.latest_index, t.latest_peak, t.ws, st));
+    return MICLOC_OK;
+}
+
 // the launches of a tile behind the encoder: horizon, LIF + beamforming of the chunks that became final, accumulation, (the window
-// read-out in front of the commit,) commit, tick.  win_state == nullptr: no read-out; loc_state, power and argmax end with the same bits
-// either way.
+// read-out in front of the commit,) (the tracked read-out, there as well,) commit, tick.  win_state == nullptr / trk == nullptr: no such
+// read-out; loc_state, power and argmax end with the same bits either way.
 int stream_localize(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *raster, int B, int window_frames,
                     int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window,
                     int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power, int32_t *latest_argmax,
-                    void *stream)
+                    void *stream, const TrackArgs *trk = nullptr)
 {
     if (!p || !enc_state || !loc_state || !raster || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
     DeviceGuard guard(p->device);
@@ -222,6 +255,11 @@ int stream_localize(const micloc_plan *p, const void *enc_state, void *loc_state
     if (win_state) rc = stream_window_args(rc, window, hop, max_windows, &CH);
     if (rc != MICLOC_OK) return rc;
     if (window_frames % CH != 0) return MICLOC_ERR_SHAPE;
+    if (trk) {  // a tile can make every frame of the window final; the LIF history of a chunk is the one chunk in front of it
+        rc = stream_track_args(p, *trk, B, window_frames, window_frames);
+        if (rc != MICLOC_OK) return rc;
+        if (stream_track_halo(p->ntab) > CH) return MICLOC_ERR_SHAPE;
+    }
     const int G = p->G_out, Gp = 16 * p->W.GT;
     if (bad_ws(loc_state, loc_bytes, micloc_stream_localize_state_bytes(p, B))) return MICLOC_ERR_WORKSPACE;
     if (bad_ws(ws, ws_bytes, beamform_partial_bytes(B, window_frames, Gp))) return MICLOC_ERR_WORKSPACE;
@@ -241,6 +279,10 @@ int stream_localize(const micloc_plan *p, const void *enc_state, void *loc_state
     if (win_state)
         HIP_TRY(launch_stream_windows(partial, B, nch, Gp, G, 0, 0, CH, ctl, final_tile ? 1 : 0, window, hop, max_windows, win_state, window_power,
                                       window_argmax, latest_power, latest_argmax, st));
+    if (trk) {  // in front of the commit as well: the range and ctl[0] as the horizon left them
+        rc = stream_track_launch(p, *trk, raster, ctl, B, window_frames, CH, st);
+        if (rc != MICLOC_OK) return rc;
+    }
     HIP_TRY(launch_stream_commit(ctl, STREAM_BLOCK_CHUNKS, st));
     HIP_TRY(launch_stream_tick(ctl, st));
     return MICLOC_OK;
@@ -342,7 +384,7 @@ int sc_args(const micloc_plan *p, int B, int max_tile, ScArgs *a)
 // the launches behind the band-pass of a tile: contraction, accumulation, (windows,) slide + commit -- one chain on one stream
 int sc_localize(const micloc_plan *p, const ScArgs &a, void *state, int B, int final_tile, double *power, int32_t *argmax, void *ws,
                 void *win_state, int window, int hop, int max_windows, double *window_power, int32_t *window_argmax, double *latest_power,
-                int32_t *latest_argmax, hipStream_t st)
+                int32_t *latest_argmax, hipStream_t st, const TrackArgs *trk = nullptr)
 {
     double *staging = reinterpret_cast<double *>(ws);
     double *partial = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(ws) + a.ws_partial);
@@ -354,6 +396,10 @@ int sc_localize(const micloc_plan *p, const ScArgs &a, void *state, int B, int f
     if (win_state)
         HIP_TRY(launch_stream_windows(partial, B, a.Ks, a.Gp, p->G_out, 1, a.Gp / 2, a.CH, reinterpret_cast<const int *>(state), final_tile ? 1 : 0,
                                       window, hop, max_windows, win_state, window_power, window_argmax, latest_power, latest_argmax, st));
+    if (trk) {  // in front of the slide: the carry fill and the clock as they were before the tile
+        const int rc = stream_track_launch(p, *trk, staging, reinterpret_cast<const int *>(state), B, a.S, a.CH, st);
+        if (rc != MICLOC_OK) return rc;
+    }
     HIP_TRY(launch_stream_complex_slide(staging, B * p->C, a.S, a.CH, state, a.L, st));
     return MICLOC_OK;
 }
@@ -447,6 +493,78 @@ int micloc_stream_complex_localize_tile_windows_f64(const micloc_plan *p, void *
     if (bad_ws(win_state, win_bytes, stream_window_state_bytes(B, p->G_out, window, hop))) return MICLOC_ERR_WORKSPACE;
     return sc_localize(p, a, state, B, final_tile, power, argmax, ws, win_state, window, hop, max_windows, window_power, window_argmax,
                        latest_power, latest_argmax, (hipStream_t)stream);
+}
+
+// ---- streaming, tracking (stream_track.hip; the rule: include/micloc_hip.h) --------------------------------------------------------------
+size_t micloc_stream_track_state_bytes(const micloc_plan *p, int B)
+{
+    if (!p || bad_batch(B) || p->G_out < 1 || micloc_track_is_fused(p) != 1) return 0;
+    return stream_track_state_bytes(B, p->G_out);
+}
+
+size_t micloc_stream_track_workspace_bytes(const micloc_plan *p, int B, int window_frames)
+{
+    if (!p || bad_batch(B) || window_frames < 1 || p->G_out < 1 || micloc_track_is_fused(p) != 1) return 0;
+    int cap = window_frames;
+    if (p->W_is_complex) {  // the staging array of a complex stream whose longest tile has window_frames frames
+        ScArgs a;
+        if (sc_args(p, B, window_frames, &a) != MICLOC_OK) return 0;
+        cap = a.S;
+    }
+    return stream_track_pairs_bytes(B, cap, p->G_out);
+}
+
+int micloc_stream_track_reset(const micloc_plan *p, int B, void *track_state, size_t track_bytes, void *stream)
+{
+    if (!p || !track_state || bad_batch(B)) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    const int fused = micloc_track_is_fused(p);
+    if (fused < 0) return fused;
+    if (fused != 1) return MICLOC_ERR_SHAPE;
+    const size_t need = stream_track_state_bytes(B, p->G_out);
+    if (bad_ws(track_state, track_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    HIP_TRY(launch_zero_fill(track_state, need, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_localize_tile_track_f64(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
+                                          int B, int window_frames, int final_tile, double *power, int32_t *argmax, void *ws, size_t ws_bytes,
+                                          void *win_state, size_t win_bytes, int window, int hop, int max_windows, double *window_power,
+                                          int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *track_state,
+                                          size_t track_bytes, double a_rise, double i_rise, double a_fall, int max_track, int32_t *track_index,
+                                          double *track_peak, int32_t *latest_index, double *latest_peak, void *track_ws, size_t track_ws_bytes,
+                                          void *stream)
+{
+    if (win_state && !window_argmax) return MICLOC_ERR_INVALID;
+    const TrackArgs trk{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, track_ws,
+                        track_ws_bytes};
+    return stream_localize(p, enc_state, loc_state, loc_bytes, window_raster, B, window_frames, final_tile, power, argmax, ws, ws_bytes, win_state,
+                           win_bytes, window, hop, max_windows, window_power, window_argmax, latest_power, latest_argmax, stream, &trk);
+}
+
+int micloc_stream_complex_localize_tile_track_f64(const micloc_plan *p, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
+                                                  double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes,
+                                                  int window, int hop, int max_windows, double *window_power, int32_t *window_argmax,
+                                                  double *latest_power, int32_t *latest_argmax, void *track_state, size_t track_bytes,
+                                                  double a_rise, double i_rise, double a_fall, int max_track, int32_t *track_index,
+                                                  double *track_peak, int32_t *latest_index, double *latest_peak, void *track_ws,
+                                                  size_t track_ws_bytes, void *stream)
+{
+    if (!p || !state || !ws || (win_state && !window_argmax) || bad_batch(B) || max_tile < 1) return MICLOC_ERR_INVALID;
+    DeviceGuard guard(p->device);
+    ScArgs a;
+    int rc = sc_args(p, B, max_tile, &a);
+    if (win_state) rc = stream_window_args(rc, window, hop, max_windows, &a.CH);
+    if (rc != MICLOC_OK) return rc;
+    const TrackArgs trk{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, track_ws,
+                        track_ws_bytes};
+    rc = stream_track_args(p, trk, B, max_tile, a.S);  // a tile makes its own frames final, no more
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, a.ws_total)) return MICLOC_ERR_WORKSPACE;
+    if (win_state && bad_ws(win_state, win_bytes, stream_window_state_bytes(B, p->G_out, window, hop))) return MICLOC_ERR_WORKSPACE;
+    return sc_localize(p, a, state, B, final_tile, power, argmax, ws, win_state, window, hop, max_windows, window_power, window_argmax,
+                       latest_power, latest_argmax, (hipStream_t)stream, &trk);
 }
 
 /* status[0] = chunks contracted, [1] = frames contracted, [2] = carry fill, [3] = frames pushed (synchronises the stream) */

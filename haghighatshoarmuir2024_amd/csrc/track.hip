@@ -20,32 +20,11 @@
 // No buffer grows with T G.  The chain is latency (one wave, ~8 dependent instructions per step); the matrix work of a chunk is a few
 // hundred cycles per wave, and several workgroups share a compute unit (46 KB of LDS), so one workgroup's chain runs beside the
 // others' staging and matrix phases.
-#include <math.h>
-
-#include "micloc_internal.h"
+#include "track_rows.h"
 
 namespace micloc {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-constexpr int TRK_WAVES = 4;
-constexpr int TRK_THREADS = TRK_WAVES * 64;
-constexpr int TRK_CH = TRK_WAVES * 16;  // frames per chunk: one 16-frame tile per wave
-constexpr int TRK_COLS = 64;            // DoA columns per workgroup = lanes of the chain wave
-constexpr int TRK_LD = TRK_COLS + 1;    // row stride of the magnitude tile (odd: the row reduction reads down columns)
-constexpr int TRK_NONE = 0x7fffffff;
-
 int track_col_groups(int G) { return (G + TRK_COLS - 1) / TRK_COLS; }
-
-static size_t track_lds_bytes(bool complex_src, int NK)
-{
-    size_t d = (size_t)TRK_CH * TRK_LD;
-    if (complex_src)
-        d += (size_t)TRK_WAVES * 64;
-    else
-        d += (size_t)(4 * NK + 16) + (size_t)(TRK_CH + 4 * NK - 16) * 16;
-    return d * sizeof(double);
-}
 
 // The shapes the fused kernels serve: those whose y the bf_mat-stationary kernels of beamform.hip produce (their eligibility rules,
 // restated), as long as this kernel's own LDS tile fits as well.
@@ -60,68 +39,15 @@ bool track_fused_eligible(const BeamformW &W, const NeuronTab &nt, int is_comple
     return ws_y <= 160 * 1024 && track_lds_bytes(false, nt.NK) <= 160 * 1024;
 }
 
-// steps 3 and 4 of the header for the chunk [cs, cs + nrow) whose magnitudes lie in Y
-__device__ __forceinline__ void track_chain_reduce(double *Y, int wv, int l, int tid, int cs, int nrow, int T, int G, int cg, int ncg,
-                                                   double a_rise, double i_rise, double a_fall, double &state, size_t row0,
-                                                   double *__restrict__ pval, int32_t *__restrict__ pidx)
+// where the one-shot kernels leave the pair of frame cs + row: with one column group the result itself, else pval / pidx for the combine
+__device__ __forceinline__ void track_store_pair(size_t o, int ncg, double best, int bi, double *__restrict__ pval, int32_t *__restrict__ pidx)
 {
-    if (wv == 0) {
-        double *y = Y + l;
-        auto step = [&](int j) {
-            const double m = y[j * TRK_LD];
-            const double up = __dadd_rn(__dmul_rn(a_rise, state), __dmul_rn(i_rise, m));
-            const double down = __dmul_rn(a_fall, state);
-            state = (m >= state) ? up : down;
-            y[j * TRK_LD] = state;
-        };
-        int j0 = 0;
-        if (cs == 0) {  // state_0 = |y_0|: the tile already holds it
-            state = y[0];
-            j0 = 1;
-        }
-        if (nrow == TRK_CH && j0 == 0) {
-#pragma unroll 16
-            for (int j = 0; j < TRK_CH; ++j) step(j);
-        } else {
-            for (int j = j0; j < nrow; ++j) step(j);
-        }
-    }
-    __syncthreads();
-    {
-        const int row = tid >> 2, part = tid & 3;
-        double best = -1.0;
-        int bi = TRK_NONE;
-        if (row < nrow) {
-            const double *r = Y + row * TRK_LD + part * 16;
-            const int g0 = cg * TRK_COLS + part * 16;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {  // ascending: this thread's first maximum
-                const double v = r[i];
-                if (g0 + i < G && v > best) {
-                    best = v;
-                    bi = g0 + i;
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 1; s <= 2; s <<= 1) {
-            const double ov = __shfl_xor(best, s, 64);
-            const int oi = __shfl_xor(bi, s, 64);
-            if (ov > best || (ov == best && oi < bi)) {
-                best = ov;
-                bi = oi;
-            }
-        }
-        if (part == 0 && row < nrow) {
-            const size_t o = (row0 + (size_t)(cs + row)) * ncg + cg;
-            if (ncg == 1) {  // the result itself: an all-NaN row gives index 0
-                pidx[o] = bi == TRK_NONE ? 0 : bi;
-                if (pval) pval[o] = bi == TRK_NONE ? (double)NAN : best;
-            } else {
-                pidx[o] = bi;
-                pval[o] = best;
-            }
-        }
+    if (ncg == 1) {
+        pidx[o] = track_row_index(bi);
+        if (pval) pval[o] = track_row_peak(best, bi);
+    } else {
+        pidx[o] = bi;
+        pval[o] = best;
     }
 }
 
@@ -193,7 +119,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_ws_kernel(const int8_t *__r
         }
         __syncthreads();
         const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs, nrow, T, G, cg, ncg, a_rise, i_rise, a_fall, state, row0, pval, pidx);
+        track_chain_reduce(Y, wv, l, tid, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, [&](int row, double best, int bi) {
+            track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+        });
         // (the next chunk's staging touches S only; its writes to Y come after the barrier behind the staging)
     }
     if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
@@ -272,7 +200,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_wsc_kernel(const double *__
         }
         __syncthreads();
         const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs, nrow, T, G, cg, ncg, a_rise, i_rise, a_fall, state, row0, pval, pidx);
+        track_chain_reduce(Y, wv, l, tid, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, [&](int row, double best, int bi) {
+            track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+        });
     }
     if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
 }
@@ -283,18 +213,11 @@ __global__ __launch_bounds__(256) void track_combine_kernel(const double *__rest
 {
     const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
-    double best = -1.0;
-    int bi = TRK_NONE;
-    for (int c = 0; c < ncg; ++c) {
-        const double v = pval[row * ncg + c];
-        const int i = pidx[row * ncg + c];
-        if (i != TRK_NONE && v > best) {
-            best = v;
-            bi = i;
-        }
-    }
-    index[row] = bi == TRK_NONE ? 0 : bi;
-    if (peak) peak[row] = bi == TRK_NONE ? (double)NAN : best;
+    double best;
+    int bi;
+    track_combine_row(pval + row * ncg, pidx + row * ncg, ncg, best, bi);
+    index[row] = track_row_index(bi);
+    if (peak) peak[row] = track_row_peak(best, bi);
 }
 
 size_t track_pairs_bytes(int B, int T, int G)

@@ -211,6 +211,14 @@ class SNNBeamformer:
         return plan.track(plan.to_device(sig_batch), envelope.win_lens[0], envelope.win_lens[1], want_envelope_last=want_envelope_last,
                           budget_bytes=budget_bytes)
 
+    def streaming_localizer(self, bf_mat, batch=1, **kw):
+        """localize_batch (and, with track=, track_batch) for recordings that arrive tile by tile: a streaming.StreamingLocalizer (push /
+        push_replay / finish; total_frames, wrap_tail, max_tile, lag_frames, window, hop, max_windows, track, max_track as there) whose
+        results after the last tile are the one-shot calls' on the whole recording bit for bit."""
+        from .streaming import StreamingLocalizer
+
+        return StreamingLocalizer(self, bf_mat, batch, **kw)
+
     def membrane_covariance_batch(self, sig_batch, time_vec=None, t_start=0, out=None):
         """[B, T, M] -> device tensor [B, 2M, 2M] (`out`, if given): V^T V / (T - t_start) of the membrane signal over frames >= t_start."""
         B, T, M = sig_batch.shape

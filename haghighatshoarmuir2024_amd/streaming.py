@@ -32,6 +32,13 @@ that moves after a minute of audio.  With `window` the localizer also emits the 
 final, bit for bit the one-shot rows -- into a ring of `max_windows` rows: latest_window() / windows() / finish().  The state is
 2 x G doubles per trial and open window (ceil(window / hop) of them) whatever the length of the stream, and a tile is still one graph.
 
+TRACKING (track=, max_track=; StreamingLocalizer and ComplexStreamingLocalizer): the read-out meant for a MOVING source, which neither the
+running power nor a window of 256 frames follows -- `np.argmax(Envelope.evolve(y), axis=1)`, track_batch's rule (include/micloc_hip.h
+"streaming, tracking").  With `track` (a utils.Envelope) every push also emits the DoA index and the peak envelope of every frame that became
+final in it, bit for bit the rows of track_batch on the whole recording, into a ring of `max_track` frames: latest_track() / tracked() /
+finish().  The state is the envelope in front of the next frame, 64 doubles per 64 DoAs and trial, whatever the length of the stream, and a
+tile is still one graph.  track_setup is the host-side rule (which plans, which ring depths), ring_rows the arithmetic of a ring's rows.
+
 THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
@@ -54,6 +61,42 @@ import numpy as np
 
 from . import _lib, runtime, utils
 from .snn_beamformer import neuron_impulse_response
+
+
+def ring_rows(count, depth):
+    """The rows of a ring of `depth` rows that holds items 0 .. count - 1, item n in row n % depth: -> (first, k, rows), the k = min(count,
+    depth) newest items first .. count - 1 in ascending order and the ring rows they sit in.  Pure host arithmetic (windows(), tracked())."""
+    k = min(int(count), int(depth))
+    first = int(count) - k
+    return first, k, [n % int(depth) for n in range(first, first + k)]
+
+
+def track_setup(envelope, channels, num_doa, complex_bf, most, total_frames=None, max_track=None):
+    """The host-side rule of a tracked stream (track=, max_track=), checked before any device work: -> (a_rise, i_rise, a_fall, R).
+    envelope: utils.Envelope; channels: rows of the beamforming kernels' input (2 x microphones); num_doa: columns of bf_mat; most: the
+    frames one tile can make final (SNN: the raster window's capacity, complex: max_tile).  ValueError for a plan off the fused route of
+    csrc/track.hip (more than 16 channels, more than 512 DoAs with a real bf_mat), envelope windows below one sample, a ring shorter than
+    `most`.  The constants are NumPy's own arithmetic, exactly as runtime.Plan.track builds them.  R defaults to total_frames when that is
+    given (never below `most`), else to the smallest multiple of 64 that is >= 4 x most."""
+    if int(channels) > 16 or (not complex_bf and int(num_doa) > 512):
+        raise ValueError(f"a tracked stream runs the fused tracking kernels: up to 16 channels and, with a real bf_mat, up to 512 DoAs (got {channels} "
+                         f"channels, {num_doa} DoAs); use track_batch on the whole recording")
+    win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
+    if win_fall < 1 or win_rise < 1:
+        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+    wl = np.asarray([win_fall, win_rise])
+    inv = 1 / wl
+    a = 1 - inv
+    most = int(most)
+    if max_track is not None:
+        R = int(max_track)
+    elif total_frames is not None:
+        R = max(int(total_frames), most)
+    else:
+        R = -(-4 * most // 64) * 64
+    if R < most:
+        raise ValueError(f"max_track must be at least the {most} frames one tile can make final (got {R})")
+    return float(a[1]), float(inv[1]), float(a[0]), R
 
 
 class _TileStream:
@@ -108,6 +151,38 @@ class _TileStream:
         self.t = 0
         self.done = False
         self._seen, self._graphs = set(), {}
+
+    track = None  # the tracked read-out is off unless _set_track has been called
+
+    def _set_track(self, envelope, max_track, channels, num_doa, complex_bf, most):
+        """self.track (the rule's constants, None without track=), self.max_track and self.min_track (what one tile can make final):
+        track_setup's refusals, before any device work."""
+        self.track = self.max_track = None
+        self.min_track = int(most)
+        if envelope is None:
+            if max_track is not None:
+                raise ValueError("max_track belongs to the tracked read-out: give track as well")
+            return
+        *self.track, self.max_track = track_setup(envelope, channels, num_doa, complex_bf, most, self.T, max_track)
+
+    def _alloc_track(self, capacity):
+        """The device side of track=: the envelope state (zero-filled on the stream), the pair scratch for `capacity` (the raster window's
+        frames / max_tile), the ring and the newest frame."""
+        if self.track is None:
+            return
+        torch = runtime._torch()
+        dev, lib, h = self.device, self.lib, self.plan.handle
+        self.ntst = int(lib.micloc_stream_track_state_bytes(h, self.B))
+        self.ntws = int(lib.micloc_stream_track_workspace_bytes(h, self.B, int(capacity)))
+        if self.ntst == 0 or self.ntws == 0:
+            raise ValueError("micloc stream_track_state_bytes: the fused tracking kernels do not serve this plan and bf_mat")
+        self.tst = torch.empty(self.ntst, dtype=torch.uint8, device=dev)
+        self.tws = torch.empty(self.ntws, dtype=torch.uint8, device=dev)
+        self.track_index = torch.zeros((self.B, self.max_track), dtype=torch.int32, device=dev)
+        self.track_peak = torch.zeros((self.B, self.max_track), dtype=torch.float64, device=dev)
+        self.latest_index = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self.latest_peak = torch.zeros((self.B,), dtype=torch.float64, device=dev)
+        _lib.check(lib.micloc_stream_track_reset(h, self.B, runtime._ptr(self.tst), self.ntst, runtime._stream(dev)), "stream_track_reset")
 
     def _reset_window_state(self, name, lead=None, who="the plan", hint=""):
         """wst / nwst, the device state of the open windows (None / 0 without window=): sized by micloc_<name>_state_bytes, zero-filled by
@@ -192,7 +267,15 @@ class _TileStream:
         """The read-out launches of a tile: micloc_<name>_f64(*tile, stream) or, with window=, micloc_<name>_windows_f64 -- the same
         launches with the window read-out in front of the commit -- which takes the window state, the rule and the ring behind `tile`."""
         st = runtime._stream(self.device)
-        if self.window is None:
+        if self.track is not None:  # the same launches again with the tracked read-out behind the window read-out (NULL state: no windows)
+            wargs = (None, 0, 0, 0, 0, None, None, None, None) if self.window is None else \
+                (runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows, runtime._ptr(self.window_power),
+                 runtime._ptr(self.window_argmax), runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax))
+            _lib.check(getattr(self.lib, f"micloc_{name}_track_f64")(*tile, *wargs, runtime._ptr(self.tst), self.ntst, *self.track, self.max_track,
+                                                                     runtime._ptr(self.track_index), runtime._ptr(self.track_peak),
+                                                                     runtime._ptr(self.latest_index), runtime._ptr(self.latest_peak),
+                                                                     runtime._ptr(self.tws), self.ntws, st), f"{name}_track")
+        elif self.window is None:
             _lib.check(getattr(self.lib, f"micloc_{name}_f64")(*tile, st), name)
         else:
             _lib.check(getattr(self.lib, f"micloc_{name}_windows_f64")(*tile, runtime._ptr(self.wst), self.nwst, self.window, self.hop, self.max_windows,
@@ -270,11 +353,43 @@ class _TileStream:
         self._need_windows()
         torch = runtime._torch()
         count = self._window_count()
-        k = min(count, self.max_windows)
-        first = count - k
-        rows = torch.arange(first, count, device=self.device) % self.max_windows
+        first, _, rows = ring_rows(count, self.max_windows)
+        rows = torch.tensor(rows, dtype=torch.int64, device=self.device)
         return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
                     window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+
+    def _need_track(self):
+        if self.track is None:
+            raise ValueError("the localizer was built without track=")
+
+    def latest_track(self):
+        """(index [B], peak_envelope [B]) of the newest tracked frame: device tensors, overwritten by the next push that makes a frame
+        final, zeros until the first one exists.  Does not synchronise."""
+        self._need_track()
+        return self.latest_index, self.latest_peak
+
+    def tracked(self):
+        """dict(count, first, index [B, k], peak_envelope [B, k]): `count` frames have been tracked so far; the k = min(count, max_track)
+        newest of them, frames first .. count - 1 in ascending order, as device tensors (copies: later pushes do not change them).
+        Synchronises the stream."""
+        self._need_track()
+        torch = runtime._torch()
+        count = self._track_count()
+        first, _, rows = ring_rows(count, self.max_track)
+        rows = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        return dict(count=count, first=first, index=self.track_index.index_select(1, rows), peak_envelope=self.track_peak.index_select(1, rows))
+
+    def _finish_track(self, out):
+        """finish()'s tracked tail: `out` with track_index [B, T], track_peak_envelope [B, T] and envelope_last [B, G] (a live source
+        without total_frames: the max_track newest frames, see tracked())."""
+        if self.track is not None:
+            if self.T is not None and self.max_track < self.T:
+                raise _lib.MiclocError(f"the recording has {self.T} frames and the ring keeps {self.max_track}: raise max_track (or read "
+                                       "tracked() while the stream runs)")
+            w = self.tracked()
+            env = self.tst.view(runtime._torch().float64).view(self.B, -1)  # [B][column groups x 64]
+            out.update(track_index=w["index"], track_peak_envelope=w["peak_envelope"], track_count=w["count"], envelope_last=env[:, : self.G].clone())
+        return out
 
     def _need_done(self):
         if not self.done:
@@ -352,7 +467,7 @@ class StreamingLocalizer(_TileStream):
     TILE_MULTIPLE = 16  # the encoder takes its frames sixteen at a time
 
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False,
-                 window=None, hop=None, max_windows=None, _share=None):
+                 window=None, hop=None, max_windows=None, track=None, max_track=None, time_vec=None, _share=None):
         """beamf: SNNBeamformer; bf_mat [2M, G]; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself, and the neuron kernel is
                       normalised over exactly that many samples like apply_to_signal does, snn_beamformer.py:342-361); None: a
@@ -366,19 +481,29 @@ class StreamingLocalizer(_TileStream):
                       and arg-max per window (module docstring); None: the running estimate only, with exactly the launches it always had.
         max_windows   rows of the ring the windows are kept in (window n in row n % max_windows); default: every window of the
                       recording when total_frames is given, else 64.
+        track         a utils.Envelope: also emit the moving-target read-out of track_batch -- the DoA index and the peak envelope of every
+                      frame, as soon as the frame is final, bit for bit the one-shot rows (latest_track() / tracked() / finish()); needs a
+                      plan on the fused tracking route (up to 16 channels, up to 512 DoAs).  None: exactly the launches without it.
+        max_track     rows of the ring the tracked frames are kept in (frame t in row t % max_track), at least min_track = the raster
+                      window's capacity; default: total_frames when that is given (never below min_track), else the smallest multiple of 64 >= 4 x min_track.
+        time_vec      the time axis the neuron kernel is normalised over, where the one-shot call to be matched was given one of its own
+                      (track_batch(time_vec=)); default: total_frames (or 1 s of) samples on the fs grid, from 0.
         _share        (WidebandStreamingLocalizer) another StreamingLocalizer whose tile-sized scratch (`ext`, `h`, `ws`, the slide's staging
                       copy) this one uses instead of allocating its own, where it is large enough: for localizers whose tiles run one
                       after the other on one stream.  None: nothing changes."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.beamf = beamf
-        self.plan = beamf.new_plan()
-        self.device = self.plan.device
         self.B, self.M = int(batch), len(beamf.geometry)
         self.T = None if total_frames is None else int(total_frames)
+        self.max_tile = -(-int(max_tile) // 16) * 16
+        if track is not None:  # the refusals that need no plan, before any device work (the ring depth follows the chunk length, below)
+            track_setup(track, 2 * self.M, np.shape(bf_mat)[1], False, 0)
+        self.plan = beamf.new_plan()
+        self.device = self.plan.device
         self._set_stht(beamf.kernel)
         nir_frames = self.T if self.T is not None else int(beamf.fs)
-        self.plan.set_neuron_kernel(neuron_impulse_response(np.arange(nir_frames) / beamf.fs, beamf.tau_vec))
+        self.plan.set_neuron_kernel(neuron_impulse_response(np.arange(nir_frames) / beamf.fs if time_vec is None else time_vec, beamf.tau_vec))
         self.plan.set_bf_mat(np.asarray(bf_mat, dtype=np.float64))
         self.lib = _lib.load()
         self.G = self.plan.G
@@ -386,9 +511,9 @@ class StreamingLocalizer(_TileStream):
         if self.CH <= 0:
             _lib.check(self.CH, "stream_chunk_frames")
         self._set_windows(self.plan, window, hop, max_windows)
-        self.max_tile = -(-int(max_tile) // 16) * 16
         # window: the tile being encoded + the frames that may still be waiting for their spikes + one chunk of LIF history
         self.cap = -(-(self.max_tile + int(lag_frames) + 2 * self.CH) // self.CH) * self.CH
+        self._set_track(track, max_track, 2 * self.M, self.G, False, self.cap)
         dev = self.device
         self.nstate = self.lib.micloc_stream_state_bytes(self.plan.handle, self.B)
         self.state = torch.empty(int(self.nstate), dtype=torch.uint8, device=dev)
@@ -413,6 +538,7 @@ class StreamingLocalizer(_TileStream):
         self.h = scratch("h", ((self.B * self.C + 1) * self.plan.padded_T(self.halo + self.max_tile),), torch.float64)
         self._alloc_results()
         self._reset_window_state("stream_window", hint=" (a complex bf_mat?)")
+        self._alloc_track(self.cap)
         self._set_wrap(wrap_tail)
         self.raster = None
         if keep_raster:
@@ -477,7 +603,10 @@ class StreamingLocalizer(_TileStream):
             self._save_window(self.t)
             spikes = self.raster
         out = dict(power=self.power, argmax=self.argmax, spikes=spikes)
-        return self._finish_windows(out)
+        return self._finish_track(self._finish_windows(out))
+
+    def _track_count(self):
+        return self.status()["frames"]  # a frame is tracked by the launch sequence that beamforms its chunk
 
 
 class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
@@ -629,35 +758,39 @@ class ComplexStreamingLocalizer(_TileStream):
     chunks, (the window read-out,) the slide of the ragged remainder into the carry with the clock commit -- a chain of launches on one
     stream, one graph per tile length in push_replay().  The state is 2M (CH + n_coef - 1) + 2G doubles per trial however long the stream."""
 
-    def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None):
+    def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None, track=None,
+                 max_track=None):
         """beamf: beamformer.Beamformer; bf_mat [M, G] complex; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
                       final=True with the last tile.
         wrap_tail     [batch, L // 2, M]: np.roll's wrap-around rows, np.roll(x, L // 2, axis=1)[:, : L // 2] -- the last L // 2 frames of a
                       recording of at least that length (shorter ones: wrap_rows()) -- or None (zeros: a live source cannot know them).
         max_tile      longest tile push() will be given.
-        window, hop, max_windows   the windowed read-out, as StreamingLocalizer's (multiples of the plan's window quantum, hop <= window)."""
+        window, hop, max_windows   the windowed read-out, as StreamingLocalizer's (multiples of the plan's window quantum, hop <= window).
+        track, max_track           the tracked read-out, as StreamingLocalizer's (Beamformer.track_batch's rows; up to 8 microphones); a tile
+                                   makes its own frames final, so min_track = max_tile."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         bf_mat = np.asarray(bf_mat)
         if not np.iscomplexobj(bf_mat):
             raise ValueError("ComplexStreamingLocalizer takes the complex bf_mat of a Beamformer (a real one belongs to StreamingLocalizer)")
         self.beamf = beamf
-        self.plan = beamf.new_plan()  # the stream's own
-        self.device = self.plan.device
         self.B, self.M = int(batch), len(beamf.geometry)
         if bf_mat.shape[0] != self.M:
             raise ValueError(f"number of channels in the input siganl {bf_mat.shape[0]} should be the same as the number of microphones {self.M}!")
         self.T = None if total_frames is None else int(total_frames)
+        self.max_tile = int(max_tile)
+        if self.max_tile < 1:
+            raise ValueError("max_tile must be at least 1")
+        self._set_track(track, max_track, 2 * self.M, bf_mat.shape[1], True, self.max_tile)  # (refusals before any device work)
+        self.plan = beamf.new_plan()  # the stream's own
+        self.device = self.plan.device
         self._set_stht(beamf.kernel)
         self.plan.set_bf_mat(bf_mat.astype(np.complex128))
         self.lib = _lib.load()
         self.G = self.plan.G
         self.CH = self.plan.window_quantum()
         self._set_windows(self.plan, window, hop, max_windows)
-        self.max_tile = int(max_tile)
-        if self.max_tile < 1:
-            raise ValueError("max_tile must be at least 1")
         dev = self.device
         self.nstate = int(self.lib.micloc_stream_complex_state_bytes(self.plan.handle, self.B))
         self.nws = int(self.lib.micloc_stream_complex_workspace_bytes(self.plan.handle, self.B, self.max_tile))
@@ -668,6 +801,7 @@ class ComplexStreamingLocalizer(_TileStream):
         self._alloc_stht(self.B)
         self._alloc_results()
         self._reset_window_state("stream_complex_window")
+        self._alloc_track(self.max_tile)
         self._set_wrap(wrap_tail)
         _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
                    "stream_complex_reset")
@@ -708,7 +842,10 @@ class ComplexStreamingLocalizer(_TileStream):
         self._need_done()
         self._need_clock(self.status())
         out = dict(power=self.power, argmax=self.argmax)
-        return self._finish_windows(out)
+        return self._finish_track(self._finish_windows(out))
+
+    def _track_count(self):
+        return self.status()["pushed"]  # a frame is tracked by the tile that brings it
 
 
 class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):

@@ -985,6 +985,43 @@ def track_localizer(beamf, bf_mat, envelope, max_batch=1100):
     return run
 
 
+def stream_track_localizer(beamf, bf_mat, envelope, tile, max_batch=1100):
+    """track_localizer's place in moving_target_sweep(localizer=) for audio that arrives while it is tracked: every batch is pushed in
+    tiles of `tile` frames through a tracked stream (beamf.streaming_localizer(track=envelope); an SNN stream takes multiples of 16) and
+    the index [B, T] of finish() comes back -- the bits of track_batch on the whole batch, which the wrap-around rows of np.roll (known
+    here: the batch is complete) and the one-shot call's time axis of the neuron kernel make possible."""
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("tile must be at least 1 frame")
+    snn = hasattr(beamf, "tau_vec")
+    half = len(beamf.kernel) // 2
+
+    def wrap_rows(x):  # np.roll(x, half, axis=1)[:, :half], zero rows behind a recording shorter than `half`
+        if isinstance(x, np.ndarray):
+            from .streaming import ComplexStreamingLocalizer
+
+            return ComplexStreamingLocalizer.wrap_rows(x, 2 * half)
+        import torch
+
+        out = torch.zeros((x.shape[0], half, x.shape[2]), dtype=x.dtype, device=x.device)
+        k = min(half, x.shape[1])
+        out[:, :k, :] = torch.roll(x, half, dims=1)[:, :k, :]
+        return out
+
+    def run(sig_batch, time_vec):
+        def one(x):
+            B, T, _ = x.shape
+            kw = dict(time_vec=time_vec) if snn else {}
+            s = beamf.streaming_localizer(bf_mat, batch=B, total_frames=T, wrap_tail=wrap_rows(x), max_tile=min(tile, T), track=envelope, **kw)
+            for t in range(0, T, tile):
+                s.push(x[:, t : t + tile, :])
+            return (s.finish()["track_index"],)
+
+        return _in_batches(sig_batch, max_batch, one)[0]
+
+    return run
+
+
 def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, num_period=0.5, lag_frames=None, settle_frames=None,
                         snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None, freq_design=2000.0,
                         test_duration=100e-3, snr_gain_due_to_bandwidth=None, localizer=None, batch_trials=1100, out_dir=None, store_key=None):
@@ -996,7 +1033,8 @@ def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, nu
     `doa_list[index[t]]` with index = argmax_g Envelope(y)[t, g], is scored against the truth of frame t - lag_frames (default
     int(kernel_duration * fs), the script's alignment at :628) over the frames t >= settle_frames (default int(fs * fall_time)) by the
     pi-periodic error (track_errors: on the device; only per-trial scalars are gathered, in one all-gather).
-    `localizer(sig_batch, time_vec) -> index [B, T]` (device tensor or array) replaces the fused call (track_localizer).
+    `localizer(sig_batch, time_vec) -> index [B, T]` (device tensor or array) replaces the fused call (track_localizer), e.g. by the
+    tracked stream (stream_track_localizer).
     Returns dict(phase, err (mean error over frames), med (median over frames): [num_snr, num_sim]; track_mae_deg [num_snr], the mean of
     err over trials; track_median_deg [num_snr], the median over trials of med; mae_deg = track_mae_deg).  out_dir resume as the other
     sweeps; the key also covers doa_max, num_period, lag_frames, settle_frames, the envelope's window lengths and the method's

@@ -637,6 +637,47 @@ int micloc_beamformer_pipeline_track_f64(const micloc_plan *plan, const double *
                                          double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes,
                                          void *stream);
 
+/* ---- streaming, tracking: a DoA per frame while the recording arrives ---------------------------- */
+/* The tracking rule above for a recording that arrives tile by tile ("streaming" and "streaming, complex Beamformer"): every frame is
+ * EMITTED -- its index and its peak envelope written -- by the localize call of the tile that makes it final, and the emitted rows equal,
+ * bit for bit, index / peak_env of the one-shot tracking call on the whole recording, whatever the tiling; after the last tile the first
+ * G columns of every trial's row of track_state equal env_last.
+ *   - When a frame is final.  SNN stream: when the chunk of the stream that holds it is beamformed (the chunk range the horizon leaves;
+ *     micloc_stream_localize_status' frames count the emitted frames).  Complex stream: when its tile is band-passed (the frames pushed).
+ *   - Where it goes.  Frame t of trial b goes to row t % max_track of track_index [B][max_track] int32 / track_peak [B][max_track] double;
+ *     the newest emitted frame also to latest_index [B] / latest_peak [B].  All four are required device buffers.  max_track must be at
+ *     least what one tile can make final: window_frames (SNN), max_tile (complex).
+ *   - State.  track_state holds e[t-1][g] in front of the next frame: [B][ceil(G / 64) * 64] doubles (micloc_stream_track_state_bytes),
+ *     zero-filled once by micloc_stream_track_reset; e[0] = m[0] is taken where the stream's clock says frame 0.  Nothing grows with the
+ *     stream.  track_ws is scratch of micloc_stream_track_workspace_bytes (one (value, index) pair per window frame and 64 DoA columns;
+ *     for a complex plan its third argument is max_tile).
+ * The entries are micloc_stream_localize_tile_f64 / micloc_stream_complex_localize_tile_f64 with the tracking launch (and its combine
+ * launch when G > 64) in front of the commit / the slide, where the window read-out sits; they take the window arguments too: with
+ * win_state == NULL (the other window arguments are then not read) there is no window read-out, otherwise it is that of the *_windows
+ * entry.  power, argmax and the window rows have the bits of the entries without tracking.  No launch argument depends on time: a tile
+ * stays one capturable sequence.
+ * Status codes before any launch: MICLOC_ERR_SHAPE for a plan the fused kernels do not serve (micloc_track_is_fused() != 1), a plan of
+ * the other kind, max_track below what one tile can make final, or (SNN) a neuron kernel whose LIF history 4 NK - 16 is longer than a
+ * chunk of the stream; MICLOC_ERR_WORKSPACE for a missing, misaligned or short state / scratch; MICLOC_ERR_INVALID (a NULL track_state
+ * or result buffer among them) / MICLOC_ERR_NOT_SET as everywhere. */
+size_t micloc_stream_track_state_bytes(const micloc_plan *plan, int B); /* 0 on bad arguments or a plan the fused kernels do not serve */
+size_t micloc_stream_track_workspace_bytes(const micloc_plan *plan, int B, int window_frames); /* likewise */
+int micloc_stream_track_reset(const micloc_plan *plan, int B, void *track_state, size_t track_bytes, void *stream);
+int micloc_stream_localize_tile_track_f64(const micloc_plan *plan, const void *enc_state, void *loc_state, size_t loc_bytes,
+                                          const int8_t *window_raster, int B, int window_frames, int final_tile, double *power, int32_t *argmax,
+                                          void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop, int max_windows,
+                                          double *window_power, int32_t *window_argmax, double *latest_power, int32_t *latest_argmax,
+                                          void *track_state, size_t track_bytes, double a_rise, double i_rise, double a_fall, int max_track,
+                                          int32_t *track_index, double *track_peak, int32_t *latest_index, double *latest_peak, void *track_ws,
+                                          size_t track_ws_bytes, void *stream);
+int micloc_stream_complex_localize_tile_track_f64(const micloc_plan *plan, void *state, size_t state_bytes, int B, int max_tile, int final_tile,
+                                                  double *power, int32_t *argmax, void *ws, size_t ws_bytes, void *win_state, size_t win_bytes,
+                                                  int window, int hop, int max_windows, double *window_power, int32_t *window_argmax,
+                                                  double *latest_power, int32_t *latest_argmax, void *track_state, size_t track_bytes,
+                                                  double a_rise, double i_rise, double a_fall, int max_track, int32_t *track_index,
+                                                  double *track_peak, int32_t *latest_index, double *latest_peak, void *track_ws,
+                                                  size_t track_ws_bytes, void *stream);
+
 /* ---- wideband localisation: filterbank, one SNN chain per band, band sum ------------------------ */
 /* The deployed form of the method (micloc/localization_demo_snn.py:125-193): a filterbank splits the recording into F bands
  * (:160-164, micloc/filterbank.py:25-46), every band runs its own SNNBeamformer.apply_to_signal with its own band-pass, neuron
