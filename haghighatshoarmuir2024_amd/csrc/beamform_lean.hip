@@ -5,6 +5,8 @@
 // on a gfx950 SIMD a vector instruction is never hidden behind a v_mfma_f64 (DESIGN.md 4.3 holds the instruction census of both):
 //   * NK (k-steps of the LIF product) is a template parameter: the LIF is straight-line code, every LDS read an immediate offset from one
 //     base, the first matrix instruction of a chain takes a literal zero C (no accumulator clears, no pointer updates, no loop);
+//     -- and at 35 taps, the sweep's neuron kernel, the LIF leaves the matrix cores altogether: a sliding-window FIR on the vector ALU
+//     without the product's padding (the kernel's own header, below; 32.9 KB of LDS);
 //   * LDS is a static array: the parked fragments and the nir table sit at compile-time addresses;
 //   * an interior chunk's (240 + 4 NK) x 14 raster bytes are ONE contiguous range: 8 bytes per lane, one coalesced load per wave, every
 //     lane converts its 8 values and writes them as four 16-byte pairs (a pair never straddles a row: 14 is even); the two padding
@@ -140,21 +142,43 @@ __device__ __forceinline__ void lean_stage2(const double *Vl, const double *__re
 
 }  // namespace
 
-template <int NK, int NGW>
+// NTAPS == 0: stage 1 on the matrix cores (any tap count of NK k-steps).  NTAPS > 0: stage 1 as a sliding-window FIR of exactly NTAPS taps
+// on the vector ALU.  The Toeplitz product pads: 16 rows for 14 channels, 4 NK lags for NTAPS, two triangles of zeros -- 41 % of its matrix
+// cycles at 35 taps; the FIR issues only the NTAPS x 14 useful multiply-adds per frame, at the same peak rate.  Lane = (channel, 8 consecutive
+// frames of the wave's 32): 56 lanes, 8 independent chains per lane, each chain lag NTAPS - 1 down to 0 -- past samples in chronological
+// order, one fma per sample from +0, which is what the matrix core does with the same operands; the lags it also multiplies (zero taps, zero
+// rows) leave a +0-started chain as it is.  Same membrane bits, same fragments in LDS, same stage 2.
+//   * the spike tile is channel-major, [14][FP] doubles: a lane's 8 + NTAPS - 1 values are contiguous and 16-byte aligned, each is read once
+//     (21 ds_read_b128 per lane at 35 taps); FP = 2 (mod 4) doubles keeps the four 16-lane groups of a b128 read on distinct banks
+//     (lane = 4 c + block: slot (FP / 2) c + 4 block mod 16);
+//   * the window lives in registers: with the loop unrolled its advance by one value per lag is register renaming;
+//   * the taps are wave-uniform: scalar loads of the global table (tap k at tab[15 + k], see micloc_plan_set_neuron_kernel), the scalar
+//     operand of every fma; no table in LDS.  They are requested where they are used, not at the kernel's start: 70 SGPRs live across
+//     staging made 105 in all, one wave per SIMD fewer than the 100 that eight waves allow, and the three-stream step LOST 0.03 ms to
+//     it while the launch alone won (96 now; profiles/ws_lean_fir/RECORD.json);
+//   * the wave runs its fmas at raised priority: on a SIMD whose other waves issue fp64 matrix instructions a vector instruction between
+//     two of them pays the switch, a run of 280 of them must not be dealt out one at a time (step 1.42 -> 1.39 ms);
+//   * staging keeps its one 8-byte load and one conversion per element; the stores go to [channel][row], there are no padding columns.
+template <int NK, int NGW, int NTAPS>
 __global__ __launch_bounds__(LEAN_THREADS, 6) void beamform_ws_kernel_lean(const int8_t *__restrict__ spikes, const double *__restrict__ ntab_g,
                                                                             const double *__restrict__ Wp, int GT, int T,
                                                                             double *__restrict__ partial)
 {
+    constexpr bool FIR = NTAPS > 0;
     constexpr int R = LEAN_CH + 4 * NK - 16;    // spike rows of a chunk: its frames and the LIF halo in front of them
-    constexpr int NTAB = 4 * NK + 16;
+    constexpr int FP = R + 2;                   // FIR: doubles per channel row of the spike tile
+    constexpr int FOFF = 4 * NK - 16 - (NTAPS - 1);  // FIR: the row of frame 0's oldest sample
+    constexpr int NTAB = FIR ? 0 : 4 * NK + 16;
+    constexpr int NSPK = FIR ? LEAN_C * FP : R * 16;
     constexpr int NB8 = R * LEAN_C / 8;         // 8-byte words of an interior chunk's raster bytes
-    static_assert(R * 16 >= LEAN_TILES * 256, "the parked fragments alias the spike tile");
+    static_assert(FIR || R * 16 >= LEAN_TILES * 256, "the parked fragments alias the spike tile");
+    static_assert(!FIR || (FOFF >= 0 && FOFF % 2 == 0 && FP % 4 == 2 && (NTAPS + 7) % 2 == 0), "FIR: 16-byte window reads, conflict-free pitch");
     static_assert((R * LEAN_C) % 8 == 0 && 4 * NB8 < 13000, "wide staging: whole 8-byte words, and the division by 7 below");
-    // [ union{ spike tile as fp64 [R][16] , V fragments [16 tiles][4][64 lanes] } ][ nir table ]
-    __shared__ __attribute__((aligned(16))) double smem[R * 16 + NTAB];
+    // [ union{ spike tile as fp64 [R][16] (FIR: [14][FP]) , V fragments [16 tiles][4][64 lanes] } ][ nir table (matrix form only) ]
+    __shared__ __attribute__((aligned(16))) double smem[(NSPK > LEAN_TILES * 256 ? NSPK : LEAN_TILES * 256) + NTAB];
     double *S = smem;
     double *Vl = smem;
-    double *ntab = smem + R * 16;
+    double *ntab = smem + (NSPK > LEAN_TILES * 256 ? NSPK : LEAN_TILES * 256);
     const int Gp = 16 * GT;
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -166,7 +190,8 @@ __global__ __launch_bounds__(LEAN_THREADS, 6) void beamform_ws_kernel_lean(const
     const int nchunks = gridDim.x;
     const int cs = chunk * LEAN_CH;
 
-    for (int e = tid; e < NTAB; e += LEAN_THREADS) ntab[e] = ntab_g[e];
+    if constexpr (!FIR)
+        for (int e = tid; e < NTAB; e += LEAN_THREADS) ntab[e] = ntab_g[e];
     {
         const int8_t *sb = spikes + (size_t)b * T * LEAN_C;
         const int tau0 = cs + 16 - 4 * NK;
@@ -179,26 +204,40 @@ __global__ __launch_bounds__(LEAN_THREADS, 6) void beamform_ws_kernel_lean(const
                 const int row0 = (4 * i * 9363) >> 16;   // (8 i) / 14, exact below 13107
                 const int col0 = 8 * i - LEAN_C * row0;  // even
                 const int k = (LEAN_C - col0) >> 1;      // pairs in front of the row's end
-                double *d = S + row0 * 16 + col0;
+                if constexpr (FIR) {
+                    double *d = S + col0 * FP + row0;
 #pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const unsigned h = w[p >> 1] >> (16 * (p & 1));
-                    double2_t v;
-                    v[0] = (double)(int)(int8_t)(h & 0xff);
-                    v[1] = (double)(int)(int8_t)((h >> 8) & 0xff);
-                    // behind the row's end: over the two padding columns, into the next row.  k >= 1, so never the first pair: `p > 0` says so at compile time and spares that pair's compare and select
-                    double *dp = (p > 0 && p >= k) ? d + 2 : d;
-                    *reinterpret_cast<double2_t *>(dp + 2 * p) = v;
+                    for (int p = 0; p < 4; ++p) {
+                        const unsigned h = w[p >> 1] >> (16 * (p & 1));
+                        // behind the row's end: channel 0 of the next row (k >= 1: never the first pair)
+                        double *dp = (p > 0 && p >= k) ? d + (1 - LEAN_C * FP) : d;
+                        dp[(2 * p) * FP] = (double)(int)(int8_t)(h & 0xff);
+                        dp[(2 * p + 1) * FP] = (double)(int)(int8_t)((h >> 8) & 0xff);
+                    }
+                } else {
+                    double *d = S + row0 * 16 + col0;
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const unsigned h = w[p >> 1] >> (16 * (p & 1));
+                        double2_t v;
+                        v[0] = (double)(int)(int8_t)(h & 0xff);
+                        v[1] = (double)(int)(int8_t)((h >> 8) & 0xff);
+                        // behind the row's end: over the two padding columns, into the next row.  k >= 1, so never the first pair: `p > 0` says so at compile time and spares that pair's compare and select
+                        double *dp = (p > 0 && p >= k) ? d + 2 : d;
+                        *reinterpret_cast<double2_t *>(dp + 2 * p) = v;
+                    }
                 }
             }
-            for (int rho = tid; rho < R; rho += LEAN_THREADS) *reinterpret_cast<double2_t *>(S + rho * 16 + LEAN_C) = double2_t{0.0, 0.0};
+            if constexpr (!FIR)
+                for (int rho = tid; rho < R; rho += LEAN_THREADS) *reinterpret_cast<double2_t *>(S + rho * 16 + LEAN_C) = double2_t{0.0, 0.0};
         } else {
             // first / last chunk of a trial: rows outside [0, T) are zero (element-wise, as in beamform_ws_kernel)
             const int c = tid & 15;
             constexpr int RP = LEAN_THREADS / 16;
             const int rr = tid >> 4;
             if (c >= LEAN_C) {
-                for (int rho = rr; rho < R; rho += RP) S[rho * 16 + c] = 0.0;
+                if constexpr (!FIR)
+                    for (int rho = rr; rho < R; rho += RP) S[rho * 16 + c] = 0.0;
             } else {
                 for (int r0 = rr; r0 < R; r0 += RP * 6) {
                     int8_t v[6];
@@ -212,7 +251,7 @@ __global__ __launch_bounds__(LEAN_THREADS, 6) void beamform_ws_kernel_lean(const
                     for (int i = 0; i < 6; ++i) {
                         const int rho = r0 + RP * i;
                         const int tau = tau0 + rho;
-                        if (rho < R) S[rho * 16 + c] = (tau >= 0 && tau < T) ? (double)v[i] : 0.0;
+                        if (rho < R) S[FIR ? c * FP + rho : rho * 16 + c] = (tau >= 0 && tau < T) ? (double)v[i] : 0.0;
                     }
                 }
             }
@@ -220,39 +259,77 @@ __global__ __launch_bounds__(LEAN_THREADS, 6) void beamform_ws_kernel_lean(const
     }
     __syncthreads();
 
-    // ---- stage 1: membrane fragments of this wave's 2 time tiles; k-steps ascending = past samples in chronological order ----------
+    // ---- stage 1: membrane fragments of this wave's 2 time tiles; past samples in chronological order ------------------------------
     const int tb0 = cs + wv * LEAN_NT * 16;
     const bool active = tb0 < T;  // wave-uniform
-    double4_t vacc[LEAN_NT];
-    if (active) {
-        const double *sp = S + (wv * LEAN_NT * 16 + q) * 16 + lc;
-        const double *np_ = ntab + (lc - q + 3);  // the tap row of the LAST k-step: non-negative immediate offsets only
+    if constexpr (FIR) {
+        constexpr int NW = NTAPS + 7;            // the lane's window: 8 frames and NTAPS - 1 samples in front of them
+        const int fc = l >> 2, fb = l & 3;       // channel, block of 8 frames
+        const bool mine = active && fc < LEAN_C;
+        double facc[8];
+        // one unbroken run of fmas, ahead of the other waves' matrix instructions
+        if (active) __builtin_amdgcn_s_setprio(3);
+        if (mine) {
+            double tap[NTAPS];
 #pragma unroll
-        for (int ks = 0; ks < NK; ++ks) {
-            const double bn = np_[4 * (NK - 1 - ks)];
-            double a[LEAN_NT];
+            for (int k = 0; k < NTAPS; ++k) tap[k] = ntab_g[15 + k];
+            const double2_t *sp = reinterpret_cast<const double2_t *>(S + fc * FP + wv * LEAN_NT * 16 + 8 * fb + FOFF);
+            double wnd[NW];
 #pragma unroll
-            for (int tt = 0; tt < LEAN_NT; ++tt) a[tt] = sp[(16 * tt + 4 * ks) * 16];
+            for (int m = 0; m < NW / 2; ++m) {
+                const double2_t v = sp[m];
+                wnd[2 * m] = v[0];
+                wnd[2 * m + 1] = v[1];
+            }
 #pragma unroll
-            for (int tt = 0; tt < LEAN_NT; ++tt)
-                vacc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tt], bn, ks == 0 ? double4_t{0.0, 0.0, 0.0, 0.0} : vacc[tt], 0, 0, 0);
+            for (int s = 0; s < NTAPS; ++s)      // lag NTAPS - 1 - s: frame i takes the sample s + i of the window
+#pragma unroll
+                for (int i = 0; i < 8; ++i) facc[i] = __builtin_fma(tap[NTAPS - 1 - s], wnd[s + i], s == 0 ? 0.0 : facc[i]);
         }
-    }
-    __syncthreads();  // every wave is done with the spike tile: the V fragments may overwrite it
-    if (active) {
-        if (tb0 + LEAN_NT * 16 > T) {  // only the wave that straddles the end of the trial masks
+        if (active) __builtin_amdgcn_s_setprio(0);
+        __syncthreads();  // every wave is done with the spike tile: the V fragments may overwrite it
+        if (mine) {
+            if (tb0 + LEAN_NT * 16 > T) {  // only the wave that straddles the end of the trial masks
 #pragma unroll
-            for (int tt = 0; tt < LEAN_NT; ++tt) {
-                const bool tvalid = (tb0 + 16 * tt + lc) < T;
+                for (int i = 0; i < 8; ++i) facc[i] = (tb0 + 8 * fb + i) < T ? facc[i] : 0.0;
+            }
+            // frame 8 fb + i of channel fc, where the matrix form's accumulator rows lie: tile [c][t]
+            double2_t *vp = reinterpret_cast<double2_t *>(Vl + (wv * LEAN_NT + (fb >> 1)) * 256 + 16 * fc + 8 * (fb & 1));
 #pragma unroll
-                for (int r = 0; r < 4; ++r) vacc[tt][r] = tvalid ? vacc[tt][r] : 0.0;
+            for (int i = 0; i < 4; ++i) vp[i] = double2_t{facc[2 * i], facc[2 * i + 1]};
+        }
+    } else {
+        double4_t vacc[LEAN_NT];
+        if (active) {
+            const double *sp = S + (wv * LEAN_NT * 16 + q) * 16 + lc;
+            const double *np_ = ntab + (lc - q + 3);  // the tap row of the LAST k-step: non-negative immediate offsets only
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                const double bn = np_[4 * (NK - 1 - ks)];
+                double a[LEAN_NT];
+#pragma unroll
+                for (int tt = 0; tt < LEAN_NT; ++tt) a[tt] = sp[(16 * tt + 4 * ks) * 16];
+#pragma unroll
+                for (int tt = 0; tt < LEAN_NT; ++tt)
+                    vacc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[tt], bn, ks == 0 ? double4_t{0.0, 0.0, 0.0, 0.0} : vacc[tt], 0, 0, 0);
             }
         }
+        __syncthreads();  // every wave is done with the spike tile: the V fragments may overwrite it
+        if (active) {
+            if (tb0 + LEAN_NT * 16 > T) {  // only the wave that straddles the end of the trial masks
 #pragma unroll
-        for (int tt = 0; tt < LEAN_NT; ++tt) {
-            double *vp = Vl + (wv * LEAN_NT + tt) * 256 + l;
+                for (int tt = 0; tt < LEAN_NT; ++tt) {
+                    const bool tvalid = (tb0 + 16 * tt + lc) < T;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) vp[64 * r] = vacc[tt][r];
+                    for (int r = 0; r < 4; ++r) vacc[tt][r] = tvalid ? vacc[tt][r] : 0.0;
+                }
+            }
+#pragma unroll
+            for (int tt = 0; tt < LEAN_NT; ++tt) {
+                double *vp = Vl + (wv * LEAN_NT + tt) * 256 + l;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) vp[64 * r] = vacc[tt][r];
+            }
         }
     }
     __syncthreads();
@@ -277,8 +354,11 @@ bool launch_lif_beamform_lean(const BeamformW &W, const NeuronTab &nt, const int
     const int nch = (T + LEAN_CH - 1) / LEAN_CH;
     const dim3 grid(nch, B), block(LEAN_THREADS);
     switch (nt.NK) {
-        case 13:  // 35 taps: the neuron kernel of the 48 kHz sweeps (BASELINE configs 2 and 3)
-            hipLaunchKernelGGL((beamform_ws_kernel_lean<13, 3>), grid, block, 0, stream, spikes, nt.tab, W.Wp, W.GT, T, partial);
+        case 13:
+            if (nt.n == 35)  // the neuron kernel of the 48 kHz sweeps (BASELINE configs 2 and 3): stage 1 as a vector FIR
+                hipLaunchKernelGGL((beamform_ws_kernel_lean<13, 3, 35>), grid, block, 0, stream, spikes, nt.tab, W.Wp, W.GT, T, partial);
+            else  // 34 .. 37 taps: stage 1 on the matrix cores
+                hipLaunchKernelGGL((beamform_ws_kernel_lean<13, 3, 0>), grid, block, 0, stream, spikes, nt.tab, W.Wp, W.GT, T, partial);
             break;
         default: return false;
     }
