@@ -6,7 +6,7 @@ src=$1; pat=${2:-.}
 root=$(cd "$(dirname "$0")/../.." && pwd)
 out=$root/build_dev/isa; mkdir -p $out
 extra=""
-[ "$src" = xylo.hip ] && extra="-mllvm -amdgpu-mfma-vgpr-form"
+case "$src" in xylo.hip|stream_xylo.hip) extra="-mllvm -amdgpu-mfma-vgpr-form" ;; esac  # (as the Makefile does)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --cuda-device-only -S $extra \
     -o $out/${src%.hip}.s $root/haghighatshoarmuir2024_amd/csrc/$src 2>/dev/null
 python3 - "$out/${src%.hip}.s" "$pat" <<'PY'
@@ -16,7 +16,7 @@ pat = re.compile(sys.argv[2])
 for m in re.finditer(r'\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel', s, re.S):
     name, body = m.group(1), m.group(2)
     dn = subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()
-    dn = re.sub(r'\(.*', '', dn).replace('void micloc::', '')
+    dn = re.sub(r'\(.*', '', dn.replace('(anonymous namespace)::', '')).replace('void micloc::', '')
     if not pat.search(dn):
         continue
     g = lambda k: (re.search(r'\.amdhsa_' + k + r'\s+(\S+)', body) or [None, '?'])[1]

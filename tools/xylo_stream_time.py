@@ -28,7 +28,7 @@ from tools.wideband_time import timed  # noqa: E402
 
 FS, T, M, G = 48_000, 12_000, 7, 449
 SOURCES = ["haghighatshoarmuir2024_amd/csrc/stream_xylo.hip", "haghighatshoarmuir2024_amd/csrc/api_xylo_stream.hip", "haghighatshoarmuir2024_amd/csrc/xylo.hip",
-           "haghighatshoarmuir2024_amd/csrc/rzcc.hip", "haghighatshoarmuir2024_amd/streaming.py", "haghighatshoarmuir2024_amd/xylo_snn_localization.py",
+           "haghighatshoarmuir2024_amd/csrc/xylo_rows.h", "haghighatshoarmuir2024_amd/csrc/rzcc.hip", "haghighatshoarmuir2024_amd/streaming.py", "haghighatshoarmuir2024_amd/xylo_snn_localization.py",
            "tools/wideband_time.py", "tools/xylo_stream_time.py"]
 
 
