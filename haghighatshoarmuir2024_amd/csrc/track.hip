@@ -11,7 +11,7 @@
 //   2. y = V W for the wave's tile and the workgroup's four DoA tiles: v_mfma_f64_16x16x4_f64 over k = 0 .. 3 in that order from a
 //      zero accumulator (complex: the k-steps that hold channels, then the tail channels as plain FMAs) -- the instruction sequence
 //      of the WANT_Y paths of beamform.hip, so every y[t][g] has the bits apply_to_signal(to_host=False) gives it.  |y| (fabs, or
-//      hypot(re, im) as EnvIn<MICLOC_ENV_C128>) goes to an LDS tile [64 frames][64 columns].
+//      the device hypot of (re, im) as EnvIn<MICLOC_ENV_C128>) goes to an LDS tile [64 frames][64 columns].
 //   3. wave 0 walks the 64 envelope chains (one lane per column) over the tile in place: envelope_kernel's recurrence, __dmul_rn /
 //      __dadd_rn, nothing fused, state_0 = |y_0|, rise when |y_t| >= state.  The chain state stays in a register across chunks.
 //   4. every frame of the tile is reduced to (max envelope, first index) over the workgroup's columns by rows_argmax_kernel's rule
@@ -20,6 +20,9 @@
 // No buffer grows with T G.  The chain is latency (one wave, ~8 dependent instructions per step); the matrix work of a chunk is a few
 // hundred cycles per wave, and several workgroups share a compute unit (46 KB of LDS), so one workgroup's chain runs beside the
 // others' staging and matrix phases.
+// The four stages are written once, in track_rows.h (track_ws_walk / track_wsc_walk over track_chain_reduce), for these kernels and for
+// the streaming ones of stream_track.hip, with the channel-count table and the pairs layout of the launchers.  Here: the kernels as a walk
+// from frame 0 with a zero chain state, the store of a pair, the last envelope row; the combine; the read-out of the two-step route.
 #include "track_rows.h"
 
 namespace micloc {
@@ -58,72 +61,14 @@ __global__ __launch_bounds__(TRK_THREADS) void track_ws_kernel(const int8_t *__r
                                                                int32_t *__restrict__ pidx, double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Gp = 16 * GT;
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;
-    const int lc = l & 15;
-    const int q = l >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
     const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    const int R = TRK_CH + 4 * NK - 16;
-    const int ntab_len = 4 * NK + 16;
-    double *Y = reinterpret_cast<double *>(smem);  // [TRK_CH][TRK_LD]
-    double *ntab = Y + TRK_CH * TRK_LD;
-    double *S = ntab + ntab_len;  // spike tile as fp64 [R][16]
-
-    for (int e = tid; e < ntab_len; e += TRK_THREADS) ntab[e] = ntab_g[e];
-    // bf_mat fragments of the workgroup's four DoA tiles, once (a tile beyond the grid multiplies a clamped one; its columns are never read)
-    double Wf[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int gt = 4 * cg + j;
-        const double *wp = Wp + 16 * (gt < GT ? gt : GT - 1) + lc;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) Wf[j][k] = wp[(size_t)(4 * k + q) * Gp];
-    }
-    const int8_t *sb = spikes + (size_t)b * T * C;
     const size_t row0 = (size_t)b * T;
     double state = 0.0;
-    for (int cs = 0; cs < T; cs += TRK_CH) {
-        {  // rows tau0 .. tau0 + R - 1 of the raster; rows outside [0, T) and the channel padding are zero
-            const int tau0 = cs + 16 - 4 * NK;
-            const int c = tid & 15;
-            for (int rho = tid >> 4; rho < R; rho += TRK_THREADS / 16) {
-                const int tau = tau0 + rho;
-                const bool ok = c < C && tau >= 0 && tau < T;
-                S[rho * 16 + c] = ok ? (double)sb[(size_t)tau * C + c] : 0.0;
-            }
-        }
-        __syncthreads();
-        // ---- membrane fragments of this wave's tile (beamform_ws_kernel, stage 1) ----
-        const int tb0 = cs + wv * 16;
-        double4_t vacc = double4_t{0.0, 0.0, 0.0, 0.0};
-        if (tb0 < T) {  // (wave-uniform)
-            const double *sp = S + (size_t)(wv * 16 + q) * 16 + lc;
-            const double *np_ = ntab + (lc - q + 4 * NK - 1);
-            for (int ks = 0; ks < NK; ++ks) vacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sp[ks * 64], np_[-4 * ks], vacc, 0, 0, 0);
-            if (tb0 + 16 > T) {
-                const bool tvalid = (tb0 + lc) < T;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) vacc[r] = tvalid ? vacc[r] : 0.0;
-            }
-        }
-        // ---- y of the tile against the four DoA tiles, |y| into the LDS tile ----
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double4_t acc = double4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vacc[k], Wf[j][k], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Y[(wv * 16 + q + 4 * r) * TRK_LD + 16 * j + lc] = fabs(acc[r]);
-        }
-        __syncthreads();
-        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, [&](int row, double best, int bi) {
-            track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
-        });
-        // (the next chunk's staging touches S only; its writes to Y come after the barrier behind the staging)
-    }
+    track_ws_walk(smem, spikes + (size_t)b * T * C, C, 0, T, 0, ntab_g, NK, Wp, GT, G, cg, a_rise, i_rise, a_fall, state,
+                  [&](int cs, int row, double best, int bi) {
+                      track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+                  });
     if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
 }
 
@@ -135,75 +80,14 @@ __global__ __launch_bounds__(TRK_THREADS) void track_wsc_kernel(const double *__
                                                                 double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int KF = KM + (KV > 0 ? 1 : 0);
-    constexpr int KVD = KV > 0 ? KV : 1;
-    const int Gp = 16 * GT, GTc = GT >> 1;
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;
-    const int lc = l & 15;
-    const int q = l >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
     const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    double *Y = reinterpret_cast<double *>(smem);
-    double *tail = Y + TRK_CH * TRK_LD + wv * 64;  // this wave's fragment of the KV tail channels
-
-    double Wf[4][2][KM], Wv[4][2][KVD];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ct = 4 * cg + j;
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-            const double *wp = Wp + 16 * ((ct < GTc ? ct : GTc - 1) + part * GTc) + lc;
-#pragma unroll
-            for (int k = 0; k < KM; ++k) Wf[j][part][k] = wp[(size_t)(4 * k + q) * Gp];
-#pragma unroll
-            for (int i = 0; i < KV; ++i) Wv[j][part][i] = wp[(size_t)(4 * KM + i) * Gp];
-        }
-    }
-    const double *pb = pre + (size_t)b * C * Ts;
     const size_t row0 = (size_t)b * T;
     double state = 0.0;
-    for (int cs = 0; cs < T; cs += TRK_CH) {
-        // ---- this wave's tile as A-fragments (beamform_wsc_kernel, stage 1): lane l of k-step k = channel 4k + (l >> 4), frame l & 15 ----
-        double V[KF];
-        {
-            const int t = cs + wv * 16 + lc;
-#pragma unroll
-            for (int k = 0; k < KF; ++k) {
-                const int c = 4 * k + q;
-                const double v = pb[(size_t)(c < C ? c : C - 1) * Ts + (t < T ? t : T - 1)];  // (clamped: unconditional loads)
-                V[k] = (t < T && c < C) ? v : 0.0;
-            }
-        }
-        if (KV > 0) tail[l] = V[KF - 1];
-        __syncthreads();  // (also: the previous chunk's row reduction is done with Y)
-        double Vv[KVD][4];
-#pragma unroll
-        for (int i = 0; i < KV; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Vv[i][r] = tail[16 * i + q + 4 * r];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            double4_t acc[2];
-#pragma unroll
-            for (int part = 0; part < 2; ++part) {
-                acc[part] = double4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int k = 0; k < KM; ++k) acc[part] = __builtin_amdgcn_mfma_f64_16x16x4f64(V[k], Wf[j][part][k], acc[part], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < KV; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[part][r] = __builtin_fma(Vv[i][r], Wv[j][part][i], acc[part][r]);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Y[(wv * 16 + q + 4 * r) * TRK_LD + 16 * j + lc] = hypot(acc[0][r], acc[1][r]);
-        }
-        __syncthreads();
-        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, [&](int row, double best, int bi) {
-            track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
-        });
-    }
+    track_wsc_walk<KM, KV>(smem, pre + (size_t)b * C * Ts, C, Ts, 0, T, 0, Wp, GT, G, cg, a_rise, i_rise, a_fall, state,
+                           [&](int cs, int row, double best, int bi) {
+                               track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+                           });
     if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
 }
 
@@ -220,11 +104,7 @@ __global__ __launch_bounds__(256) void track_combine_kernel(const double *__rest
     if (peak) peak[row] = track_row_peak(best, bi);
 }
 
-size_t track_pairs_bytes(int B, int T, int G)
-{
-    const size_t n = (size_t)B * T * track_col_groups(G);
-    return ((n * sizeof(double) + 255) & ~(size_t)255) + ((n * sizeof(int32_t) + 255) & ~(size_t)255);
-}
+size_t track_pairs_bytes(int B, int T, int G) { return track_pairs_size((size_t)B * T * track_col_groups(G)); }
 
 // src: the spike raster (real bf_mat) or the planar band-passed rows (complex); G: the DoA grid the caller sees; pairs: track_pairs_bytes
 hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_complex, const void *src, int B, int T, int Ts, int G,
@@ -232,9 +112,9 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
                               hipStream_t stream)
 {
     const int ncg = track_col_groups(G);
-    const size_t n = (size_t)B * T * ncg;
-    double *pval = ncg == 1 ? peak : reinterpret_cast<double *>(pairs);
-    int32_t *pidx = ncg == 1 ? index : reinterpret_cast<int32_t *>(reinterpret_cast<unsigned char *>(pairs) + ((n * sizeof(double) + 255) & ~(size_t)255));
+    double *pval = peak;  // one column group: the kernel writes the result itself
+    int32_t *pidx = index;
+    if (ncg > 1) track_pairs_split(pairs, (size_t)B * T * ncg, pval, pidx);
     const size_t lds = track_lds_bytes(is_complex != 0, nt.NK);
     dim3 grid(ncg, B), block(TRK_THREADS);
     if (!is_complex) {
@@ -245,21 +125,11 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
                            a_fall, pval, pidx, env_last);
     } else {
         const double *pre = static_cast<const double *>(src);
-#define TRK_K(KM_, KV_)                                                                                                                   \
-    hipLaunchKernelGGL((track_wsc_kernel<KM_, KV_>), grid, block, lds, stream, pre, W.Wp, W.GT, W.C, T, Ts, G, a_rise, i_rise, a_fall, pval, \
-                       pidx, env_last);                                                                                                   \
-    break
-        switch (W.C) {  // (2 x microphones: even; beamform_wsc_kernel's table)
-            case 2: case 4: TRK_K(1, 0);
-            case 6: TRK_K(1, 2);
-            case 8: TRK_K(2, 0);
-            case 10: TRK_K(2, 2);
-            case 12: TRK_K(3, 0);
-            case 14: TRK_K(3, 2);
-            case 16: TRK_K(4, 0);
-            default: return hipErrorInvalidValue;
-        }
-#undef TRK_K
+        const bool served = track_wsc_dispatch(W.C, [&](auto k) {
+            hipLaunchKernelGGL((track_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, pre, W.Wp, W.GT, W.C, T, Ts, G, a_rise,
+                               i_rise, a_fall, pval, pidx, env_last);
+        });
+        if (!served) return hipErrorInvalidValue;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || ncg == 1) return e;

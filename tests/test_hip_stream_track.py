@@ -344,6 +344,28 @@ def test_complex_beamformer_equals_track_batch_for_any_tiling(fx, G):
         _assert_finish(out, one, f"G={G} tiles={tiles[:4]}...")
 
 
+@pytest.mark.parametrize("M", range(1, 9))
+def test_every_row_of_the_complex_channel_table_equals_track_batch(fx, M):
+    """C = 2M = 2 .. 16 channels: every <KM, KV> of csrc/track_rows.h's table.  G = 65: two column groups and the combine launch; tiles of
+    100 frames: the carry fill is no multiple of 16."""
+    from micloc.array_geometry import CenterCircularArray
+    from micloc.beamformer import Beamformer
+    from haghighatshoarmuir2024_amd.streaming import ComplexStreamingLocalizer
+
+    bm = Beamformer(CenterCircularArray(4.5e-2, M), 10e-3, [1000.0, 2000.0], fs=FS)
+    rng = np.random.RandomState(260 + M)
+    T, G = 209, 65
+    W = (rng.randn(M, G) + 1j * rng.randn(M, G)) / np.sqrt(2 * M)
+    x = rng.randn(1, T, M)
+    one = {k: _np(v) for k, v in bm.track_batch(W, x, fx.env, want_envelope_last=True).items() if k in ("index", "peak_envelope", "envelope_last")}
+    for tiles in ([T], [100, 100, 9]):
+        s = ComplexStreamingLocalizer(bm, W, 1, T, wrap_tail=ComplexStreamingLocalizer.wrap_rows(x, len(bm.kernel)), track=fx.env, max_tile=max(tiles))
+        _push_all(s, x, tiles)
+        out = s.finish()
+        assert out["track_count"] == T
+        _assert_finish(out, one, f"M={M} tiles={tiles}")
+
+
 def test_sweep_through_the_tracked_stream_equals_the_fused_call(fx):
     from haghighatshoarmuir2024_amd.sweep import moving_target_sweep, stream_track_localizer
 

@@ -113,6 +113,33 @@ def test_complex_beamformer_equals_the_two_step_route(torch, G):
     assert bm.plan().track_is_fused()
 
 
+# every row of the complex channel table of csrc/track_rows.h (C = 2M = 2 .. 16 -> <KM, KV>): G = 65 is two column groups, the second one
+# of a single column, so the combine launch runs; 15 frames are less than one 16-frame tile, 130 are two full chunks and a 2-frame ragged one
+@pytest.mark.parametrize("M", range(1, 9))
+def test_every_row_of_the_complex_channel_table_equals_the_two_step_route(torch, M):
+    from micloc.array_geometry import CenterCircularArray
+    from micloc.beamformer import Beamformer
+
+    bm = Beamformer(CenterCircularArray(4.5e-2, M), 10e-3, [1000.0, 2000.0], fs=FS)
+    rng = np.random.RandomState(160 + M)
+    W = (rng.randn(M, 65) + 1j * rng.randn(M, 65)) / np.sqrt(2 * M)
+    for T in (15, 130):
+        _check_batch(bm, W, [rng.randn(T, M) for _ in range(2)], _env(2e-3, 13e-3), 65)
+    assert bm.plan().track_is_fused()
+
+
+@pytest.mark.parametrize("M", [1, 5, 8])
+def test_snn_channel_counts_equal_the_two_step_route(torch, M):
+    """The same shapes on the spike raster: 2, 10 and 16 channels (at 16 the channel padding of the spike tile vanishes)."""
+    bf = _snn(num_mic=M)
+    rng = np.random.RandomState(170 + M)
+    W = rng.randn(2 * M, 65)
+    W /= np.linalg.norm(W, axis=0, keepdims=True)
+    for T in (15, 130):
+        _check_batch(bf, W, [rng.randn(T, M) for _ in range(2)], _env(2e-3, 13e-3), 65)
+    assert bf.plan().track_is_fused()
+
+
 def test_forty_channel_plan_takes_the_two_step_route_inside_the_call(torch):
     bf = _snn(num_mic=20)
     rng = np.random.RandomState(40)

@@ -68,6 +68,22 @@ def test_header_declares_and_lib_binds_the_symbols():
     assert "atomic" not in src.lower() and "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src
 
 
+def test_the_chunk_walk_is_written_once():
+    """csrc/track_rows.h holds stages 1 and 2 of the one-shot and of the stream kernels, which decide the bits of every y[t][g]: the fp64
+    matrix-core product and the complex magnitude occur there and in neither kernel file, and both objects are rebuilt when the header
+    changes."""
+    csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in ("track_rows.h", "track.hip", "stream_track.hip", "Makefile")}
+    for word in ("mfma_f64_16x16x4f64", "hypot("):
+        assert word in text["track_rows.h"], word
+        assert word not in text["track.hip"] and word not in text["stream_track.hip"], word
+    for f in ("track.hip", "stream_track.hip"):
+        assert '#include "track_rows.h"' in text[f], f
+    rules = [m.group(1).split() for m in re.finditer(r"^([^\t#\n:]+):[^\n]*\btrack_rows\.h\b", text["Makefile"], re.M)]
+    targets = {t for rule in rules for t in rule}
+    assert {"track.o", "stream_track.o"} <= targets, rules
+
+
 def test_size_entries_return_zero_and_entries_refuse_null_before_any_device_work():
     from haghighatshoarmuir2024_amd import _lib
 
