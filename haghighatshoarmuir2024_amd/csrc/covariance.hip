@@ -10,7 +10,7 @@
 // (A[i=c][k=t]) and the B fragment (B[k=t][j=c']) of the Gram product  R += V^T V  -- one register feeds both
 // operands of v_mfma_f64_16x16x4_f64.  The LIF summation order (chronological) is unchanged, so V is bit-identical
 // to the beamforming kernel's.
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void cov_power_kernel(const double *__restrict
         }
     }
     double best = -1.0;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     if (power || argmax) {
         for (int g = tid; g < G; g += 256) {
             double p = 0.0;
@@ -320,21 +320,8 @@ __global__ __launch_bounds__(256) void cov_power_kernel(const double *__restrict
             }
         }
     }
-    sv[tid] = best;
-    si[tid] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            const double ov = sv[tid + s];
-            const int oi = si[tid + s];
-            if (ov > sv[tid] || (ov == sv[tid] && oi < si[tid])) {
-                sv[tid] = ov;
-                si[tid] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0 && argmax) argmax[b] = si[0] == 0x7fffffff ? 0 : si[0];
+    const int a = block_first_max<256>(best, bi, sv, si, tid);
+    if (tid == 0 && argmax) argmax[b] = a;
 }
 
 size_t cov_partial_bytes(int B, int T, int CT)

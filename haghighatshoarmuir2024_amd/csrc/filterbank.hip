@@ -25,6 +25,7 @@
 // from p_0: the additions of Demo.power_grid) and argmax [R] with power_argmax_kernel's rule (first maximum, a NaN never wins, a
 // row of NaN only gives 0).  One workgroup per row, no atomics.
 #include "bandpass_rows.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -210,6 +211,7 @@ hipError_t launch_filterbank_tile(const FilterbankCoef &co, const double *x, int
     return dispatch_iir_order(co.n, [&](auto N) { return fb_tile_launch<decltype(N)::value>(co, x, F, B, T, M, xf, state, stream); });
 }
 
+// (the arg-max: this kernel's scan -- band sums may be negative -- then block_first_max of readout_rows.h)
 // ---- band sum + arg-max ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void band_sum_kernel(const double *__restrict__ band_power, int F, size_t R, int G,
                                                         double *__restrict__ power, int32_t *__restrict__ argmax)
@@ -220,32 +222,18 @@ __global__ __launch_bounds__(256) void band_sum_kernel(const double *__restrict_
     const size_t band = R * (size_t)G;  // doubles per band
     const double *p0 = band_power + r * G;
     double best = 0.0;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     for (int g = threadIdx.x; g < G; g += 256) {
         double s = p0[g];
         for (int f = 1; f < F; ++f) s = __dadd_rn(s, p0[(size_t)f * band + g]);
         if (power) power[r * G + g] = s;
-        if (s == s && (bi == 0x7fffffff || s > best)) {  // ascending g per thread: the first maximum; a NaN never wins
+        if (s == s && (bi == RO_NONE || s > best)) {  // ascending g per thread: the first maximum; a NaN never wins
             best = s;
             bi = g;
         }
     }
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            const double ov = sv[threadIdx.x + s];
-            const int oi = si[threadIdx.x + s];
-            const int mi = si[threadIdx.x];
-            if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > sv[threadIdx.x] || (ov == sv[threadIdx.x] && oi < mi))) {
-                sv[threadIdx.x] = ov;
-                si[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0 && argmax) argmax[r] = si[0] == 0x7fffffff ? 0 : si[0];
+    const int a = block_first_max<256>(best, bi, sv, si, (int)threadIdx.x);
+    if (threadIdx.x == 0 && argmax) argmax[r] = a;
 }
 
 hipError_t launch_band_sum(const double *band_power, int F, long long R, int G, double *power, int32_t *argmax, hipStream_t stream)

@@ -11,7 +11,7 @@
 #pragma once
 #include <type_traits>
 
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -179,7 +179,7 @@ __device__ __forceinline__ int music_first_argmax(double best, int besti, double
         if ((int)threadIdx.x < h) {
             const double ov = bv[threadIdx.x + h];
             const int oi = bi[threadIdx.x + h];
-            if (oi >= 0 && (bi[threadIdx.x] < 0 || ov > bv[threadIdx.x] || (ov == bv[threadIdx.x] && oi < bi[threadIdx.x]))) {
+            if (better<-1>(ov, oi, bv[threadIdx.x], bi[threadIdx.x])) {  // readout_rows.h's rule; "none" is any index < 0 here, and only -1 occurs
                 bv[threadIdx.x] = ov;
                 bi[threadIdx.x] = oi;
             }

@@ -4,48 +4,24 @@
 //
 // stream_band_sum_kernel, one workgroup per trial (the grid depends on B only, no argument on time: part of the tile's graph):
 //   * running read-out: power[b][g] = ((p_0 + p_1) + p_2) + ... over the bands' running power [B][G], __dadd_rn in ascending band order
-//     from p_0, arg-max by band_sum_kernel's rule (first maximum, a NaN never wins, a row of NaN gives 0);
+//     from p_0, arg-max by band_sum_kernel's scan and block_first_max of readout_rows.h (a NaN never wins, a row of NaN gives 0);
 //   * windows: band f keeps its windows in a ring [B][Kb][G], window n in row n % Kb, and counts them in a device word.  With
 //     `emitted` wideband windows so far, window n is emitted -- the ascending band sum of the bands' rows, into row n % max_windows of
 //     the outputs -- for n = emitted .. min_f count_f - 1.  A band that leads by more than Kb windows has overwritten the rows of
 //     the windows n < count_f - Kb: those are given up (counted as failures, nothing written), never summed from a row that holds a
-//     later window.
+//     later window (ready_windows of readout_rows.h, shared with the Xylo stream's read-out).
 // The F running-power pointers, ring pointers and count pointers travel by value in the kernel argument: no device table.
 // State block: int words {0: windows emitted or given up, 1: windows given up, 2 / 3: what this launch adds to them}.  Every workgroup
 // reads word 0; workgroup 0 writes words 2 / 3 only, and stream_bands_commit_kernel (one thread, the next launch on the stream) folds
 // them into words 0 / 1 -- the read is ordered against the write by the launch boundary, as stream_window_kernel's count is against
 // the commit of its tile.  No atomics, no host synchronisation.
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
 namespace {
 
 constexpr int SB_COLS = 256;
-
-// (value, index) of the row's first maximum over the workgroup; idx 0x7fffffff = this thread saw no number.  Ends with a barrier.
-__device__ __forceinline__ int sb_argmax(double best, int bi, double *sv, int *si)
-{
-    const int col = threadIdx.x;
-    sv[col] = best;
-    si[col] = bi;
-    __syncthreads();
-    for (int s = SB_COLS / 2; s > 0; s >>= 1) {
-        if (col < s) {
-            const double ov = sv[col + s];
-            const int oi = si[col + s];
-            const int mi = si[col];
-            if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > sv[col] || (ov == sv[col] && oi < mi))) {
-                sv[col] = ov;
-                si[col] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    const int a = si[0] == 0x7fffffff ? 0 : si[0];
-    __syncthreads();  // sv / si are rewritten by the next row
-    return a;
-}
 
 __global__ __launch_bounds__(SB_COLS) void stream_band_sum_kernel(const StreamBandsArgs args, int F, int G, int windowed, int Kb, int max_windows,
                                                                    int *__restrict__ state, double *__restrict__ power,
@@ -59,55 +35,49 @@ __global__ __launch_bounds__(SB_COLS) void stream_band_sum_kernel(const StreamBa
     const int col = threadIdx.x;
     {  // the running read-out
         double best = 0.0;
-        int bi = 0x7fffffff;
+        int bi = RO_NONE;
         for (int g = col; g < G; g += SB_COLS) {
             double s = args.power[0][b * G + g];
             for (int f = 1; f < F; ++f) s = __dadd_rn(s, args.power[f][b * G + g]);
             if (power) power[b * G + g] = s;
-            if (s == s && (bi == 0x7fffffff || s > best)) {  // ascending g per thread: the first maximum; a NaN never wins
+            if (s == s && (bi == RO_NONE || s > best)) {  // ascending g per thread: the first maximum; a NaN never wins
                 best = s;
                 bi = g;
             }
         }
-        const int a = sb_argmax(best, bi, sv, si);
+        const int a = block_first_max<SB_COLS, double, true>(best, bi, sv, si, col);  // (trailing barrier: the next row rewrites sv / si)
         if (col == 0 && argmax) argmax[b] = a;
     }
     if (!windowed) return;
     const int emitted = state[0];
-    int cmin = 0x7fffffff, cmax = 0;
-    for (int f = 0; f < F; ++f) {
-        const int c = args.count[f][0];
-        cmin = c < cmin ? c : cmin;
-        cmax = c > cmax ? c : cmax;
-    }
-    // windows below `lo` have left the ring of the band that leads: given up
-    const int lo = cmax - Kb > emitted ? cmax - Kb : emitted;
-    for (int n = lo; n < cmin; ++n) {  // (uniform over the workgroup)
+    // windows below rw.lo have left the ring of the band that leads: given up
+    const ReadyWindows rw = ready_windows(F, emitted, Kb, [&](int f) { return args.count[f][0]; });
+    for (int n = rw.lo; n < rw.hi; ++n) {  // (uniform over the workgroup)
         const size_t in_row = (b * Kb + n % Kb) * (size_t)G;
         const size_t out_row = b * max_windows + n % max_windows;
-        const bool newest = n == cmin - 1;
+        const bool newest = n == rw.hi - 1;
         double best = 0.0;
-        int bi = 0x7fffffff;
+        int bi = RO_NONE;
         for (int g = col; g < G; g += SB_COLS) {
             double s = args.rows[0][in_row + g];
             for (int f = 1; f < F; ++f) s = __dadd_rn(s, args.rows[f][in_row + g]);
             if (power_w) power_w[out_row * G + g] = s;
             if (newest && latest_power) latest_power[b * G + g] = s;
-            if (s == s && (bi == 0x7fffffff || s > best)) {
+            if (s == s && (bi == RO_NONE || s > best)) {
                 best = s;
                 bi = g;
             }
         }
-        const int a = sb_argmax(best, bi, sv, si);
+        const int a = block_first_max<SB_COLS, double, true>(best, bi, sv, si, col);  // (trailing barrier: the next row rewrites sv / si)
         if (col == 0) {
             if (argmax_w) argmax_w[out_row] = a;
             if (newest && latest_argmax) latest_argmax[b] = a;
         }
     }
     if (b == 0 && col == 0) {
-        const int next = lo > cmin ? lo : cmin;  // never below `emitted`: lo >= emitted
+        const int next = rw.lo > rw.hi ? rw.lo : rw.hi;  // never below `emitted`: lo >= emitted
         state[2] = next - emitted;
-        state[3] = lo - emitted;
+        state[3] = rw.given(next);
     }
 }
 

@@ -19,6 +19,7 @@
 // length}, the accumulate kernel {[4] = 0, [5] new chunk rows, [6] chunks contracted after this tile -- the words stream_window_kernel
 // reads --, [SC_SRC] first staging column behind the rows, [SC_REM] frames that stay, [SC_FRAMES] frames contracted after this tile}.
 #include "bandpass_rows.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -41,30 +42,9 @@ __global__ __launch_bounds__(BR_THREADS) void stream_bandpass_tile_kernel(const 
 
 constexpr int SA_COLS = 256;
 
-// first maximum of (best, bi) over the workgroup -> thread 0's return value (0 for a row without a winner)
-__device__ __forceinline__ int sc_argmax(double best, int bi, double *sv, int *si)
-{
-    const int col = threadIdx.x;
-    sv[col] = best;
-    si[col] = bi;
-    __syncthreads();
-    for (int s = SA_COLS / 2; s > 0; s >>= 1) {
-        if (col < s) {
-            const double ov = sv[col + s];
-            const int oi = si[col + s];
-            if (ov > sv[col] || (ov == sv[col] && oi < si[col])) {
-                sv[col] = ov;
-                si[col] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    return si[0] == 0x7fffffff ? 0 : si[0];
-}
-
 // partial [B][Ks][Gp]: rows 0 .. nrows - 1 are the chunks [done, done + nrows) of the stream, columns [0, Ghp) Re and [Ghp, Gp) Im.  The
-// additions are power_argmax_kernel's with complex_pairs = 1 (beamform.hip): s += Re; s += Im per chunk in ascending order inside blocks of
-// STREAM_BLOCK_CHUNKS chunks counted from chunk 0, block sums in ascending order onto the total; the open block is added last.
+// additions are power_argmax_kernel's with complex_pairs = 1 (beamform.hip), chunks counted from chunk 0: BlockedSum of readout_rows.h,
+// s += Re; s += Im per chunk.  The arg-max is its block_first_max.
 __global__ __launch_bounds__(SA_COLS) void stream_complex_accumulate_kernel(const double *__restrict__ partial, int Ks, int Gp, int G, int Ghp,
                                                                              int CH, int final_tile, int *__restrict__ ctl,
                                                                              double *__restrict__ acc, double *__restrict__ power,
@@ -83,30 +63,20 @@ __global__ __launch_bounds__(SA_COLS) void stream_complex_accumulate_kernel(cons
     const double *pb = partial + (size_t)b * Ks * Gp;
     double *tot = acc + (size_t)b * 2 * G, *blk = tot + G;
     double best = -1.0;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     for (int g = col; g < G; g += SA_COLS) {
-        double total = tot[g], s = blk[g];
-        int open = done % STREAM_BLOCK_CHUNKS;
-        for (int ch = 0; ch < nrows; ++ch) {
-            s += pb[(size_t)ch * Gp + g];
-            s += pb[(size_t)ch * Gp + Ghp + g];
-            if (++open == STREAM_BLOCK_CHUNKS) {
-                total += s;
-                s = 0.0;
-                open = 0;
-            }
-        }
-        tot[g] = total;
-        blk[g] = s;
-        const double now = open > 0 ? total + s : total;
-        const double p = frames > 0.0 ? now / frames : 0.0;
+        BlockedSum sum{tot[g], blk[g], done % STREAM_BLOCK_CHUNKS};
+        for (int ch = 0; ch < nrows; ++ch) sum.add(pb[(size_t)ch * Gp + g], pb[(size_t)ch * Gp + Ghp + g]);
+        tot[g] = sum.total;
+        blk[g] = sum.s;
+        const double p = frames > 0.0 ? sum.close() / frames : 0.0;
         if (power) power[(size_t)b * G + g] = p;
         if (p > best) {  // ascending g per thread: its first maximum; a NaN never wins
             best = p;
             bi = g;
         }
     }
-    const int a = sc_argmax(best, bi, sv, si);
+    const int a = block_first_max<SA_COLS>(best, bi, sv, si, col);
     if (col == 0 && argmax) argmax[b] = a;
     if (b == 0 && col == 0) {  // pending words: no thread of this launch reads them
         ctl[4] = 0;

@@ -23,6 +23,7 @@
 //
 // The lane's constants, the step functions, the MFMA `produce`, the staging loop and the walk over a range are XpLif of xylo_rows.h,
 // the one-shot kernel's; here are the range, the state's load and store and the counts.
+#include "readout_rows.h"
 #include "stream_xylo.h"
 #include "xylo_rows.h"
 
@@ -89,39 +90,26 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_stream_kernel(const in
 
 static_assert(SX_CH == 256, "the chunk row of a tile is t0 >> 8");
 
-// ---- the windows of one band: stream_window_kernel's bookkeeping (stream_windows.hip) on integer counts -------------------------------
-// between the LIF launch and the commit of a tile.  chunk_counts [B][chunk_rows][N] holds the chunks that became final in this call at
-// the window-relative rows [lo, hi); ctl[0] = chunks done before this call, ctl[6] = after it.  Window n keeps its sum so far in slot
-// n % K of acc [B][K][N]; a window whose last chunk arrived (or, on the final tile, which the end of the recording cuts) goes to row
-// n % Kb of ring [B][Kb][N] and head[0] becomes the number of windows emitted.
+// ---- the windows of one band: stream_window_kernel's schedule (StreamWindowWalk, readout_rows.h) on integer counts, between the LIF
+// launch and the commit of a tile.  chunk_counts [B][chunk_rows][N] holds the chunks that became final in this call.  Window n keeps its
+// sum so far in slot n % K of acc [B][K][N]; a window that is emitted goes to row n % Kb of ring [B][Kb][N] and head[0] becomes the
+// number of windows emitted.
 __global__ __launch_bounds__(256) void xylo_stream_window_kernel(const int *__restrict__ chunk_counts, int chunk_rows, int N,
                                                                   const int *__restrict__ ctl, int final_tile, int wchunks, int hchunks, int K,
                                                                   int Kb, int *__restrict__ acc, int *__restrict__ head, int *__restrict__ ring)
 {
     const int b = blockIdx.x;
-    const int done = ctl[0], lo = ctl[4], hi = ctl[5], ready = ctl[6];
-    const int T = ctl[STREAM_CLK_TEND];
-    const bool ended = final_tile && (long long)ready * SX_CH >= T;
-    if (ready - done != hi - lo || hi < lo || lo < 0 || hi > chunk_rows) return;  // (never: the horizon writes both)
-    const int n0 = done < wchunks ? 0 : (done - wchunks) / hchunks + 1;  // first window not emitted before this call
-    const int n_started = ready > 0 ? (ready - 1) / hchunks : -1;        // last window that holds a chunk
-    long long n_emit;                                                    // windows emitted after this call
-    if (ended)
-        n_emit = T <= (long long)wchunks * SX_CH ? 1 : 1 + ((long long)T - (long long)wchunks * SX_CH + (long long)hchunks * SX_CH - 1) / ((long long)hchunks * SX_CH);
-    else
-        n_emit = ready < wchunks ? 0 : (ready - wchunks) / hchunks + 1;
+    const StreamWindowWalk walk(ctl, final_tile, SX_CH, wchunks, hchunks, chunk_rows);
+    if (!walk.ok) return;
     const int *cb_ = chunk_counts + (size_t)b * chunk_rows * N;
-    for (int n = n0; n <= n_started; ++n) {
-        const int c0 = n * hchunks;
-        const int ca = done > c0 ? done : c0;
-        const int cb = ready - c0 < wchunks ? ready : c0 + wchunks;
-        const bool emit = n < n_emit;
+    for (int n = walk.n0; n <= walk.n_started; ++n) {
+        const StreamWindowWalk::Window w = walk.window(n);
         int *slot = acc + ((size_t)b * K + n % K) * N;
         int *row = ring + ((size_t)b * Kb + n % Kb) * N;
         for (int g = threadIdx.x; g < N; g += 256) {
-            int total = ca > c0 ? slot[g] : 0;  // (the window opened in an earlier call)
-            for (int ch = ca; ch < cb; ++ch) total += cb_[(size_t)(lo + ch - done) * N + g];
-            if (emit) {
+            int total = w.ca > w.c0 ? slot[g] : 0;  // (the window opened in an earlier call)
+            for (int ch = w.ca; ch < w.cb; ++ch) total += cb_[(size_t)walk.row(ch) * N + g];
+            if (w.emit) {
                 row[g] = total;
                 slot[g] = 0;
             } else {
@@ -129,16 +117,16 @@ __global__ __launch_bounds__(256) void xylo_stream_window_kernel(const int *__re
             }
         }
     }
-    if (b == 0 && threadIdx.x == 0) head[0] = (int)(n_emit > 0x7fffffffll ? 0x7fffffffll : n_emit);
+    if (b == 0 && threadIdx.x == 0) head[0] = walk.head();
 }
 
 // ---- the read-out over the bands -----------------------------------------------------------------------------------------------------
 // peak_location_kernel's estimator (sweep.hip) on the band sums pw[G] in LDS: box-car of `win` samples by a full, non-circular
-// convolution, first maximum, minus win / 2, modulo G.  Every thread of the workgroup calls it; thread 0 returns the index.
+// convolution, first maximum (block_first_max, readout_rows.h), minus win / 2, modulo G.  Every thread of the workgroup calls it.
 __device__ int sx_peak(const long long *pw, int G, int win, long long *bestv, int *besti)
 {
     long long bv = -1;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     for (int n = threadIdx.x; n < G + win - 1; n += 256) {
         long long s = 0;
         for (int k = 0; k < win; ++k) {
@@ -150,21 +138,7 @@ __device__ int sx_peak(const long long *pw, int G, int win, long long *bestv, in
             bi = n;
         }
     }
-    bestv[threadIdx.x] = bv;
-    besti[threadIdx.x] = bi;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            const long long ov = bestv[threadIdx.x + h];
-            const int oi = besti[threadIdx.x + h];
-            if (ov > bestv[threadIdx.x] || (ov == bestv[threadIdx.x] && oi < besti[threadIdx.x])) {
-                bestv[threadIdx.x] = ov;
-                besti[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    int idx = besti[0] - win / 2;
+    int idx = block_first_max<256>(bv, bi, bestv, besti, (int)threadIdx.x) - win / 2;
     idx %= G;
     return idx < 0 ? idx + G : idx;
 }
@@ -205,21 +179,14 @@ __global__ __launch_bounds__(256) void xylo_stream_readout_kernel(XyloReadoutArg
     if (threadIdx.x == 0) peak[b] = idx;
     if (!windowed) return;
     const int emitted = state[0];
-    int newc = 0x7fffffff;
-    for (int f = 0; f < F; ++f) newc = a.head[f][0] < newc ? a.head[f][0] : newc;
+    // a window below rw.lo has been overwritten in the ring of the band that leads: given up (uniform over the launch)
+    const ReadyWindows rw = ready_windows(F, emitted, Kb, [&](int f) { return a.head[f][0]; });
     const long long Tend = a.ctl[0][STREAM_CLK_T];  // frames pushed (the bands share the clock; the tick is behind every band's tile)
-    int given = 0;
-    for (int n = emitted; n < newc; ++n) {
-        bool lost = false;
-        for (int f = 0; f < F; ++f) lost = lost || a.head[f][0] - n > Kb;
-        if (lost) {  // (uniform over the launch)
-            ++given;
-            continue;
-        }
+    for (int n = rw.lo; n < rw.hi; ++n) {
         long long frames = Tend - (long long)n * hop;
         frames = frames > window ? window : (frames < 1 ? 1 : frames);
         const size_t row = (size_t)b * max_windows + n % max_windows;
-        const bool newest = n == newc - 1;
+        const bool newest = n == rw.hi - 1;
         __syncthreads();  // pw is rewritten
         for (int g = threadIdx.x; g < G; g += 256) {
             double s = 0.0;
@@ -244,8 +211,9 @@ __global__ __launch_bounds__(256) void xylo_stream_readout_kernel(XyloReadoutArg
         }
     }
     if (b == 0 && threadIdx.x == 0) {
-        state[2] = newc > emitted ? newc : emitted;
-        state[3] = state[1] + given;
+        const int next = rw.hi > emitted ? rw.hi : emitted;
+        state[2] = next;
+        state[3] = state[1] + rw.given(next);
     }
 }
 
@@ -292,17 +260,16 @@ hipError_t launch_xylo_resume(const int8_t *raster, int tc, int stride_frames, i
     return hipGetLastError();
 }
 
-// win_state: [256 B: int windows emitted][acc [B][K][N] ints][ring [B][Kb][N] ints], K = ceil(window / hop)
+// win_state: [256 B: int windows emitted][acc [B][K][N] ints][ring [B][Kb][N] ints], K = stream_window_slots
 size_t xylo_stream_window_state_bytes(int B, int N, int window, int hop, int Kb)
 {
-    const int K = (window + hop - 1) / hop;
-    return 256 + sx_al((size_t)B * K * N * sizeof(int)) + sx_al((size_t)B * Kb * N * sizeof(int));
+    return 256 + sx_al((size_t)B * stream_window_slots(window, hop) * N * sizeof(int)) + sx_al((size_t)B * Kb * N * sizeof(int));
 }
 
 static int *sx_ring(void *win_state, int B, int N, int window, int hop)
 {
-    const int K = (window + hop - 1) / hop;
-    return reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(win_state) + 256 + sx_al((size_t)B * K * N * sizeof(int)));
+    return reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(win_state) + 256 +
+                                   sx_al((size_t)B * stream_window_slots(window, hop) * N * sizeof(int)));
 }
 
 hipError_t launch_xylo_stream_windows(const int32_t *chunk_counts, int B, int chunk_rows, int N, const int *ctl, int final_tile, int window, int hop,
@@ -312,7 +279,7 @@ hipError_t launch_xylo_stream_windows(const int32_t *chunk_counts, int B, int ch
     int *head = reinterpret_cast<int *>(win_state);
     int *acc = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(win_state) + 256);
     hipLaunchKernelGGL(xylo_stream_window_kernel, dim3(B), dim3(256), 0, stream, chunk_counts, chunk_rows, N, ctl, final_tile ? 1 : 0, window / SX_CH,
-                       hop / SX_CH, (window + hop - 1) / hop, Kb, acc, head, sx_ring(win_state, B, N, window, hop));
+                       hop / SX_CH, stream_window_slots(window, hop), Kb, acc, head, sx_ring(win_state, B, N, window, hop));
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // Reference: paper_plots/target_snn_localization.py:464-467 (DoA estimate from the arg-max, pi-periodic error) and :520
 // (mean absolute error per SNR).  Keeps the timed sweep free of framework element-wise launches: one tiny kernel after
 // power_argmax_kernel instead of index / sin / abs / asin / mean.
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void peak_location_kernel(const int32_t *__res
     }
     __syncthreads();
     long long bv = -1;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     for (int n = threadIdx.x; n < G + win - 1; n += 256) {
         long long s = 0;
         for (int k = 0; k < win; ++k) {
@@ -72,22 +72,9 @@ __global__ __launch_bounds__(256) void peak_location_kernel(const int32_t *__res
             bi = n;
         }
     }
-    bestv[threadIdx.x] = bv;
-    besti[threadIdx.x] = bi;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) {
-            const long long ov = bestv[threadIdx.x + h];
-            const int oi = besti[threadIdx.x + h];
-            if (ov > bestv[threadIdx.x] || (ov == bestv[threadIdx.x] && oi < besti[threadIdx.x])) {
-                bestv[threadIdx.x] = ov;
-                besti[threadIdx.x] = oi;
-            }
-        }
-        __syncthreads();
-    }
+    const int first = block_first_max<256>(bv, bi, bestv, besti, (int)threadIdx.x);
     if (threadIdx.x == 0) {
-        int idx = besti[0] - win / 2;
+        int idx = first - win / 2;
         idx %= G;
         index[b] = idx < 0 ? idx + G : idx;
     }
@@ -252,32 +239,16 @@ __global__ __launch_bounds__(64 * (1 + ENV_LOADERS)) void envelope_kernel(const 
     }
 }
 
-// index[row] = np.argmax(env[row, :]): the FIRST maximum (one wave per row; env >= 0, NaN never wins)
+// index[row] = np.argmax(env[row, :]): row_first_max of readout_rows.h (one wave per row; env >= 0, NaN never wins)
 __global__ __launch_bounds__(256) void rows_argmax_kernel(const double *__restrict__ env, size_t rows, int G, int32_t *__restrict__ index)
 {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int l = threadIdx.x & 63;
-    const double *r = env + row * G;
-    double best = -1.0;
-    int bi = 0x7fffffff;
-    for (int g = l; g < G; g += 64) {  // ascending per lane: its first maximum
-        const double v = r[g];
-        if (v > best) {
-            best = v;
-            bi = g;
-        }
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const double ov = __shfl_xor(best, s, 64);
-        const int oi = __shfl_xor(bi, s, 64);
-        if (ov > best || (ov == best && oi < bi)) {
-            best = ov;
-            bi = oi;
-        }
-    }
-    if (l == 0) index[row] = bi == 0x7fffffff ? 0 : bi;
+    double best;
+    int bi;
+    row_first_max(env + row * G, G, l, best, bi);
+    if (l == 0) index[row] = bi == RO_NONE ? 0 : bi;
 }
 
 template <int KIND>

@@ -14,8 +14,8 @@
 //      the device hypot of (re, im) as EnvIn<MICLOC_ENV_C128>) goes to an LDS tile [64 frames][64 columns].
 //   3. wave 0 walks the 64 envelope chains (one lane per column) over the tile in place: envelope_kernel's recurrence, __dmul_rn /
 //      __dadd_rn, nothing fused, state_0 = |y_0|, rise when |y_t| >= state.  The chain state stays in a register across chunks.
-//   4. every frame of the tile is reduced to (max envelope, first index) over the workgroup's columns by rows_argmax_kernel's rule
-//      (first maximum; a NaN never wins).  With one column group (G <= 64) that is the result; otherwise the pairs go to
+//   4. every frame of the tile is reduced to (max envelope, first index) over the workgroup's columns by the first-maximum rule of
+//      readout_rows.h (a NaN never wins).  With one column group (G <= 64) that is the result; otherwise the pairs go to
 //      pval / pidx [B][T][ceil(G / 64)] and track_combine_kernel finishes in ascending column order.
 // No buffer grows with T G.  The chain is latency (one wave, ~8 dependent instructions per step); the matrix work of a chunk is a few
 // hundred cycles per wave, and several workgroups share a compute unit (46 KB of LDS), so one workgroup's chain runs beside the
@@ -139,35 +139,19 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
 }
 
 // ---- the read-out of the two-step route (the shapes the general beamforming kernel serves): rows of a stored envelope ----
-// index[row] = first maximum of env[row, :], peak[row] = its value (rows_argmax_kernel's rule; one wave per row)
+// index[row] = first maximum of env[row, :], peak[row] = its value (row_first_max of readout_rows.h, as rows_argmax_kernel; one wave per row)
 __global__ __launch_bounds__(256) void track_rows_kernel(const double *__restrict__ env, size_t rows, int G, int32_t *__restrict__ index,
                                                          double *__restrict__ peak)
 {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int l = threadIdx.x & 63;
-    const double *r = env + row * G;
-    double best = -1.0;
-    int bi = TRK_NONE;
-    for (int g = l; g < G; g += 64) {
-        const double v = r[g];
-        if (v > best) {
-            best = v;
-            bi = g;
-        }
-    }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const double ov = __shfl_xor(best, s, 64);
-        const int oi = __shfl_xor(bi, s, 64);
-        if (ov > best || (ov == best && oi < bi)) {
-            best = ov;
-            bi = oi;
-        }
-    }
+    double best;
+    int bi;
+    row_first_max(env + row * G, G, l, best, bi);
     if (l == 0) {
-        index[row] = bi == TRK_NONE ? 0 : bi;
-        if (peak) peak[row] = bi == TRK_NONE ? (double)NAN : best;
+        index[row] = track_row_index(bi);
+        if (peak) peak[row] = track_row_peak(best, bi);
     }
 }
 

@@ -8,7 +8,7 @@
 #pragma once
 #include <math.h>
 
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -19,7 +19,7 @@ constexpr int TRK_THREADS = TRK_WAVES * 64;
 constexpr int TRK_CH = TRK_WAVES * 16;  // frames per chunk: one 16-frame tile per wave
 constexpr int TRK_COLS = 64;            // DoA columns per workgroup = lanes of the chain wave
 constexpr int TRK_LD = TRK_COLS + 1;    // row stride of the magnitude tile (odd: the row reduction reads down columns)
-constexpr int TRK_NONE = 0x7fffffff;
+constexpr int TRK_NONE = RO_NONE;
 
 // LDS of a tracking workgroup: the magnitude tile, then the tail fragments (complex) or the Toeplitz table and the spike tile (SNN)
 inline size_t track_lds_bytes(bool complex_src, int NK)
@@ -112,15 +112,7 @@ __device__ __forceinline__ void track_chain_reduce(double *Y, int wv, int l, int
                 }
             }
         }
-#pragma unroll
-        for (int s = 1; s <= 2; s <<= 1) {
-            const double ov = __shfl_xor(best, s, 64);
-            const int oi = __shfl_xor(bi, s, 64);
-            if (ov > best || (ov == best && oi < bi)) {
-                best = ov;
-                bi = oi;
-            }
-        }
+        wave_first_max<4>(best, bi);  // the four parts of a row are adjacent lanes
         if (part == 0 && row < nrow) emit(cs, row, best, bi);
     }
 }

@@ -11,8 +11,9 @@
 // chunk: chunk sums ascending inside blocks of STREAM_BLOCK_CHUNKS chunks counted from that chunk, block sums ascending onto
 // the total.  A single window with window >= T therefore returns the bits of the unwindowed power and arg-max.  Long windows
 // (>= 128 chunks) sum four blocks side by side like the one-shot kernel does -- the same additions, four of them in flight.
+// The arg-max is the first maximum of readout_rows.h (block_first_max); window_count is its window_count64.
 // No atomics, no host synchronisation, no state: safe on any stream and graph-capturable.
-#include "micloc_internal.h"
+#include "readout_rows.h"
 
 namespace micloc {
 
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(WN_COLS * S) void window_power_kernel(const double 
     const int nblocks = (nc + WN_BLOCK - 1) / WN_BLOCK;
     const size_t row = (size_t)b * nW + n;
     double best = -1.0;
-    int bi = 0x7fffffff;
+    int bi = RO_NONE;
     for (int g0 = 0; g0 < G; g0 += WN_COLS) {
         const int g = g0 + col;
         double total = 0.0;
@@ -88,32 +89,14 @@ __global__ __launch_bounds__(WN_COLS * S) void window_power_kernel(const double 
         }
     }
     if (!argmax_w) return;  // (uniform over the workgroup)
-    if (slice == 0) {
-        sv[col] = best;
-        si[col] = bi;
-    }
-    __syncthreads();
-    for (int s = WN_COLS / 2; s > 0; s >>= 1) {
-        if (slice == 0 && col < s) {
-            const double ov = sv[col + s];
-            const int oi = si[col + s];
-            if (ov > sv[col] || (ov == sv[col] && oi < si[col])) {
-                sv[col] = ov;
-                si[col] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) argmax_w[row] = si[0] == 0x7fffffff ? 0 : si[0];
+    // (S = 4: slice 0 holds the pairs; every thread passes the barriers)
+    const int a = block_first_max<WN_COLS>(best, bi, sv, si, col, slice == 0);
+    if (threadIdx.x == 0) argmax_w[row] = a;
 }
 
 }  // namespace
 
-long long window_count(int T, int window, int hop)
-{
-    if (T <= window) return 1;
-    return 1 + ((long long)T - window + hop - 1) / hop;
-}
+long long window_count(int T, int window, int hop) { return window_count64(T, window, hop); }
 
 hipError_t launch_window_power(const double *partial, int B, int T, int nchunks, int Gp, int G, int complex_pairs, int Ghalf_pad,
                                int chunk_frames, int window, int hop, double *power_w, int32_t *argmax_w, hipStream_t stream)
