@@ -162,6 +162,10 @@ SYMBOLS = {
     "micloc_beamform_c128_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_snn_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_beamformer_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_xylo_track_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "micloc_xylo_track_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "micloc_xylo_lif_track_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "micloc_stream_track_state_bytes": (c_size_t, [c_void_p, c_int]),
     "micloc_stream_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "micloc_stream_track_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

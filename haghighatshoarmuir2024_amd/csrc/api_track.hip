@@ -1,6 +1,8 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations):
-// moving-target tracking, the per-step arg-max of the envelope of the beamformer output (track.hip).
+// moving-target tracking, the per-step arg-max of the envelope of the beamformer output (track.hip) and of the Xylo network's spike
+// counts (the tracking form of the packed walk, stream_xylo.hip).
 #include "api_internal.h"
+#include "xylo_track.h"
 
 using namespace micloc;
 
@@ -79,9 +81,83 @@ int track_run(const micloc_plan *p, const void *src, int B, int T, int Ts, doubl
     return MICLOC_OK;
 }
 
+// ---- Xylo ----
+// ws of micloc_xylo_lif_track_i16.  Fused networks: the pairs.  Others (the two-step route): the uint8 raster [T][N] and its envelope
+// [T][N] doubles for as many trials at a time as the caller's buffer holds, one at least.
+struct XyloTrackLayout {
+    size_t per_trial, raster, min_total;  // per_trial == 0: fused
+};
+
+bool xylo_track_served(int ternary_C, int Cin, int N, int w_rec)
+{
+    return !(Cin < 1 || Cin > 64 || N < 1 || ternary_C < 0 || (ternary_C > 0 && Cin != 2 * ternary_C) || (w_rec != 0 && N > 1024));
+}
+
+XyloTrackLayout xylo_track_layout(bool fused, int B, int T, int N)
+{
+    XyloTrackLayout t{};
+    if (fused) {
+        t.min_total = xylo_track_pairs_bytes(B, T, N);
+    } else {
+        t.raster = align256((size_t)T * N);
+        t.per_trial = t.raster + align256((size_t)T * N * sizeof(double));
+        t.min_total = t.per_trial;
+    }
+    return t;
+}
+
 }  // namespace
 
 extern "C" {
+
+int micloc_xylo_track_is_fused(int ternary_C, int Cin, int N, int w_rec, int max_spikes)
+{
+    if (max_spikes < 1) return MICLOC_ERR_INVALID;
+    if (Cin > 64 && N >= 1) return 0;  // (no Xylo kernel takes more than 64 input channels: the call itself answers MICLOC_ERR_SHAPE)
+    if (!xylo_track_served(ternary_C, Cin, N, w_rec)) return MICLOC_ERR_SHAPE;
+    return xylo_track_fused(ternary_C, Cin, w_rec, max_spikes) ? 1 : 0;
+}
+
+size_t micloc_xylo_track_workspace_bytes(int ternary_C, int Cin, int N, int w_rec, int B, int T)
+{
+    if (!xylo_track_served(ternary_C, Cin, N, w_rec) || bad_batch(B) || T < 1 || (long long)B * T > 0x7fffffffll) return 0;
+    return xylo_track_layout(xylo_track_fused(ternary_C, Cin, w_rec, 1), B, T, N).min_total;
+}
+
+int micloc_xylo_lif_track_i16(const void *spikes_in, int ternary_C, int B, int T, int Cin, int N, int w_rec, int max_spikes, double a_rise,
+                              double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last, int32_t *rate, void *net_ws,
+                              size_t net_ws_bytes, void *ws, size_t ws_bytes, void *stream)
+{
+    if (!spikes_in || !index || bad_batch(B) || max_spikes < 1) return MICLOC_ERR_INVALID;
+    if (T < 1 || N < 1 || (long long)B * T > 0x7fffffffll || !xylo_track_served(ternary_C, Cin, N, w_rec)) return MICLOC_ERR_SHAPE;
+    if (bad_ws(net_ws, net_ws_bytes, xylo_ws_bytes(Cin, N))) return MICLOC_ERR_WORKSPACE;
+    // (an unaligned ternary raster is served by the general kernel: the two-step route, if its workspace is there)
+    const bool fused = xylo_track_fused(ternary_C, Cin, w_rec, max_spikes) && (reinterpret_cast<uintptr_t>(spikes_in) & 15) == 0;
+    const XyloTrackLayout lay = xylo_track_layout(fused, B, T, N);
+    if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(net_ws));
+    hipStream_t st = (hipStream_t)stream;
+    if (fused) {
+        HIP_TRY(launch_xylo_track(static_cast<const int8_t *>(spikes_in), ternary_C, B, T, Cin, N, max_spikes, a_rise, i_rise, a_fall, index,
+                                  peak_env, env_last, rate, net_ws, ws, st));
+        return MICLOC_OK;
+    }
+    // the two-step route over sub-batches of independent trials: the LIF with its raster stored, envelope_kernel, the row read-out
+    const size_t fit = ws_bytes / lay.per_trial;
+    const int nb_max = fit > (size_t)B ? B : (int)fit;
+    const int Crow = ternary_C > 0 ? ternary_C : Cin;
+    for (int b0 = 0; b0 < B; b0 += nb_max) {
+        const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+        uint8_t *raster = static_cast<uint8_t *>(ws);
+        double *env = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + align256((size_t)nb * T * N));
+        HIP_TRY(launch_xylo_resident(static_cast<const uint8_t *>(spikes_in) + (size_t)b0 * T * Crow, ternary_C, nb, T, Cin, N, w_rec, max_spikes,
+                                     raster, rate ? rate + (size_t)b0 * N : nullptr, net_ws, st));
+        HIP_TRY(launch_envelope_track(raster, MICLOC_ENV_U8, nb, T, N, a_rise, i_rise, a_fall, env, nullptr, st));
+        HIP_TRY(launch_track_rows(env, nb, T, N, index + (size_t)b0 * T, peak_env ? peak_env + (size_t)b0 * T : nullptr,
+                                  env_last ? env_last + (size_t)b0 * N : nullptr, st));
+    }
+    return MICLOC_OK;
+}
 
 size_t micloc_track_workspace_bytes(const micloc_plan *p, int B, int T)
 {

@@ -56,10 +56,27 @@ __device__ __forceinline__ int xy_div(int v, int th)
     return n;
 }
 
+// What a launch form may hang on the walk to see every step's FINAL spike counts (the tracking kernel of stream_xylo.hip: XpTrackTap).  A tap
+// with `on` gets, exactly once per step and in step order, the packed counts of the lane's two neurons (low half: n0, high half: n1):
+//   begin(off, first)   in front of a run of steps: `off` = position of its first step in the staged tile, `first` = that step is frame 0
+//   put(j, cw)          step j (a compile-time index after unrolling) of a whole 16-step group; a group that is walked again calls it
+//                       again for every j, and only the last call counts
+//   group()             the 16 counts of the group are final
+//   single(j, cw)       step j of the ragged last group of a range: final at once (those steps run the exact sequence)
+// XpNoTap is the walk of the counting and the streaming kernels: nothing is called, nothing is kept.
+struct XpNoTap {
+    static constexpr bool on = false;
+    __device__ __forceinline__ void begin(int, bool) {}
+    __device__ __forceinline__ void put(int, int) {}
+    __device__ __forceinline__ void group() {}
+    __device__ __forceinline__ void single(int, int) {}
+};
+
 // One lane of a packed workgroup: its constants, its two neurons' state and the walk over a range of frames.  The kernels declare the
 // LDS (tile [XP_TT][32 KQ] static, cur_dyn dynamic: xp_shape) and own everything around run_range: where the state comes from and goes.
-template <int KQ, bool WANT_OUT>
+template <int KQ, bool WANT_OUT, class Tap = XpNoTap>
 struct XpLif {
+    Tap tap;
     long Bw[8][KQ];  // weight fragments of the wave's 8 column tiles: lane (q, lc) holds channels 8 q .. 8 q + 7 (+ 32 kq) of neuron 16 j + lc
     short2_t ds, dm, th;
     int th_hi;  // v.hi >= th.hi  <=>  (int)word >= th.hi << 16
@@ -132,7 +149,7 @@ struct XpLif {
     // The second-spike test (v >= th again after the reset: two compares, a scalar or and a branch per step) is not run per step
     // in whole tiles: the steps only keep the largest membrane word they left behind, one test per 16 steps decides, and a group in
     // which some step did need the exact sequence is walked again from its saved state with the per-step test (`step` below).
-    __device__ __forceinline__ void step_fast(int in_word, int t)
+    __device__ __forceinline__ void step_fast(int in_word, int t, int j)
     {
         short2_t i2 = xp_decay(isyn, ds);
         short2_t v2 = xp_decay(vmem, dm);
@@ -144,6 +161,7 @@ struct XpLif {
         const int vw = (xp_i(m) & xp_i(v2)) | (~xp_i(m) & xp_i(d));
         cnt += m;
         vmx = __builtin_elementwise_max(vmx, xp_s2(vw));
+        if constexpr (Tap::on) tap.put(j, xp_i(m + short2_t{1, 1}));
         if constexpr (WANT_OUT) {
             const size_t row = (size_t)t * N;
             if (act0) ob[row + n0] = (uint8_t)(1 + m.x);
@@ -153,7 +171,8 @@ struct XpLif {
         vmem = xp_s2(vw);
     }
 
-    __device__ __forceinline__ void step(int in_word, int t)
+    template <bool RAGGED = false>
+    __device__ __forceinline__ void step(int in_word, int t, int j)
     {
         short2_t i2 = xp_decay(isyn, ds);
         short2_t v2 = xp_decay(vmem, dm);
@@ -184,6 +203,13 @@ struct XpLif {
             vw = (lo & 0xffff) | (hi << 16);
             total0 += extra0;
             total1 += extra1;
+        }
+        if constexpr (Tap::on) {
+            const int cw = xp_i(m + short2_t{1, 1}) + extra0 + (extra1 << 16);  // (counts <= 31: no carry between the halves)
+            if constexpr (RAGGED)
+                tap.single(j, cw);
+            else
+                tap.put(j, cw);
         }
         if constexpr (WANT_OUT) {
             const size_t row = (size_t)t * N;
@@ -254,13 +280,14 @@ struct XpLif {
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) in4[t4] = cw[64 * t4];
                 if (i + 1 < ntile) produce(i + 1);  // (overwrites the slice: after the reads above, in program order)
+                if constexpr (Tap::on) tap.begin(16 * i, t0 + 16 * i == 0);
                 if (jn == 16) {
                     const short2_t isyn_s = isyn, vmem_s = vmem, cnt_s = cnt;
                     vmx = short2_t{-32768, -32768};
 #pragma unroll
                     for (int t4 = 0; t4 < 4; ++t4) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) step_fast(in4[t4][r], t0 + 16 * i + 4 * t4 + r);
+                        for (int r = 0; r < 4; ++r) step_fast(in4[t4][r], t0 + 16 * i + 4 * t4 + r, 4 * t4 + r);
                     }
                     const short2_t fifteen = {15, 15};
                     const short2_t below = __builtin_elementwise_sub_sat(vmx, th) >> fifteen;  // all ones: never reached th again
@@ -271,9 +298,10 @@ struct XpLif {
 #pragma unroll
                         for (int t4 = 0; t4 < 4; ++t4) {
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) step(in4[t4][r], t0 + 16 * i + 4 * t4 + r);
+                            for (int r = 0; r < 4; ++r) step(in4[t4][r], t0 + 16 * i + 4 * t4 + r, 4 * t4 + r);
                         }
                     }
+                    if constexpr (Tap::on) tap.group();
                 } else {  // the last steps of the range
                     for (int j = 0; j < jn; ++j) {
                         int w_in = 0;
@@ -281,7 +309,7 @@ struct XpLif {
                         for (int t4 = 0; t4 < 4; ++t4)
 #pragma unroll
                             for (int r = 0; r < 4; ++r) w_in = (j == 4 * t4 + r) ? in4[t4][r] : w_in;
-                        step(w_in, t0 + 16 * i + j);
+                        step<true>(w_in, t0 + 16 * i + j, j);
                     }
                 }
             }

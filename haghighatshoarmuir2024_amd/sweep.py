@@ -15,7 +15,8 @@ Sweeps: noisy_target_sweep (target_snn_localization.py:435-467), speech_target_s
 target_localization_MUSIC.py), multi_target_sweep (K simultaneous targets, the statistical counterpart of
 paper_plots/multiple_targets_*.py: K peaks per trial, matched errors and resolution rate), windowed_target_sweep (the noisy-target
 sweep with the time-resolved read-out: one estimate per window of every trial), moving_target_sweep (a moving target scored per
-frame, target_snn_localization.py:585-628).
+frame, target_snn_localization.py:585-628), xylo_moving_target_sweep (the same read from the Xylo network's spikes,
+target_xylo_localization.py:672-789; integer-LIF stage parity-unpinned).
 
 Every sweep runs through ONE trial loop, `_monte_carlo`: shard range, ShardStore and resume, the parity replay of the global stream
 (also across skipped trials), the throughput range loop, the flush of a finished batch, the one all-gather.  A sweep hands it only
@@ -1082,6 +1083,36 @@ def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, nu
     return res
 
 
+def xylo_track_localizer(demo, envelope, max_batch=1100):
+    """track_localizer's place in moving_target_sweep(localizer=) for the Xylo chain: Demo.track_batch (encoder, integer LIF, envelope
+    and arg-max per frame in one read-out of the LIF walk); index [B, T] stays on the device."""
+
+    def run(sig_batch, time_vec):
+        return _in_batches(sig_batch, max_batch, lambda x: (demo.track_batch(x, envelope)["index"],))[0]
+
+    return run
+
+
+def xylo_moving_target_sweep(demo, envelope, localizer=None, batch_trials=1100, store_key=None, **kw):
+    """moving_target_sweep for the Xylo chain (paper_plots/target_xylo_localization.py:672-789, `test_moving_target`, and its
+    `_unipolar` twin): the same moving test signal, SNR grid and scoring, the estimate of frame t read from the hidden layer's spikes,
+    `np.argmax(Envelope.evolve(spikes_out), axis=1)`.  `demo` is a xylo_snn_localization.Demo with one band; its beamformer and bf_mat
+    give the geometry, the lag and the store key, which also covers the quantised specification and `bipolar`.  PARITY UNPINNED for
+    the integer-LIF stage, as xylo_target_sweep.  Other keywords as moving_target_sweep."""
+    if len(demo.beamfs) != 1:
+        raise ValueError(f"xylo_moving_target_sweep takes a demo with one band ({len(demo.beamfs)} given)")
+    if localizer is None:
+        localizer = xylo_track_localizer(demo, envelope, max_batch=batch_trials)
+    spec = demo.spec
+    key = dict(chain="xylo", bipolar=bool(demo.bipolar_spikes), xylo_W_in=np.asarray(spec["W_in"]), xylo_w_rec=int(spec["w_rec"]),
+               xylo_dash_syn=np.asarray(spec["dash_syn"]), xylo_dash_mem=np.asarray(spec["dash_mem"]), xylo_threshold=np.asarray(spec["threshold"]),
+               **(store_key or {}))
+    res = moving_target_sweep(demo.beamfs[0], demo.bf_mats[0], demo.doa_list, envelope, localizer=localizer, batch_trials=batch_trials,
+                              store_key=key, **kw)
+    res["parity"] = "unpinned (integer LIF)"
+    return res
+
+
 def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau, rank, world):
     """--sweep multi-noisy: multi_target_sweep with the noisy sweep's SNN or complex beamformer (design as --sweep noisy) or the MUSIC
     noisy sweep's MUSIC (1 s test signal, band [0.8, 1.2] x freq_design, k = 1, N = 2048)."""
@@ -1130,7 +1161,8 @@ def main(argv=None):
                     help="wideband-speech: the bands as low:high pairs in Hz, comma separated (at most 16)")
     ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
-    ap.add_argument("--method", choices=["snn", "beamformer", "music"], default="snn", help="multi-noisy, moving-noisy and wideband-speech (snn | beamformer): the localizer")
+    ap.add_argument("--method", choices=["snn", "beamformer", "music", "xylo"], default="snn",
+                    help="multi-noisy, wideband-speech (snn | beamformer) and moving-noisy (snn | beamformer | xylo): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
@@ -1160,7 +1192,16 @@ def main(argv=None):
     music_grid = args.sweep == "music-noisy" or (args.sweep == "multi-noisy" and args.method == "music")
     grid = args.grid if args.grid is not None else (8 * 7 + 1 if music_grid else 64 * 7 + 1)
     doa_list = np.linspace(-np.pi, np.pi, grid)
-    if args.sweep == "moving-noisy" and args.method == "beamformer":
+    if args.method == "xylo" and args.sweep != "moving-noisy":
+        ap.error("--method xylo goes with --sweep moving-noisy (the Xylo accuracy sweep is --sweep xylo)")
+    if args.sweep == "moving-noisy" and args.method == "xylo":
+        from .utils import Envelope
+        from .xylo_snn_localization import Demo
+
+        demo = Demo(geometry=geometry, freq_bands=[freq_range], doa_list=doa_list, recording_duration=0.25, bipolar_spikes=True, fs=fs)
+        res = xylo_moving_target_sweep(demo, Envelope(rise_time=1e-3, fall_time=10e-3, fs=fs), num_sim=args.num_sim or 100, seed=args.seed,
+                                       mode=args.mode, rank=rank, world_size=world)
+    elif args.sweep == "moving-noisy" and args.method == "beamformer":
         from .beamformer import Beamformer
         from .utils import Envelope
 
@@ -1233,7 +1274,7 @@ def main(argv=None):
             res = speech_target_sweep(beamf, bf_mat, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
         elif args.sweep == "moving-noisy":
             if args.method != "snn":
-                ap.error("--sweep moving-noisy takes --method snn or beamformer")
+                ap.error("--sweep moving-noisy takes --method snn, beamformer or xylo")
             from .utils import Envelope
 
             # (a 0.1 s trial: the script's 10 ms / 100 ms envelope would still be settling at its end)

@@ -162,6 +162,58 @@ class XyloNetwork:
                                                          runtime._stream(self.device)), "xylo_lif_resident")
         return out, rate
 
+    # ---- moving-target tracking (micloc_xylo_lif_track_i16; PARITY UNPINNED like run) ----------------------------------------------
+    def track_is_fused(self, ternary, max_spikes=31):
+        """True when the fused kernel serves this network and input (w_rec == 0, the ternary raster, at most 64 input channels)."""
+        rc = self.lib.micloc_xylo_track_is_fused(self.Cin // 2 if ternary else 0, self.Cin, self.N, self.w_rec, int(max_spikes))
+        if rc < 0:
+            _lib.check(rc, "xylo_track_is_fused")
+        return rc == 1
+
+    def track(self, spikes, envelope, ternary=False, max_spikes=31, want_rate=False, budget_bytes=1 << 30):
+        """`np.argmax(envelope.evolve(spikes_out), axis=1)` per trial (paper_plots/target_xylo_localization.py:757-789) without the
+        [B, T, N] raster or its envelope in device memory.  spikes as in run(); envelope: a utils.Envelope.  Returns a dict of device
+        tensors: index int32 [B, T], peak_env float64 [B, T], env_last float64 [B, N] and, with want_rate, rate int32 [B, N] (run()'s
+        counts).  Networks the fused kernel does not serve (a recurrent weight, uint8 events) run the two-step route inside the call over
+        sub-batches whose raster + envelope stay under `budget_bytes` (one trial at least); the results do not depend on it.  No host
+        access, no synchronisation."""
+        import torch
+
+        B, T, C = spikes.shape
+        if (2 * C if ternary else C) != self.Cin:
+            raise ValueError(f"number of input spike channels {2 * C if ternary else C} should match the weight matrix {self.Cin}")
+        if spikes.dtype != (torch.int8 if ternary else torch.uint8) or not spikes.is_contiguous():
+            raise ValueError("spikes must be a contiguous int8 (ternary) / uint8 (events) device tensor")
+        win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
+        if win_fall < 1 or win_rise < 1:
+            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        B, T = int(B), int(T)
+        if B * T > 0x7FFFFFFF:
+            raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
+        # NumPy's own arithmetic for the filter constants, as runtime.envelope_track
+        wl = np.asarray([win_fall, win_rise])
+        inv = 1 / wl
+        a = 1 - inv
+        tc = C if ternary else 0
+        nbytes = int(self.lib.micloc_xylo_track_workspace_bytes(tc, self.Cin, self.N, self.w_rec, B, T))
+        if nbytes == 0:
+            raise ValueError(f"micloc xylo_track_workspace_bytes: {B} trials x {T} frames of this network do not fit the rule")
+        fused = self.track_is_fused(ternary, max_spikes) and spikes.data_ptr() % 16 == 0
+        if not fused:  # (an unaligned ternary raster takes the two-step route too: its size, which the call checks)
+            per_trial = 9 * T * self.N + 512
+            nbytes = max(per_trial, min(B * per_trial, int(budget_bytes)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)  # one per call: calls of several streams run side by side
+        out = dict(index=torch.empty((B, T), dtype=torch.int32, device=self.device),
+                   peak_env=torch.empty((B, T), dtype=torch.float64, device=self.device),
+                   env_last=torch.empty((B, self.N), dtype=torch.float64, device=self.device))
+        if want_rate:
+            out["rate"] = torch.empty((B, self.N), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.micloc_xylo_lif_track_i16(runtime._ptr(spikes), tc, B, T, self.Cin, self.N, self.w_rec, int(max_spikes), float(a[1]),
+                                                      float(inv[1]), float(a[0]), runtime._ptr(out["index"]), runtime._ptr(out["peak_env"]),
+                                                      runtime._ptr(out["env_last"]), runtime._ptr(out.get("rate")), runtime._ptr(self.ws),
+                                                      self.nbytes, runtime._ptr(ws), nbytes, runtime._stream(self.device)), "xylo_lif_track")
+        return out
+
     # ---- resumable across launches (micloc_xylo_lif_resume_i16; PARITY UNPINNED like run) ------------------------------------------
     def new_state(self, B):
         """A zeroed LIF state for `B` trials (micloc_xylo_stream_reset): dict(state, counts int32 [B, N], B).  Zero synaptic current,
@@ -318,6 +370,20 @@ class Demo:
         if not self.bipolar_spikes:  # unipolar encoder: the raster holds 0 / +1 only and IS the event tensor (same bytes, read as uint8)
             return self.network().run(raster.view(dtype=torch.uint8), ternary=False)[1]
         return self.network().run(raster, ternary=True)[1]
+
+    def track_batch(self, sig_batch, envelope, want_rate=False, budget_bytes=1 << 30):
+        """[B, T, M] array signals -> the DoA index per time step, `np.argmax(envelope.evolve(xylo_process(spike_encoding(sig))), axis=1)`
+        (paper_plots/target_xylo_localization.py:672-789, `test_moving_target`), as XyloNetwork.track's dict of device tensors: the
+        estimate of frame t is `doa_list[index[:, t]]`.  One band only: beyond G columns an index names no direction.  A unipolar demo
+        runs the two-step route inside the call."""
+        import torch
+
+        if len(self.beamfs) != 1:
+            raise ValueError(f"track_batch takes a demo with one band ({len(self.beamfs)} given): doa_list[index] has no meaning beyond G columns")
+        raster = self.raster_device(sig_batch)
+        if not self.bipolar_spikes:  # (the raster holds 0 / +1 only and IS the event tensor: counts_batch)
+            return self.network().track(raster.view(dtype=torch.uint8), envelope, ternary=False, want_rate=want_rate, budget_bytes=budget_bytes)
+        return self.network().track(raster, envelope, ternary=True, want_rate=want_rate, budget_bytes=budget_bytes)
 
     def rate_batch(self, sig_batch):
         """[B, T, M] noisy array signals -> spike rate per DoA [B, G] (device tensor): mean(spikes_out) * fs averaged over

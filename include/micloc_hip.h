@@ -637,6 +637,45 @@ int micloc_beamformer_pipeline_track_f64(const micloc_plan *plan, const double *
                                          double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes,
                                          void *stream);
 
+/* ---- Xylo moving-target tracking: the DoA per time step from the hidden layer's spikes ----------- */
+/* paper_plots/target_xylo_localization.py:672-789 (`test_moving_target`, and its `_unipolar` twin): `sig_bf = spikes_out`, then
+ * `Envelope.evolve`, then `np.argmax(axis=1)` -- for a batch, as ONE read-out of the integer LIF ("Xylo-A2 hidden-layer integer LIF"
+ * above; PARITY UNPINNED like every Xylo entry).  The rule, for every trial b and neuron n independently:
+ *   c[t][n]   the spike count of step t: exactly the value micloc_xylo_lif_resident_i16 stores in spikes_out (the second spike within a
+ *             step and the max_spikes cap included);
+ *   m[t][n]   = (double)c[t][n];
+ *   e[0][n]   = m[0][n];   for t >= 1:  rise = m[t][n] >= e[t-1][n];
+ *   e[t][n]   = rise ? a_rise * e[t-1][n] + i_rise * m[t][n] : a_fall * e[t-1][n]      -- two rounded products, one rounded sum,
+ *             nothing fused: micloc_envelope_track_f64's recurrence, with a_rise = 1 - 1/w_rise, i_rise = 1/w_rise, a_fall = 1 - 1/w_fall
+ *             as NumPy computes them (w = int(fs * time) >= 1);
+ *   index[b][t]    = the FIRST n in [0, N) with e[t][n] = max_n e[t][n]  (np.argmax; counts are integers, so a row always has a winner);
+ *   peak_env[b][t] = that value  (may be NULL);
+ *   env_last[b][n] = e[T-1][n]  (may be NULL);
+ *   rate[b][n]     = sum_t c[t][n], the counts of micloc_xylo_lif_resident_i16  (may be NULL).
+ * All four equal, bit for bit, what micloc_xylo_lif_resident_i16 with spikes_out followed by micloc_envelope_track_any (MICLOC_ENV_U8)
+ * and a row arg-max compute from the stored raster.
+ * Arguments as micloc_xylo_lif_resident_i16: spikes_in is the encoder's int8 raster [B][T][ternary_channels] (ternary_channels > 0,
+ * Cin = 2 * ternary_channels) or uint8 event counts [B][T][Cin] (ternary_channels == 0); net_ws / net_ws_bytes: micloc_xylo_upload's.
+ * Networks the packed kernel serves -- w_rec == 0, the ternary raster, Cin <= 64, max_spikes >= 1 (micloc_xylo_track_is_fused() == 1)
+ * and a 16-byte aligned raster -- run the tracking form of the packed LIF walk (csrc/stream_xylo.hip): one workgroup per 512-neuron block and
+ * trial, neither the spikes nor the envelope is stored; up to 512 neurons the workgroup writes index and peak_env itself, beyond that
+ * the scratch is one (value, index) pair per frame and block and a small launch combines the blocks in ascending order.  Every other
+ * network (a recurrent weight, event counts, the unipolar input) runs the two-step route inside the call over sub-batches of trials:
+ * the minimum workspace holds the raster and the envelope of ONE trial (9 T N bytes), and a caller that passes more has as many trials
+ * per sub-batch as fit (the results do not depend on it).
+ * Status codes before any launch: MICLOC_ERR_SHAPE for T < 1, N < 1, B * T > 2^31 - 1 (and Cin > 64, Cin != 2 * ternary_channels,
+ * w_rec != 0 with N > 1024, as micloc_xylo_lif_resident_i16); MICLOC_ERR_WORKSPACE for a missing, misaligned (256 bytes) or short net_ws
+ * or ws; MICLOC_ERR_INVALID for a NULL index or input, a bad B or max_spikes < 1.  No atomics on results, no host synchronisation, no
+ * allocation: re-entrant per stream with workspaces of their own, and graph-capturable. */
+/* 1: the fused kernel serves this network and input, 0: it does not (the two-step route; also Cin > 64, which no Xylo kernel takes:
+ * the call itself then answers MICLOC_ERR_SHAPE); < 0: a status code */
+int micloc_xylo_track_is_fused(int ternary_channels, int Cin, int N, int w_rec, int max_spikes);
+/* minimum ws bytes of the call below (never 0 for valid arguments; fused: at most 16 B T ceil(N / 512) + 4096); 0 on bad arguments */
+size_t micloc_xylo_track_workspace_bytes(int ternary_channels, int Cin, int N, int w_rec, int B, int T);
+int micloc_xylo_lif_track_i16(const void *spikes_in, int ternary_channels, int B, int T, int Cin, int N, int w_rec, int max_spikes,
+                              double a_rise, double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last,
+                              int32_t *rate, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- streaming, tracking: a DoA per frame while the recording arrives ---------------------------- */
 /* The tracking rule above for a recording that arrives tile by tile ("streaming" and "streaming, complex Beamformer"): every frame is
  * EMITTED -- its index and its peak envelope written -- by the localize call of the tile that makes it final, and the emitted rows equal,
