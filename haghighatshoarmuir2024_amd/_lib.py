@@ -242,6 +242,16 @@ SYMBOLS = {
                                            c_int, c_int, c_int, ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "micloc_stream_xylo_readout_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "micloc_xylo_stream_track_state_bytes": (c_size_t, [c_int, c_int]),
+    "micloc_xylo_stream_track_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "micloc_xylo_stream_track_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "micloc_xylo_lif_track_resume_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                                 c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_stream_xylo_tile_track_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
+                                                  c_int, c_void_p, c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_abi_version": (c_int, []),
     "micloc_status_string": (ctypes.c_char_p, [c_int]),
     "micloc_last_hip_error": (c_int, []),

@@ -1,5 +1,6 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h "streaming, Xylo" for the contract): the packed integer LIF resumable across
-// launches, one tile of a band's Xylo stream behind micloc_stream_encode_tile_f64, and the read-out over the bands.  PARITY UNPINNED
+// launches, one tile of a band's Xylo stream behind micloc_stream_encode_tile_f64, the read-out over the bands, and the tracked form of the
+// first two ("streaming, Xylo tracking": a DoA index and a peak envelope per frame).  PARITY UNPINNED
 // like every Xylo entry (the oracle restates the published update rule; it is not checked against XyloSim).
 #include "api_internal.h"
 #include "stream_xylo.h"
@@ -27,10 +28,36 @@ int xs_window_args(int window, int hop, int ring_depth)
     return MICLOC_OK;
 }
 
-// the launches of a tile behind the encoder: horizon, the resumable LIF over the chunks that became final, (the window read-out,) commit, tick
+// the tracked read-out of a call (track == NULL: the counting LIF): the envelope state, the rule's constants, the ring, the scratch
+struct XsTrack {
+    void *state;
+    size_t state_bytes;
+    double a_rise, i_rise, a_fall;
+    int R;
+    int32_t *index;
+    double *peak;
+    int32_t *latest_index;
+    double *latest_peak;
+    double *env_last;
+    void *ws;
+    size_t ws_bytes;
+};
+
+// its status, before any launch; cap: the positions of the pair scratch, most: the frames one call can make final
+int xs_track_args(const XsTrack &t, int B, int N, int cap, int most)
+{
+    if (!t.state || !t.index || !t.peak || !t.latest_index || !t.latest_peak || !t.env_last || !t.ws || t.R < 1) return MICLOC_ERR_INVALID;
+    if (t.R < most) return MICLOC_ERR_SHAPE;
+    if (bad_ws(t.state, t.state_bytes, xylo_stream_track_state_bytes(B, N))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(t.ws, t.ws_bytes, xylo_stream_track_pairs_bytes(B, N, cap))) return MICLOC_ERR_WORKSPACE;
+    return MICLOC_OK;
+}
+
+// the launches of a tile behind the encoder: horizon, the resumable LIF over the chunks that became final -- counting or (track) tracking --,
+// (the window read-out,) commit, tick
 int xs_tile(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *raster, int B, int window_frames,
             int final_tile, int N, int max_spikes, int32_t *counts, void *lif_state, size_t lif_bytes, void *net_ws, size_t net_bytes, void *ws,
-            size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop, int ring_depth, void *stream)
+            size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop, int ring_depth, void *stream, const XsTrack *track = nullptr)
 {
     if (!p || !enc_state || !loc_state || !raster || !counts || !lif_state || !net_ws || bad_batch(B) || window_frames < 1) return MICLOC_ERR_INVALID;
     if (win_state && !ws) return MICLOC_ERR_INVALID;
@@ -45,14 +72,20 @@ int xs_tile(const micloc_plan *p, const void *enc_state, void *loc_state, size_t
     if (bad_ws(net_ws, net_bytes, xylo_ws_bytes(Cin, N))) return MICLOC_ERR_WORKSPACE;
     if (ws && bad_ws(ws, ws_bytes, xylo_stream_chunk_bytes(B, N, rows))) return MICLOC_ERR_WORKSPACE;
     if (win_state && bad_ws(win_state, win_bytes, xylo_stream_window_state_bytes(B, N, window, hop, ring_depth))) return MICLOC_ERR_WORKSPACE;
+    if (track && (rc = xs_track_args(*track, B, N, window_frames, window_frames)) != MICLOC_OK) return rc;
     DeviceGuard guard(p->device);
     hipStream_t st = (hipStream_t)stream;
     int *ctl = reinterpret_cast<int *>(loc_state);
     int32_t *chunk_counts = win_state ? reinterpret_cast<int32_t *>(ws) : nullptr;
     HIP_TRY(launch_stream_horizon(enc_state, B * p->C, p->bipolar, 0, final_tile ? 1 : 0, CH, 0, rows, ctl, st, 1));
     // the whole window as the launch shape; the kernel takes its frame range from the control words
-    HIP_TRY(launch_xylo_resume(raster, p->C, window_frames, B, 0, 0, ctl, Cin, N, max_spikes, nullptr, 0, counts, lif_state, net_ws, chunk_counts, rows,
-                               st));
+    if (track)
+        HIP_TRY(launch_xylo_track_resume(raster, p->C, window_frames, B, 0, 0, ctl, Cin, N, max_spikes, counts, lif_state, track->state, net_ws,
+                                         chunk_counts, rows, track->a_rise, track->i_rise, track->a_fall, track->R, track->index, track->peak,
+                                         track->latest_index, track->latest_peak, track->env_last, track->ws, window_frames, st));
+    else
+        HIP_TRY(launch_xylo_resume(raster, p->C, window_frames, B, 0, 0, ctl, Cin, N, max_spikes, nullptr, 0, counts, lif_state, net_ws, chunk_counts, rows,
+                                   st));
     if (win_state) HIP_TRY(launch_xylo_stream_windows(chunk_counts, B, rows, N, ctl, final_tile, window, hop, ring_depth, win_state, st));
     HIP_TRY(launch_stream_commit(ctl, STREAM_BLOCK_CHUNKS, st));
     HIP_TRY(launch_stream_tick(ctl, st));
@@ -93,6 +126,52 @@ int micloc_xylo_lif_resume_i16(const int8_t *raster, int ternary_channels, int t
     DeviceGuard guard(device_of(ws));
     HIP_TRY(launch_xylo_resume(raster, ternary_channels, trial_stride_frames, B, t0, n, nullptr, Cin, N, max_spikes, spikes_out, T_out, counts, state, ws,
                                nullptr, 0, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+// ---- the tracked read-out ("streaming, Xylo tracking") ---------------------------------------------------------------------------
+size_t micloc_xylo_stream_track_state_bytes(int B, int N)
+{
+    if (bad_batch(B) || N < 1) return 0;
+    return xylo_stream_track_state_bytes(B, N);
+}
+
+size_t micloc_xylo_stream_track_workspace_bytes(int B, int N, int window_frames)
+{
+    if (bad_batch(B) || N < 1 || window_frames < 1) return 0;
+    return xylo_stream_track_pairs_bytes(B, N, window_frames);
+}
+
+int micloc_xylo_stream_track_reset(void *track_state, size_t track_bytes, int B, int N, void *stream)
+{
+    if (!track_state || bad_batch(B) || N < 1) return MICLOC_ERR_INVALID;
+    const size_t need = xylo_stream_track_state_bytes(B, N);
+    if (bad_ws(track_state, track_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(track_state));
+    HIP_TRY(launch_zero_fill(track_state, need, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_xylo_lif_track_resume_i16(const int8_t *raster, int ternary_channels, int trial_stride_frames, int B, int t0, int n, int Cin, int N,
+                                     int max_spikes, void *state, size_t state_bytes, void *track_state, size_t track_bytes, double a_rise,
+                                     double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                     double *latest_peak, double *env_last, int32_t *counts, void *ws, size_t ws_bytes, void *track_ws,
+                                     size_t track_ws_bytes, void *stream)
+{
+    if (!raster || !counts || !state || !ws || bad_batch(B) || trial_stride_frames < 1 || t0 < 0 || n < 0) return MICLOC_ERR_INVALID;
+    int rc = xs_net_args(ternary_channels, Cin, N, max_spikes);
+    if (rc != MICLOC_OK) return rc;
+    if (t0 % 16 != 0 || (long long)t0 + n > trial_stride_frames || (reinterpret_cast<uintptr_t>(raster) & 15) != 0) return MICLOC_ERR_SHAPE;
+    if (bad_ws(state, state_bytes, xylo_stream_state_bytes(B, N))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, xylo_ws_bytes(Cin, N))) return MICLOC_ERR_WORKSPACE;
+    const XsTrack t{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, env_last,
+                    track_ws, track_ws_bytes};
+    const int cap = n > 0 ? n : 1;  // the pair scratch holds the frames of this call
+    if ((rc = xs_track_args(t, B, N, cap, n)) != MICLOC_OK) return rc;
+    DeviceGuard guard(device_of(ws));
+    HIP_TRY(launch_xylo_track_resume(raster, ternary_channels, trial_stride_frames, B, t0, n, nullptr, Cin, N, max_spikes, counts, state, track_state, ws,
+                                     nullptr, 0, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, env_last, track_ws,
+                                     cap, (hipStream_t)stream));
     return MICLOC_OK;
 }
 
@@ -168,6 +247,23 @@ int micloc_stream_xylo_tile_windows_i16(const micloc_plan *p, const void *enc_st
     if (!win_state || !ws) return MICLOC_ERR_INVALID;
     return xs_tile(p, enc_state, loc_state, loc_bytes, window_raster, B, window_frames, final_tile, N, max_spikes, counts, lif_state, lif_bytes, net_ws,
                    net_ws_bytes, ws, ws_bytes, win_state, win_bytes, window, hop, ring_depth, stream);
+}
+
+// xs_tile with the tracking LIF (and its combine launch beyond 512 neurons) in place of the counting one; win_state == NULL: no windows
+int micloc_stream_xylo_tile_track_i16(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
+                                      int B, int window_frames, int final_tile, int N, int max_spikes, int32_t *counts, void *lif_state,
+                                      size_t lif_bytes, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *win_state,
+                                      size_t win_bytes, int window, int hop, int ring_depth, void *track_state, size_t track_bytes, double a_rise,
+                                      double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                      double *latest_peak, double *env_last, void *track_ws, size_t track_ws_bytes, void *stream)
+{
+    const XsTrack t{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, env_last,
+                    track_ws, track_ws_bytes};
+    if (!win_state) return xs_tile(p, enc_state, loc_state, loc_bytes, window_raster, B, window_frames, final_tile, N, max_spikes, counts, lif_state,
+                                   lif_bytes, net_ws, net_ws_bytes, nullptr, 0, nullptr, 0, 0, 0, 0, stream, &t);
+    if (!ws) return MICLOC_ERR_INVALID;
+    return xs_tile(p, enc_state, loc_state, loc_bytes, window_raster, B, window_frames, final_tile, N, max_spikes, counts, lif_state, lif_bytes, net_ws,
+                   net_ws_bytes, ws, ws_bytes, win_state, win_bytes, window, hop, ring_depth, stream, &t);
 }
 
 /* status[0] = chunks integrated, [1] = frames integrated, [2] = window-lag failures, [3] = frames pushed (synchronises the stream) */

@@ -32,4 +32,15 @@ hipError_t launch_xylo_stream_readout(XyloReadoutArgs a, void *const *win_states
                                       int max_windows, void *state, int32_t *counts, double *rate, int32_t *peak, int32_t *wcounts, double *wrate,
                                       int32_t *wpeak, int32_t *lcounts, double *lrate, int32_t *lpeak, hipStream_t stream);
 
+// ---- the tracked stream (include/micloc_hip.h "streaming, Xylo tracking") ----
+size_t xylo_stream_track_state_bytes(int B, int N);           // [B][Npad / 2] x {e0, e1} doubles, the lane order of the LIF state
+size_t xylo_stream_track_pairs_bytes(int B, int N, int cap);  // 256 up to 512 neurons, else one (value, index) pair per position and block
+// launch_xylo_resume's range and state hand-off (no spikes_out) with the tracked read-out: the envelope in front of the range in and out
+// (env_state), frame t of the range into row t % R of index / peak [B][R], the newest also into latest_*, env_last [B][N] and counts [B][N]
+// rewritten (an empty range: nothing).  cap: positions per trial of `pairs` (a stream: the raster window's frames; by value: >= n).
+hipError_t launch_xylo_track_resume(const int8_t *raster, int tc, int stride_frames, int B, int t0, int n, const int *ctl, int Cin, int N,
+                                    int max_spikes, int32_t *counts, void *state, void *env_state, void *ws, int32_t *chunk_counts, int chunk_rows,
+                                    double a_rise, double i_rise, double a_fall, int R, int32_t *index, double *peak, int32_t *latest_index,
+                                    double *latest_peak, double *env_last, void *pairs, int cap, hipStream_t stream);
+
 }  // namespace micloc

@@ -25,7 +25,7 @@
 // the one-shot kernel's; here are the range, the state's load and store and the counts.
 //
 // At the end of the file stands a one-shot kernel all the same: xylo_lif_track_kernel, the tracking form of the packed walk (why here:
-// see there).
+// see there), and behind it that walk as a stream, xylo_lif_track_stream_kernel: this file's range and state around that kernel's tap.
 #include "readout_rows.h"
 #include "stream_xylo.h"
 #include "xylo_rows.h"
@@ -37,6 +37,38 @@ namespace {
 
 constexpr int SX_CH = XYLO_STREAM_CHUNK;
 constexpr int SX_MAXG = 4096;  // DoA grid of the read-out (its band sums live in LDS)
+
+// The range and the chunk counts of xylo_lif_stream_kernel below as functions, for its tracking form xylo_lif_track_stream_kernel at the end
+// of the file.  The counting kernel keeps its own text of both, and of the state's load and store: it is the live loop's kernel, and
+// with these functions in it its 12 000-frame tile measured 1 % slower at equal registers (with the state helpers as well: 82 VGPRs
+// instead of 80, five waves per SIMD instead of six); DESIGN 4.24.
+// The frames of a launch: [t_lo, t_hi) by value, or (ctl != NULL) the range of this tile, decided on the device by the horizon launch in
+// front.  false: an empty range (uniform over the launch; the caller returns in front of every barrier and rewrites nothing).
+__device__ __forceinline__ bool sx_range(const int *__restrict__ ctl, int chunk_rows, int &t_lo, int &t_hi)
+{
+    if (ctl) {
+        const int lo = ctl[4], hi = ctl[5], exist = ctl[10];
+        if (lo < 0 || hi > chunk_rows) return false;  // (never: the horizon flags a window that does not hold the range and leaves it empty)
+        t_lo = lo * SX_CH;
+        t_hi = hi * SX_CH < exist ? hi * SX_CH : exist;
+    }
+    return t_hi > t_lo;
+}
+
+// run_range's `done` for the windowed read-out: a chunk of the stream ends with the tile [t0, t0 + steps) (the recording's last one may
+// be ragged): its count goes to its window-relative row.  chunk0 / chunk1: the totals at the start of the open chunk.
+template <class Lif>
+__device__ __forceinline__ void sx_chunk_done(const Lif &lif, int *__restrict__ chunk_counts, int chunk_rows, int b, int t0, int steps, int t_hi,
+                                              int &chunk0, int &chunk1)
+{
+    if (chunk_counts && (((t0 + steps) & (SX_CH - 1)) == 0 || t0 + steps == t_hi)) {
+        int *cc = chunk_counts + ((size_t)b * chunk_rows + (t0 >> 8)) * lif.N;
+        if (lif.act0) cc[lif.n0] = lif.total0 - chunk0;
+        if (lif.act1) cc[lif.n1] = lif.total1 - chunk1;
+        chunk0 = lif.total0;
+        chunk1 = lif.total1;
+    }
+}
 
 template <int KQ, bool WANT_OUT>
 __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_stream_kernel(const int8_t *__restrict__ raster, int tc, int stride_frames, int Cin,
@@ -402,6 +434,59 @@ struct XpTrackTap {
     }
 };
 
+// What the one-shot and the stream form of the tracking walk share around the tap: its set-up from the lane's constants (the envelopes
+// e0 / e1 are the kernel's: zero, or the stream's state) ...
+template <class Lif>
+__device__ __forceinline__ void xp_track_tap_init(Lif &lif, double a_rise, double i_rise, double a_fall, double (*sv)[XP_TT], int (*si)[XP_TT])
+{
+    auto &tap = lif.tap;
+    tap.a_rise = a_rise, tap.i_rise = i_rise, tap.a_fall = a_fall;
+    tap.n0 = lif.n0, tap.n1 = lif.n1, tap.act0 = lif.act0, tap.act1 = lif.act1;
+    tap.l = lif.l, tap.off = 0, tap.first = false;
+    tap.sv = sv[lif.wv];
+    tap.si = si[lif.wv];
+}
+
+// ... and run_range's `done`: behind the staged tile one thread per frame takes the waves' pairs in ascending order (ascending neurons: a
+// strictly larger value takes over) and hands emit(f, best, bi) the result of the tile's frame f.  (The barrier at the head of the next
+// tile of run_range keeps these reads in front of the next pairs.)
+template <class Emit>
+__device__ __forceinline__ void xp_track_rows(const double (*sv)[XP_TT], const int (*si)[XP_TT], int waves, int tid, int nthreads, int steps,
+                                              Emit emit)
+{
+    __syncthreads();
+    for (int f = tid; f < steps; f += nthreads) {
+        double best = -1.0;
+        int bi = RO_NONE;
+        for (int w = 0; w < waves; ++w) {
+            const double v = sv[w][f];
+            const int i = si[w][f];
+            if (i != RO_NONE && v > best) {
+                best = v;
+                bi = i;
+            }
+        }
+        emit(f, best, bi);
+    }
+}
+
+// the pairs of one frame over the neuron blocks, ascending = ascending neurons: only a strictly larger value takes over (counts are
+// integers: every block has a winner)
+__device__ __forceinline__ void xylo_track_combine_row(const double *__restrict__ pval, const int32_t *__restrict__ pidx, int nblk, double &best,
+                                                       int &bi)
+{
+    best = -1.0;
+    bi = RO_NONE;
+    for (int c = 0; c < nblk; ++c) {
+        const double v = pval[c];
+        const int i = pidx[c];
+        if (better(v, i, best, bi)) {
+            best = v;
+            bi = i;
+        }
+    }
+}
+
 // grid (neuron blocks, trials) as xylo_lif_pk_kernel's one-shot form.  One neuron block: pval / pidx are peak_env (may be NULL) and index
 // [B][T]; more: the pairs [B T][blocks] that xylo_track_combine_kernel reduces.
 template <int KQ>
@@ -421,29 +506,13 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_kernel(const int
     XpLif<KQ, false, XpTrackTap> lif;
     lif.init(tile, cur_dyn, blockIdx.x * XP_NEUR, Wb, N, dash_syn, dash_mem, thr, max_spikes);
     XpTrackTap &tap = lif.tap;
-    tap.a_rise = a_rise, tap.i_rise = i_rise, tap.a_fall = a_fall;
+    xp_track_tap_init(lif, a_rise, i_rise, a_fall, sv, si);
     tap.e0 = tap.e1 = 0.0;
-    tap.n0 = lif.n0, tap.n1 = lif.n1, tap.act0 = lif.act0, tap.act1 = lif.act1;
-    tap.l = lif.l, tap.off = 0, tap.first = false;
-    tap.sv = sv[lif.wv];
-    tap.si = si[lif.wv];
     const int b = blockIdx.y, nblk = gridDim.x, blk = blockIdx.x;
     const int tid = lif.tid, nthreads = lif.nthreads, waves = nthreads >> 6;
     const int8_t *rend = raster + (size_t)gridDim.y * T * tc;
-    // (the barrier at the head of the next tile of run_range keeps these reads in front of the next pairs)
     auto done = [&](int t0, int steps) {
-        __syncthreads();
-        for (int f = tid; f < steps; f += nthreads) {
-            double best = -1.0;
-            int bi = RO_NONE;
-            for (int w = 0; w < waves; ++w) {  // ascending neurons: a strictly larger value takes over
-                const double v = sv[w][f];
-                const int i = si[w][f];
-                if (i != RO_NONE && v > best) {
-                    best = v;
-                    bi = i;
-                }
-            }
+        xp_track_rows(sv, si, waves, tid, nthreads, steps, [&](int f, double best, int bi) {
             const size_t row = (size_t)b * T + t0 + f;
             if (nblk == 1) {
                 pidx[row] = bi == RO_NONE ? 0 : bi;
@@ -452,7 +521,7 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_kernel(const int
                 pval[row * nblk + blk] = best;
                 pidx[row * nblk + blk] = bi;
             }
-        }
+        });
     };
     lif.run_range(raster + (size_t)b * T * tc, rend, tc, Cin, 0, T, done);
     if (env_last) {
@@ -465,24 +534,178 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_kernel(const int
     }
 }
 
-// the pairs of a frame over the neuron blocks, ascending -> index, peak (counts are integers: every block has a winner)
+// the pairs of a frame over the neuron blocks -> index, peak
 __global__ __launch_bounds__(256) void xylo_track_combine_kernel(const double *__restrict__ pval, const int32_t *__restrict__ pidx, size_t rows,
                                                                  int nblk, int32_t *__restrict__ index, double *__restrict__ peak)
 {
     const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= rows) return;
-    double best = -1.0;
-    int bi = RO_NONE;
-    for (int c = 0; c < nblk; ++c) {  // ascending blocks = ascending neurons: only a strictly larger value takes over
-        const double v = pval[row * nblk + c];
-        const int i = pidx[row * nblk + c];
-        if (better(v, i, best, bi)) {
-            best = v;
-            bi = i;
-        }
-    }
+    double best;
+    int bi;
+    xylo_track_combine_row(pval + row * nblk, pidx + row * nblk, nblk, best, bi);
     index[row] = bi == RO_NONE ? 0 : bi;
     if (peak) peak[row] = best;
+}
+
+// ==== the tracking walk as a STREAM: xylo_lif_stream_kernel's range, early return and state hand-off around xylo_lif_track_kernel's tap,
+// pair tile and combine over the waves (include/micloc_hip.h "streaming, Xylo tracking") ===================================
+// The walk hands its tap first = (position in the range's raster == 0).  In a stream that position is relative to the raster WINDOW; the
+// rule's e[0] = m[0] belongs to ABSOLUTE frame 0 alone.  The stream's tap wraps the one-shot tap and lets `first` through only where
+// position 0 is absolute frame 0: the window's base word ctl[STREAM_CLK_BASE], written by the clock launch in front of the tile, is 0 (by
+// value: the raster is the recording, always).  No flag the kernel writes for itself is read (4.21's rule).
+struct XpTrackStreamTap : XpTrackTap {
+    bool at_origin;
+    __device__ __forceinline__ void begin(int off_, bool first_) { XpTrackTap::begin(off_, first_ && at_origin); }
+};
+
+struct XyloTrackSink {
+    int R;  // ring depth
+    int32_t *index;
+    double *peak;
+    int32_t *latest_index;
+    double *latest_peak;
+};
+
+// a finished row of trial b: frame `abs` into its ring row, the newest frame of the launch also into the latest words
+__device__ __forceinline__ void xylo_track_ring_store(const XyloTrackSink &o, int b, int abs, bool newest, double best, int bi)
+{
+    const size_t r = (size_t)b * o.R + (size_t)((unsigned)abs % (unsigned)o.R);  // (abs >= 0: the clock's)
+    const int idx = bi == RO_NONE ? 0 : bi;
+    o.index[r] = idx;
+    o.peak[r] = best;
+    if (newest) {
+        o.latest_index[b] = idx;
+        o.latest_peak[b] = best;
+    }
+}
+
+// grid (neuron blocks, trials), the range and the state of xylo_lif_stream_kernel; env_state [B][Npad / 2] x {e0, e1}, the lane order of
+// `state`.  Position p of the range's raster is absolute frame abs0 + p.  One neuron block: the workgroup writes ring row (abs0 + p) % R
+// itself; more: the pairs go to pval / pidx [B][cap][blocks] at p - p0 (p0: 0 in a stream, the by-value range's start otherwise) and
+// xylo_track_stream_combine_kernel finishes them.
+template <int KQ>
+__global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_stream_kernel(const int8_t *__restrict__ raster, int tc, int stride_frames, int Cin,
+                                                                               const long *__restrict__ Wb /*[Npad][4 KQ]*/, int N,
+                                                                               const uint8_t *__restrict__ dash_syn,
+                                                                               const uint8_t *__restrict__ dash_mem,
+                                                                               const short *__restrict__ thr, int max_spikes,
+                                                                               int *__restrict__ counts, int4_t *__restrict__ state,
+                                                                               double2 *__restrict__ env_state, int t_lo, int t_hi,
+                                                                               const int *__restrict__ ctl, int *__restrict__ chunk_counts,
+                                                                               int chunk_rows, double a_rise, double i_rise, double a_fall,
+                                                                               const XyloTrackSink out, double *__restrict__ env_last,
+                                                                               double *__restrict__ pval, int32_t *__restrict__ pidx, int cap)
+{
+    const int p0 = ctl ? 0 : t_lo;
+    if (!sx_range(ctl, chunk_rows, t_lo, t_hi)) return;  // uniform over the launch, in front of every barrier: nothing is rewritten
+    const int abs0 = ctl ? ctl[STREAM_CLK_BASE] : 0;
+
+    __shared__ __attribute__((aligned(16))) unsigned char tile[XP_TT][32 * KQ];
+    extern __shared__ __attribute__((aligned(16))) int cur_dyn[];  // [waves][4][64][4]
+    __shared__ double sv[XP_WAVES][XP_TT];
+    __shared__ int si[XP_WAVES][XP_TT];
+    const int b = blockIdx.y, nblk = gridDim.x, blk = blockIdx.x;
+    XpLif<KQ, false, XpTrackStreamTap> lif;
+    lif.init(tile, cur_dyn, blk * XP_NEUR, Wb, N, dash_syn, dash_mem, thr, max_spikes);
+    XpTrackStreamTap &tap = lif.tap;
+    xp_track_tap_init(lif, a_rise, i_rise, a_fall, sv, si);
+    tap.at_origin = abs0 == 0;
+    // the trial's state of this lane pair, as xylo_lif_stream_kernel's; its envelopes in the same order
+    const size_t lane = (((size_t)b * nblk + blk) * XP_WAVES + lif.wv) * 64 + lif.l;
+    const int4_t sw = state[lane];
+    lif.isyn = xp_s2(sw[0]);
+    lif.vmem = xp_s2(sw[1]);
+    lif.total0 = sw[2];
+    lif.total1 = sw[3];
+    const double2 ev = env_state[lane];
+    tap.e0 = ev.x, tap.e1 = ev.y;
+    int chunk0 = lif.total0, chunk1 = lif.total1;
+    const int tid = lif.tid, nthreads = lif.nthreads, waves = nthreads >> 6;
+
+    lif.run_range(raster + (size_t)b * stride_frames * tc, raster + (size_t)gridDim.y * stride_frames * tc, tc, Cin, t_lo, t_hi,
+                  [&](int t0, int steps) {
+                      sx_chunk_done(lif, chunk_counts, chunk_rows, b, t0, steps, t_hi, chunk0, chunk1);
+                      xp_track_rows(sv, si, waves, tid, nthreads, steps, [&](int f, double best, int bi) {
+                          const int p = t0 + f;
+                          if (nblk == 1) {
+                              xylo_track_ring_store(out, b, abs0 + p, p == t_hi - 1, best, bi);
+                          } else {
+                              const size_t e = ((size_t)b * cap + (p - p0)) * nblk + blk;
+                              pval[e] = best;
+                              pidx[e] = bi;
+                          }
+                      });
+                  });
+    state[lane] = int4_t{xp_i(lif.isyn), xp_i(lif.vmem), lif.total0, lif.total1};
+    env_state[lane] = double2{tap.e0, tap.e1};
+    if (lif.act0) {
+        counts[(size_t)b * N + lif.n0] = lif.total0;
+        env_last[(size_t)b * N + lif.n0] = tap.e0;
+    }
+    if (lif.act1) {
+        counts[(size_t)b * N + lif.n1] = lif.total1;
+        env_last[(size_t)b * N + lif.n1] = tap.e1;
+    }
+}
+
+// one thread per position of the pair scratch; positions outside the launch's range (the same words) return
+__global__ __launch_bounds__(256) void xylo_track_stream_combine_kernel(const double *__restrict__ pval, const int32_t *__restrict__ pidx,
+                                                                        const int *__restrict__ ctl, int chunk_rows, int t_lo, int t_hi, int cap,
+                                                                        int nblk, const XyloTrackSink out)
+{
+    const int p0 = ctl ? 0 : t_lo;
+    if (!sx_range(ctl, chunk_rows, t_lo, t_hi)) return;
+    const int abs0 = ctl ? ctl[STREAM_CLK_BASE] : 0;
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    const int p = p0 + j;
+    if (j >= cap || p < t_lo || p >= t_hi) return;
+    const size_t e = ((size_t)b * cap + j) * nblk;
+    double best;
+    int bi;
+    xylo_track_combine_row(pval + e, pidx + e, nblk, best, bi);
+    xylo_track_ring_store(out, b, abs0 + p, p == t_hi - 1, best, bi);
+}
+
+size_t xylo_stream_track_state_bytes(int B, int N) { return (size_t)B * (xp_npad(N) / 2) * sizeof(double2); }
+
+size_t xylo_stream_track_pairs_bytes(int B, int N, int cap)
+{
+    const int nblk = xp_npad(N) / XP_NEUR;
+    return nblk == 1 ? 256 : xylo_track_pairs_size((size_t)B * cap * nblk);  // (one block writes the ring itself; never 0: that is "bad arguments")
+}
+
+// launch_xylo_resume's range and state with the tracked read-out; cap: the positions per trial of the pair scratch (a stream: the raster
+// window's frames; by value: n)
+hipError_t launch_xylo_track_resume(const int8_t *raster, int tc, int stride_frames, int B, int t0, int n, const int *ctl, int Cin, int N,
+                                    int max_spikes, int32_t *counts, void *state, void *env_state, void *ws, int32_t *chunk_counts, int chunk_rows,
+                                    double a_rise, double i_rise, double a_fall, int R, int32_t *index, double *peak, int32_t *latest_index,
+                                    double *latest_peak, double *env_last, void *pairs, int cap, hipStream_t stream)
+{
+    if (Cin > 64 || Cin != 2 * tc || max_spikes < 1 || R < 1 || (reinterpret_cast<uintptr_t>(raster) & 15) != 0) return hipErrorInvalidValue;
+    if (!ctl && n < 1) return hipSuccess;  // an empty range: nothing is launched, nothing rewritten
+    if (cap < (ctl ? stride_frames : n)) return hipErrorInvalidValue;
+    const XyloWs w = xylo_ws(ws, Cin, N);
+    const XpShape sh = xp_shape(N, tc);
+    const dim3 grid(sh.nblk, B), block(sh.waves * 64);
+    const XyloTrackSink out{R, index, peak, latest_index, latest_peak};
+    double *pval = nullptr;
+    int32_t *pidx = nullptr;
+    if (sh.nblk > 1) xylo_track_pairs_split(pairs, (size_t)B * cap * sh.nblk, pval, pidx);
+    int4_t *stp = reinterpret_cast<int4_t *>(state);
+    double2 *esp = reinterpret_cast<double2 *>(env_state);
+    if (xp_kq(Cin) == 1)
+        hipLaunchKernelGGL(xylo_lif_track_stream_kernel<1>, grid, block, sh.lds, stream, raster, tc, stride_frames, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                           max_spikes, counts, stp, esp, t0, t0 + n, ctl, chunk_counts, chunk_rows, a_rise, i_rise, a_fall, out, env_last, pval, pidx,
+                           cap);
+    else
+        hipLaunchKernelGGL(xylo_lif_track_stream_kernel<2>, grid, block, sh.lds, stream, raster, tc, stride_frames, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                           max_spikes, counts, stp, esp, t0, t0 + n, ctl, chunk_counts, chunk_rows, a_rise, i_rise, a_fall, out, env_last, pval, pidx,
+                           cap);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || sh.nblk == 1) return e;
+    hipLaunchKernelGGL(xylo_track_stream_combine_kernel, dim3((unsigned)((cap + 255) / 256), B), dim3(256), 0, stream, pval, pidx, ctl, chunk_rows, t0,
+                       t0 + n, cap, sh.nblk, out);
+    return hipGetLastError();
 }
 
 bool xylo_track_fused(int ternary_C, int Cin, int w_rec, int max_spikes)

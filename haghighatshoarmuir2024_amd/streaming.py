@@ -38,6 +38,8 @@ running power nor a window of 256 frames follows -- `np.argmax(Envelope.evolve(y
 final in it, bit for bit the rows of track_batch on the whole recording, into a ring of `max_track` frames: latest_track() / tracked() /
 finish().  The state is the envelope in front of the next frame, 64 doubles per 64 DoAs and trial, whatever the length of the stream, and a
 tile is still one graph.  track_setup is the host-side rule (which plans, which ring depths), ring_rows the arithmetic of a ring's rows.
+XyloStreamingLocalizer (one band) takes track= too: Demo.track_batch's rows, from the tracking form of the packed integer LIF walk -- its
+ring rule is track_ring, track_setup's without the limits of the fused kernels of csrc/track.hip (LIF parity unpinned).
 
 THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
@@ -81,6 +83,13 @@ def track_setup(envelope, channels, num_doa, complex_bf, most, total_frames=None
     if int(channels) > 16 or (not complex_bf and int(num_doa) > 512):
         raise ValueError(f"a tracked stream runs the fused tracking kernels: up to 16 channels and, with a real bf_mat, up to 512 DoAs (got {channels} "
                          f"channels, {num_doa} DoAs); use track_batch on the whole recording")
+    return track_ring(envelope, most, total_frames, max_track)
+
+
+def track_ring(envelope, most, total_frames=None, max_track=None):
+    """track_setup's constants-and-ring part, which does not depend on the kernels behind the stream (the Xylo stream's tracked read-out is
+    the packed LIF walk, not csrc/track.hip): -> (a_rise, i_rise, a_fall, R), with track_setup's refusals of an envelope window below one
+    sample and of a ring shorter than `most`, and its default for R."""
     win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
     if win_fall < 1 or win_rise < 1:
         raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
@@ -154,16 +163,20 @@ class _TileStream:
 
     track = None  # the tracked read-out is off unless _set_track has been called
 
-    def _set_track(self, envelope, max_track, channels, num_doa, complex_bf, most):
+    def _set_track(self, envelope, max_track, channels, num_doa, complex_bf, most, fused=True):
         """self.track (the rule's constants, None without track=), self.max_track and self.min_track (what one tile can make final):
-        track_setup's refusals, before any device work."""
+        track_setup's refusals, before any device work.  fused=False: a stream whose tracked read-out is not csrc/track.hip's (the Xylo
+        stream) -- track_ring's refusals alone."""
         self.track = self.max_track = None
         self.min_track = int(most)
         if envelope is None:
             if max_track is not None:
                 raise ValueError("max_track belongs to the tracked read-out: give track as well")
             return
-        *self.track, self.max_track = track_setup(envelope, channels, num_doa, complex_bf, most, self.T, max_track)
+        if fused:
+            *self.track, self.max_track = track_setup(envelope, channels, num_doa, complex_bf, most, self.T, max_track)
+        else:
+            *self.track, self.max_track = track_ring(envelope, most, self.T, max_track)
 
     def _alloc_track(self, capacity):
         """The device side of track=: the envelope state (zero-filled on the stream), the pair scratch for `capacity` (the raster window's
@@ -379,16 +392,17 @@ class _TileStream:
         rows = torch.tensor(rows, dtype=torch.int64, device=self.device)
         return dict(count=count, first=first, index=self.track_index.index_select(1, rows), peak_envelope=self.track_peak.index_select(1, rows))
 
-    def _finish_track(self, out):
+    def _finish_track(self, out, env_last=None):
         """finish()'s tracked tail: `out` with track_index [B, T], track_peak_envelope [B, T] and envelope_last [B, G] (a live source
-        without total_frames: the max_track newest frames, see tracked())."""
+        without total_frames: the max_track newest frames, see tracked()).  env_last: where the stream keeps envelope_last outside `tst`."""
         if self.track is not None:
             if self.T is not None and self.max_track < self.T:
                 raise _lib.MiclocError(f"the recording has {self.T} frames and the ring keeps {self.max_track}: raise max_track (or read "
                                        "tracked() while the stream runs)")
             w = self.tracked()
-            env = self.tst.view(runtime._torch().float64).view(self.B, -1)  # [B][column groups x 64]
-            out.update(track_index=w["index"], track_peak_envelope=w["peak_envelope"], track_count=w["count"], envelope_last=env[:, : self.G].clone())
+            if env_last is None:
+                env_last = self.tst.view(runtime._torch().float64).view(self.B, -1)[:, : self.G]  # [B][column groups x 64]
+            out.update(track_index=w["index"], track_peak_envelope=w["peak_envelope"], track_count=w["count"], envelope_last=env_last.clone())
         return out
 
     def _need_done(self):
@@ -1102,16 +1116,28 @@ class XyloStreamingLocalizer(_TileStream):
     reset between windows: one stream is one continuous run of the network.  EMISSION RULE: the ring-depth one of
     WidebandStreamingLocalizer -- every band emits its windows into a ring of Kb rows as its own horizon passes them, a window of the
     stream is emitted by the read-out once every band has emitted it; Kb is WidebandStreamingLocalizer._ring_depth's bound with the
-    256-frame chunk, and the read-out counts a failure instead of reading an overwritten row (finish() then raises)."""
+    256-frame chunk, and the read-out counts a failure instead of reading an overwritten row (finish() then raises).
+
+    TRACKING (track=, max_track=; one band): the read-out for a MOVING source, Demo.track_batch's rule (include/micloc_hip.h "streaming, Xylo
+    tracking") -- every push also emits the neuron (DoA) index and the peak envelope of every frame the LIF integrated in it, bit for bit
+    the rows of Demo.track_batch on the whole recording whatever the tiling, into a ring of `max_track` frames: latest_track() / tracked()
+    / finish().  The state is the envelope in front of the next frame, two doubles per lane pair beside the LIF state, whatever the length
+    of the stream; a tile is still one graph.  PARITY UNPINNED like everything behind the integer LIF."""
 
     TILE_MULTIPLE = 16  # the encoder takes its frames sixteen at a time
     CHUNK = 256         # frames per chunk of the LIF's stream: the quantum of window and hop
 
     def __init__(self, demo, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, win_size=1, window=None, hop=None,
-                 max_windows=None, max_spikes=31):
+                 max_windows=None, max_spikes=31, track=None, max_track=None):
         """demo: xylo_snn_localization.Demo; `batch` recordings are streamed in lock step.  total_frames, wrap_tail [batch, L // 2, M],
         max_tile, lag_frames, window, hop, max_windows: as StreamingLocalizer's (the window quantum is 256 frames); win_size: the
-        box-car of peak_batch (odd, at most G / 2)."""
+        box-car of peak_batch (odd, at most G / 2).
+        track      a utils.Envelope: also emit Demo.track_batch's moving-target read-out -- the DoA index and the peak envelope of every
+                   frame, as soon as the LIF has integrated it, bit for bit the one-shot rows (latest_track() / tracked() / finish();
+                   LIF parity unpinned).  One band only: beyond G columns an index names no direction.  None: exactly the launches without it.
+        max_track  rows of the ring the tracked frames are kept in (frame t in row t % max_track), at least min_track = the raster window's
+                   capacity; default: total_frames when that is given (never below min_track), else the smallest multiple of 64 >= 4 x
+                   min_track."""
         # ---- the refusals, in front of any device work ----
         self._check_window_given(window, hop, max_windows)
         spec = demo.spec
@@ -1135,6 +1161,11 @@ class XyloStreamingLocalizer(_TileStream):
         self.max_tile = -(-int(max_tile) // 16) * 16
         self.lag_frames = int(lag_frames)
         self._set_windows(None, window, hop, max_windows)
+        CH = self.CHUNK
+        self.cap = -(-(self.max_tile + self.lag_frames + 2 * CH) // CH) * CH
+        if track is not None and F != 1:
+            raise ValueError(f"a tracked Xylo stream takes a demo with one band ({F} given): doa_list[index] has no meaning beyond G columns")
+        self._set_track(track, max_track, None, self.G, False, self.cap, fused=False)
         W = np.asarray(spec["W_in"])
         C = 2 * self.M
         if W.shape != (2 * F * C, F * self.G):
@@ -1151,8 +1182,6 @@ class XyloStreamingLocalizer(_TileStream):
         self.device = dev = self.plan.device
         self.lib = lib = _lib.load()
         self._set_stht(demo.beamfs[0].kernel)
-        CH = self.CHUNK
-        self.cap = -(-(self.max_tile + self.lag_frames + 2 * CH) // CH) * CH
         self.Kb = self._ring_depth() if self.window is not None else 0
         from .xylo_snn_localization import XyloNetwork
 
@@ -1193,6 +1222,7 @@ class XyloStreamingLocalizer(_TileStream):
         if self.window is not None:
             self.window_counts = torch.zeros((self.B, self.max_windows, F * self.G), dtype=torch.int32, device=dev)
             self.latest_counts = torch.zeros((self.B, F * self.G), dtype=torch.int32, device=dev)
+        self._alloc_track(self.cap)
         self._set_wrap(wrap_tail)
         vp = ctypes.c_void_p
         self._p_counts = (vp * F)(*[b["counts"].data_ptr() for b in self.bands])
@@ -1212,6 +1242,26 @@ class XyloStreamingLocalizer(_TileStream):
         cols = slice(f * G, (f + 1) * G)
         return dict(W_in=np.ascontiguousarray(W[rows][:, cols]), w_rec=0, dash_syn=np.asarray(spec["dash_syn"])[cols],
                     dash_mem=np.asarray(spec["dash_mem"])[cols], threshold=np.asarray(spec["threshold"])[cols])
+
+    def _alloc_track(self, capacity):
+        """_TileStream's device side of track= with the Xylo stream's own state (the envelopes of the lane pairs, beside the band's LIF
+        state), scratch and envelope_last [B, G], which the tracking launch rewrites."""
+        if self.track is None:
+            return
+        torch = runtime._torch()
+        dev, lib = self.device, self.lib
+        self.ntst = int(lib.micloc_xylo_stream_track_state_bytes(self.B, self.G))
+        self.ntws = int(lib.micloc_xylo_stream_track_workspace_bytes(self.B, self.G, int(capacity)))
+        if self.ntst == 0 or self.ntws == 0:
+            raise ValueError(f"micloc xylo_stream_track_state_bytes: {self.B} trials x {self.G} neurons do not fit the rule")
+        self.tst = torch.empty(self.ntst, dtype=torch.uint8, device=dev)
+        self.tws = torch.empty(self.ntws, dtype=torch.uint8, device=dev)
+        self.track_index = torch.zeros((self.B, self.max_track), dtype=torch.int32, device=dev)
+        self.track_peak = torch.zeros((self.B, self.max_track), dtype=torch.float64, device=dev)
+        self.latest_index = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+        self.latest_peak = torch.zeros((self.B,), dtype=torch.float64, device=dev)
+        self.envelope_last = torch.zeros((self.B, self.G), dtype=torch.float64, device=dev)
+        _lib.check(lib.micloc_xylo_stream_track_reset(runtime._ptr(self.tst), self.ntst, self.B, self.G, runtime._stream(dev)), "xylo_stream_track_reset")
 
     def _set_windows(self, plan, window, hop, max_windows):
         """_TileStream's rule with the Xylo stream's own quantum, 256 frames, on the host alone (no plan has been built yet)."""
@@ -1254,7 +1304,15 @@ class XyloStreamingLocalizer(_TileStream):
             net = band["net"]
             tile = (plan.handle, runtime._ptr(band["state"]), loc, self.nloc, win, B, self.cap, int(final), self.G, self.max_spikes,
                     runtime._ptr(band["counts"]), runtime._ptr(band["lif"]), band["nlif"], runtime._ptr(net.ws), net.nbytes)
-            if self.window is None:
+            if self.track is not None:  # the same launches with the tracking LIF in place of the counting one (NULL state: no windows)
+                wargs = (None, 0, None, 0, 0, 0, 0) if self.window is None else \
+                    (runtime._ptr(self.ws), self.nws, runtime._ptr(band["wst"]), band["nwst"], self.window, self.hop, self.Kb)
+                _lib.check(lib.micloc_stream_xylo_tile_track_i16(*tile, *wargs, runtime._ptr(self.tst), self.ntst, *self.track, self.max_track,
+                                                                 runtime._ptr(self.track_index), runtime._ptr(self.track_peak),
+                                                                 runtime._ptr(self.latest_index), runtime._ptr(self.latest_peak),
+                                                                 runtime._ptr(self.envelope_last), runtime._ptr(self.tws), self.ntws, st),
+                           "stream_xylo_tile_track")
+            elif self.window is None:
                 _lib.check(lib.micloc_stream_xylo_tile_i16(*tile, st), "stream_xylo_tile")
             else:
                 _lib.check(lib.micloc_stream_xylo_tile_windows_i16(*tile, runtime._ptr(self.ws), self.nws, runtime._ptr(band["wst"]), band["nwst"],
@@ -1289,6 +1347,9 @@ class XyloStreamingLocalizer(_TileStream):
     def _window_count(self):
         return self._readout_status()[0]
 
+    def _track_count(self):
+        return self.status()["frames"]  # a frame is tracked by the launch that integrates it: the band's integrated frames
+
     def latest_window(self):
         """(rate [B, G], peak [B], counts [B, F G]) of the most recently emitted window: device tensors, overwritten when the next window
         is emitted, zeros until the first one exists.  Does not synchronise."""
@@ -1307,7 +1368,9 @@ class XyloStreamingLocalizer(_TileStream):
     def finish(self):
         """-> dict(counts [B, F G] int32, rate [B, G] float64, peak [B] int32; power and argmax name the same rate and peak) as device
         tensors; with window= also window_counts [B, nW, F G], window_rate / window_power [B, nW, G], window_peak / window_argmax [B, nW]
-        and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        and window_count (a live source without total_frames: the max_windows newest, see windows()); with track= also track_index [B, T]
+        int32, track_peak_envelope [B, T], track_count and envelope_last [B, G] -- Demo.track_batch's index, peak_env and env_last (a live
+        source: the max_track newest frames, see tracked()).  LIF parity unpinned."""
         self._need_done()
         s = self.status()
         self._need_spikes_final(s, self.cap, whose="a band's", by=" by the slowest band")
@@ -1317,4 +1380,4 @@ class XyloStreamingLocalizer(_TileStream):
         if self.window is not None:
             self._finish_windows(out)
             out.update(window_rate=out["window_power"], window_peak=out["window_argmax"])
-        return out
+        return self._finish_track(out, env_last=self.envelope_last if self.track is not None else None)

@@ -986,6 +986,21 @@ def track_localizer(beamf, bf_mat, envelope, max_batch=1100):
     return run
 
 
+def _wrap_rows(x, half):
+    """np.roll(x, half, axis=1)[:, :half] of a complete batch [B, T, M] (array or device tensor), zero rows behind a recording shorter
+    than `half`: the wrap_tail of a stream that is to reproduce the one-shot call."""
+    if isinstance(x, np.ndarray):
+        from .streaming import ComplexStreamingLocalizer
+
+        return ComplexStreamingLocalizer.wrap_rows(x, 2 * half)
+    import torch
+
+    out = torch.zeros((x.shape[0], half, x.shape[2]), dtype=x.dtype, device=x.device)
+    k = min(half, x.shape[1])
+    out[:, :k, :] = torch.roll(x, half, dims=1)[:, :k, :]
+    return out
+
+
 def stream_track_localizer(beamf, bf_mat, envelope, tile, max_batch=1100):
     """track_localizer's place in moving_target_sweep(localizer=) for audio that arrives while it is tracked: every batch is pushed in
     tiles of `tile` frames through a tracked stream (beamf.streaming_localizer(track=envelope); an SNN stream takes multiples of 16) and
@@ -997,23 +1012,11 @@ def stream_track_localizer(beamf, bf_mat, envelope, tile, max_batch=1100):
     snn = hasattr(beamf, "tau_vec")
     half = len(beamf.kernel) // 2
 
-    def wrap_rows(x):  # np.roll(x, half, axis=1)[:, :half], zero rows behind a recording shorter than `half`
-        if isinstance(x, np.ndarray):
-            from .streaming import ComplexStreamingLocalizer
-
-            return ComplexStreamingLocalizer.wrap_rows(x, 2 * half)
-        import torch
-
-        out = torch.zeros((x.shape[0], half, x.shape[2]), dtype=x.dtype, device=x.device)
-        k = min(half, x.shape[1])
-        out[:, :k, :] = torch.roll(x, half, dims=1)[:, :k, :]
-        return out
-
     def run(sig_batch, time_vec):
         def one(x):
             B, T, _ = x.shape
             kw = dict(time_vec=time_vec) if snn else {}
-            s = beamf.streaming_localizer(bf_mat, batch=B, total_frames=T, wrap_tail=wrap_rows(x), max_tile=min(tile, T), track=envelope, **kw)
+            s = beamf.streaming_localizer(bf_mat, batch=B, total_frames=T, wrap_tail=_wrap_rows(x, half), max_tile=min(tile, T), track=envelope, **kw)
             for t in range(0, T, tile):
                 s.push(x[:, t : t + tile, :])
             return (s.finish()["track_index"],)
@@ -1093,12 +1096,36 @@ def xylo_track_localizer(demo, envelope, max_batch=1100):
     return run
 
 
+def xylo_stream_track_localizer(demo, envelope, tile, max_batch=1100):
+    """stream_track_localizer's twin for the Xylo chain, for xylo_moving_target_sweep(localizer=): every batch is pushed in tiles of `tile`
+    frames (multiples of 16) through a tracked Xylo stream (demo.streaming_localizer(track=envelope)) and the index [B, T] of finish()
+    comes back -- the bits of Demo.track_batch on the whole batch, with np.roll's wrap-around rows known here because the batch is
+    complete.  PARITY UNPINNED for the integer-LIF stage."""
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("tile must be at least 1 frame")
+    half = len(demo.beamfs[0].kernel) // 2
+
+    def run(sig_batch, time_vec):
+        def one(x):
+            B, T, _ = x.shape
+            s = demo.streaming_localizer(batch=B, total_frames=T, wrap_tail=_wrap_rows(x, half), max_tile=min(tile, T), track=envelope)
+            for t in range(0, T, tile):
+                s.push(x[:, t : t + tile, :])
+            return (s.finish()["track_index"],)
+
+        return _in_batches(sig_batch, max_batch, one)[0]
+
+    return run
+
+
 def xylo_moving_target_sweep(demo, envelope, localizer=None, batch_trials=1100, store_key=None, **kw):
     """moving_target_sweep for the Xylo chain (paper_plots/target_xylo_localization.py:672-789, `test_moving_target`, and its
     `_unipolar` twin): the same moving test signal, SNR grid and scoring, the estimate of frame t read from the hidden layer's spikes,
     `np.argmax(Envelope.evolve(spikes_out), axis=1)`.  `demo` is a xylo_snn_localization.Demo with one band; its beamformer and bf_mat
     give the geometry, the lag and the store key, which also covers the quantised specification and `bipolar`.  PARITY UNPINNED for
-    the integer-LIF stage, as xylo_target_sweep.  Other keywords as moving_target_sweep."""
+    the integer-LIF stage, as xylo_target_sweep.  `localizer`: e.g. the tracked stream (xylo_stream_track_localizer).  Other keywords as
+    moving_target_sweep."""
     if len(demo.beamfs) != 1:
         raise ValueError(f"xylo_moving_target_sweep takes a demo with one band ({len(demo.beamfs)} given)")
     if localizer is None:

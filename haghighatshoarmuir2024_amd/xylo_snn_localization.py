@@ -258,6 +258,72 @@ class XyloNetwork:
                    "xylo_lif_resume")
         return out, state["counts"]
 
+    # ---- tracking, resumable across launches (micloc_xylo_lif_track_resume_i16; PARITY UNPINNED like run) ---------------------------
+    def new_track_state(self, B):
+        """A zeroed envelope state for `B` trials beside new_state's LIF state (micloc_xylo_stream_track_reset): dict(state, nbytes, B).
+        track_resume only ever continues a state."""
+        import torch
+
+        if self.w_rec != 0:
+            raise ValueError("the resumable LIF is the w_rec == 0 form (a recurrent weight couples all neurons per step)")
+        nb = int(self.lib.micloc_xylo_stream_track_state_bytes(int(B), self.N))
+        if nb == 0:
+            raise ValueError(f"micloc xylo_stream_track_state_bytes: {B} trials x {self.N} neurons do not fit the rule")
+        state = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.micloc_xylo_stream_track_reset(runtime._ptr(state), nb, int(B), self.N, runtime._stream(self.device)),
+                   "xylo_stream_track_reset")
+        return dict(state=state, nbytes=nb, B=int(B))
+
+    def track_resume(self, raster, t0, n, state, track_state, envelope, out=None, max_spikes=31):
+        """run_resume with track()'s read-out: integrate the frames [t0, t0 + n) of the encoder's int8 raster [B, T, Cin / 2] from `state`
+        (new_state) and `track_state` (new_track_state), leave both behind them, and emit index and peak envelope of every one of those
+        frames: frame t goes to row t % R of out["index"] int32 [B, R] / out["peak_env"] float64 [B, R], the newest frame also to
+        out["latest_index"] / out["latest_peak"] [B]; out["env_last"] float64 [B, N] and out["rate"] (= state["counts"]) are rewritten.
+        out=None: a new dict with R = T; pass the dict of an earlier call to assemble a recording (any R >= n).  t0 is a multiple of 16, n
+        may be 0 (nothing is rewritten).  Consecutive ranges from new states give XyloNetwork.track's bits for every cut.  Refuses what
+        run_resume refuses.  No host access, no synchronisation."""
+        import torch
+
+        if self.w_rec != 0:
+            raise ValueError("the resumable LIF is the w_rec == 0 form (a recurrent weight couples all neurons per step)")
+        if getattr(raster, "dtype", None) != torch.int8 or raster.dim() != 3 or not raster.is_contiguous():
+            raise ValueError("raster must be a contiguous int8 device tensor [B, T, Cin / 2] (the encoder's ternary raster)")
+        t0, n = int(t0), int(n)
+        if t0 % 16 != 0:
+            raise ValueError(f"t0 ({t0}) must be a multiple of 16 frames")
+        B, T, C = raster.shape
+        if 2 * C != self.Cin:
+            raise ValueError(f"number of input spike channels {2 * C} should match the weight matrix {self.Cin}")
+        if B != state["B"] or B != track_state["B"] or t0 < 0 or n < 0 or t0 + n > T:
+            raise ValueError(f"the range [{t0}, {t0 + n}) or the batch {B} does not fit the raster [{B}, {T}] and the states of {state['B']} / "
+                             f"{track_state['B']} trials")
+        win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
+        if win_fall < 1 or win_rise < 1:
+            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        wl = np.asarray([win_fall, win_rise])  # NumPy's own arithmetic for the filter constants, as track()
+        inv = 1 / wl
+        a = 1 - inv
+        if out is None:
+            out = dict(index=torch.zeros((B, T), dtype=torch.int32, device=self.device),
+                       peak_env=torch.zeros((B, T), dtype=torch.float64, device=self.device),
+                       latest_index=torch.zeros((B,), dtype=torch.int32, device=self.device),
+                       latest_peak=torch.zeros((B,), dtype=torch.float64, device=self.device),
+                       env_last=torch.zeros((B, self.N), dtype=torch.float64, device=self.device))
+        R = int(out["index"].shape[1])
+        if R < n:
+            raise ValueError(f"the ring of {R} frames is shorter than the {n} frames of this range")
+        out["rate"] = state["counts"]
+        nws = int(self.lib.micloc_xylo_stream_track_workspace_bytes(B, self.N, max(n, 1)))
+        ws = torch.empty(nws, dtype=torch.uint8, device=self.device)  # one per call: calls of several streams run side by side
+        _lib.check(self.lib.micloc_xylo_lif_track_resume_i16(runtime._ptr(raster), C, T, B, t0, n, self.Cin, self.N, int(max_spikes),
+                                                             runtime._ptr(state["state"]), state["nbytes"], runtime._ptr(track_state["state"]),
+                                                             track_state["nbytes"], float(a[1]), float(inv[1]), float(a[0]), R,
+                                                             runtime._ptr(out["index"]), runtime._ptr(out["peak_env"]),
+                                                             runtime._ptr(out["latest_index"]), runtime._ptr(out["latest_peak"]),
+                                                             runtime._ptr(out["env_last"]), runtime._ptr(state["counts"]), runtime._ptr(self.ws),
+                                                             self.nbytes, runtime._ptr(ws), nws, runtime._stream(self.device)), "xylo_lif_track_resume")
+        return out
+
     def queue_status(self):
         """dict(tickets, gave_up) of the last ticket-queue launch (micloc_xylo_sweep_status; synchronises): gave_up must be 0."""
         st = (ctypes.c_int * 2)()
@@ -427,7 +493,8 @@ class Demo:
 
     def streaming_localizer(self, batch=1, **kw):
         """The demo's chain for audio that arrives in tiles (streaming.XyloStreamingLocalizer): encoder and network carry their state
-        across the tiles instead of restarting on every pack.  PARITY UNPINNED like xylo_process."""
+        across the tiles instead of restarting on every pack.  track= (a utils.Envelope; max_track=: the ring's frames) adds track_batch's
+        read-out, a DoA index and a peak envelope per frame while the recording arrives (one band).  PARITY UNPINNED like xylo_process."""
         from .streaming import XyloStreamingLocalizer
 
         return XyloStreamingLocalizer(self, batch, **kw)

@@ -1053,6 +1053,59 @@ int micloc_stream_xylo_readout(int F, int B, int G, double fs, int win_size, con
                                int32_t *latest_counts, double *latest_rate, int32_t *latest_peak, void *stream);
 int micloc_stream_xylo_readout_status(const void *ro_state, int *status2, void *stream);
 
+/* ---- streaming, Xylo tracking: a DoA per frame from the Xylo chain while the recording arrives --- */
+/* "Xylo moving-target tracking" above for a recording that arrives tile by tile ("streaming, Xylo"): every frame the integer LIF
+ * integrates in a call is EMITTED by that call -- its neuron (DoA) index and its peak envelope written -- and the emitted rows equal, bit
+ * for bit, index / peak_env of micloc_xylo_lif_track_i16 on the whole raster, whatever the cuts; behind the last frame env_last and counts
+ * equal its env_last and rate.  PARITY UNPINNED like every Xylo entry: the LIF equals oracle_xylo_lif bit for bit, the oracle is not
+ * checked against XyloSim.  The rule, in full, for every trial b and neuron n independently, t the ABSOLUTE frame of the recording:
+ *   c[t][n]   the spike count of step t, exactly the value micloc_xylo_lif_resident_i16 stores in spikes_out (the second spike within a
+ *             step and the max_spikes cap included);   m[t][n] = (double)c[t][n];
+ *   e[0][n]   = m[0][n];   for t >= 1:  rise = m[t][n] >= e[t-1][n];
+ *   e[t][n]   = rise ? a_rise * e[t-1][n] + i_rise * m[t][n] : a_fall * e[t-1][n]      -- two rounded products, one rounded sum,
+ *             nothing fused; a_rise = 1 - 1/w_rise, i_rise = 1/w_rise, a_fall = 1 - 1/w_fall as NumPy computes them (w >= 1);
+ *   index of frame t    = the FIRST n in [0, N) with e[t][n] = max_n e[t][n]  (counts are integers, so a row always has a winner);
+ *   peak of frame t     = that value.
+ *   - Frame 0.  e[0] = m[0] is taken where the ABSOLUTE frame is 0: t0 == 0 by value; in a band's stream where the clock words of
+ *     loc_state say so (the base of the raster window, written by micloc_stream_xylo_begin_tile, plus the position in the window).
+ *     Position 0 of a raster window that has slid is NOT frame 0.  No flag that the kernel writes for itself is read.
+ *   - State.  lif_state is "streaming, Xylo"'s, unchanged (micloc_xylo_stream_state_bytes).  track_state holds e[t-1] in front of the
+ *     next frame, two doubles per lane pair in lif_state's order: [B][N rounded up to 512 / 2] x {e of the pair's neurons}
+ *     (micloc_xylo_stream_track_state_bytes), zero-filled by micloc_xylo_stream_track_reset -- never by the kernel.  Nothing of size
+ *     T x N is stored and nothing grows with the stream.
+ *   - Where a frame goes.  Frame t of trial b goes to row t % max_track of track_index [B][max_track] int32 / track_peak [B][max_track]
+ *     double, the newest frame of the call also to latest_index [B] / latest_peak [B]; env_last [B][N] (e of the newest frame) and counts
+ *     [B][N] are rewritten by every call that integrates a frame.  All are required device buffers.  A call that integrates nothing (n ==
+ *     0; a tile that makes no chunk final) rewrites nothing.  max_track must be at least what one call can make final: n by value,
+ *     window_frames in a stream.
+ *   - Scratch.  track_ws (micloc_xylo_stream_track_workspace_bytes(B, N, frames), frames = n by value, window_frames in a stream; 256-B
+ *     aligned): 256 bytes up to 512 neurons, where the workgroup of a trial writes the ring itself; beyond that one (value, index) pair
+ *     per frame and 512-neuron block, which a second launch combines in ascending block order (a strictly larger value takes over).
+ *   micloc_xylo_lif_track_resume_i16: the by-value form beside micloc_xylo_lif_resume_i16 -- the frames [t0, t0 + n) of raster
+ *   [B][trial_stride_frames][ternary_channels], t0 a multiple of 16, from lif_state and track_state, which it leaves behind them.
+ *   micloc_stream_xylo_tile_track_i16: micloc_stream_xylo_tile_i16's launch sequence with the tracking LIF (and the combine launch) in place
+ *   of the counting one -- horizon, tracking LIF, (windows,) commit, tick -- with the window arguments of micloc_stream_xylo_tile_windows_i16:
+ *   win_state == NULL (the other window arguments are then not read) means no window read-out.  counts, the window rows and lif_state have
+ *   the bits of the entries without tracking.  No launch argument depends on time: a tile stays one capturable sequence; no workgroup waits
+ *   for another, no atomics.  micloc_stream_xylo_status' frames integrated count the emitted frames.
+ *   Status, before any launch: as the entries without tracking, and MICLOC_ERR_INVALID for a NULL track_state, result buffer or track_ws or
+ *   max_track < 1; MICLOC_ERR_SHAPE for max_track below what the call can make final; MICLOC_ERR_WORKSPACE for a short or misaligned
+ *   track_state / track_ws.  The size functions return 0 for bad arguments and never for valid ones. */
+size_t micloc_xylo_stream_track_state_bytes(int B, int N);
+size_t micloc_xylo_stream_track_workspace_bytes(int B, int N, int frames);
+int micloc_xylo_stream_track_reset(void *track_state, size_t track_bytes, int B, int N, void *stream);
+int micloc_xylo_lif_track_resume_i16(const int8_t *raster, int ternary_channels, int trial_stride_frames, int B, int t0, int n, int Cin, int N,
+                                     int max_spikes, void *lif_state, size_t lif_bytes, void *track_state, size_t track_bytes, double a_rise,
+                                     double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                     double *latest_peak, double *env_last, int32_t *counts, void *ws, size_t ws_bytes, void *track_ws,
+                                     size_t track_ws_bytes, void *stream);
+int micloc_stream_xylo_tile_track_i16(const micloc_plan *p, const void *enc_state, void *loc_state, size_t loc_bytes, const int8_t *window_raster,
+                                      int B, int window_frames, int final_tile, int N, int max_spikes, int32_t *counts, void *lif_state,
+                                      size_t lif_bytes, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *win_state,
+                                      size_t win_bytes, int window, int hop, int ring_depth, void *track_state, size_t track_bytes, double a_rise,
+                                      double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                      double *latest_peak, double *env_last, void *track_ws, size_t track_ws_bytes, void *stream);
+
 /* ---- misc ------------------------------------------------------------------------------------- */
 int micloc_abi_version(void);
 const char *micloc_status_string(int status);
