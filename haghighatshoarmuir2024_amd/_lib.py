@@ -166,6 +166,11 @@ SYMBOLS = {
     "micloc_xylo_track_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "micloc_xylo_lif_track_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_xylo_window_quantum": (c_int, []),
+    "micloc_xylo_windows_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "micloc_xylo_lif_windows_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p, c_size_t, c_void_p]),
+    "micloc_xylo_window_readout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "micloc_stream_track_state_bytes": (c_size_t, [c_void_p, c_int]),
     "micloc_stream_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "micloc_stream_track_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

@@ -1,8 +1,10 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations):
 // moving-target tracking, the per-step arg-max of the envelope of the beamformer output (track.hip) and of the Xylo network's spike
-// counts (the tracking form of the packed walk, stream_xylo.hip).
+// counts (the tracking form of the packed walk, stream_xylo.hip) -- and, beside that one-shot Xylo read-out, the other: counts, rate and
+// peak per time window (xylo.hip, sweep.hip).
 #include "api_internal.h"
 #include "xylo_track.h"
+#include "xylo_windows.h"
 
 using namespace micloc;
 
@@ -228,6 +230,53 @@ int micloc_beamformer_pipeline_track_f64(const micloc_plan *p, const double *x, 
     const Front f = front_end(p, true, x, B, T, ws, lay, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
     if (f.rc != MICLOC_OK) return f.rc;
     return track_run(p, f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
+}
+
+// ---- time-resolved DoA, Xylo: counts, rate and peak per window (the rule: include/micloc_hip.h; every refusal in front of any launch) ----
+int micloc_xylo_window_quantum(void) { return 256; }
+
+size_t micloc_xylo_windows_workspace_bytes(int B, int T, int N)
+{
+    if (bad_batch(B) || T < 1 || N < 1) return 0;
+    return align256(xylo_windows_chunk_bytes(B, T, N));
+}
+
+// window_args' statuses for the quantum of 256 frames, and hop <= window (a window past the recording would hold no frame)
+static int xylo_window_args(int T, int window, int hop, int B, int *nW)
+{
+    const int rc = window_args(T, window, hop, micloc_xylo_window_quantum(), B, nW);
+    if (rc != MICLOC_OK) return rc;
+    return hop > window ? MICLOC_ERR_SHAPE : MICLOC_OK;
+}
+
+int micloc_xylo_lif_windows_i16(const void *spikes_in, int ternary_channels, int B, int T, int Cin, int N, int w_rec, int max_spikes, int window,
+                                int hop, int32_t *window_counts, int32_t *counts, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes,
+                                void *stream)
+{
+    if (!spikes_in || !window_counts || bad_batch(B) || T < 1 || Cin < 1 || N < 1 || max_spikes < 1) return MICLOC_ERR_INVALID;
+    if (!xylo_track_served(ternary_channels, Cin, N, w_rec)) return MICLOC_ERR_SHAPE;  // (the shapes micloc_xylo_lif_resident_i16 refuses)
+    int nW = 0;
+    const int rc = xylo_window_args(T, window, hop, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(net_ws, net_ws_bytes, xylo_ws_bytes(Cin, N))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, xylo_windows_chunk_bytes(B, T, N))) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(device_of(net_ws));
+    HIP_TRY(launch_xylo_windows(spikes_in, ternary_channels, B, T, Cin, N, w_rec, max_spikes, window, hop, nW, window_counts, counts, net_ws,
+                                reinterpret_cast<int32_t *>(ws), (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_xylo_window_readout(const int32_t *window_counts, int B, int T, int window, int hop, int G, int bands, double fs, int win_size,
+                               double *window_rate, int32_t *window_peak, void *stream)
+{
+    if (!window_counts || bad_batch(B) || T < 1 || G < 1 || bands < 1 || !(fs > 0.0) || (!window_rate && !window_peak)) return MICLOC_ERR_INVALID;
+    if (window_peak && (win_size < 1 || win_size % 2 != 1 || win_size > G / 2 || G > 16384)) return MICLOC_ERR_INVALID;  // micloc_peak_location_i32's rule
+    int nW = 0;
+    const int rc = xylo_window_args(T, window, hop, B, &nW);
+    if (rc != MICLOC_OK) return rc;
+    DeviceGuard guard(device_of(window_counts));
+    HIP_TRY(launch_xylo_window_readout(window_counts, B, nW, T, window, hop, G, bands, fs, win_size, window_rate, window_peak, (hipStream_t)stream));
+    return MICLOC_OK;
 }
 
 }  // extern "C"

@@ -38,9 +38,9 @@ namespace {
 constexpr int SX_CH = XYLO_STREAM_CHUNK;
 constexpr int SX_MAXG = 4096;  // DoA grid of the read-out (its band sums live in LDS)
 
-// The range and the chunk counts of xylo_lif_stream_kernel below as functions, for its tracking form xylo_lif_track_stream_kernel at the end
-// of the file.  The counting kernel keeps its own text of both, and of the state's load and store: it is the live loop's kernel, and
-// with these functions in it its 12 000-frame tile measured 1 % slower at equal registers (with the state helpers as well: 82 VGPRs
+// The range of xylo_lif_stream_kernel below as a function, for its tracking form xylo_lif_track_stream_kernel at the end of the file; the
+// chunk counts as a function are xp_chunk_done of xylo_rows.h, shared with the one-shot chunk-count kernel of xylo.hip.  The counting
+// kernel keeps its own text of both, and of the state's load and store: it is the live loop's kernel, and with these functions in it its 12 000-frame tile measured 1 % slower at equal registers (with the state helpers as well: 82 VGPRs
 // instead of 80, five waves per SIMD instead of six); DESIGN 4.24.
 // The frames of a launch: [t_lo, t_hi) by value, or (ctl != NULL) the range of this tile, decided on the device by the horizon launch in
 // front.  false: an empty range (uniform over the launch; the caller returns in front of every barrier and rewrites nothing).
@@ -53,21 +53,6 @@ __device__ __forceinline__ bool sx_range(const int *__restrict__ ctl, int chunk_
         t_hi = hi * SX_CH < exist ? hi * SX_CH : exist;
     }
     return t_hi > t_lo;
-}
-
-// run_range's `done` for the windowed read-out: a chunk of the stream ends with the tile [t0, t0 + steps) (the recording's last one may
-// be ragged): its count goes to its window-relative row.  chunk0 / chunk1: the totals at the start of the open chunk.
-template <class Lif>
-__device__ __forceinline__ void sx_chunk_done(const Lif &lif, int *__restrict__ chunk_counts, int chunk_rows, int b, int t0, int steps, int t_hi,
-                                              int &chunk0, int &chunk1)
-{
-    if (chunk_counts && (((t0 + steps) & (SX_CH - 1)) == 0 || t0 + steps == t_hi)) {
-        int *cc = chunk_counts + ((size_t)b * chunk_rows + (t0 >> 8)) * lif.N;
-        if (lif.act0) cc[lif.n0] = lif.total0 - chunk0;
-        if (lif.act1) cc[lif.n1] = lif.total1 - chunk1;
-        chunk0 = lif.total0;
-        chunk1 = lif.total1;
-    }
 }
 
 template <int KQ, bool WANT_OUT>
@@ -124,7 +109,7 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_stream_kernel(const in
     if (act1) counts[(size_t)b * N + n1] = lif.total1;
 }
 
-static_assert(SX_CH == 256, "the chunk row of a tile is t0 >> 8");
+static_assert(SX_CH == 256 && SX_CH == XP_CHUNK, "the chunk row of a tile is t0 >> 8 (xp_chunk_done, xylo_rows.h)");
 
 // ---- the windows of one band: stream_window_kernel's schedule (StreamWindowWalk, readout_rows.h) on integer counts, between the LIF
 // launch and the commit of a tile.  chunk_counts [B][chunk_rows][N] holds the chunks that became final in this call.  Window n keeps its
@@ -624,7 +609,7 @@ __global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_stream_kernel(co
 
     lif.run_range(raster + (size_t)b * stride_frames * tc, raster + (size_t)gridDim.y * stride_frames * tc, tc, Cin, t_lo, t_hi,
                   [&](int t0, int steps) {
-                      sx_chunk_done(lif, chunk_counts, chunk_rows, b, t0, steps, t_hi, chunk0, chunk1);
+                      xp_chunk_done(lif, chunk_counts, chunk_rows, b, t0, steps, t_hi, chunk0, chunk1);
                       xp_track_rows(sv, si, waves, tid, nthreads, steps, [&](int f, double best, int bi) {
                           const int p = t0 + f;
                           if (nblk == 1) {

@@ -3,6 +3,7 @@
 // (mean absolute error per SNR).  Keeps the timed sweep free of framework element-wise launches: one tiny kernel after
 // power_argmax_kernel instead of index / sin / abs / asin / mean.
 #include "readout_rows.h"
+#include "xylo_windows.h"
 
 namespace micloc {
 
@@ -45,14 +46,11 @@ hipError_t launch_doa_error(const int32_t *argmax, const double *doa_list, int G
 // normalises power by its maximum and by T / fs first -- positive factors that do not move the arg-max -- and sums in
 // floating point; here the window sums are exact integers (first maximum wins, as np.argmax), so the two can differ
 // only where the float sums of the reference break an exact integer tie by rounding.
-__global__ __launch_bounds__(256) void peak_location_kernel(const int32_t *__restrict__ rate, int G, int F, int win,
-                                                             int32_t *__restrict__ index)
+// The estimator on one row r [F][G] of counts, for peak_location_kernel and xylo_window_readout_kernel: every thread of a workgroup of 256
+// calls it (pw: G words of LDS, bestv / besti: 256) and gets the index.  TRAIL: block_first_max's, for a caller that loops over rows.
+template <bool TRAIL = false>
+__device__ __forceinline__ int peak_location_row(const int32_t *__restrict__ r, int G, int F, int win, long long *pw, long long *bestv, int *besti)
 {
-    extern __shared__ long long pw[];  // [G]
-    __shared__ long long bestv[256];
-    __shared__ int besti[256];
-    const int b = blockIdx.x;
-    const int32_t *r = rate + (size_t)b * F * G;
     for (int g = threadIdx.x; g < G; g += 256) {
         long long s = 0;
         for (int f = 0; f < F; ++f) s += r[(size_t)f * G + g];
@@ -72,12 +70,21 @@ __global__ __launch_bounds__(256) void peak_location_kernel(const int32_t *__res
             bi = n;
         }
     }
-    const int first = block_first_max<256>(bv, bi, bestv, besti, (int)threadIdx.x);
-    if (threadIdx.x == 0) {
-        int idx = first - win / 2;
-        idx %= G;
-        index[b] = idx < 0 ? idx + G : idx;
-    }
+    const int first = block_first_max<256, long long, TRAIL>(bv, bi, bestv, besti, (int)threadIdx.x);
+    int idx = first - win / 2;
+    idx %= G;
+    return idx < 0 ? idx + G : idx;
+}
+
+__global__ __launch_bounds__(256) void peak_location_kernel(const int32_t *__restrict__ rate, int G, int F, int win,
+                                                             int32_t *__restrict__ index)
+{
+    extern __shared__ long long pw[];  // [G]
+    __shared__ long long bestv[256];
+    __shared__ int besti[256];
+    const int b = blockIdx.x;
+    const int idx = peak_location_row(rate + (size_t)b * F * G, G, F, win, pw, bestv, besti);
+    if (threadIdx.x == 0) index[b] = idx;
 }
 
 hipError_t launch_peak_location(const int32_t *rate, int B, int G, int F, int win, int32_t *index, hipStream_t stream)
@@ -315,20 +322,66 @@ hipError_t launch_pack_events(const int8_t *raster, size_t rows, int C, uint8_t 
 
 // rate[b][g] = mean over the F bands of (counts[b][f G + g] / T) * fs -- np.mean(spikes_out, 0) * fs, then .reshape(-1, G).mean(0),
 // in that order of operations (the counts are exact integers, so the time mean is one division)
+// (column g of one row r [F][G]: the expression, for rate_from_counts_kernel and xylo_window_readout_kernel)
+__device__ __forceinline__ double rate_from_counts_row(const int32_t *__restrict__ r, int g, int G, int F, double T, double fs)
+{
+    double s = 0.0;
+    for (int f = 0; f < F; ++f) s += (double)r[(size_t)f * G + g] / T * fs;
+    return s / (double)F;
+}
+
 __global__ __launch_bounds__(256) void rate_from_counts_kernel(const int32_t *__restrict__ counts, int B, int G, int F, double T, double fs,
                                                                 double *__restrict__ rate)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B * G) return;
     const int b = i / G, g = i - b * G;
-    double s = 0.0;
-    for (int f = 0; f < F; ++f) s += (double)counts[((size_t)b * F + f) * G + g] / T * fs;
-    rate[i] = s / (double)F;
+    rate[i] = rate_from_counts_row(counts + (size_t)b * F * G, g, G, F, T, fs);
 }
 
 hipError_t launch_rate_from_counts(const int32_t *counts, int B, int G, int F, int T, double fs, double *rate, hipStream_t stream)
 {
     hipLaunchKernelGGL(rate_from_counts_kernel, dim3((B * G + 255) / 256), dim3(256), 0, stream, counts, B, G, F, (double)T, fs, rate);
+    return hipGetLastError();
+}
+
+// ---- time-resolved DoA, Xylo: rate and peak of every window row (include/micloc_hip.h) ---------------------------------
+// window_counts [B nW][F G] -> window_rate [B nW][G], window_peak [B nW] (either may be NULL): rate_from_counts_row over the frames the
+// window holds -- window n of a recording of T frames is [n hop, min(n hop + window, T)) -- and peak_location_row.  A workgroup per
+// (trial, window) pair, striding over them where there are more than the grid holds.
+__global__ __launch_bounds__(256) void xylo_window_readout_kernel(const int32_t *__restrict__ window_counts, int nW, unsigned pairs, int T, int window,
+                                                                   int hop, int G, int F, double fs, int win, double *__restrict__ window_rate,
+                                                                   int32_t *__restrict__ window_peak)
+{
+    extern __shared__ long long pw[];  // [G] (window_peak only)
+    __shared__ long long bestv[256];
+    __shared__ int besti[256];
+    for (unsigned bw = blockIdx.x; bw < pairs; bw += gridDim.x) {
+        const int n = (int)(bw % (unsigned)nW);
+        const long long left = (long long)T - (long long)n * hop;  // (>= 1: window n starts inside the recording)
+        const double frames = (double)(left < window ? left : window);
+        const int32_t *r = window_counts + (size_t)bw * F * G;
+        if (window_rate)
+            for (int g = threadIdx.x; g < G; g += 256) window_rate[(size_t)bw * G + g] = rate_from_counts_row(r, g, G, F, frames, fs);
+        if (window_peak) {  // (uniform)
+            const int idx = peak_location_row<true>(r, G, F, win, pw, bestv, besti);
+            if (threadIdx.x == 0) window_peak[bw] = idx;
+        }
+    }
+}
+
+hipError_t launch_xylo_window_readout(const int32_t *window_counts, int B, int nW, int T, int window, int hop, int G, int F, double fs, int win,
+                                      double *window_rate, int32_t *window_peak, hipStream_t stream)
+{
+    const size_t dyn = window_peak ? (size_t)G * sizeof(long long) : 0;
+    if (dyn > 48 * 1024) {  // (as launch_peak_location)
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xylo_window_readout_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned pairs = (unsigned)B * (unsigned)nW;
+    hipLaunchKernelGGL(xylo_window_readout_kernel, dim3(xylo_window_grid(pairs)), dim3(256), dyn, stream, window_counts, nW, pairs, T, window, hop, G,
+                       F, fs, win, window_rate, window_peak);
     return hipGetLastError();
 }
 

@@ -14,10 +14,14 @@
 // (broadcast) dwords.  xylo_lif_pk_kernel (the sweep: binary events, no recurrence): two neurons per lane in packed
 // 16-bit arithmetic, input currents from the int8 matrix cores -- the lane's walk is XpLif of xylo_rows.h, shared with the stream's
 // kernel (stream_xylo.hip); here are its two launch forms.
+// Each has a CHUNK-COUNT form for the time-resolved read-out (xylo_lif_chunks_kernel, xylo_lif_pk_chunks_kernel: the same walk, which
+// also leaves the spike count of every 256 frames), and xylo_window_kernel adds those rows per window: "time-resolved DoA" below,
+// PARITY UNPINNED like everything here.
 #include <vector>
 
 #include "micloc_internal.h"
 #include "xylo_rows.h"
+#include "xylo_windows.h"
 
 // (the recurrent instantiations keep a barrier inside the step loop, which the requested unrolling skips)
 #pragma clang diagnostic ignored "-Wpass-failed"
@@ -25,6 +29,7 @@
 namespace micloc {
 
 constexpr int XY_TT = 256;   // time steps staged per LDS tile
+static_assert(XY_TT == XP_CHUNK, "a staged tile of the general kernel is one chunk of the windowed read-out");
 constexpr int XY_MAXQ = 16;  // up to 64 input channels
 
 __device__ __forceinline__ int xy_sat16(int v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
@@ -122,6 +127,98 @@ __global__ __launch_bounds__(1024) void xylo_lif_kernel(const uint8_t *__restric
                 prev_total = tot;
             }
         }
+    }
+    if (rate && act) rate[(size_t)b * N + g] = total;
+}
+
+// The chunk-count form (the windowed read-out, "time-resolved DoA" below): the staged tile is one chunk of XP_CHUNK frames, and at its end
+// the lane also writes its count since the previous tile to chunk_counts [B][ceil(T / XP_CHUNK)][N]; rate may be NULL; no raster out.
+// The walk is xylo_lif_kernel's, line for line, except the lines marked CHUNKS and the raster's (tests/test_xylo_windows_cpu.py compares
+// the two texts): written once as a function inlined into both, xylo_lif_kernel came out with commutative operands swapped in all ten
+// instantiations, and the kernels that exist keep their instructions.
+template <bool REC, int NQ>
+__global__ __launch_bounds__(1024) void xylo_lif_chunks_kernel(const uint8_t *__restrict__ spikes_in, int ternary_C, int T, int Cin,
+                                                                const int *__restrict__ Wpk /*[nq][N]*/, int nq, int N, int w_rec,
+                                                                const uint8_t *__restrict__ dash_syn,
+                                                                const uint8_t *__restrict__ dash_mem,
+                                                                const short *__restrict__ thr, int max_spikes, int *__restrict__ rate,
+                                                                int *__restrict__ chunk_counts)
+{
+    __shared__ __attribute__((aligned(16))) int tile[XY_TT][NQ];
+    __shared__ int wsum[2][16];
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    const bool act = g < N;
+    int w[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) w[k] = (act && k < nq) ? Wpk[(size_t)k * N + g] : 0;
+    const int ds = act ? dash_syn[g] : 0, dm = act ? dash_mem[g] : 0;
+    const int th = act ? thr[g] : 32767;
+    int isyn = 0, vmem = 0, total = 0, prev_total = 0;
+    int chunk_total = 0;  // CHUNKS: `total` at the start of the tile
+    // ternary_C > 0: the input is the encoder's int8 raster [B][T][ternary_C] in {-1, 0, +1}; channel c carries its +1
+    // events, channel ternary_C + c its -1 events (Demo.spike_encoding's split, xylo_snn_localization.py:350-354)
+    const int Crow = ternary_C > 0 ? ternary_C : Cin;
+    const uint8_t *sb = spikes_in + (size_t)b * T * Crow;
+    const int8_t *sbt = reinterpret_cast<const int8_t *>(sb);
+    const int nwaves = blockDim.x >> 6;
+
+    for (int t0 = 0; t0 < T; t0 += XY_TT) {
+        const int steps = (T - t0) < XY_TT ? (T - t0) : XY_TT;
+        __syncthreads();
+        // stage `steps` rows of Cin bytes, zero padded to NQ dwords
+        uint8_t *tb = reinterpret_cast<uint8_t *>(&tile[0][0]);
+        for (int e = threadIdx.x; e < steps * NQ * 4; e += blockDim.x) {
+            const int r = e / (NQ * 4), c = e % (NQ * 4);
+            uint8_t v = 0;
+            if (c < Cin) {
+                if (ternary_C > 0)
+                    v = c < ternary_C ? (uint8_t)(sbt[(size_t)(t0 + r) * Crow + c] > 0) : (uint8_t)(sbt[(size_t)(t0 + r) * Crow + c - ternary_C] < 0);
+                else
+                    v = sb[(size_t)(t0 + r) * Cin + c];
+            }
+            tb[e] = v;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < steps; ++j) {
+            int in = 0;
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) in = __builtin_amdgcn_sdot4(w[k], tile[j][k], in, false);
+            int i2 = xy_decay(isyn, ds);
+            int v2 = xy_decay(vmem, dm);
+            i2 = xy_sat16(i2 + in + (REC ? w_rec * prev_total : 0));
+            v2 = xy_sat16(v2 + i2);
+            // subtractive reset until below threshold or until the per-step cap: almost always zero or one spike, so the
+            // first one is branch-free and only a wave in which some neuron still sits above threshold takes the division
+            int n = v2 >= th ? 1 : 0;
+            v2 -= n ? th : 0;
+            if (__builtin_expect(__any(v2 >= th), 0)) {  // (cap >= 1 by the API contract)
+                if (v2 >= th) {
+                    int more = xy_div(v2, th);
+                    more = more < max_spikes - 1 ? more : max_spikes - 1;
+                    n += more;
+                    v2 -= more * th;
+                }
+            }
+            isyn = i2;
+            vmem = v2;
+            total += n;
+            if (REC) {
+                // block-wide sum of this step's spikes feeds every neuron at the next step
+                int s = n;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                const int p = j & 1;
+                if ((threadIdx.x & 63) == 0) wsum[p][threadIdx.x >> 6] = s;
+                __syncthreads();
+                int tot = 0;
+                for (int k2 = 0; k2 < nwaves; ++k2) tot += wsum[p][k2];
+                prev_total = tot;
+            }
+        }
+        if (act) chunk_counts[((size_t)b * ((T + XY_TT - 1) / XY_TT) + t0 / XY_TT) * N + g] = total - chunk_total;  // CHUNKS
+        chunk_total = total;                                                                                      // CHUNKS
     }
     if (rate && act) rate[(size_t)b * N + g] = total;
 }
@@ -321,6 +418,114 @@ hipError_t launch_xylo_resident(const void *spikes_in, int ternary_C, int B, int
     else
         XY_LAUNCH(16);
 #undef XY_LAUNCH
+    return hipGetLastError();
+}
+
+// ---- time-resolved DoA: the counts per window of `window` frames every `hop` frames (include/micloc_hip.h "time-resolved DoA, Xylo";
+// DESIGN 4.25) ----------------------------------------------------------------------------------------------------------------------------
+// The LIF walks a trial ONCE, without a reset between windows, and leaves the count of every chunk of 256 frames -- the stream's quantum --
+// in chunk_counts [B][ceil(T / 256)][N]; xylo_window_kernel adds the chunk rows of every window.  Integers: no ordering contract.
+//
+// The chunk-count form of the packed one-shot launch (xylo_lif_pk_kernel<KQ, false>: one workgroup per trial and neuron block): the walk is
+// XpLif's, `done` is the stream's (xp_chunk_done, xylo_rows.h).
+template <int KQ>
+__global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_pk_chunks_kernel(const int8_t *__restrict__ raster, int tc, int T, int Cin,
+                                                                            const long *__restrict__ Wb /*[Npad][4 KQ]*/, int N,
+                                                                            const uint8_t *__restrict__ dash_syn,
+                                                                            const uint8_t *__restrict__ dash_mem,
+                                                                            const short *__restrict__ thr, int max_spikes, int *__restrict__ rate,
+                                                                            int *__restrict__ chunk_counts /*[B][chunk_rows][N]*/, int chunk_rows)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char tile[XP_TT][32 * KQ];
+    extern __shared__ __attribute__((aligned(16))) int cur_dyn[];  // [waves][4][64][4]: only the waves that hold neurons
+    XpLif<KQ, false> lif;
+    lif.init(tile, cur_dyn, blockIdx.x * XP_NEUR, Wb, N, dash_syn, dash_mem, thr, max_spikes);
+    const int b = blockIdx.y;
+    int chunk0 = 0, chunk1 = 0;  // the totals at the start of the open chunk
+    lif.run_range(raster + (size_t)b * T * tc, raster + (size_t)gridDim.y * T * tc, tc, Cin, 0, T,
+                  [&](int t0, int steps) { xp_chunk_done(lif, chunk_counts, chunk_rows, b, t0, steps, T, chunk0, chunk1); });
+    if (rate) {
+        if (lif.act0) rate[(size_t)b * N + lif.n0] = lif.total0;
+        if (lif.act1) rate[(size_t)b * N + lif.n1] = lif.total1;
+    }
+}
+
+// window_counts[b][n][g] = sum of the chunk rows [n hchunks, min(n hchunks + wchunks, chunk_rows)) of trial b.  Workgroup = 256 adjacent
+// neurons of one (trial, window): every row is read with coalesced loads, every output has one writer (no atomics).
+__global__ __launch_bounds__(256) void xylo_window_kernel(const int *__restrict__ chunk_counts, int chunk_rows, int N, int nW, unsigned pairs,
+                                                           int wchunks, int hchunks, int *__restrict__ window_counts)
+{
+    const int g = blockIdx.y * 256 + threadIdx.x;
+    if (g >= N) return;
+    for (unsigned bw = blockIdx.x; bw < pairs; bw += gridDim.x) {  // (trial, window) pairs, B nW of them
+        const int b = (int)(bw / (unsigned)nW), n = (int)(bw - (unsigned)b * (unsigned)nW);
+        const int c0 = n * hchunks;  // (< chunk_rows: window n starts inside the recording)
+        const int c1 = chunk_rows - c0 < wchunks ? chunk_rows : c0 + wchunks;
+        const int *rows = chunk_counts + (size_t)b * chunk_rows * N + g;
+        int total = 0;
+        for (int c = c0; c < c1; ++c) total += rows[(size_t)c * N];
+        window_counts[(size_t)bw * N + g] = total;
+    }
+}
+
+// workgroups over the (trial, window) pairs of the two window kernels: one each, or a fixed number that strides over them (a grid's
+// x extent times the workgroup size stays below 2^32)
+unsigned xylo_window_grid(unsigned pairs) { return pairs < (1u << 20) ? pairs : (1u << 20); }
+
+size_t xylo_windows_chunk_bytes(int B, int T, int N) { return (size_t)B * ((T + XP_CHUNK - 1) / XP_CHUNK) * N * sizeof(int); }
+
+// launch_xylo_resident's routing with the chunk-count forms, then the window sums: two launches whatever B and nW; no host access, no
+// synchronisation (graph-capturable).  window, hop: multiples of XP_CHUNK, hop <= window; nW: window_count(T, window, hop); B nW < 2^31.
+hipError_t launch_xylo_windows(const void *spikes_in, int ternary_C, int B, int T, int Cin, int N, int w_rec, int max_spikes, int window, int hop,
+                               int nW, int32_t *window_counts, int32_t *rate, void *ws, int32_t *chunk_counts, hipStream_t stream)
+{
+    const int nq = (Cin + 3) / 4;
+    if (nq > XY_MAXQ || (w_rec != 0 && N > 1024) || max_spikes < 1) return hipErrorInvalidValue;
+    if (window < 1 || hop < 1 || hop > window || window % XP_CHUNK != 0 || hop % XP_CHUNK != 0 || nW < 1) return hipErrorInvalidValue;
+    const XyloWs w = xylo_ws(ws, Cin, N);
+    const int chunk_rows = (T + XP_CHUNK - 1) / XP_CHUNK;
+    if (w_rec == 0 && ternary_C > 0 && Cin <= 64 && (reinterpret_cast<uintptr_t>(spikes_in) & 15) == 0) {
+        const XpShape sh = xp_shape(N, ternary_C);
+        const dim3 pgrid(sh.nblk, B), pblock(sh.waves * 64);
+        const int8_t *rs = reinterpret_cast<const int8_t *>(spikes_in);
+        if (xp_kq(Cin) == 1)
+            hipLaunchKernelGGL(xylo_lif_pk_chunks_kernel<1>, pgrid, pblock, sh.lds, stream, rs, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                               max_spikes, rate, chunk_counts, chunk_rows);
+        else
+            hipLaunchKernelGGL(xylo_lif_pk_chunks_kernel<2>, pgrid, pblock, sh.lds, stream, rs, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                               max_spikes, rate, chunk_counts, chunk_rows);
+    } else {
+        const uint8_t *sp = reinterpret_cast<const uint8_t *>(spikes_in);
+        // (the workgroups of launch_xylo_resident's general form)
+        const int nblocks = w_rec != 0 ? 1 : (N + 511) / 512;
+        const int per = (N + nblocks - 1) / nblocks;
+        const dim3 block(((per + 63) / 64) * 64), grid(nblocks, B);
+#define XY_LAUNCH(NQ)                                                                                                                 \
+    do {                                                                                                                              \
+        if (w_rec != 0)                                                                                                               \
+            hipLaunchKernelGGL((xylo_lif_chunks_kernel<true, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, w_rec, \
+                               w.dds, w.ddm, w.dth, max_spikes, rate, chunk_counts);                                                  \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((xylo_lif_chunks_kernel<false, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, 0,    \
+                               w.dds, w.ddm, w.dth, max_spikes, rate, chunk_counts);                                                  \
+    } while (0)
+        if (nq <= 2)
+            XY_LAUNCH(2);
+        else if (nq <= 4)
+            XY_LAUNCH(4);
+        else if (nq <= 7)
+            XY_LAUNCH(7);
+        else if (nq <= 8)
+            XY_LAUNCH(8);
+        else
+            XY_LAUNCH(16);
+#undef XY_LAUNCH
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const unsigned pairs = (unsigned)B * (unsigned)nW;
+    hipLaunchKernelGGL(xylo_window_kernel, dim3(xylo_window_grid(pairs), (N + 255) / 256), dim3(256), 0, stream, chunk_counts, chunk_rows, N, nW,
+                       pairs, window / XP_CHUNK, hop / XP_CHUNK, window_counts);
     return hipGetLastError();
 }
 

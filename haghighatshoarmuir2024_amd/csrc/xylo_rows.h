@@ -1,7 +1,7 @@
 // What the packed Xylo LIF kernels share -- the one-shot xylo_lif_pk_kernel of xylo.hip (one workgroup per trial, or persistent
 // workgroups on a ticket queue) and the resumable xylo_lif_stream_kernel of stream_xylo.hip: the shape of a workgroup, the lane's
-// constants and state, the matrix-core `produce`, the two step functions, the staging loop of a 128-step tile and the walk over a range
-// of frames; on the host the layout of xylo_upload's workspace and the launch shape.  Stated once, so that a frame has the same bits
+// constants and state, the matrix-core `produce`, the two step functions, the staging loop of a 128-step tile, the walk over a range
+// of frames and the count of a 256-frame chunk for the windowed read-outs (xp_chunk_done); on the host the layout of xylo_upload's workspace and the launch shape.  Stated once, so that a frame has the same bits
 // whether its trial was walked in one launch, handed from ticket to ticket or cut at launch borders.  PARITY UNPINNED like xylo.hip.
 //
 // ---------------------------------------------------------------------------------------------------------------
@@ -319,6 +319,25 @@ struct XpLif {
         }
     }
 };
+
+// run_range's `done` for the windowed read-outs (the stream's tracking kernel, stream_xylo.hip; the one-shot chunk-count kernel,
+// xylo.hip): a chunk of XP_CHUNK frames ends with the tile [t0, t0 + steps) (the recording's last one may be ragged): its count goes to
+// row t0 / XP_CHUNK of chunk_counts [B][chunk_rows][N].  chunk0 / chunk1: the totals at the start of the open chunk.
+constexpr int XP_CHUNK = 256;
+static_assert(XP_CHUNK == 256 && XP_CHUNK % XP_TT == 0, "the chunk row of a tile is t0 >> 8; a chunk ends with a tile");
+
+template <class Lif>
+__device__ __forceinline__ void xp_chunk_done(const Lif &lif, int *__restrict__ chunk_counts, int chunk_rows, int b, int t0, int steps, int t_hi,
+                                              int &chunk0, int &chunk1)
+{
+    if (chunk_counts && (((t0 + steps) & (XP_CHUNK - 1)) == 0 || t0 + steps == t_hi)) {
+        int *cc = chunk_counts + ((size_t)b * chunk_rows + (t0 >> 8)) * lif.N;
+        if (lif.act0) cc[lif.n0] = lif.total0 - chunk0;
+        if (lif.act1) cc[lif.n1] = lif.total1 - chunk1;
+        chunk0 = lif.total0;
+        chunk1 = lif.total1;
+    }
+}
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 inline int xp_npad(int N) { return ((N + XP_NEUR - 1) / XP_NEUR) * XP_NEUR; }

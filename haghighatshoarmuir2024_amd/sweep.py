@@ -666,18 +666,16 @@ def music_speech_sweep(music, source, snr_db_vec=None, num_sim=100, seed=0, mode
     return res
 
 
-def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None,
-                      test_duration=1000e-3, snr_gain_due_to_bandwidth=None, batch_trials=None, device_delays=None, peak=None, out_dir=None):
-    """The Xylo accuracy sweep of paper_plots/target_xylo_localization.py:540-608 (and its `_unipolar` twin): chirp test
-    signal over the design band (:549-560), per trial `signal_from_template` -> AWGN -> `spike_encoding` -> `xylo_process`
-    -> spike rate -> `find_peak_location(win_size)` with win_size = 2 * ((num_grid // 32) // 2) + 1 (:600-603) -> error.
+def _xylo_win_size(doa_list):
+    """find_peak_location's window of the Xylo sweeps (target_xylo_localization.py:600-603)."""
+    return 2 * ((len(doa_list) // 32) // 2) + 1
 
-    PARITY UNPINNED for the integer-LIF stage (rockpool / XyloSim absent: xylo_snn_localization.py module docstring);
-    everything around it follows the reference's arithmetic.  `demo` is a xylo_snn_localization.Demo with one band.
-    batch_trials: trials per device batch -- default 50 in parity mode (host arrays of 2.7 MB per trial), 1100 in throughput mode: the
-    integer LIF is one serial chain per trial, a launch takes as long for 50 trials as for 1100."""
+
+def _xylo_trials(demo, snr_db_vec, num_sim, test_duration, snr_gain_due_to_bandwidth, device_delays):
+    """The trials of the Xylo sweeps (target_xylo_localization.py:549-560, :575-588): the chirp over the design band, `signal_from_template`
+    at the drawn DoA plus white noise.  Returns dict(geometry, fs, snr_db_vec, time_test, sig_test, snr_trial, frames and mc, the draw /
+    host_trial / device_batch / skip_frames entries of _monte_carlo)."""
     from . import synthesis
-    from .utils import find_peak_location
     from .xylo_snn_localization import signal_from_template
 
     fs = demo.fs
@@ -690,20 +688,42 @@ def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity",
     freq_inst = f_min + (f_max - f_min) * (time_test % period) / period
     sig_test = np.sin(2 * np.pi * np.cumsum(freq_inst) * 1 / fs)
     geometry = demo.beamfs[0].geometry
-    doa_list = demo.doa_list
-    win_size = 2 * ((len(doa_list) // 32) // 2) + 1
     snr_trial = np.repeat(snr_db_vec - 10 * np.log10(snr_gain_due_to_bandwidth), num_sim)
+
+    def host_trial(doa, snr_db):
+        sig = signal_from_template(geometry, (time_test, sig_test, doa))
+        noise_sigma = np.sqrt(np.mean(sig**2) / 10 ** (snr_db / 10))
+        return None, sig + noise_sigma * np.random.randn(*sig.shape)
+
+    mc = dict(draw=_one_doa, host_trial=host_trial, skip_frames=len(time_test),
+              device_batch=lambda doas: (None, synthesis.signal_from_template_batch(geometry, (time_test, sig_test), doas, device=demo.device,
+                                                                                    device_delays=device_delays)))
+    return dict(geometry=geometry, fs=fs, snr_db_vec=snr_db_vec, time_test=time_test, sig_test=sig_test, snr_trial=snr_trial,
+                frames=len(time_test), mc=mc)
+
+
+def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None,
+                      test_duration=1000e-3, snr_gain_due_to_bandwidth=None, batch_trials=None, device_delays=None, peak=None, out_dir=None):
+    """The Xylo accuracy sweep of paper_plots/target_xylo_localization.py:540-608 (and its `_unipolar` twin): chirp test
+    signal over the design band (:549-560), per trial `signal_from_template` -> AWGN -> `spike_encoding` -> `xylo_process`
+    -> spike rate -> `find_peak_location(win_size)` with win_size = 2 * ((num_grid // 32) // 2) + 1 (:600-603) -> error.
+
+    PARITY UNPINNED for the integer-LIF stage (rockpool / XyloSim absent: xylo_snn_localization.py module docstring);
+    everything around it follows the reference's arithmetic.  `demo` is a xylo_snn_localization.Demo with one band.
+    batch_trials: trials per device batch -- default 50 in parity mode (host arrays of 2.7 MB per trial), 1100 in throughput mode: the
+    integer LIF is one serial chain per trial, a launch takes as long for 50 trials as for 1100."""
+    from .utils import find_peak_location
+
+    doa_list = demo.doa_list
+    win_size = _xylo_win_size(doa_list)
     if batch_trials is None:
         batch_trials = 1100 if mode == "throughput" else 50
     if device_delays is None:
         device_delays = mode == "throughput"
     if peak is None:
         peak = "device" if mode == "throughput" else "host"
-
-    def host_trial(doa, snr_db):
-        sig = signal_from_template(geometry, (time_test, sig_test, doa))
-        noise_sigma = np.sqrt(np.mean(sig**2) / 10 ** (snr_db / 10))
-        return None, sig + noise_sigma * np.random.randn(*sig.shape)
+    tr = _xylo_trials(demo, snr_db_vec, num_sim, test_duration, snr_gain_due_to_bandwidth, device_delays)
+    geometry, fs, snr_db_vec, time_test, sig_test, snr_trial = (tr[k] for k in ("geometry", "fs", "snr_db_vec", "time_test", "sig_test", "snr_trial"))
 
     def read_out(x, time_in, doas):
         if peak == "device":  # find_peak_location on the device (exact integer window sums): only indices come back
@@ -724,10 +744,7 @@ def xylo_target_sweep(demo, snr_db_vec=None, num_sim=100, seed=0, mode="parity",
         "xylo", geometry, fs, doa_list, time_test, sig_test, snr_trial, seed, mode, rank, world_size, group, batch_trials, out_dir,
         key=dict(bf_mat=np.asarray(demo.bf_mats[0]), bipolar=bool(demo.bipolar_spikes), peak=peak, device_delays=bool(device_delays),
                  win_size=int(win_size)),
-        fields=(("index", "index", np.int64, (), 0),), draw=_one_doa, host_trial=host_trial, skip_frames=len(time_test),
-        device_batch=lambda doas: (None, synthesis.signal_from_template_batch(geometry, (time_test, sig_test), doas, device=demo.device,
-                                                                              device_delays=device_delays)),
-        read_out=read_out)
+        fields=(("index", "index", np.int64, (), 0),), read_out=read_out, **tr["mc"])
     del extra["exchange"]  # (this sweep's result has never reported its exchange)
     err = doa_error(np.asarray(doa_list)[full["index"]], doa_all)
     shape = (len(snr_db_vec), num_sim)
@@ -902,7 +919,7 @@ def median_window_index(doa_list, index):
 
 def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0,
                           world_size=1, group=None, freq_design=2000.0, test_duration=100e-3, snr_gain_due_to_bandwidth=None,
-                          localizer=None, batch_trials=1100, out_dir=None, store_key=None):
+                          localizer=None, batch_trials=1100, out_dir=None, store_key=None, trials=None):
     """The noisy-target sweep with the time-resolved read-out: the trials of noisy_target_sweep (the same draws in both modes),
     every one localised per window of `window` frames every `hop` frames (default: `window`; utils.window_bounds, hop <= window so
     that every window holds frames; the device wants multiples of plan().window_quantum()).
@@ -912,7 +929,10 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
     (median_window_index) argmax, pmax (the power of the window that gave it), err [num_snr, num_sim] and mae_deg [num_snr]).  With
     window >= T there is one window and argmax, pmax, err, mae_deg are noisy_target_sweep's, bit for bit.
     Sharding, the one exchange and out_dir resume as noisy_target_sweep; the ShardStore key also covers window, hop, the record
-    width nW and the method's parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer)."""
+    width nW and the method's parameters (class, plan key, tau_vec; store_key adds to it, e.g. a tag for an injected localizer).
+    trials: another test signal and synthesis in place of the sine trials (_xylo_trials' dict: snr_db_vec, time_test, sig_test, snr_trial,
+    the `frames` of a trial and `mc`, _monte_carlo's draw / host_trial / device_batch entries); freq_design, test_duration and
+    snr_gain_due_to_bandwidth then belong to whoever made it."""
     from .utils import window_bounds
 
     window = int(window)
@@ -923,9 +943,13 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
         raise ValueError("the windowed sweep needs hop <= window (a window past the recording would hold no frame)")
     doa_list = np.asarray(doa_list, dtype=np.float64)
     fs = beamf.fs
-    snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
+    if trials is None:
+        snr_db_vec, time_test, sig_test, snr_trial = _sine_trials(fs, snr_db_vec, num_sim, freq_design, test_duration, snr_gain_due_to_bandwidth)
+        frames, mc = len(np.arange(time_test.min(), time_test.max(), step=1 / fs)), _one_target(beamf, time_test, sig_test)
+    else:
+        snr_db_vec, time_test, sig_test, snr_trial, frames, mc = (trials[k] for k in ("snr_db_vec", "time_test", "sig_test", "snr_trial", "frames", "mc"))
     total = len(snr_trial)
-    start, _ = window_bounds(len(np.arange(time_test.min(), time_test.max(), step=1 / fs)), window, hop)
+    start, _ = window_bounds(frames, window, hop)
     nW = len(start)
     if localizer is None:
         localizer = device_localizer(beamf, bf_mat, max_batch=batch_trials, window=window, hop=hop)
@@ -934,7 +958,7 @@ def windowed_target_sweep(beamf, bf_mat, doa_list, window, hop=None, snr_db_vec=
         key=dict(record_width=nW, window=window, hop=hop, **_localizer_key(beamf, bf_mat, store_key)),
         rec=[("trial", "<i8"), ("doa", "<f8"), ("index", "<i8", (nW,)), ("pmax", "<f8", (nW,))],
         fields=(("index", "index", np.int64, (nW,), 0), ("value", "pmax", np.float64, (nW,), 0.0)),
-        read_out=lambda x, time_in, doas: localizer(x, time_in), **_one_target(beamf, time_test, sig_test))
+        read_out=lambda x, time_in, doas: localizer(x, time_in), **mc)
     w_index, w_value = full["index"], full["value"]
     w_err = doa_error(doa_list[w_index], doa_all[:, None])
     med = median_window_index(doa_list, w_index)
@@ -1130,12 +1154,63 @@ def xylo_moving_target_sweep(demo, envelope, localizer=None, batch_trials=1100, 
         raise ValueError(f"xylo_moving_target_sweep takes a demo with one band ({len(demo.beamfs)} given)")
     if localizer is None:
         localizer = xylo_track_localizer(demo, envelope, max_batch=batch_trials)
-    spec = demo.spec
-    key = dict(chain="xylo", bipolar=bool(demo.bipolar_spikes), xylo_W_in=np.asarray(spec["W_in"]), xylo_w_rec=int(spec["w_rec"]),
-               xylo_dash_syn=np.asarray(spec["dash_syn"]), xylo_dash_mem=np.asarray(spec["dash_mem"]), xylo_threshold=np.asarray(spec["threshold"]),
-               **(store_key or {}))
+    key = _xylo_store_key(demo, store_key)
     res = moving_target_sweep(demo.beamfs[0], demo.bf_mats[0], demo.doa_list, envelope, localizer=localizer, batch_trials=batch_trials,
                               store_key=key, **kw)
+    res["parity"] = "unpinned (integer LIF)"
+    return res
+
+
+def _xylo_store_key(demo, store_key=None):
+    """ShardStore key entries of a Xylo chain: the quantised specification and `bipolar`, then store_key."""
+    spec = demo.spec
+    return dict(chain="xylo", bipolar=bool(demo.bipolar_spikes), xylo_W_in=np.asarray(spec["W_in"]), xylo_w_rec=int(spec["w_rec"]),
+                xylo_dash_syn=np.asarray(spec["dash_syn"]), xylo_dash_mem=np.asarray(spec["dash_mem"]), xylo_threshold=np.asarray(spec["threshold"]),
+                **(store_key or {}))
+
+
+def xylo_window_localizer(demo, window, hop, win_size, max_batch=1100):
+    """device_localizer(window=)'s place in windowed_target_sweep(localizer=) for the Xylo chain: Demo.windows_batch (encoder, integer LIF
+    and the read-out per window in one walk of the LIF) -> (window_peak [B, nW] int64, the window's rate at that index [B, nW])."""
+
+    def run(sig_batch, time_vec):
+        def one(x):
+            out = demo.windows_batch(x, window, hop, win_size=win_size)
+            a = out["window_peak"].long()
+            return a.cpu().numpy(), out["window_rate"].gather(2, a.unsqueeze(2)).squeeze(2).cpu().numpy()
+
+        return _in_batches(sig_batch, max_batch, one)
+
+    return run
+
+
+def xylo_windowed_target_sweep(demo, window, hop=None, win_size=None, localizer=None, snr_db_vec=None, num_sim=100, mode="parity",
+                               test_duration=1000e-3, snr_gain_due_to_bandwidth=None, batch_trials=None, device_delays=None, store_key=None, **kw):
+    """windowed_target_sweep for the Xylo chain: the trials of xylo_target_sweep (the chirp over the design band, signal_from_template,
+    the same draws in both modes), every one localised per window of `window` frames every `hop` frames (multiples of 256, hop <= window)
+    by find_peak_location(win_size) on the window's spike counts -- how the accuracy of the Xylo read-out depends on the pack length, the
+    parameter the reference's live loop (`recording_duration`) and its snn_localization_benchmark.py (`frame_duration`) vary.  The
+    network runs each trial ONCE, without a reset between windows (Demo.windows_batch).  win_size defaults to xylo_target_sweep's; the
+    `window_pmax` of a window is its rate at the peak index.  With window >= T, `argmax` is xylo_target_sweep's `index`.  `demo` is a
+    xylo_snn_localization.Demo with one band; the store key also covers the quantised specification, `bipolar` and win_size.
+    batch_trials, device_delays: xylo_target_sweep's defaults.  PARITY UNPINNED for the integer-LIF stage, as xylo_target_sweep.
+    Other keywords (seed, rank, world_size, group, out_dir) as windowed_target_sweep."""
+    if len(demo.beamfs) != 1:
+        raise ValueError(f"xylo_windowed_target_sweep takes a demo with one band ({len(demo.beamfs)} given)")
+    window = int(window)
+    hop = window if hop is None else int(hop)
+    win_size = _xylo_win_size(demo.doa_list) if win_size is None else int(win_size)
+    if batch_trials is None:
+        batch_trials = 1100 if mode == "throughput" else 50
+    if device_delays is None:
+        device_delays = mode == "throughput"
+    if localizer is None:
+        localizer = xylo_window_localizer(demo, window, hop, win_size, max_batch=batch_trials)
+    trials = _xylo_trials(demo, snr_db_vec, num_sim, test_duration, snr_gain_due_to_bandwidth, device_delays)
+    key = _xylo_store_key(demo, dict(win_size=win_size, device_delays=bool(device_delays), **(store_key or {})))
+    res = windowed_target_sweep(demo.beamfs[0], demo.bf_mats[0], demo.doa_list, window, hop=hop, num_sim=num_sim, mode=mode, localizer=localizer,
+                                batch_trials=batch_trials, store_key=key, trials=trials, **kw)
+    res["win_size"] = win_size
     res["parity"] = "unpinned (integer LIF)"
     return res
 
@@ -1186,10 +1261,10 @@ def main(argv=None):
                     default="noisy")
     ap.add_argument("--bands", type=parse_bands, default=parse_bands("1000:1600,1600:2400,2400:3400"),
                     help="wideband-speech: the bands as low:high pairs in Hz, comma separated (at most 16)")
-    ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum)")
+    ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum; --method xylo: of 256)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
     ap.add_argument("--method", choices=["snn", "beamformer", "music", "xylo"], default="snn",
-                    help="multi-noisy, wideband-speech (snn | beamformer) and moving-noisy (snn | beamformer | xylo): the localizer")
+                    help="multi-noisy, wideband-speech (snn | beamformer), moving-noisy and windowed-noisy (snn | beamformer | xylo): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
@@ -1219,9 +1294,17 @@ def main(argv=None):
     music_grid = args.sweep == "music-noisy" or (args.sweep == "multi-noisy" and args.method == "music")
     grid = args.grid if args.grid is not None else (8 * 7 + 1 if music_grid else 64 * 7 + 1)
     doa_list = np.linspace(-np.pi, np.pi, grid)
-    if args.method == "xylo" and args.sweep != "moving-noisy":
-        ap.error("--method xylo goes with --sweep moving-noisy (the Xylo accuracy sweep is --sweep xylo)")
-    if args.sweep == "moving-noisy" and args.method == "xylo":
+    if args.method == "xylo" and args.sweep not in ("moving-noisy", "windowed-noisy"):
+        ap.error("--method xylo goes with --sweep moving-noisy or windowed-noisy (the Xylo accuracy sweep is --sweep xylo)")
+    if args.sweep == "windowed-noisy" and args.method == "xylo":
+        from .xylo_snn_localization import Demo
+
+        if args.window_frames is None:
+            ap.error("--sweep windowed-noisy needs --window-frames")
+        demo = Demo(geometry=geometry, freq_bands=[freq_range], doa_list=doa_list, recording_duration=0.25, bipolar_spikes=True, fs=fs)
+        res = xylo_windowed_target_sweep(demo, args.window_frames, hop=args.hop_frames, num_sim=args.num_sim or 100, seed=args.seed, mode=args.mode,
+                                         rank=rank, world_size=world)
+    elif args.sweep == "moving-noisy" and args.method == "xylo":
         from .utils import Envelope
         from .xylo_snn_localization import Demo
 

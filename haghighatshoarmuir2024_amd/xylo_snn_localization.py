@@ -162,6 +162,60 @@ class XyloNetwork:
                                                          runtime._stream(self.device)), "xylo_lif_resident")
         return out, rate
 
+    # ---- time-resolved DoA (micloc_xylo_lif_windows_i16; PARITY UNPINNED like run) -------------------------------------------------
+    def window_starts(self, T, window, hop=None):
+        """(window, hop, window_start [nW]) of a recording of T frames under the window rule: window and hop (default: window) positive
+        multiples of 256 frames (micloc_xylo_window_quantum), hop <= window, utils.window_bounds' windows.  Raises ValueError otherwise."""
+        from .utils import window_bounds
+
+        window = int(window)
+        hop = window if hop is None else int(hop)
+        q = int(self.lib.micloc_xylo_window_quantum())
+        if window < 1 or hop < 1 or window % q != 0 or hop % q != 0:
+            raise ValueError(f"window ({window}) and hop ({hop}) must be positive multiples of {q} frames")
+        if hop > window:
+            raise ValueError(f"hop ({hop}) must not exceed the window ({window}): a window past the recording would hold no frame")
+        nW = int(self.lib.micloc_window_count(int(T), window, hop, q))
+        if nW < 1:
+            raise ValueError(f"micloc window_count: {T} frames in windows of {window} every {hop} do not fit the rule")
+        start, _ = window_bounds(int(T), window, hop)
+        assert len(start) == nW
+        return window, hop, np.asarray(start, dtype=np.int64)
+
+    def run_windows(self, spikes, window, hop=None, ternary=False, max_spikes=31):
+        """The spike counts per time window of `window` frames every `hop` frames (default: window; multiples of 256, hop <= window) for
+        every network run() serves: spikes as in run().  The network is not reset between windows -- a trial is one continuous run --
+        and nothing of size T x N is stored (the scratch is one count per neuron and 256 frames).  Returns a dict of device tensors:
+        window_counts int32 [B, nW, N] (window n: the frames [n hop, min(n hop + window, T)), utils.window_bounds), counts int32 [B, N]
+        (run()'s counts, from the same walk) and window_start [nW] (host).  Equals, bit for bit, the window counts of the stream
+        (streaming.XyloStreamingLocalizer(window=, hop=)) where the stream serves the network.  Raises ValueError before any device work
+        for what the entry refuses.  No host access, no synchronisation."""
+        import torch
+
+        B, T, C = spikes.shape
+        if (2 * C if ternary else C) != self.Cin:
+            raise ValueError(f"number of input spike channels {2 * C if ternary else C} should match the weight matrix {self.Cin}")
+        if spikes.dtype != (torch.int8 if ternary else torch.uint8) or not spikes.is_contiguous():
+            raise ValueError("spikes must be a contiguous int8 (ternary) / uint8 (events) device tensor")
+        B, T = int(B), int(T)
+        window, hop, start = self.window_starts(T, window, hop)
+        nW = len(start)
+        if B * nW > 0x7FFFFFFF:
+            raise ValueError(f"{B} trials x {nW} windows exceed the 2^31 - 1 rows of one call")
+        if int(max_spikes) < 1:
+            raise ValueError("max_spikes must be at least 1")
+        nws = int(self.lib.micloc_xylo_windows_workspace_bytes(B, T, self.N))
+        if nws == 0:
+            raise ValueError(f"micloc xylo_windows_workspace_bytes: {B} trials x {T} frames x {self.N} neurons do not fit the rule")
+        ws = torch.empty(nws, dtype=torch.uint8, device=self.device)  # one per call: calls of several streams run side by side
+        out = dict(window_counts=torch.empty((B, nW, self.N), dtype=torch.int32, device=self.device),
+                   counts=torch.empty((B, self.N), dtype=torch.int32, device=self.device), window_start=start)
+        _lib.check(self.lib.micloc_xylo_lif_windows_i16(runtime._ptr(spikes), C if ternary else 0, B, T, self.Cin, self.N, self.w_rec, int(max_spikes),
+                                                        window, hop, runtime._ptr(out["window_counts"]), runtime._ptr(out["counts"]),
+                                                        runtime._ptr(self.ws), self.nbytes, runtime._ptr(ws), nws, runtime._stream(self.device)),
+                   "xylo_lif_windows")
+        return out
+
     # ---- moving-target tracking (micloc_xylo_lif_track_i16; PARITY UNPINNED like run) ----------------------------------------------
     def track_is_fused(self, ternary, max_spikes=31):
         """True when the fused kernel serves this network and input (w_rec == 0, the ternary raster, at most 64 input channels)."""
@@ -427,15 +481,53 @@ class Demo:
         per_band = self._band_rasters(sig_batch)
         return per_band[0] if len(per_band) == 1 else self._pack(per_band, 0)
 
-    def counts_batch(self, sig_batch):
+    def counts_batch(self, sig_batch, queued=True):
         """[B, T, M] noisy array signals -> output spike counts per hidden neuron, int32 device tensor [B, F * G]; nothing of
-        size T x N is materialised and only micloc kernels run."""
+        size T x N is materialised and only micloc kernels run.  queued: XyloNetwork.run's (False: one workgroup per trial)."""
         import torch
 
         raster = self.raster_device(sig_batch)
         if not self.bipolar_spikes:  # unipolar encoder: the raster holds 0 / +1 only and IS the event tensor (same bytes, read as uint8)
-            return self.network().run(raster.view(dtype=torch.uint8), ternary=False)[1]
-        return self.network().run(raster, ternary=True)[1]
+            return self.network().run(raster.view(dtype=torch.uint8), ternary=False, queued=queued)[1]
+        return self.network().run(raster, ternary=True, queued=queued)[1]
+
+    def windows_batch(self, sig_batch, window, hop=None, win_size=None):
+        """[B, T, M] array signals -> the read-out of counts_batch / rate_batch / peak_batch per time window of `window` frames every
+        `hop` frames (default: window; multiples of 256, hop <= window; utils.window_bounds): encoder -> integer LIF with the windowed
+        read-out (XyloNetwork.run_windows: one continuous run per trial, no reset between windows), one or several bands, bipolar or
+        unipolar.  Returns a dict of device tensors: window_counts int32 [B, nW, F G], window_rate float64 [B, nW, G] (rate_batch's
+        expression over the frames the window holds), window_start [nW] (host), counts int32 [B, F G] and rate float64 [B, G] of the
+        whole recording (counts_batch, rate_batch) and, with win_size, window_peak int32 [B, nW] and peak int32 [B] (peak_batch).
+        Nothing of size T x N is allocated.  Equals, bit for bit, what streaming_localizer(window=, hop=) has emitted after finish()
+        where the stream serves the demo.  PARITY UNPINNED like xylo_process."""
+        import torch
+
+        G = len(self.doa_list)
+        if win_size is not None and (int(win_size) < 1 or int(win_size) % 2 != 1 or int(win_size) > G // 2):
+            raise ValueError(f"win_size ({win_size}) must be odd, at least 1 and at most G / 2 = {G // 2}")
+        B, T = int(sig_batch.shape[0]), int(sig_batch.shape[1])
+        net = self.network()
+        net.window_starts(T, window, hop)  # (the refusals, in front of the encoder)
+        raster = self.raster_device(sig_batch)
+        if not self.bipolar_spikes:  # (the raster holds 0 / +1 only and IS the event tensor: counts_batch)
+            out = net.run_windows(raster.view(dtype=torch.uint8), window, hop, ternary=False)
+        else:
+            out = net.run_windows(raster, window, hop, ternary=True)
+        window, hop = int(window), int(window if hop is None else hop)
+        nW, F = len(out["window_start"]), net.N // G
+        lib, dev = _lib.load(), out["counts"].device
+        out["window_rate"] = torch.empty((B, nW, G), dtype=torch.float64, device=dev)
+        out["rate"] = torch.empty((B, G), dtype=torch.float64, device=dev)
+        if win_size is not None:
+            out["window_peak"] = torch.empty((B, nW), dtype=torch.int32, device=dev)
+        _lib.check(lib.micloc_xylo_window_readout(runtime._ptr(out["window_counts"]), B, T, window, hop, G, F, float(self.fs),
+                                                  int(win_size) if win_size is not None else 1, runtime._ptr(out["window_rate"]),
+                                                  runtime._ptr(out.get("window_peak")), runtime._stream(dev)), "xylo_window_readout")
+        _lib.check(lib.micloc_rate_from_counts_f64(runtime._ptr(out["counts"]), B, G, F, T, float(self.fs), runtime._ptr(out["rate"]),
+                                                   runtime._stream(dev)), "rate_from_counts")
+        if win_size is not None:
+            out["peak"] = runtime.peak_location(out["counts"], G, int(win_size))
+        return out
 
     def track_batch(self, sig_batch, envelope, want_rate=False, budget_bytes=1 << 30):
         """[B, T, M] array signals -> the DoA index per time step, `np.argmax(envelope.evolve(xylo_process(spike_encoding(sig))), axis=1)`

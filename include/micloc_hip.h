@@ -676,6 +676,39 @@ int micloc_xylo_lif_track_i16(const void *spikes_in, int ternary_channels, int B
                               double a_rise, double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last,
                               int32_t *rate, void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- time-resolved DoA, Xylo: counts, rate and peak per window of a batch ------------------------ */
+/* The windows of "streaming, Xylo" below (micloc_stream_xylo_tile_windows_i16 / micloc_stream_xylo_readout) for recordings that are
+ * complete: one call for a batch, for EVERY network micloc_xylo_lif_resident_i16 serves (unipolar input, uint8 event counts, a recurrent
+ * weight with N <= 1024).  PARITY UNPINNED like every Xylo entry: the LIF equals oracle_xylo_lif bit for bit, the oracle is not checked
+ * against XyloSim.  The rule:
+ *   - the quantum is 256 frames (micloc_xylo_window_quantum); window and hop are positive multiples of it, hop <= window;
+ *     nW = micloc_window_count(T, window, hop, 256); window n covers the frames [n hop, min(n hop + window, T));
+ *   - window_counts[b][n][j] = the sum over the window's frames of the spike count of neuron j, the value micloc_xylo_lif_resident_i16
+ *     stores in spikes_out -- exact integers.  The network is NOT reset between windows: a trial is one continuous run.  With
+ *     hop == window the windows of a trial add up to counts[b]; a single window >= T IS counts[b];
+ *   - counts[b][j] (may be NULL) = micloc_xylo_lif_resident_i16's rate, from the same walk: the LIF runs once;
+ *   - window_rate[b][n][g] = micloc_rate_from_counts_f64's expression and band order on the row window_counts[b][n] with the window's
+ *     own frame count in place of T; window_peak[b][n] = what micloc_peak_location_i32 returns for that row and win_size.
+ * All of them equal, bit for bit, what the stream has emitted after the last tile wherever the stream serves the network.
+ * micloc_xylo_lif_windows_i16: arguments as micloc_xylo_lif_resident_i16 (net_ws: micloc_xylo_upload's); ws
+ * (micloc_xylo_windows_workspace_bytes, 256-B aligned) holds the counts per chunk of 256 frames, 4 B ceil(T / 256) N bytes -- nothing of
+ * size T x N is stored.  The routing is micloc_xylo_lif_resident_i16's: w_rec == 0, the ternary raster, Cin <= 64 and a 16-byte aligned
+ * raster run the chunk-count form of the packed kernel (one workgroup per trial and 512 neurons; the ticket queue of
+ * micloc_xylo_lif_sweep_i16 has no such form), everything else the chunk-count form of the general kernel; then one launch adds the chunk
+ * rows of every window.  micloc_xylo_window_readout: one launch; either output may be NULL, not both.
+ * Status codes, all before any launch: MICLOC_ERR_SHAPE for a window or hop off the quantum, hop > window, B nW > 2^31 - 1 and the
+ * shapes micloc_xylo_lif_resident_i16 refuses; MICLOC_ERR_INVALID for NULL or out-of-range arguments, a win_size
+ * micloc_peak_location_i32 refuses (with window_peak) and both read-out outputs NULL; MICLOC_ERR_WORKSPACE for a missing, misaligned or
+ * short net_ws or ws.  Two launches and one, whatever B and nW; no atomics, no host synchronisation, no allocation: re-entrant per
+ * stream with workspaces of their own, and graph-capturable. */
+int micloc_xylo_window_quantum(void);                            /* 256 */
+size_t micloc_xylo_windows_workspace_bytes(int B, int T, int N); /* the chunk rows; 0 on bad arguments */
+int micloc_xylo_lif_windows_i16(const void *spikes_in, int ternary_channels, int B, int T, int Cin, int N, int w_rec, int max_spikes,
+                                int window, int hop, int32_t *window_counts /*[B][nW][N]*/, int32_t *counts /*[B][N], may be NULL*/,
+                                void *net_ws, size_t net_ws_bytes, void *ws, size_t ws_bytes, void *stream);
+int micloc_xylo_window_readout(const int32_t *window_counts, int B, int T, int window, int hop, int G, int bands, double fs, int win_size,
+                               double *window_rate /*[B][nW][G], may be NULL*/, int32_t *window_peak /*[B][nW], may be NULL*/, void *stream);
+
 /* ---- streaming, tracking: a DoA per frame while the recording arrives ---------------------------- */
 /* The tracking rule above for a recording that arrives tile by tile ("streaming" and "streaming, complex Beamformer"): every frame is
  * EMITTED -- its index and its peak envelope written -- by the localize call of the tile that makes it final, and the emitted rows equal,
