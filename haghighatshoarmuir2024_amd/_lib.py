@@ -192,6 +192,20 @@ SYMBOLS = {
                                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "micloc_beamformer_bands_bandpass_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                                      c_void_p]),
+    "micloc_snn_bands_track_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
+    "micloc_beamformer_bands_track_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
+    "micloc_snn_bands_track_is_fused": (c_int, [ctypes.POINTER(c_void_p), c_int]),
+    "micloc_beamformer_bands_track_is_fused": (c_int, [ctypes.POINTER(c_void_p), c_int]),
+    "micloc_lif_beamform_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_beamform_c128_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
+                                                     ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "micloc_snn_pipeline_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int,
+                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_size_t, c_void_p]),
+    "micloc_beamformer_pipeline_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int,
+                                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p, c_size_t, c_void_p]),
     "micloc_filterbank_stream_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "micloc_filterbank_stream_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
     "micloc_filterbank_tile_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),

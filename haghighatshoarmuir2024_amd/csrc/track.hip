@@ -22,8 +22,10 @@
 // others' staging and matrix phases.
 // The four stages are written once, in track_rows.h (track_ws_walk / track_wsc_walk over track_chain_reduce), for these kernels and for
 // the streaming ones of stream_track.hip, with the channel-count table and the pairs layout of the launchers.  Here: the kernels as a walk
-// from frame 0 with a zero chain state, the store of a pair, the last envelope row; the combine; the read-out of the two-step route.
+// from frame 0 with a zero chain state, the store of a pair, the last envelope row; the combine; the walks and kernels over F bands
+// (wideband tracking: one magnitude tile summed over the bands); the read-out of the two-step route.
 #include "track_rows.h"
+#include "track_bands.h"
 
 namespace micloc {
 
@@ -135,6 +137,177 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
     if (e != hipSuccess || ncg == 1) return e;
     const size_t rows = (size_t)B * T;
     hipLaunchKernelGGL(track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, ncg, index, peak);
+    return hipGetLastError();
+}
+
+// ---- wideband: F bands, one magnitude tile (the rule: include/micloc_hip.h, "wideband moving-target tracking") ----
+// The launch shape above: a workgroup owns 64 DoA columns of one trial and walks it in 64-frame chunks.  Per chunk it loops over the
+// bands in ascending order; band f runs the per-chunk step of the single-plan walks with ITS operands -- rows, neuron table, bf_mat --
+// in that step's order, so y_f[t][g] has the bits of band f's own chain.  Band 0 stores |y_0| into the tile, every later band adds |y_f| with
+// one rounded add: m = ((a_0 + a_1) + a_2) + ...  Behind the last band track_chain_reduce runs on the summed tile, unchanged.  The
+// bf_mat fragments of F bands do not fit in registers: they are loaded again per band and chunk (16 KB per band and column group at
+// most, which stays in L2) in front of the barrier, so the loads are in flight while the rows are staged.  No workgroup waits for
+// another; nothing of size T x G exists.
+struct TrackBandPut {  // a thread meets the same elements of Y in every band: the bands need no barrier for Y among themselves
+    double *Y;
+    bool first;
+    __device__ __forceinline__ void operator()(int row, int col, double a) const
+    {
+        double *y = Y + row * TRK_LD + col;
+        *y = first ? a : __dadd_rn(*y, a);
+    }
+};
+
+// SNN bands: trial b of every band's raster [B][T][C], the whole recording from frame 0; the LDS regions are sized for NKmax
+template <class Emit>
+__device__ __forceinline__ void track_bands_ws_walk(unsigned char *smem, const TrackBandsArgs &a, int F, int NKmax, int b, int C, int T, int G,
+                                                    int cg, double a_rise, double i_rise, double a_fall, double &state, const Emit &emit)
+{
+    const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l = tid & 63;
+    const int lc = l & 15;
+    const int q = l >> 4;
+    double *Y = reinterpret_cast<double *>(smem);  // [TRK_CH][TRK_LD]
+    double *ntab = Y + TRK_CH * TRK_LD;
+    double *S = ntab + 4 * NKmax + 16;
+
+    for (int cs = 0; cs < T; cs += TRK_CH) {
+        for (int f = 0; f < F; ++f) {
+            const int NK = a.NK[f];
+            if (f > 0) __syncthreads();  // every wave is done with the previous band's table and rows
+            double Wf[4][4];
+            track_ws_weights(Wf, a.Wp[f], a.GT[f], cg, lc, q);
+            track_ws_table(ntab, a.tab[f], NK, tid);
+            track_ws_stage(S, static_cast<const int8_t *>(a.src[f]) + (size_t)b * T * C, C, cs, T, NK, tid);
+            __syncthreads();  // (f == 0 also: the previous chunk's row reduction is done with Y)
+            track_ws_tile(S, ntab, NK, cs, T, wv, lc, q, Wf, TrackBandPut{Y, f == 0});
+        }
+        __syncthreads();
+        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
+        track_chain_reduce(Y, wv, l, tid, cs, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, emit);
+    }
+}
+
+// complex bands: trial b of every band's planar rows [B][C][Ts]
+template <int KM, int KV, class Emit>
+__device__ __forceinline__ void track_bands_wsc_walk(unsigned char *smem, const TrackBandsArgs &a, int F, int b, int C, int Ts, int T, int G, int cg,
+                                                     double a_rise, double i_rise, double a_fall, double &state, const Emit &emit)
+{
+    constexpr int KF = KM + (KV > 0 ? 1 : 0);
+    const int tid = threadIdx.x;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l = tid & 63;
+    const int lc = l & 15;
+    const int q = l >> 4;
+    double *Y = reinterpret_cast<double *>(smem);
+    double *tail = Y + TRK_CH * TRK_LD + wv * 64;
+
+    for (int cs = 0; cs < T; cs += TRK_CH) {
+        for (int f = 0; f < F; ++f) {
+            double V[KF];
+            TrackCW<KM, KV> w;
+            track_wsc_weights<KM, KV>(w, a.Wp[f], a.GT[f], cg, lc, q);
+            if (f > 0) __syncthreads();  // the reads of the previous band's tail fragment are done
+            track_wsc_frags<KM, KV>(V, tail, static_cast<const double *>(a.src[f]) + (size_t)b * C * Ts, C, Ts, cs, T, wv, l);
+            __syncthreads();  // (f == 0 also: the previous chunk's row reduction is done with Y)
+            track_wsc_tile<KM, KV>(V, tail, w, wv, lc, q, TrackBandPut{Y, f == 0});
+        }
+        __syncthreads();
+        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
+        track_chain_reduce(Y, wv, l, tid, cs, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, emit);
+    }
+}
+
+__global__ __launch_bounds__(TRK_THREADS) void track_bands_ws_kernel(TrackBandsArgs a, int F, int NKmax, int C, int T, int G, double a_rise,
+                                                                     double i_rise, double a_fall, double *__restrict__ pval,
+                                                                     int32_t *__restrict__ pidx, double *__restrict__ env_last)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
+    const size_t row0 = (size_t)b * T;
+    double state = 0.0;
+    track_bands_ws_walk(smem, a, F, NKmax, b, C, T, G, cg, a_rise, i_rise, a_fall, state, [&](int cs, int row, double best, int bi) {
+        track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+    });
+    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
+}
+
+template <int KM, int KV>
+__global__ __launch_bounds__(TRK_THREADS) void track_bands_wsc_kernel(TrackBandsArgs a, int F, int C, int T, int Ts, int G, double a_rise,
+                                                                      double i_rise, double a_fall, double *__restrict__ pval,
+                                                                      int32_t *__restrict__ pidx, double *__restrict__ env_last)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
+    const size_t row0 = (size_t)b * T;
+    double state = 0.0;
+    track_bands_wsc_walk<KM, KV>(smem, a, F, b, C, Ts, T, G, cg, a_rise, i_rise, a_fall, state, [&](int cs, int row, double best, int bi) {
+        track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+    });
+    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
+}
+
+bool track_bands_fused_eligible(const BeamformW *const *W, const NeuronTab *const *nt, int F, int is_complex)
+{
+    int NKmax = 0;
+    for (int f = 0; f < F; ++f) {
+        if (!track_fused_eligible(*W[f], *nt[f], is_complex)) return false;
+        if (W[f]->GT != W[0]->GT || W[f]->C != W[0]->C) return false;  // (one grid and one channel count: one launch shape)
+        if (!is_complex && nt[f]->NK > NKmax) NKmax = nt[f]->NK;
+    }
+    return track_lds_bytes(is_complex != 0, NKmax) <= 160 * 1024;
+}
+
+hipError_t launch_track_bands_fused(const TrackBandsArgs &a, int F, int NKmax, int is_complex, int C, int B, int T, int Ts, int G, double a_rise,
+                                    double i_rise, double a_fall, int32_t *index, double *peak, double *env_last, void *pairs,
+                                    hipStream_t stream)
+{
+    const int ncg = track_col_groups(G);
+    double *pval = peak;  // one column group: the kernel writes the result itself
+    int32_t *pidx = index;
+    if (ncg > 1) track_pairs_split(pairs, (size_t)B * T * ncg, pval, pidx);
+    const size_t lds = track_lds_bytes(is_complex != 0, NKmax);
+    dim3 grid(ncg, B), block(TRK_THREADS);
+    if (!is_complex) {
+        auto k = &track_bands_ws_kernel;
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k, grid, block, lds, stream, a, F, NKmax, C, T, G, a_rise, i_rise, a_fall, pval, pidx, env_last);
+    } else {
+        const bool served = track_wsc_dispatch(C, [&](auto k) {
+            hipLaunchKernelGGL((track_bands_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, a, F, C, T, Ts, G, a_rise, i_rise,
+                               a_fall, pval, pidx, env_last);
+        });
+        if (!served) return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || ncg == 1) return e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, ncg, index, peak);
+    return hipGetLastError();
+}
+
+// the band sum of the two-step route, element by element: the magnitude expressions of the tiles above and their one rounded add
+template <bool CPX>
+__global__ __launch_bounds__(256) void track_bands_magnitude_kernel(const double *__restrict__ y, size_t n, int first, double *__restrict__ m)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double v = CPX ? track_magnitude(y[2 * i], y[2 * i + 1]) : fabs(y[i]);
+    m[i] = first ? v : __dadd_rn(m[i], v);
+}
+
+hipError_t launch_track_bands_magnitude(const double *y, int is_complex, size_t n, int first, double *m, hipStream_t stream)
+{
+    const size_t nblk = (n + 255) / 256;
+    if (nblk > 0x7fffffffull) return hipErrorInvalidValue;
+    if (is_complex)
+        hipLaunchKernelGGL(track_bands_magnitude_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, stream, y, n, first, m);
+    else
+        hipLaunchKernelGGL(track_bands_magnitude_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, stream, y, n, first, m);
     return hipGetLastError();
 }
 

@@ -259,6 +259,148 @@ __device__ __forceinline__ void track_wsc_walk(unsigned char *smem, const double
     }
 }
 
+// ---- the per-chunk step "stage -> membrane -> |y| fragments" in pieces, for the walks over F bands of track.hip (wideband tracking) ----
+// The text of track_ws_walk / track_wsc_walk above, cut where a band walk needs to get in -- between the bands' staging, and where the
+// magnitude is put -- with the magnitude handed to `put`.  (The walks above were not rebuilt from these pieces: doing so changed the
+// instruction text of track_ws_kernel, track_wsc_kernel and the stream kernels -- schedule and register numbers, DESIGN 4.26 -- so
+// they stay as they are.  A change to a stage belongs in both.)
+// |y| of a complex value: the expression of the tiles, for the band sum of the two-step route as well
+__device__ __forceinline__ double track_magnitude(double re, double im) { return hypot(re, im); }
+
+// the neuron table of a plan into LDS
+__device__ __forceinline__ void track_ws_table(double *ntab, const double *__restrict__ ntab_g, int NK, int tid)
+{
+    const int ntab_len = 4 * NK + 16;
+    for (int e = tid; e < ntab_len; e += TRK_THREADS) ntab[e] = ntab_g[e];
+}
+
+// bf_mat fragments of the workgroup's four DoA tiles (a tile beyond the grid multiplies a clamped one; its columns are never read)
+__device__ __forceinline__ void track_ws_weights(double (&Wf)[4][4], const double *__restrict__ Wp, int GT, int cg, int lc, int q)
+{
+    const int Gp = 16 * GT;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int gt = 4 * cg + j;
+        const double *wp = Wp + 16 * (gt < GT ? gt : GT - 1) + lc;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) Wf[j][k] = wp[(size_t)(4 * k + q) * Gp];
+    }
+}
+
+// rows tau0 .. tau0 + R - 1 of the raster, tau0 = cs + 16 - 4 NK, as fp64 [R][16]; rows outside [0, T) and the channel padding are zero
+__device__ __forceinline__ void track_ws_stage(double *S, const int8_t *__restrict__ sb, int C, int cs, int T, int NK, int tid)
+{
+    const int R = TRK_CH + 4 * NK - 16;
+    const int tau0 = cs + 16 - 4 * NK;
+    const int c = tid & 15;
+    for (int rho = tid >> 4; rho < R; rho += TRK_THREADS / 16) {
+        const int tau = tau0 + rho;
+        const bool ok = c < C && tau >= 0 && tau < T;
+        S[rho * 16 + c] = ok ? (double)sb[(size_t)tau * C + c] : 0.0;
+    }
+}
+
+// stages 1 and 2 of this wave's 16-frame tile of the chunk at cs: put(row of the chunk, column of the workgroup, |y|)
+template <class Put>
+__device__ __forceinline__ void track_ws_tile(const double *S, const double *ntab, int NK, int cs, int T, int wv, int lc, int q,
+                                              const double (&Wf)[4][4], const Put &put)
+{
+    // ---- membrane fragments of this wave's tile (beamform_ws_kernel, stage 1) ----
+    const int tb0 = cs + wv * 16;
+    double4_t vacc = double4_t{0.0, 0.0, 0.0, 0.0};
+    if (tb0 < T) {  // (wave-uniform)
+        const double *sp = S + (size_t)(wv * 16 + q) * 16 + lc;
+        const double *np_ = ntab + (lc - q + 4 * NK - 1);
+        for (int ks = 0; ks < NK; ++ks) vacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sp[ks * 64], np_[-4 * ks], vacc, 0, 0, 0);
+        if (tb0 + 16 > T) {
+            const bool tvalid = (tb0 + lc) < T;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vacc[r] = tvalid ? vacc[r] : 0.0;
+        }
+    }
+    // ---- y of the tile against the four DoA tiles, |y| to the caller ----
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double4_t acc = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vacc[k], Wf[j][k], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) put(wv * 16 + q + 4 * r, 16 * j + lc, fabs(acc[r]));
+    }
+}
+
+// the same step, complex
+template <int KM, int KV>
+struct TrackCW {
+    static constexpr int KVD = KV > 0 ? KV : 1;
+    double Wf[4][2][KM], Wv[4][2][KVD];
+};
+
+template <int KM, int KV>
+__device__ __forceinline__ void track_wsc_weights(TrackCW<KM, KV> &w, const double *__restrict__ Wp, int GT, int cg, int lc, int q)
+{
+    const int Gp = 16 * GT, GTc = GT >> 1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int ct = 4 * cg + j;
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            const double *wp = Wp + 16 * ((ct < GTc ? ct : GTc - 1) + part * GTc) + lc;
+#pragma unroll
+            for (int k = 0; k < KM; ++k) w.Wf[j][part][k] = wp[(size_t)(4 * k + q) * Gp];
+#pragma unroll
+            for (int i = 0; i < KV; ++i) w.Wv[j][part][i] = wp[(size_t)(4 * KM + i) * Gp];
+        }
+    }
+}
+
+// this wave's tile as A-fragments (beamform_wsc_kernel, stage 1): lane l of k-step k = channel 4k + (l >> 4), frame l & 15; the fragment
+// of the KV tail channels goes to the wave's `tail`, which track_wsc_tile reads behind a barrier
+template <int KM, int KV>
+__device__ __forceinline__ void track_wsc_frags(double (&V)[KM + (KV > 0 ? 1 : 0)], double *tail, const double *__restrict__ pb, int C, int stride,
+                                                int cs, int T, int wv, int l)
+{
+    constexpr int KF = KM + (KV > 0 ? 1 : 0);
+    const int lc = l & 15, q = l >> 4;
+    const int t = cs + wv * 16 + lc;
+#pragma unroll
+    for (int k = 0; k < KF; ++k) {
+        const int c = 4 * k + q;
+        const double v = pb[(size_t)(c < C ? c : C - 1) * stride + (t < T ? t : T - 1)];  // (clamped: unconditional loads)
+        V[k] = (t < T && c < C) ? v : 0.0;
+    }
+    if (KV > 0) tail[l] = V[KF - 1];
+}
+
+// stage 2 of the tile: put(row of the chunk, column of the workgroup, |y| = hypot(re, im))
+template <int KM, int KV, class Put>
+__device__ __forceinline__ void track_wsc_tile(const double (&V)[KM + (KV > 0 ? 1 : 0)], const double *tail, const TrackCW<KM, KV> &w, int wv, int lc,
+                                               int q, const Put &put)
+{
+    constexpr int KVD = KV > 0 ? KV : 1;
+    double Vv[KVD][4];
+#pragma unroll
+    for (int i = 0; i < KV; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Vv[i][r] = tail[16 * i + q + 4 * r];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double4_t acc[2];
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            acc[part] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < KM; ++k) acc[part] = __builtin_amdgcn_mfma_f64_16x16x4f64(V[k], w.Wf[j][part][k], acc[part], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < KV; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[part][r] = __builtin_fma(Vv[i][r], w.Wv[j][part][i], acc[part][r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) put(wv * 16 + q + 4 * r, 16 * j + lc, track_magnitude(acc[0][r], acc[1][r]));
+    }
+}
+
 // pairs of one row in ascending column order -> the first maximum (a strictly larger value takes over)
 __device__ __forceinline__ void track_combine_row(const double *__restrict__ pval, const int32_t *__restrict__ pidx, int ncg, double &best, int &bi)
 {

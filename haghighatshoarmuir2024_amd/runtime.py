@@ -603,6 +603,92 @@ def beamformer_pipeline_bands(plans, ba_list, x, window=None, hop=None, want_ban
                            want_band_power, ws)
 
 
+def bands_track_is_fused(plans, complex_bands=False):
+    """True when ONE fused kernel of csrc/track.hip serves this set of bands (micloc_*_bands_track_is_fused); False: the two-step route
+    inside the call."""
+    lib = _lib.load()
+    F, handles = _band_handles(plans)
+    name = "beamformer" if complex_bands else "snn"
+    r = getattr(lib, f"micloc_{name}_bands_track_is_fused")(handles, F)
+    if r < 0:
+        _lib.check(r, f"{name}_bands_track_is_fused")
+    return bool(r)
+
+
+def _bands_track(name, plans, ba_list, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws):
+    """The caller of the wideband tracking entries (the rule: include/micloc_hip.h, "wideband moving-target tracking").  name: "snn"
+    or "beamformer"; kind: "pipeline" (src = x [B, T, M], with ba_list), "spikes" (snn: src = int8 rasters [F, B, T, 2M]) or "planar"
+    (beamformer: src = band-passed rows [F * B, 2M, Ts], with T)."""
+    torch = _torch()
+    lib = _lib.load()
+    F, handles = _band_handles(plans)
+    p0 = plans[0]
+    if any(p.G != p0.G for p in plans):
+        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
+    if int(win_fall) < 1 or int(win_rise) < 1:
+        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+    if kind == "pipeline":
+        if len(ba_list) != F:
+            raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
+        bb, aa, n = pad_ba_list(ba_list)
+        B, T, M = src.shape
+        if M != p0.num_mic:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {p0.num_mic}!")
+    elif kind == "spikes" and name == "snn":
+        if src.dim() != 4 or src.shape[0] != F or src.shape[3] != 2 * p0.num_mic or src.dtype != torch.int8 or not src.is_contiguous():
+            raise ValueError(f"the rasters must be a contiguous int8 device tensor [{F}, B, T, {2 * p0.num_mic}]")
+        B, T = src.shape[1], src.shape[2]
+    elif kind == "planar" and name == "beamformer":
+        if src.dim() != 3 or src.shape[0] % F or src.shape[1] != 2 * p0.num_mic or src.dtype != torch.float64 or not src.is_contiguous() or T is None:
+            raise ValueError(f"the planar rows must be a contiguous float64 device tensor [{F} * B, {2 * p0.num_mic}, Ts], with T")
+        B, Ts = src.shape[0] // F, src.shape[2]
+    else:
+        raise ValueError("kind must be 'pipeline', 'spikes' (snn) or 'planar' (beamformer)")
+    B, T, G, dev = int(B), int(T), p0.G, p0.device
+    if B * T > 0x7FFFFFFF:
+        raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
+    # NumPy's own arithmetic for the filter constants, as envelope_track
+    wl = np.asarray([int(win_fall), int(win_rise)])
+    inv = 1 / wl
+    a = 1 - inv
+    consts = (float(a[1]), float(inv[1]), float(a[0]))
+    nbytes = getattr(lib, f"micloc_{name}_bands_track_workspace_bytes")(handles, F, B, T)
+    if nbytes == 0:
+        raise ValueError(f"micloc {name}_bands_track_workspace_bytes: the plans or the batch do not fit the wideband tracking rule")
+    if B > 1 and not bands_track_is_fused(plans, name == "beamformer"):
+        per_trial = (32 if name == "beamformer" else 24) * T * G + 768  # y, the band sum and its envelope of one trial
+        nbytes = max(nbytes, min(nbytes + (B - 1) * per_trial, nbytes - per_trial + max(per_trial, int(budget_bytes))))
+    buf = (ws or p0.ws).get(nbytes)
+    out = dict(index=torch.empty((B, T), dtype=torch.int32, device=dev), peak_envelope=torch.empty((B, T), dtype=torch.float64, device=dev),
+               envelope_last=torch.empty((B, G), dtype=torch.float64, device=dev) if want_envelope_last else None)
+    tail = (*consts, _ptr(out["index"]), _ptr(out["peak_envelope"]), _ptr(out["envelope_last"]), _ptr(buf), nbytes, _stream(dev))
+    if kind == "pipeline":
+        _lib.check(getattr(lib, f"micloc_{name}_pipeline_bands_track_f64")(handles, F, _dptr(bb), _dptr(aa), n, _ptr(src), B, T, *tail),
+                   f"{name}_pipeline_bands_track")
+    elif kind == "spikes":
+        _lib.check(lib.micloc_lif_beamform_bands_track_f64(handles, F, _ptr(src), B, T, *tail), "lif_beamform_bands_track")
+    else:
+        _lib.check(lib.micloc_beamform_c128_bands_track_f64(handles, F, _ptr(src), B, T, int(Ts), *tail), "beamform_c128_bands_track")
+    return out
+
+
+def snn_bands_track(plans, ba_list, src, win_fall, win_rise, kind="pipeline", want_envelope_last=False, budget_bytes=1 << 30, ws=None):
+    """micloc_snn_pipeline_bands_track_f64: the moving-target read-out of a wideband SNN localizer -- the filterbank `ba_list`, per band the
+    front end of plans[f] (neuron kernel and real bf_mat set), the bands' |y| added in ascending band order, Envelope.evolve and the
+    arg-max per frame -- x [B, T, M] on the plans' device -> dict(index [B, T] int32, peak_envelope [B, T], envelope_last [B, G] or None),
+    without an array of size T x G where the fused kernel serves the set (bands_track_is_fused); other sets run the two-step route over
+    sub-batches whose arrays stay under `budget_bytes`.  kind="spikes": src = the bands' int8 rasters [F, B, T, 2M]
+    (micloc_lif_beamform_bands_track_f64; ba_list is not read)."""
+    return _bands_track("snn", plans, ba_list, src, win_fall, win_rise, kind, None, want_envelope_last, budget_bytes, ws)
+
+
+def beamformer_bands_track(plans, ba_list, src, win_fall, win_rise, kind="pipeline", T=None, want_envelope_last=False, budget_bytes=1 << 30,
+                           ws=None):
+    """micloc_beamformer_pipeline_bands_track_f64: snn_bands_track for the complex Beamformer chains of all bands (|y| = hypot(re, im)).
+    kind="planar": src = the bands' band-passed rows [F * B, 2M, Ts] with T (micloc_beamform_c128_bands_track_f64)."""
+    return _bands_track("beamformer", plans, ba_list, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws)
+
+
 def beamformer_bands_bandpass(plans, xf, one_launch=True, pre=None, h=None):
     """Stages (2) and (3) of the complex band pipeline alone (micloc_beamformer_bands_bandpass_f64): xf [F, B, T, M] on the plans' device
     -> (h, pre), planar [F * B, 2M, Ts] each; the in-phase rows of h are not written.  one_launch=False takes the one-shot band-pass

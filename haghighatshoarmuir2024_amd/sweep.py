@@ -1161,6 +1161,35 @@ def xylo_moving_target_sweep(demo, envelope, localizer=None, batch_trials=1100, 
     return res
 
 
+def wideband_track_localizer(loc, envelope, max_batch=1100):
+    """track_localizer's place in moving_target_sweep(localizer=) for a wideband localizer (wideband.WidebandSNNLocalizer or
+    WidebandBeamformerLocalizer): its track_batch -- the filterbank, every band's chain, the bands' |y| added, envelope and arg-max per
+    frame in one library call -- in device batches of at most `max_batch` trials; index [B, T] stays on the device.  The SNN bands'
+    neuron kernels are built on the sweep's time axis, as track_localizer's."""
+
+    def run(sig_batch, time_vec):
+        return _in_batches(sig_batch, max_batch, lambda x: (loc.track_batch(x, envelope, time_vec=time_vec)["index"],))[0]
+
+    return run
+
+
+def wideband_moving_target_sweep(loc, envelope, localizer=None, batch_trials=1100, store_key=None, **kw):
+    """moving_target_sweep read out by the WIDEBAND localizer `loc` (the form the reference deploys in its live demos) instead of one
+    band: that sweep's own moving test signal, path, SNR grid, lag, settle and scoring; the estimate of frame t is the arg-max of the
+    envelope of the bands' summed magnitudes (loc.track_batch).  The first band's beamformer gives the geometry, fs and the default lag;
+    the store key covers the band edges, the filterbank's coefficients and every band's parameters and bf_mat hash (_wideband_store_key),
+    then store_key.  `localizer`: another read-out with wideband_track_localizer's signature.  Other keywords as moving_target_sweep."""
+    if localizer is None:
+        localizer = wideband_track_localizer(loc, envelope, max_batch=batch_trials)
+    doa_list = kw.pop("doa_list", None)
+    if doa_list is None:
+        doa_list = getattr(loc, "doa_list", None)
+    if doa_list is None or len(doa_list) != loc.num_grid:
+        raise ValueError(f"wideband_moving_target_sweep needs the localizer's DoA grid (loc.doa_list or doa_list=, {loc.num_grid} entries)")
+    return moving_target_sweep(loc.beamfs[0], None, doa_list, envelope, localizer=localizer, batch_trials=batch_trials,
+                               store_key={**_wideband_store_key(loc), **(store_key or {})}, **kw)
+
+
 def _xylo_store_key(demo, store_key=None):
     """ShardStore key entries of a Xylo chain: the quantised specification and `bipolar`, then store_key."""
     spec = demo.spec
@@ -1251,20 +1280,20 @@ def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau,
 
 
 def main(argv=None):
-    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy|moving-noisy|wideband-speech]`: the accuracy sweeps of the paper scripts
+    """`python -m haghighatshoarmuir2024_amd.sweep [--sweep noisy|speech|xylo|music-noisy|music-speech|multi-noisy|windowed-noisy|moving-noisy|wideband-speech|moving-wideband]`: the accuracy sweeps of the paper scripts
     (paper_plots/target_snn_localization.py:309-520 noisy target, :97-300 speech target; target_xylo_localization.py:540-608),
     design + 11 SNRs x num_sim trials, printing what the scripts print (SNR vector and mean absolute errors in degrees)."""
     import argparse
 
     ap = argparse.ArgumentParser(description=main.__doc__)
-    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy", "wideband-speech"],
+    ap.add_argument("--sweep", choices=["noisy", "speech", "xylo", "music-noisy", "music-speech", "multi-noisy", "windowed-noisy", "moving-noisy", "wideband-speech", "moving-wideband"],
                     default="noisy")
     ap.add_argument("--bands", type=parse_bands, default=parse_bands("1000:1600,1600:2400,2400:3400"),
-                    help="wideband-speech: the bands as low:high pairs in Hz, comma separated (at most 16)")
+                    help="wideband-speech, moving-wideband: the bands as low:high pairs in Hz, comma separated (at most 16)")
     ap.add_argument("--window-frames", type=int, default=None, help="windowed-noisy: frames per window (a multiple of the plan's window quantum; --method xylo: of 256)")
     ap.add_argument("--hop-frames", type=int, default=None, help="windowed-noisy: frames between window starts (default: --window-frames)")
     ap.add_argument("--method", choices=["snn", "beamformer", "music", "xylo"], default="snn",
-                    help="multi-noisy, wideband-speech (snn | beamformer), moving-noisy and windowed-noisy (snn | beamformer | xylo): the localizer")
+                    help="multi-noisy, wideband-speech and moving-wideband (snn | beamformer), moving-noisy and windowed-noisy (snn | beamformer | xylo): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
@@ -1344,6 +1373,20 @@ def main(argv=None):
             loc = WidebandSNNLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3,
                                                   bipolar_spikes=True, fs=fs)
         res = wideband_speech_sweep(loc, doa_list, src, num_sim=args.num_sim or 20, seed=args.seed, mode=args.mode, rank=rank, world_size=world)
+    elif args.sweep == "moving-wideband":
+        from .utils import Envelope
+        from .wideband import WidebandBeamformerLocalizer, WidebandSNNLocalizer
+
+        if args.method not in ("snn", "beamformer"):
+            ap.error("--sweep moving-wideband takes --method snn or beamformer")
+        # the live demos' set-up per band, as --sweep wideband-speech; the moving target and the envelope of --sweep moving-noisy
+        if args.method == "beamformer":
+            loc = WidebandBeamformerLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3, fs=fs)
+        else:
+            loc = WidebandSNNLocalizer.from_bands(geometry, args.bands, doa_list, recording_duration=0.25, kernel_duration=10.0e-3,
+                                                  bipolar_spikes=True, fs=fs)
+        res = wideband_moving_target_sweep(loc, Envelope(rise_time=1e-3, fall_time=10e-3, fs=fs), num_sim=args.num_sim or 100, seed=args.seed,
+                                           mode=args.mode, rank=rank, world_size=world)
     elif args.sweep.startswith("music"):
         # paper_plots/target_localization_MUSIC.py: band [0.8, 1.2] x 2 kHz, frame_duration 1.0, k = 1, N = 2048
         from .music_beamformer import MUSIC

@@ -101,6 +101,15 @@ class _WidebandLocalizer:
             return _add_window_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
         return _add_peaks(out, doa_list, num_sources, min_separation, rel_threshold)
 
+    def _track_shape(self, sig_batch, envelope):
+        """track_batch's checks, in front of any device work -> (B, T)."""
+        B, T, M = sig_batch.shape
+        if M != self.num_mic:
+            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
+        if int(envelope.win_lens[0]) < 1 or int(envelope.win_lens[1]) < 1:
+            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        return B, T
+
 
 class WidebandSNNLocalizer(_WidebandLocalizer):
     """beamfs: one SNNBeamformer per band; bf_mats: their real [2M, G] matrices; filterbank: a Filterbank with one (b, a) section per
@@ -148,6 +157,20 @@ class WidebandSNNLocalizer(_WidebandLocalizer):
         x = plans[0].to_device(sig_batch)
         out = runtime.snn_pipeline_bands(plans, self.filterbank.ba_list, x, window=window, hop=hop, want_band_power=return_band_power)
         return self._read_out(out, T, window, hop, doa_list, num_sources, min_separation, rel_threshold)
+
+    def track_batch(self, sig_batch, envelope, time_vec=None, want_envelope_last=False, budget_bytes=1 << 30):
+        """The moving-target read-out (SNNBeamformer.track_batch) over all bands: per frame the arg-max over the DoA grid of
+        Envelope.evolve(m), m[t, g] = ((|y_0| + |y_1|) + |y_2|) + ... the bands' beamformer outputs added as magnitudes in ascending band
+        order -- with one band SNNBeamformer.track_batch on the filterbank's output, bit for bit.  sig_batch [B, T, M] (numpy or device
+        tensor) -> dict of device tensors: index [B, T] int32, peak_envelope [B, T] and, with want_envelope_last, envelope_last [B, G].
+        One library call (micloc_snn_pipeline_bands_track_f64); up to 16 channels and 512 DoAs one fused kernel without an array of
+        size T x G, otherwise the two-step route inside the library over sub-batches of trials within `budget_bytes`."""
+        B, T = self._track_shape(sig_batch, envelope)
+        if time_vec is None:
+            time_vec = np.arange(T) / self.fs
+        plans = self.plans(time_vec)
+        return runtime.snn_bands_track(plans, self.filterbank.ba_list, plans[0].to_device(sig_batch), envelope.win_lens[0], envelope.win_lens[1],
+                                       want_envelope_last=want_envelope_last, budget_bytes=budget_bytes)
 
 
 class WidebandBeamformerLocalizer(_WidebandLocalizer):
@@ -200,6 +223,27 @@ class WidebandBeamformerLocalizer(_WidebandLocalizer):
         if one == 0 or budget_bytes is None:
             return B  # (bad arguments: the call itself names them)
         return int(max(1, min(B, int(budget_bytes) // one)))
+
+    def track_batch(self, sig_batch, envelope, time_vec=None, want_envelope_last=False, budget_bytes=1 << 30):
+        """WidebandSNNLocalizer.track_batch for the complex chains (|y| = hypot(re, im); with one band Beamformer.track_batch on the
+        filterbank's output, bit for bit): micloc_beamformer_pipeline_bands_track_f64.  time_vec is not read (the chains have no neuron
+        kernel).  budget_bytes: B is split into sub-batches whose workspace (the filterbank output and two planar copies of every band)
+        stays inside it, one trial at least; the results do not depend on the split."""
+        import torch
+
+        from . import _lib
+
+        B, T = self._track_shape(sig_batch, envelope)
+        plans = self.plans()
+        x = plans[0].to_device(sig_batch)
+        F, handles = runtime._band_handles(plans)
+        one = _lib.load().micloc_beamformer_bands_track_workspace_bytes(handles, F, 1, T)
+        step = B if one == 0 or budget_bytes is None else int(max(1, min(B, int(budget_bytes) // one)))
+        parts = [runtime.beamformer_bands_track(plans, self.filterbank.ba_list, x[lo : lo + step], envelope.win_lens[0], envelope.win_lens[1],
+                                                want_envelope_last=want_envelope_last, budget_bytes=budget_bytes) for lo in range(0, B, step)]
+        if len(parts) == 1:
+            return parts[0]
+        return {k: (None if parts[0][k] is None else torch.cat([p[k] for p in parts], dim=0)) for k in parts[0]}
 
     def localize_batch(self, sig_batch, return_band_power=False, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0,
                        window=None, hop=None, budget_bytes=8 << 30):

@@ -828,6 +828,57 @@ int micloc_beamformer_pipeline_bands_f64(const micloc_plan *const *plans, int F,
 int micloc_beamformer_bands_bandpass_f64(const micloc_plan *const *plans, int F, const double *xf, int B, int T, double *h, double *pre, int Ts,
                                          int with_stht, int one_launch, void *stream);
 
+/* ---- wideband moving-target tracking: a DoA per frame over all bands ---------------------------- */
+/* "moving-target tracking" above for the wideband localizers: the per-frame read-out of F bands (1 <= F <= MICLOC_MAX_BANDS) whose
+ * plans agree in device, M and G, all with a real bf_mat and a neuron kernel (the snn / lif entries) or all with a complex bf_mat (the
+ * beamformer / c128 entries).  The rule, for trial b, bands f = 0 .. F-1 in ascending order, frame t, DoA column g:
+ *   y_f[t][g]  the beamformer output of band f: exactly the value band f's own chain stores for its filterbank output xf[f] when y is
+ *              kept (micloc_lif_beamform_f64 / micloc_beamform_c128_f64 with plans[f]: same instruction sequence, same bits);
+ *   a_f[t][g]  = |y_f[t][g]|  (real: fabs; complex: hypot(re, im), the device library's, as MICLOC_ENV_C128);
+ *   m[t][g]    = a_0[t][g], then m = m + a_f for f = 1 .. F-1: one addition per band, rounded to nearest, nothing fused, ascending
+ *              band order.  Magnitudes are added, not powers: with F = 1 the call IS the single-plan tracking entry on xf[0];
+ *   e, index, peak_env, env_last: the rule of "moving-target tracking" on m, unchanged -- e[0] = m[0]; rise when m[t] >= e[t-1]; two
+ *              rounded products and one rounded sum; the first maximum over g; a NaN never wins; a row of NaN only gives index 0 and
+ *              peak NaN.
+ * Sets in which every plan is one the fused kernels serve (micloc_track_is_fused() == 1) and whose workgroup, sized for the largest
+ * neuron kernel, fits in 160 KB of LDS (micloc_*_bands_track_is_fused() == 1) run ONE kernel of csrc/track.hip over all bands (and the
+ * combine launch when G > 64): no y, m or e is stored, and the workspace -- xf, the front end's arrays, every band's raster or planar
+ * rows, one (value, index) pair per frame and 64 DoA columns -- depends on G through the pairs alone.  Other sets run the two-step
+ * route inside the call over sub-batches of trials: per band y stored, m formed by the rule above, the envelope kernel on m, a row
+ * read-out; the minimum workspace holds y, m and e of ONE trial, and a caller that passes more has as many trials per sub-batch as fit.
+ * The results do not depend on the route or the sub-batches.
+ *   micloc_snn_pipeline_bands_track_f64: the filterbank of "wideband localisation", per band the first two launches of
+ *   micloc_snn_pipeline_f64 on xf[f] (the bands share the STHT rows and the encoder scratch: they run one after the other), the read-out.
+ *   micloc_beamformer_pipeline_bands_track_f64: launches (1) to (3) of micloc_beamformer_pipeline_bands_f64, the read-out.
+ *   micloc_lif_beamform_bands_track_f64 / micloc_beamform_c128_bands_track_f64: the read-out alone, of the caller's rasters
+ *   [F][B][T][2M] int8 / planar band-passed rows [F * B][2M][Ts], Ts = micloc_padded_T(T).
+ * Status, before any launch: MICLOC_ERR_INVALID for NULL (plans, a plan, coefficients, the input, index), F outside
+ * 1..MICLOC_MAX_BANDS, fb_n outside 1..MICLOC_MAX_IIR, a_f[0] == 0, B or F * B outside 1..65535; MICLOC_ERR_SHAPE for T < 1 or
+ * B * T > 2^31 - 1 (both without reading a plan); MICLOC_ERR_NOT_SET for a plan without bf_mat or (real) neuron kernel;
+ * MICLOC_ERR_SHAPE for plans on different devices, with different M or G, a bf_mat of the other kind, (complex) a different Hilbert
+ * kernel or band-pass length or T * M >= 2^32, a Ts that is not micloc_padded_T(T); MICLOC_ERR_WORKSPACE for a missing, misaligned or
+ * short ws.  The size functions return 0 for arguments the calls refuse; the is_fused functions return 1, 0 or a status code < 0.
+ * No atomics, no host synchronisation, no allocation: re-entrant per stream with workspaces of their own and capturable in a
+ * hipGraph (a straight chain on ONE stream). */
+size_t micloc_snn_bands_track_workspace_bytes(const micloc_plan *const *plans, int F, int B, int T);
+size_t micloc_beamformer_bands_track_workspace_bytes(const micloc_plan *const *plans, int F, int B, int T);
+int micloc_snn_bands_track_is_fused(const micloc_plan *const *plans, int F);
+int micloc_beamformer_bands_track_is_fused(const micloc_plan *const *plans, int F);
+int micloc_lif_beamform_bands_track_f64(const micloc_plan *const *plans, int F, const int8_t *spikes, int B, int T, double a_rise,
+                                        double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws,
+                                        size_t ws_bytes, void *stream);
+int micloc_beamform_c128_bands_track_f64(const micloc_plan *const *plans, int F, const double *pre, int B, int T, int Ts, double a_rise,
+                                         double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws,
+                                         size_t ws_bytes, void *stream);
+int micloc_snn_pipeline_bands_track_f64(const micloc_plan *const *plans, int F, const double *fb_b, const double *fb_a, int fb_n,
+                                        const double *x, int B, int T, double a_rise, double i_rise, double a_fall, int32_t *index,
+                                        double *peak_env /* [B][T] or NULL */, double *env_last /* [B][G] or NULL */, void *ws,
+                                        size_t ws_bytes, void *stream);
+int micloc_beamformer_pipeline_bands_track_f64(const micloc_plan *const *plans, int F, const double *fb_b, const double *fb_a, int fb_n,
+                                               const double *x, int B, int T, double a_rise, double i_rise, double a_fall, int32_t *index,
+                                               double *peak_env /* [B][T] or NULL */, double *env_last /* [B][G] or NULL */, void *ws,
+                                               size_t ws_bytes, void *stream);
+
 /* ---- wideband streaming: filterbank state carry, band sum per tile ------------------------------ */
 /* The wideband chain above for ONE stream that arrives in tiles: the results after the last tile are bit for bit those of
  * micloc_snn_pipeline_bands_f64 on the whole recording, for any tiling.  One tile of n frames, every launch on the caller's one
