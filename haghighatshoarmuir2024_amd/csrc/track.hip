@@ -56,6 +56,20 @@ __device__ __forceinline__ void track_store_pair(size_t o, int ncg, double best,
     }
 }
 
+// a one-shot kernel around its walk: workgroup (cg, b) of a (column groups, trials) grid walks trial b from frame 0 with a zero chain
+// state -- walk(state, emit) -- leaves every pair by track_store_pair and, asked for it, the last envelope row of its columns
+template <class Walk>
+__device__ __forceinline__ void track_one_shot(int T, int G, double *__restrict__ pval, int32_t *__restrict__ pidx, double *__restrict__ env_last,
+                                               const Walk &walk)
+{
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
+    const size_t row0 = (size_t)b * T;
+    double state = 0.0;
+    walk(state, [&](int cs, int row, double best, int bi) { track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx); });
+    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
+}
+
 // SNN: int8 spike raster [B][T][C], C <= 16 (the beamform_ws_kernel family)
 __global__ __launch_bounds__(TRK_THREADS) void track_ws_kernel(const int8_t *__restrict__ spikes, const double *__restrict__ ntab_g, int NK,
                                                                const double *__restrict__ Wp, int GT, int C, int T, int G, double a_rise,
@@ -63,15 +77,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_ws_kernel(const int8_t *__r
                                                                int32_t *__restrict__ pidx, double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
-    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    const size_t row0 = (size_t)b * T;
-    double state = 0.0;
-    track_ws_walk(smem, spikes + (size_t)b * T * C, C, 0, T, 0, ntab_g, NK, Wp, GT, G, cg, a_rise, i_rise, a_fall, state,
-                  [&](int cs, int row, double best, int bi) {
-                      track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
-                  });
-    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
+    track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
+        track_ws_walk(smem, spikes + (size_t)blockIdx.y * T * C, C, 0, T, 0, ntab_g, NK, Wp, GT, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
+    });
 }
 
 // complex Beamformer: planar band-passed analytic signal [B][C = 2M][Ts], C <= 16 (the beamform_wsc_kernel family); G = complex DoAs
@@ -82,15 +90,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_wsc_kernel(const double *__
                                                                 double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
-    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    const size_t row0 = (size_t)b * T;
-    double state = 0.0;
-    track_wsc_walk<KM, KV>(smem, pre + (size_t)b * C * Ts, C, Ts, 0, T, 0, Wp, GT, G, cg, a_rise, i_rise, a_fall, state,
-                           [&](int cs, int row, double best, int bi) {
-                               track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
-                           });
-    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
+    track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
+        track_wsc_walk<KM, KV>(smem, pre + (size_t)blockIdx.y * C * Ts, C, Ts, 0, T, 0, Wp, GT, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
+    });
 }
 
 // pairs [rows][ncg] in ascending column order -> the first maximum of every row (a strictly larger value takes over)
@@ -108,36 +110,46 @@ __global__ __launch_bounds__(256) void track_combine_kernel(const double *__rest
 
 size_t track_pairs_bytes(int B, int T, int G) { return track_pairs_size((size_t)B * T * track_col_groups(G)); }
 
+// the launches of a fused call: launch(grid, pval, pidx) starts the one-shot kernel on a (column groups, trials) grid -- with one column
+// group it writes the result itself, else the pairs of `pairs` (track_pairs_bytes), which track_combine_kernel then finishes
+template <class Launch>
+static hipError_t track_launch_fused(int B, int T, int G, int32_t *index, double *peak, void *pairs, hipStream_t stream, const Launch &launch)
+{
+    const int ncg = track_col_groups(G);
+    double *pval = peak;
+    int32_t *pidx = index;
+    if (ncg > 1) track_pairs_split(pairs, (size_t)B * T * ncg, pval, pidx);
+    hipError_t e = launch(dim3(ncg, B), pval, pidx);
+    if (e != hipSuccess || ncg == 1) return e;
+    const size_t rows = (size_t)B * T;
+    hipLaunchKernelGGL(track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, ncg, index, peak);
+    return hipGetLastError();
+}
+
 // src: the spike raster (real bf_mat) or the planar band-passed rows (complex); G: the DoA grid the caller sees; pairs: track_pairs_bytes
 hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_complex, const void *src, int B, int T, int Ts, int G,
                               double a_rise, double i_rise, double a_fall, int32_t *index, double *peak, double *env_last, void *pairs,
                               hipStream_t stream)
 {
-    const int ncg = track_col_groups(G);
-    double *pval = peak;  // one column group: the kernel writes the result itself
-    int32_t *pidx = index;
-    if (ncg > 1) track_pairs_split(pairs, (size_t)B * T * ncg, pval, pidx);
     const size_t lds = track_lds_bytes(is_complex != 0, nt.NK);
-    dim3 grid(ncg, B), block(TRK_THREADS);
-    if (!is_complex) {
-        auto k = &track_ws_kernel;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, static_cast<const int8_t *>(src), nt.tab, nt.NK, W.Wp, W.GT, W.C, T, G, a_rise, i_rise,
-                           a_fall, pval, pidx, env_last);
-    } else {
-        const double *pre = static_cast<const double *>(src);
-        const bool served = track_wsc_dispatch(W.C, [&](auto k) {
-            hipLaunchKernelGGL((track_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, pre, W.Wp, W.GT, W.C, T, Ts, G, a_rise,
-                               i_rise, a_fall, pval, pidx, env_last);
-        });
-        if (!served) return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || ncg == 1) return e;
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, ncg, index, peak);
-    return hipGetLastError();
+    return track_launch_fused(B, T, G, index, peak, pairs, stream, [&](dim3 grid, double *pval, int32_t *pidx) {
+        const dim3 block(TRK_THREADS);
+        if (!is_complex) {
+            auto k = &track_ws_kernel;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k, grid, block, lds, stream, static_cast<const int8_t *>(src), nt.tab, nt.NK, W.Wp, W.GT, W.C, T, G, a_rise, i_rise,
+                               a_fall, pval, pidx, env_last);
+        } else {
+            const double *pre = static_cast<const double *>(src);
+            const bool served = track_wsc_dispatch(W.C, [&](auto k) {
+                hipLaunchKernelGGL((track_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, pre, W.Wp, W.GT, W.C, T, Ts, G,
+                                   a_rise, i_rise, a_fall, pval, pidx, env_last);
+            });
+            if (!served) return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    });
 }
 
 // ---- wideband: F bands, one magnitude tile (the rule: include/micloc_hip.h, "wideband moving-target tracking") ----
@@ -147,17 +159,7 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
 // one rounded add: m = ((a_0 + a_1) + a_2) + ...  Behind the last band track_chain_reduce runs on the summed tile, unchanged.  The
 // bf_mat fragments of F bands do not fit in registers: they are loaded again per band and chunk (16 KB per band and column group at
 // most, which stays in L2) in front of the barrier, so the loads are in flight while the rows are staged.  No workgroup waits for
-// another; nothing of size T x G exists.
-struct TrackBandPut {  // a thread meets the same elements of Y in every band: the bands need no barrier for Y among themselves
-    double *Y;
-    bool first;
-    __device__ __forceinline__ void operator()(int row, int col, double a) const
-    {
-        double *y = Y + row * TRK_LD + col;
-        *y = first ? a : __dadd_rn(*y, a);
-    }
-};
-
+// another; nothing of size T x G exists.  (TrackBandPut of track_rows.h stores or adds.)
 // SNN bands: trial b of every band's raster [B][T][C], the whole recording from frame 0; the LDS regions are sized for NKmax
 template <class Emit>
 __device__ __forceinline__ void track_bands_ws_walk(unsigned char *smem, const TrackBandsArgs &a, int F, int NKmax, int b, int C, int T, int G,
@@ -224,14 +226,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_bands_ws_kernel(TrackBandsA
                                                                      int32_t *__restrict__ pidx, double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
-    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    const size_t row0 = (size_t)b * T;
-    double state = 0.0;
-    track_bands_ws_walk(smem, a, F, NKmax, b, C, T, G, cg, a_rise, i_rise, a_fall, state, [&](int cs, int row, double best, int bi) {
-        track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+    track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
+        track_bands_ws_walk(smem, a, F, NKmax, blockIdx.y, C, T, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
     });
-    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
 }
 
 template <int KM, int KV>
@@ -240,14 +237,9 @@ __global__ __launch_bounds__(TRK_THREADS) void track_bands_wsc_kernel(TrackBands
                                                                       int32_t *__restrict__ pidx, double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
-    const int cg = blockIdx.x, ncg = gridDim.x, b = blockIdx.y;
-    const size_t row0 = (size_t)b * T;
-    double state = 0.0;
-    track_bands_wsc_walk<KM, KV>(smem, a, F, b, C, Ts, T, G, cg, a_rise, i_rise, a_fall, state, [&](int cs, int row, double best, int bi) {
-        track_store_pair((row0 + (size_t)(cs + row)) * ncg + cg, ncg, best, bi, pval, pidx);
+    track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
+        track_bands_wsc_walk<KM, KV>(smem, a, F, blockIdx.y, C, Ts, T, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
     });
-    if (env_last && wv == 0 && cg * TRK_COLS + l < G) env_last[(size_t)b * G + cg * TRK_COLS + l] = state;
 }
 
 bool track_bands_fused_eligible(const BeamformW *const *W, const NeuronTab *const *nt, int F, int is_complex)
@@ -265,29 +257,23 @@ hipError_t launch_track_bands_fused(const TrackBandsArgs &a, int F, int NKmax, i
                                     double i_rise, double a_fall, int32_t *index, double *peak, double *env_last, void *pairs,
                                     hipStream_t stream)
 {
-    const int ncg = track_col_groups(G);
-    double *pval = peak;  // one column group: the kernel writes the result itself
-    int32_t *pidx = index;
-    if (ncg > 1) track_pairs_split(pairs, (size_t)B * T * ncg, pval, pidx);
     const size_t lds = track_lds_bytes(is_complex != 0, NKmax);
-    dim3 grid(ncg, B), block(TRK_THREADS);
-    if (!is_complex) {
-        auto k = &track_bands_ws_kernel;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, grid, block, lds, stream, a, F, NKmax, C, T, G, a_rise, i_rise, a_fall, pval, pidx, env_last);
-    } else {
-        const bool served = track_wsc_dispatch(C, [&](auto k) {
-            hipLaunchKernelGGL((track_bands_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, a, F, C, T, Ts, G, a_rise, i_rise,
-                               a_fall, pval, pidx, env_last);
-        });
-        if (!served) return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || ncg == 1) return e;
-    const size_t rows = (size_t)B * T;
-    hipLaunchKernelGGL(track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, ncg, index, peak);
-    return hipGetLastError();
+    return track_launch_fused(B, T, G, index, peak, pairs, stream, [&](dim3 grid, double *pval, int32_t *pidx) {
+        const dim3 block(TRK_THREADS);
+        if (!is_complex) {
+            auto k = &track_bands_ws_kernel;
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(k, grid, block, lds, stream, a, F, NKmax, C, T, G, a_rise, i_rise, a_fall, pval, pidx, env_last);
+        } else {
+            const bool served = track_wsc_dispatch(C, [&](auto k) {
+                hipLaunchKernelGGL((track_bands_wsc_kernel<decltype(k)::km, decltype(k)::kv>), grid, block, lds, stream, a, F, C, T, Ts, G, a_rise,
+                                   i_rise, a_fall, pval, pidx, env_last);
+            });
+            if (!served) return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    });
 }
 
 // the band sum of the two-step route, element by element: the magnitude expressions of the tiles above and their one rounded add

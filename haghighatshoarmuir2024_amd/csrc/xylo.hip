@@ -14,8 +14,8 @@
 // (broadcast) dwords.  xylo_lif_pk_kernel (the sweep: binary events, no recurrence): two neurons per lane in packed
 // 16-bit arithmetic, input currents from the int8 matrix cores -- the lane's walk is XpLif of xylo_rows.h, shared with the stream's
 // kernel (stream_xylo.hip); here are its two launch forms.
-// Each has a CHUNK-COUNT form for the time-resolved read-out (xylo_lif_chunks_kernel, xylo_lif_pk_chunks_kernel: the same walk, which
-// also leaves the spike count of every 256 frames), and xylo_window_kernel adds those rows per window: "time-resolved DoA" below,
+// Each has a CHUNK-COUNT form for the time-resolved read-out (xylo_lif_kernel<REC, NQ, true>, xylo_lif_pk_chunks_kernel: the same walk,
+// which also leaves the spike count of every 256 frames), and xylo_window_kernel adds those rows per window: "time-resolved DoA" below,
 // PARITY UNPINNED like everything here.
 #include <vector>
 
@@ -44,14 +44,17 @@ __device__ __forceinline__ int xy_decay(int v, int dash)
 }
 
 // NQ = dwords of packed input per step (compile time: the contraction unrolls into NQ v_dot4 with no branches; the
-// staged row is read with wide, wave-uniform LDS loads)
-template <bool REC, int NQ>
+// staged row is read with wide, wave-uniform LDS loads).
+// CHUNKS: the chunk-count form (the windowed read-out, "time-resolved DoA" below).  The staged tile is one chunk of XP_CHUNK frames, and at
+// its end the lane also writes its count since the previous tile to chunk_counts [B][ceil(T / XP_CHUNK)][N]; rate may be NULL; no raster out.
+template <bool REC, int NQ, bool CHUNKS = false>
 __global__ __launch_bounds__(1024) void xylo_lif_kernel(const uint8_t *__restrict__ spikes_in, int ternary_C, int T, int Cin,
                                                          const int *__restrict__ Wpk /*[nq][N]*/, int nq, int N, int w_rec,
                                                          const uint8_t *__restrict__ dash_syn,
                                                          const uint8_t *__restrict__ dash_mem,
                                                          const short *__restrict__ thr, int max_spikes,
-                                                         uint8_t *__restrict__ spikes_out, int *__restrict__ rate)
+                                                         uint8_t *__restrict__ spikes_out, int *__restrict__ rate,
+                                                         int *__restrict__ chunk_counts)
 {
     __shared__ __attribute__((aligned(16))) int tile[XY_TT][NQ];
     __shared__ int wsum[2][16];
@@ -64,12 +67,14 @@ __global__ __launch_bounds__(1024) void xylo_lif_kernel(const uint8_t *__restric
     const int ds = act ? dash_syn[g] : 0, dm = act ? dash_mem[g] : 0;
     const int th = act ? thr[g] : 32767;
     int isyn = 0, vmem = 0, total = 0, prev_total = 0;
+    [[maybe_unused]] int chunk_total = 0;  // CHUNKS: `total` at the start of the tile
     // ternary_C > 0: the input is the encoder's int8 raster [B][T][ternary_C] in {-1, 0, +1}; channel c carries its +1
     // events, channel ternary_C + c its -1 events (Demo.spike_encoding's split, xylo_snn_localization.py:350-354)
     const int Crow = ternary_C > 0 ? ternary_C : Cin;
     const uint8_t *sb = spikes_in + (size_t)b * T * Crow;
     const int8_t *sbt = reinterpret_cast<const int8_t *>(sb);
-    uint8_t *ob = spikes_out ? spikes_out + (size_t)b * T * N : nullptr;
+    [[maybe_unused]] uint8_t *ob = nullptr;
+    if constexpr (!CHUNKS) ob = spikes_out ? spikes_out + (size_t)b * T * N : nullptr;
     const int nwaves = blockDim.x >> 6;
 
     for (int t0 = 0; t0 < T; t0 += XY_TT) {
@@ -113,7 +118,8 @@ __global__ __launch_bounds__(1024) void xylo_lif_kernel(const uint8_t *__restric
             isyn = i2;
             vmem = v2;
             total += n;
-            if (ob && act) ob[(size_t)(t0 + j) * N + g] = (uint8_t)n;
+            if constexpr (!CHUNKS)
+                if (ob && act) ob[(size_t)(t0 + j) * N + g] = (uint8_t)n;
             if (REC) {
                 // block-wide sum of this step's spikes feeds every neuron at the next step
                 int s = n;
@@ -127,98 +133,10 @@ __global__ __launch_bounds__(1024) void xylo_lif_kernel(const uint8_t *__restric
                 prev_total = tot;
             }
         }
-    }
-    if (rate && act) rate[(size_t)b * N + g] = total;
-}
-
-// The chunk-count form (the windowed read-out, "time-resolved DoA" below): the staged tile is one chunk of XP_CHUNK frames, and at its end
-// the lane also writes its count since the previous tile to chunk_counts [B][ceil(T / XP_CHUNK)][N]; rate may be NULL; no raster out.
-// The walk is xylo_lif_kernel's, line for line, except the lines marked CHUNKS and the raster's (tests/test_xylo_windows_cpu.py compares
-// the two texts): written once as a function inlined into both, xylo_lif_kernel came out with commutative operands swapped in all ten
-// instantiations, and the kernels that exist keep their instructions.
-template <bool REC, int NQ>
-__global__ __launch_bounds__(1024) void xylo_lif_chunks_kernel(const uint8_t *__restrict__ spikes_in, int ternary_C, int T, int Cin,
-                                                                const int *__restrict__ Wpk /*[nq][N]*/, int nq, int N, int w_rec,
-                                                                const uint8_t *__restrict__ dash_syn,
-                                                                const uint8_t *__restrict__ dash_mem,
-                                                                const short *__restrict__ thr, int max_spikes, int *__restrict__ rate,
-                                                                int *__restrict__ chunk_counts)
-{
-    __shared__ __attribute__((aligned(16))) int tile[XY_TT][NQ];
-    __shared__ int wsum[2][16];
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    const bool act = g < N;
-    int w[NQ];
-#pragma unroll
-    for (int k = 0; k < NQ; ++k) w[k] = (act && k < nq) ? Wpk[(size_t)k * N + g] : 0;
-    const int ds = act ? dash_syn[g] : 0, dm = act ? dash_mem[g] : 0;
-    const int th = act ? thr[g] : 32767;
-    int isyn = 0, vmem = 0, total = 0, prev_total = 0;
-    int chunk_total = 0;  // CHUNKS: `total` at the start of the tile
-    // ternary_C > 0: the input is the encoder's int8 raster [B][T][ternary_C] in {-1, 0, +1}; channel c carries its +1
-    // events, channel ternary_C + c its -1 events (Demo.spike_encoding's split, xylo_snn_localization.py:350-354)
-    const int Crow = ternary_C > 0 ? ternary_C : Cin;
-    const uint8_t *sb = spikes_in + (size_t)b * T * Crow;
-    const int8_t *sbt = reinterpret_cast<const int8_t *>(sb);
-    const int nwaves = blockDim.x >> 6;
-
-    for (int t0 = 0; t0 < T; t0 += XY_TT) {
-        const int steps = (T - t0) < XY_TT ? (T - t0) : XY_TT;
-        __syncthreads();
-        // stage `steps` rows of Cin bytes, zero padded to NQ dwords
-        uint8_t *tb = reinterpret_cast<uint8_t *>(&tile[0][0]);
-        for (int e = threadIdx.x; e < steps * NQ * 4; e += blockDim.x) {
-            const int r = e / (NQ * 4), c = e % (NQ * 4);
-            uint8_t v = 0;
-            if (c < Cin) {
-                if (ternary_C > 0)
-                    v = c < ternary_C ? (uint8_t)(sbt[(size_t)(t0 + r) * Crow + c] > 0) : (uint8_t)(sbt[(size_t)(t0 + r) * Crow + c - ternary_C] < 0);
-                else
-                    v = sb[(size_t)(t0 + r) * Cin + c];
-            }
-            tb[e] = v;
+        if constexpr (CHUNKS) {
+            if (act) chunk_counts[((size_t)b * ((T + XY_TT - 1) / XY_TT) + t0 / XY_TT) * N + g] = total - chunk_total;  // CHUNKS
+            chunk_total = total;                                                                                      // CHUNKS
         }
-        __syncthreads();
-#pragma unroll 4
-        for (int j = 0; j < steps; ++j) {
-            int in = 0;
-#pragma unroll
-            for (int k = 0; k < NQ; ++k) in = __builtin_amdgcn_sdot4(w[k], tile[j][k], in, false);
-            int i2 = xy_decay(isyn, ds);
-            int v2 = xy_decay(vmem, dm);
-            i2 = xy_sat16(i2 + in + (REC ? w_rec * prev_total : 0));
-            v2 = xy_sat16(v2 + i2);
-            // subtractive reset until below threshold or until the per-step cap: almost always zero or one spike, so the
-            // first one is branch-free and only a wave in which some neuron still sits above threshold takes the division
-            int n = v2 >= th ? 1 : 0;
-            v2 -= n ? th : 0;
-            if (__builtin_expect(__any(v2 >= th), 0)) {  // (cap >= 1 by the API contract)
-                if (v2 >= th) {
-                    int more = xy_div(v2, th);
-                    more = more < max_spikes - 1 ? more : max_spikes - 1;
-                    n += more;
-                    v2 -= more * th;
-                }
-            }
-            isyn = i2;
-            vmem = v2;
-            total += n;
-            if (REC) {
-                // block-wide sum of this step's spikes feeds every neuron at the next step
-                int s = n;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-                const int p = j & 1;
-                if ((threadIdx.x & 63) == 0) wsum[p][threadIdx.x >> 6] = s;
-                __syncthreads();
-                int tot = 0;
-                for (int k2 = 0; k2 < nwaves; ++k2) tot += wsum[p][k2];
-                prev_total = tot;
-            }
-        }
-        if (act) chunk_counts[((size_t)b * ((T + XY_TT - 1) / XY_TT) + t0 / XY_TT) * N + g] = total - chunk_total;  // CHUNKS
-        chunk_total = total;                                                                                      // CHUNKS
     }
     if (rate && act) rate[(size_t)b * N + g] = total;
 }
@@ -362,6 +280,44 @@ hipError_t xylo_upload(int Cin, const int8_t *W_in_host, int N, const uint8_t *d
     return hipStreamSynchronize(stream);  // `pk` / `wb` are host temporaries
 }
 
+// The general form's launch, with the chunk counts (chunk_counts != NULL: no raster) or without.  Without recurrence the neurons are
+// independent: as few, as full workgroups as possible (N = 360 -> one of 384 threads instead of 256 + 104: every wave of the launch
+// issues the same instructions whether its lanes are used or not).
+static void xylo_launch_general(const XyloWs &w, const uint8_t *sp, int ternary_C, int B, int T, int Cin, int N, int w_rec, int max_spikes,
+                                uint8_t *spikes_out, int32_t *rate, int32_t *chunk_counts, hipStream_t stream)
+{
+    const int nq = (Cin + 3) / 4;
+    const int nblocks = w_rec != 0 ? 1 : (N + 511) / 512;
+    const int per = (N + nblocks - 1) / nblocks;
+    const dim3 block(((per + 63) / 64) * 64), grid(nblocks, B);
+#define XY_KERNEL(REC, NQ, CHUNKS)                                                                                                    \
+    hipLaunchKernelGGL((xylo_lif_kernel<REC, NQ, CHUNKS>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, REC ? w_rec : 0, \
+                       w.dds, w.ddm, w.dth, max_spikes, spikes_out, rate, chunk_counts)
+#define XY_LAUNCH(NQ)                      \
+    do {                                   \
+        if (chunk_counts && w_rec != 0)    \
+            XY_KERNEL(true, NQ, true);     \
+        else if (chunk_counts)             \
+            XY_KERNEL(false, NQ, true);    \
+        else if (w_rec != 0)               \
+            XY_KERNEL(true, NQ, false);    \
+        else                               \
+            XY_KERNEL(false, NQ, false);   \
+    } while (0)
+    if (nq <= 2)
+        XY_LAUNCH(2);
+    else if (nq <= 4)
+        XY_LAUNCH(4);
+    else if (nq <= 7)
+        XY_LAUNCH(7);
+    else if (nq <= 8)
+        XY_LAUNCH(8);
+    else
+        XY_LAUNCH(16);
+#undef XY_LAUNCH
+#undef XY_KERNEL
+}
+
 // Runs the network whose constants xylo_upload placed in `ws`: no host access, no synchronisation (graph-capturable).
 hipError_t launch_xylo_resident(const void *spikes_in, int ternary_C, int B, int T, int Cin, int N, int w_rec, int max_spikes,
                                 uint8_t *spikes_out, int32_t *rate, void *ws, hipStream_t stream)
@@ -393,31 +349,7 @@ hipError_t launch_xylo_resident(const void *spikes_in, int ternary_C, int B, int
 #undef XP_LAUNCH
         return hipGetLastError();
     }
-    // without recurrence the neurons are independent: as few, as full workgroups as possible (N = 360 -> one of 384 threads
-    // instead of 256 + 104: every wave of the launch issues the same instructions whether its lanes are used or not)
-    const int nblocks = w_rec != 0 ? 1 : (N + 511) / 512;
-    const int per = (N + nblocks - 1) / nblocks;
-    const dim3 block(((per + 63) / 64) * 64), grid(nblocks, B);
-#define XY_LAUNCH(NQ)                                                                                                          \
-    do {                                                                                                                       \
-        if (w_rec != 0)                                                                                                        \
-            hipLaunchKernelGGL((xylo_lif_kernel<true, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, w_rec, \
-                               w.dds, w.ddm, w.dth, max_spikes, spikes_out, rate);                                             \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((xylo_lif_kernel<false, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, 0,    \
-                               w.dds, w.ddm, w.dth, max_spikes, spikes_out, rate);                                             \
-    } while (0)
-    if (nq <= 2)
-        XY_LAUNCH(2);
-    else if (nq <= 4)
-        XY_LAUNCH(4);
-    else if (nq <= 7)
-        XY_LAUNCH(7);
-    else if (nq <= 8)
-        XY_LAUNCH(8);
-    else
-        XY_LAUNCH(16);
-#undef XY_LAUNCH
+    xylo_launch_general(w, sp, ternary_C, B, T, Cin, N, w_rec, max_spikes, spikes_out, rate, nullptr, stream);
     return hipGetLastError();
 }
 
@@ -495,31 +427,8 @@ hipError_t launch_xylo_windows(const void *spikes_in, int ternary_C, int B, int 
             hipLaunchKernelGGL(xylo_lif_pk_chunks_kernel<2>, pgrid, pblock, sh.lds, stream, rs, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
                                max_spikes, rate, chunk_counts, chunk_rows);
     } else {
-        const uint8_t *sp = reinterpret_cast<const uint8_t *>(spikes_in);
-        // (the workgroups of launch_xylo_resident's general form)
-        const int nblocks = w_rec != 0 ? 1 : (N + 511) / 512;
-        const int per = (N + nblocks - 1) / nblocks;
-        const dim3 block(((per + 63) / 64) * 64), grid(nblocks, B);
-#define XY_LAUNCH(NQ)                                                                                                                 \
-    do {                                                                                                                              \
-        if (w_rec != 0)                                                                                                               \
-            hipLaunchKernelGGL((xylo_lif_chunks_kernel<true, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, w_rec, \
-                               w.dds, w.ddm, w.dth, max_spikes, rate, chunk_counts);                                                  \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((xylo_lif_chunks_kernel<false, NQ>), grid, block, 0, stream, sp, ternary_C, T, Cin, w.dW, nq, N, 0,    \
-                               w.dds, w.ddm, w.dth, max_spikes, rate, chunk_counts);                                                  \
-    } while (0)
-        if (nq <= 2)
-            XY_LAUNCH(2);
-        else if (nq <= 4)
-            XY_LAUNCH(4);
-        else if (nq <= 7)
-            XY_LAUNCH(7);
-        else if (nq <= 8)
-            XY_LAUNCH(8);
-        else
-            XY_LAUNCH(16);
-#undef XY_LAUNCH
+        xylo_launch_general(w, reinterpret_cast<const uint8_t *>(spikes_in), ternary_C, B, T, Cin, N, w_rec, max_spikes, nullptr, rate, chunk_counts,
+                            stream);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

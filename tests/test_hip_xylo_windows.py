@@ -113,6 +113,16 @@ def test_unaligned_raster_takes_the_general_kernel():
     _check_windows(net, view, True, out_t, 1100, "unaligned")
 
 
+@pytest.mark.parametrize("Cin", [8, 32])
+def test_general_kernel_with_two_and_eight_input_dwords(Cin):
+    """The general kernel unrolls its contraction over NQ packed dwords; Cin = 14, 28 and 36 elsewhere in this file reach NQ = 4, 7 and 16,
+    these reach 2 and 8.  uint8 event counts, a chunk and one frame, three trials: counts and window counts against the oracle's raster."""
+    import torch
+
+    spec, _, events, _, out_e = _case(33, Cin, 257)
+    _check_windows(_net(spec), torch.from_numpy(np.array(events)).cuda(), False, out_e, 257, f"general Cin={Cin}")
+
+
 def test_recurrent_network():
     import torch
 

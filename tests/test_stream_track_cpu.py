@@ -69,13 +69,14 @@ def test_header_declares_and_lib_binds_the_symbols():
 
 
 def test_the_chunk_walk_is_written_once():
-    """csrc/track_rows.h holds stages 1 and 2 of the one-shot and of the stream kernels, which decide the bits of every y[t][g]: the fp64
-    matrix-core product and the complex magnitude occur there and in neither kernel file, and both objects are rebuilt when the header
-    changes."""
+    """csrc/track_rows.h holds stages 1 and 2 of the one-shot, the band and the stream kernels, which decide the bits of every y[t][g], once:
+    with the comments stripped the fp64 matrix-core product occurs there three times (membrane loop, SNN product, complex product) and the
+    complex magnitude once, and neither occurs in a kernel file; both objects are rebuilt when the header changes."""
     csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
     text = {f: open(os.path.join(csrc, f)).read() for f in ("track_rows.h", "track.hip", "stream_track.hip", "Makefile")}
-    for word in ("mfma_f64_16x16x4f64", "hypot("):
-        assert word in text["track_rows.h"], word
+    code = re.sub(r"//[^\n]*|/\*.*?\*/", "", text["track_rows.h"], flags=re.S)
+    for word, times in (("mfma_f64_16x16x4f64", 3), ("hypot(", 1)):
+        assert code.count(word) == times, word
         assert word not in text["track.hip"] and word not in text["stream_track.hip"], word
     for f in ("track.hip", "stream_track.hip"):
         assert '#include "track_rows.h"' in text[f], f

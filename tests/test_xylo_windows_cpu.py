@@ -147,24 +147,27 @@ def test_cli_routes_windowed_noisy_xylo_to_the_xylo_sweep(monkeypatch, capsys):
     assert seen["call"][1:3] == (2048, None) and seen["call"][3]["num_sim"] == 100
 
 
-def test_the_general_chunk_kernel_is_the_general_kernel_line_for_line():
-    """csrc/xylo.hip states the general walk twice so that xylo_lif_kernel keeps its instructions: the chunk-count form is
-    the same text without the raster's two lines and with the three lines marked CHUNKS.  The packed form shares its walk (XpLif) and its
-    flush (xp_chunk_done of xylo_rows.h, which the stream's tracking kernel calls too); no window kernel uses an atomic."""
+def test_the_general_walk_is_written_once():
+    """csrc/xylo.hip defines the general walk once: xylo_lif_kernel<REC, NQ, CHUNKS>, whose chunk-count form is the lines marked CHUNKS under
+    `if constexpr (CHUNKS)` and whose raster lines stand under `if constexpr (!CHUNKS)`; there is no second kernel to keep in step.  The
+    packed form shares its walk (XpLif) and its flush (xp_chunk_done of xylo_rows.h, which the stream's tracking kernel calls too); no
+    window kernel uses an atomic."""
     csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
     text = open(os.path.join(csrc, "xylo.hip")).read()
-
-    def body(name):
-        at = text.index(f"void {name}(")
-        start = text.index("\n{\n", at) + 3
-        return text[start : text.index("\n}\n", start)].split("\n")
-
-    plain, chunks = body("xylo_lif_kernel"), body("xylo_lif_chunks_kernel")
-    raster = [ln for ln in plain if re.search(r"\bob\b", ln)]
-    assert len(raster) == 2 and "spikes_out" in raster[0] and "ob[" in raster[1], raster
-    marked = [ln for ln in chunks if "// CHUNKS" in ln]
-    assert len(marked) == 3 and any("chunk_counts[" in ln for ln in marked)
-    assert [ln for ln in plain if ln not in raster] == [ln for ln in chunks if ln not in marked]
+    assert len(re.findall(r"\bvoid xylo_lif_kernel\(", text)) == 1 and "xylo_lif_chunks_kernel" not in text
+    assert re.search(r"template <bool REC, int NQ, bool CHUNKS = false>\s*__global__ [^\n]*void xylo_lif_kernel\(", text)
+    at = text.index("void xylo_lif_kernel(")
+    start = text.index("\n{\n", at) + 3
+    body = text[start : text.index("\n}\n", start)].split("\n")
+    raster = [i for i, ln in enumerate(body) if re.search(r"\bob\b", ln) and "ob = nullptr" not in ln]
+    assert len(raster) == 2 and "spikes_out" in body[raster[0]] and "ob[" in body[raster[1]], raster
+    for i in raster:  # each raster line is the statement of an `if constexpr (!CHUNKS)`
+        assert "if constexpr (!CHUNKS)" in body[i] or body[i - 1].strip() == "if constexpr (!CHUNKS)", body[i]
+    marked = [i for i, ln in enumerate(body) if "// CHUNKS" in ln]
+    assert len(marked) == 3 and any("chunk_counts[" in body[i] for i in marked)
+    # the count of the open chunk is a declaration; the flush, two adjacent lines, is the block of an `if constexpr (CHUNKS)`
+    assert "int chunk_total = 0;" in body[marked[0]] and marked[2] == marked[1] + 1
+    assert body[marked[1] - 1].strip() == "if constexpr (CHUNKS) {" and body[marked[2] + 1].strip() == "}"
     rows = open(os.path.join(csrc, "xylo_rows.h")).read()
     stream = open(os.path.join(csrc, "stream_xylo.hip")).read()
     assert "void xp_chunk_done(" in rows and "xp_chunk_done(lif" in text and "xp_chunk_done(lif" in stream and "sx_chunk_done" not in stream
