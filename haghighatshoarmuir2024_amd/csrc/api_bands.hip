@@ -1,8 +1,8 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations): the wideband batch entries -- the
 // filterbank, the band sum, and the pipelines of F bands, SNN (one chain per band) and complex (every band's chain in one batch), with
-// their moving-target tracking read-out (a DoA per frame over all bands).
-#include "api_internal.h"
-#include "track_bands.h"
+// the entries of their moving-target tracking read-out (a DoA per frame over all bands): the checks and the front ends, in front of the
+// layout and the run of api_track.hip.  What the plans of a set must share: api_sets.h.
+#include "api_sets.h"
 
 using namespace micloc;
 
@@ -50,16 +50,10 @@ struct BandsLayout {
 // argument checks of the band pipeline in the header's order; fills the layout
 int bands_layout(const micloc_plan *const *plans, int F, int B, int T, int window, int hop, bool own_band_power, BandsLayout *L)
 {
-    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || T < 1 || window < 0 || hop < 0) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]->d_ntab || !plans[f]->d_W) return MICLOC_ERR_NOT_SET;
+    if (set_pointers(plans, F) != MICLOC_OK || bad_batch(B) || T < 1 || window < 0 || hop < 0) return MICLOC_ERR_INVALID;
+    if (set_tables(plans, F, true, true) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
+    if (set_shares(plans, F, SET_GRID | SET_REAL) != MICLOC_OK) return MICLOC_ERR_SHAPE;
     const micloc_plan *p0 = plans[0];
-    for (int f = 0; f < F; ++f) {
-        const micloc_plan *p = plans[f];
-        if (p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out || p->W_is_complex) return MICLOC_ERR_SHAPE;
-    }
     L->nW = 1;
     if (window > 0) {
         if (hop == 0) hop = window;
@@ -163,19 +157,10 @@ struct CBandsLayout {
 // argument checks of the complex band pipeline in the header's order; fills the layout
 int cbands_layout(const micloc_plan *const *plans, int F, int B, int T, int window, int hop, bool own_band_power, CBandsLayout *L)
 {
-    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || bad_batch(F * B) || T < 1 || window < 0 || hop < 0) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]->d_W) return MICLOC_ERR_NOT_SET;
+    if (set_pointers(plans, F) != MICLOC_OK || bad_batch(B) || bad_batch(F * B) || T < 1 || window < 0 || hop < 0) return MICLOC_ERR_INVALID;
+    if (set_tables(plans, F, true, false) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
     const micloc_plan *p0 = plans[0];
-    for (int f = 0; f < F; ++f) {
-        const micloc_plan *p = plans[f];
-        if (!p->W_is_complex || p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out || p->W.GT != p0->W.GT || p->W.CT != p0->W.CT ||
-            p->L != p0->L || p->taps_host != p0->taps_host || p->iir.n != p0->iir.n)
-            return MICLOC_ERR_SHAPE;
-    }
-    if ((unsigned long long)T * (unsigned long long)p0->M > 0xffffffffull) return MICLOC_ERR_SHAPE;  // (the one-shot loaders index a trial with 32 bits)
+    if (set_shares(plans, F, SET_GRID | SET_COMPLEX | SET_CHAIN) != MICLOC_OK || trial_over_32_bits(p0, T)) return MICLOC_ERR_SHAPE;
     L->nW = 1;
     L->q = 0;
     if (window > 0) {
@@ -282,16 +267,9 @@ int micloc_beamformer_pipeline_bands_f64(const micloc_plan *const *plans, int F,
 int micloc_beamformer_bands_bandpass_f64(const micloc_plan *const *plans, int F, const double *xf, int B, int T, double *h, double *pre, int Ts,
                                          int with_stht, int one_launch, void *stream)
 {
-    if (!plans || !xf || !h || !pre) return MICLOC_ERR_INVALID;
-    if (F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || bad_batch(F * B) || T < 1) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]) return MICLOC_ERR_INVALID;
+    if (!xf || !h || !pre || set_pointers(plans, F) != MICLOC_OK || bad_batch(B) || bad_batch(F * B) || T < 1) return MICLOC_ERR_INVALID;
     const micloc_plan *p0 = plans[0];
-    for (int f = 0; f < F; ++f) {
-        const micloc_plan *p = plans[f];
-        if (p->device != p0->device || p->M != p0->M || p->L != p0->L || p->taps_host != p0->taps_host || p->iir.n != p0->iir.n) return MICLOC_ERR_SHAPE;
-    }
-    if (Ts != micloc_padded_T(T) || (unsigned long long)T * (unsigned long long)p0->M > 0xffffffffull) return MICLOC_ERR_SHAPE;
+    if (set_shares(plans, F, SET_FRONT) != MICLOC_OK || Ts != micloc_padded_T(T) || trial_over_32_bits(p0, T)) return MICLOC_ERR_SHAPE;
     DeviceGuard guard(p0->device);
     return cbands_front(plans, F, xf, B, T, Ts, h, pre, with_stht != 0, one_launch != 0, (hipStream_t)stream);
 }
@@ -301,150 +279,37 @@ int micloc_beamformer_bands_bandpass_f64(const micloc_plan *const *plans, int F,
 // ---- wideband moving-target tracking: a DoA per frame over all bands (track.hip; the rule: include/micloc_hip.h) ---------------------------
 namespace {
 
-// Workspace of the band tracking calls: [ xf | the front end: h, then (SNN) the encoder scratch, shared by the bands, which run one after
-// the other on the stream, and every band's raster -- (complex) every band's planar rows | the tracking region ].  Tracking region of fused
-// sets: the (value, index) pairs, the only part that knows G.  Other sets (the two-step route): one band's y, the band sum m and its
-// envelope for as many trials at a time as the caller's buffer holds, one at least.
-struct BandsTrackLayout {
-    size_t xf, h, pre, scratch, spikes, raster, base, per_trial, min_total;  // raster: bytes of one band's raster; per_trial == 0: fused
-    int NKmax;
-};
-
 // the argument checks of the header's order that read no plan: everything but `plans` itself may be a dummy
 int bands_track_args(const micloc_plan *const *plans, int F, int B, int T)
 {
-    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || bad_batch(F * B)) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]) return MICLOC_ERR_INVALID;
+    if (set_pointers(plans, F) != MICLOC_OK || bad_batch(B) || bad_batch(F * B)) return MICLOC_ERR_INVALID;
     if (T < 1 || (long long)B * T > 0x7fffffffll) return MICLOC_ERR_SHAPE;
     return MICLOC_OK;
 }
 
-bool bands_track_fused(const micloc_plan *const *plans, int F, bool cpx)
+// what the plans of a set must hold and share, then the layout; bands_track_args has passed
+int bands_track_layout(const micloc_plan *const *plans, int F, bool cpx, int B, int T, TrackLayout *L)
 {
-    const BeamformW *W[MICLOC_MAX_BANDS];
-    const NeuronTab *nt[MICLOC_MAX_BANDS];
-    for (int f = 0; f < F; ++f) {
-        W[f] = &plans[f]->W;
-        nt[f] = &plans[f]->ntab;
-    }
-    return track_bands_fused_eligible(W, nt, F, cpx);
-}
-
-// what the plans of a set must share, then the layout; bands_track_args has passed
-int bands_track_layout(const micloc_plan *const *plans, int F, bool cpx, int B, int T, BandsTrackLayout *L)
-{
-    const micloc_plan *p0 = plans[0];
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]->d_W) return MICLOC_ERR_NOT_SET;  // (as the other band entries: in front of the shapes, which a plan without bf_mat has not)
-    for (int f = 0; f < F; ++f) {
-        const micloc_plan *p = plans[f];
-        if (p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out) return MICLOC_ERR_SHAPE;
-        if ((p->W_is_complex != 0) != cpx) return MICLOC_ERR_SHAPE;  // a bf_mat of the other kind
-    }
-    for (int f = 0; f < F; ++f)
-        if (!cpx && !plans[f]->d_ntab) return MICLOC_ERR_NOT_SET;
-    if (cpx) {  // one STHT launch and one band-pass launch for all bands' chains: what micloc_beamformer_pipeline_bands_f64 asks for
-        for (int f = 0; f < F; ++f) {
-            const micloc_plan *p = plans[f];
-            if (p->W.GT != p0->W.GT || p->W.CT != p0->W.CT || p->L != p0->L || p->taps_host != p0->taps_host || p->iir.n != p0->iir.n)
-                return MICLOC_ERR_SHAPE;
-        }
-        if ((unsigned long long)T * (unsigned long long)p0->M > 0xffffffffull) return MICLOC_ERR_SHAPE;
-    }
-    const size_t Ts = (size_t)micloc_padded_T(T);
-    size_t off = 0;
-    L->xf = off;
-    off += align256((size_t)F * B * T * p0->M * sizeof(double));
-    L->h = off;
-    L->NKmax = 0;
-    if (cpx) {
-        const size_t planar = align256((size_t)F * B * p0->C * Ts * sizeof(double));
-        off += planar;
-        L->pre = off;
-        off += planar;
-    } else {
-        off += align256((size_t)B * p0->C * Ts * sizeof(double));
-        size_t scratch = 0;
-        for (int f = 0; f < F; ++f) {
-            const size_t n = rzcc_scratch_bytes(B * p0->C, T, plans[f]->robust_width, plans[f]->chunk_frames);
-            if (n > scratch) scratch = n;
-            if (plans[f]->ntab.NK > L->NKmax) L->NKmax = plans[f]->ntab.NK;
-        }
-        L->scratch = off;
-        off += align256(scratch);
-        L->spikes = off;
-        L->raster = align256((size_t)B * T * p0->C);
-        off += (size_t)F * L->raster;
-    }
-    L->base = off;
-    if (bands_track_fused(plans, F, cpx)) {
-        L->per_trial = 0;
-        L->min_total = L->base + align256(track_pairs_bytes(B, T, p0->G_out));
-    } else {
-        const size_t cell = (size_t)T * p0->G_out * sizeof(double);
-        L->per_trial = align256(cpx ? 2 * cell : cell) + 2 * align256(cell);
-        L->min_total = L->base + L->per_trial;
-    }
-    return MICLOC_OK;
-}
-
-// src[f]: band f's raster [B][T][C] (real bf_mat) or planar band-passed rows [B][C][Ts] (complex)
-int bands_track_run(const micloc_plan *const *plans, int F, bool cpx, const void *const *src, int B, int T, int Ts, double a_rise, double i_rise,
-                    double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, const BandsTrackLayout &L,
-                    hipStream_t st)
-{
-    const micloc_plan *p0 = plans[0];
-    const int G = p0->G_out, C = p0->C;
-    unsigned char *reg = static_cast<unsigned char *>(ws) + L.base;
-    if (L.per_trial == 0) {
-        TrackBandsArgs a{};
-        for (int f = 0; f < F; ++f) {
-            a.src[f] = src[f];
-            a.tab[f] = plans[f]->ntab.tab;
-            a.Wp[f] = plans[f]->W.Wp;
-            a.NK[f] = plans[f]->ntab.NK;
-            a.GT[f] = plans[f]->W.GT;
-        }
-        HIP_TRY(launch_track_bands_fused(a, F, L.NKmax, cpx, C, B, T, Ts, G, a_rise, i_rise, a_fall, index, peak_env, env_last, reg, st));
-        return MICLOC_OK;
-    }
-    // the two-step route, over sub-batches of independent trials: per band beamforming with y stored and the band sum m by the rule, then
-    // envelope_kernel on m and the row read-out
-    const size_t fit = (ws_bytes - L.base) / L.per_trial;
-    const int nb_max = fit > (size_t)B ? B : (int)fit;
-    const size_t cell = (size_t)T * G * sizeof(double);
-    for (int b0 = 0; b0 < B; b0 += nb_max) {
-        const int nb = B - b0 < nb_max ? B - b0 : nb_max;
-        double *y = reinterpret_cast<double *>(reg);
-        double *m = reinterpret_cast<double *>(reg + (size_t)nb * align256(cpx ? 2 * cell : cell));
-        double *env = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(m) + (size_t)nb * align256(cell));
-        for (int f = 0; f < F; ++f) {
-            const micloc_plan *p = plans[f];
-            int nch = 0;
-            if (cpx)
-                HIP_TRY(launch_planar_beamform(p->W, static_cast<const double *>(src[f]) + (size_t)b0 * C * Ts, nb, T, Ts, y, 1, nullptr, st, &nch));
-            else
-                HIP_TRY(launch_lif_beamform(p->W, p->ntab, static_cast<const int8_t *>(src[f]) + (size_t)b0 * T * C, nb, T, y, nullptr, st, &nch));
-            HIP_TRY(launch_track_bands_magnitude(y, cpx, (size_t)nb * T * G, f == 0, m, st));
-        }
-        HIP_TRY(launch_envelope_track(m, MICLOC_ENV_F64, nb, T, G, a_rise, i_rise, a_fall, env, nullptr, st));
-        HIP_TRY(launch_track_rows(env, nb, T, G, index + (size_t)b0 * T, peak_env ? peak_env + (size_t)b0 * T : nullptr,
-                                  env_last ? env_last + (size_t)b0 * G : nullptr, st));
-    }
+    // (bf_mat as the other band entries: in front of the shapes, which a plan without bf_mat has not)
+    if (set_tables(plans, F, true, false) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
+    if (set_shares(plans, F, SET_GRID | (cpx ? SET_COMPLEX : SET_REAL)) != MICLOC_OK) return MICLOC_ERR_SHAPE;
+    if (!cpx && set_tables(plans, F, false, true) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
+    // complex: one STHT launch and one band-pass launch for all bands' chains, what micloc_beamformer_pipeline_bands_f64 asks for
+    if (cpx && (set_shares(plans, F, SET_CHAIN) != MICLOC_OK || trial_over_32_bits(plans[0], T))) return MICLOC_ERR_SHAPE;
+    *L = track_layout(plans, F, cpx, true, B, T);
     return MICLOC_OK;
 }
 
 size_t bands_track_workspace(const micloc_plan *const *plans, int F, bool cpx, int B, int T)
 {
-    BandsTrackLayout L{};
+    TrackLayout L{};
     if (bands_track_args(plans, F, B, T) != MICLOC_OK || bands_track_layout(plans, F, cpx, B, T, &L) != MICLOC_OK) return 0;
     return L.min_total;
 }
 
 int bands_track_is_fused(const micloc_plan *const *plans, int F, bool cpx)
 {
-    BandsTrackLayout L{};
+    TrackLayout L{};
     int rc = bands_track_args(plans, F, 1, 1);
     if (rc == MICLOC_OK) rc = bands_track_layout(plans, F, cpx, 1, 1, &L);
     if (rc != MICLOC_OK) return rc;
@@ -453,7 +318,7 @@ int bands_track_is_fused(const micloc_plan *const *plans, int F, bool cpx)
 
 // the stage entries and the tails of the pipeline entries.  in: the caller's input array (checked for NULL only)
 int bands_track_checked(const micloc_plan *const *plans, int F, bool cpx, const void *in, int B, int T, const int32_t *index, const void *ws,
-                        size_t ws_bytes, BandsTrackLayout *L)
+                        size_t ws_bytes, TrackLayout *L)
 {
     if (!plans || !in || !index) return MICLOC_ERR_INVALID;
     int rc = bands_track_args(plans, F, B, T);
@@ -484,27 +349,27 @@ int micloc_beamformer_bands_track_is_fused(const micloc_plan *const *plans, int 
 int micloc_lif_beamform_bands_track_f64(const micloc_plan *const *plans, int F, const int8_t *spikes, int B, int T, double a_rise, double i_rise,
                                         double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    BandsTrackLayout L{};
+    TrackLayout L{};
     const int rc = bands_track_checked(plans, F, false, spikes, B, T, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     DeviceGuard guard(plans[0]->device);
     const void *src[MICLOC_MAX_BANDS];
     for (int f = 0; f < F; ++f) src[f] = spikes + (size_t)f * B * T * plans[0]->C;
-    return bands_track_run(plans, F, false, src, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
+    return track_run(plans, F, false, true, src, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
 }
 
 int micloc_beamform_c128_bands_track_f64(const micloc_plan *const *plans, int F, const double *pre, int B, int T, int Ts, double a_rise,
                                          double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws,
                                          size_t ws_bytes, void *stream)
 {
-    BandsTrackLayout L{};
+    TrackLayout L{};
     const int rc = bands_track_checked(plans, F, true, pre, B, T, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
     DeviceGuard guard(plans[0]->device);
     const void *src[MICLOC_MAX_BANDS];
     for (int f = 0; f < F; ++f) src[f] = pre + (size_t)f * B * plans[0]->C * Ts;
-    return bands_track_run(plans, F, true, src, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
+    return track_run(plans, F, true, true, src, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
 }
 
 // the filterbank, per band the first two launches of micloc_snn_pipeline_f64 on its slice, then the tracking read-out of the F rasters
@@ -516,7 +381,7 @@ int micloc_snn_pipeline_bands_track_f64(const micloc_plan *const *plans, int F, 
     FilterbankCoef co;
     int rc = filterbank_coef(fb_b, fb_a, F, fb_n, &co);
     if (rc != MICLOC_OK) return rc;
-    BandsTrackLayout L{};
+    TrackLayout L{};
     rc = bands_track_checked(plans, F, false, x, B, T, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     const micloc_plan *p0 = plans[0];
@@ -532,7 +397,7 @@ int micloc_snn_pipeline_bands_track_f64(const micloc_plan *const *plans, int F, 
         if (fr.rc != MICLOC_OK) return fr.rc;
         src[f] = fr.src;
     }
-    return bands_track_run(plans, F, false, src, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, st);
+    return track_run(plans, F, false, true, src, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, st);
 }
 
 // the filterbank, the STHT and the band-pass of all bands' chains as one batch (micloc_beamformer_pipeline_bands_f64's), then the
@@ -545,7 +410,7 @@ int micloc_beamformer_pipeline_bands_track_f64(const micloc_plan *const *plans, 
     FilterbankCoef co;
     int rc = filterbank_coef(fb_b, fb_a, F, fb_n, &co);
     if (rc != MICLOC_OK) return rc;
-    BandsTrackLayout L{};
+    TrackLayout L{};
     rc = bands_track_checked(plans, F, true, x, B, T, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     const micloc_plan *p0 = plans[0];
@@ -558,7 +423,7 @@ int micloc_beamformer_pipeline_bands_track_f64(const micloc_plan *const *plans, 
     if (rc != MICLOC_OK) return rc;
     const void *src[MICLOC_MAX_BANDS];
     for (int f = 0; f < F; ++f) src[f] = pre + (size_t)f * B * p0->C * Ts;
-    return bands_track_run(plans, F, true, src, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, st);
+    return track_run(plans, F, true, true, src, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, st);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations): recordings that arrive tile by tile --
 // the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream (each with or without the window read-out and the tracked read-out), the complex stream of F bands, and
 // the MUSIC stream.
-#include "api_internal.h"
+#include "api_sets.h"
 #include "stream_music.h"
 #include "stream_track.h"
 
@@ -605,18 +605,10 @@ constexpr size_t SCB_BANDS_WORDS = 64;
 int scb_args(const micloc_plan *const *plans, int F, int B, int max_tile, ScbArgs *s)
 {
     *s = ScbArgs{};
-    if (!plans || F < 1 || F > MICLOC_MAX_BANDS || bad_batch(B) || bad_batch(F * B) || max_tile < 0) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]) return MICLOC_ERR_INVALID;
-    for (int f = 0; f < F; ++f)
-        if (!plans[f]->d_W) return MICLOC_ERR_NOT_SET;
+    if (set_pointers(plans, F) != MICLOC_OK || bad_batch(B) || bad_batch(F * B) || max_tile < 0) return MICLOC_ERR_INVALID;
+    if (set_tables(plans, F, true, false) != MICLOC_OK) return MICLOC_ERR_NOT_SET;
+    if (set_shares(plans, F, SET_GRID | SET_COMPLEX | SET_CHAIN) != MICLOC_OK) return MICLOC_ERR_SHAPE;
     const micloc_plan *p0 = plans[0];
-    for (int f = 0; f < F; ++f) {
-        const micloc_plan *p = plans[f];
-        if (!p->W_is_complex || p->device != p0->device || p->M != p0->M || p->G_out != p0->G_out || p->W.GT != p0->W.GT || p->W.CT != p0->W.CT ||
-            p->L != p0->L || p->taps_host != p0->taps_host || p->iir.n != p0->iir.n)
-            return MICLOC_ERR_SHAPE;
-    }
     s->FB = F * B;
     const int rc = sc_args(p0, s->FB, max_tile, &s->a);  // (one chunk length: it depends on CT and GT only, which the plans share)
     if (rc != MICLOC_OK) return rc;

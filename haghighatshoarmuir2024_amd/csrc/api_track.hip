@@ -1,8 +1,10 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations):
-// moving-target tracking, the per-step arg-max of the envelope of the beamformer output (track.hip) and of the Xylo network's spike
-// counts (the tracking form of the packed walk, stream_xylo.hip) -- and, beside that one-shot Xylo read-out, the other: counts, rate and
-// peak per time window (xylo.hip, sweep.hip).
-#include "api_internal.h"
+// moving-target tracking, the per-step arg-max of the envelope of the beamformer output (track.hip) -- the workspace layout and the run of a
+// set of plans, which the wideband entries of api_bands.hip share (api_sets.h), and the entries of a single plan, the set of one -- and of
+// the Xylo network's spike counts (the tracking form of the packed walk, stream_xylo.hip); beside that one-shot Xylo read-out, the other:
+// counts, rate and peak per time window (xylo.hip, sweep.hip).
+#include "api_sets.h"
+#include "track_bands.h"
 #include "xylo_track.h"
 #include "xylo_windows.h"
 
@@ -10,78 +12,144 @@ using namespace micloc;
 
 namespace {
 
-// Workspace of the four tracking calls: [ what the first two pipeline stages need | the tracking region ] -- the STHT output, then the
-// encoder scratch and the raster (real bf_mat) or the band-passed rows (complex); not the pipeline's per-chunk sums, not the
-// planar array the plan's kind never writes.  Tracking region of fused plans: the (value, index) pairs.  Other plans (the two-step
-// route): y and its envelope for as many trials at a time as the caller's buffer holds, one at least.
-struct TrackLayout : FrontOffsets {
-    size_t base, per_trial, min_total;  // per_trial == 0: fused
-};
-
-TrackLayout track_layout(const micloc_plan *p, int B, int T)
+// the two-step route's loop: body(b0, nb) for as many trials at a time as the caller's buffer holds (fit), one at least
+template <class Body>
+int sub_batches(int B, size_t fit, Body body)
 {
-    TrackLayout t{};
-    const size_t planar = align256((size_t)B * p->C * micloc_padded_T(T) * sizeof(double));
-    size_t off = 0;
-    t.h = off;
-    off += planar;
-    if (p->W_is_complex) {
-        t.pre = off;
-        off += planar;
-    } else {
-        t.scratch = off;
-        off += align256(rzcc_scratch_bytes(B * p->C, T, p->robust_width, p->chunk_frames));
-        t.spikes = off;
-        off += align256((size_t)B * T * p->C);
-    }
-    t.base = off;
-    if (track_fused_eligible(p->W, p->ntab, p->W_is_complex)) {
-        t.min_total = t.base + align256(track_pairs_bytes(B, T, p->G_out));
-    } else {
-        const size_t cell = (size_t)T * p->G_out * sizeof(double);
-        t.per_trial = align256(p->W_is_complex ? 2 * cell : cell) + align256(cell);
-        t.min_total = t.base + t.per_trial;
-    }
-    return t;
-}
-
-// the argument checks of a tracking entry; in: its input array
-int track_args(const micloc_plan *p, const void *in, int B, int T, const int32_t *index)
-{
-    if (!p || !index || bad_batch(B)) return MICLOC_ERR_INVALID;
-    if (T < 1 || (long long)B * T > 0x7fffffffll) return MICLOC_ERR_SHAPE;
-    return in ? MICLOC_OK : MICLOC_ERR_INVALID;
-}
-
-// src: the spike raster (real bf_mat) or the planar band-passed rows [B][C][Ts] (complex)
-int track_run(const micloc_plan *p, const void *src, int B, int T, int Ts, double a_rise, double i_rise, double a_fall, int32_t *index,
-              double *peak_env, double *env_last, void *ws, size_t ws_bytes, const TrackLayout &lay, hipStream_t st)
-{
-    const int G = p->G_out, cpx = p->W_is_complex;
-    unsigned char *reg = static_cast<unsigned char *>(ws) + lay.base;
-    if (lay.per_trial == 0) {
-        HIP_TRY(launch_track_fused(p->W, p->ntab, cpx, src, B, T, Ts, G, a_rise, i_rise, a_fall, index, peak_env, env_last, reg, st));
-        return MICLOC_OK;
-    }
-    // the two-step route, over sub-batches of independent trials: beamforming with y stored, envelope_kernel, the row read-out
-    size_t fit = (ws_bytes - lay.base) / lay.per_trial;
     const int nb_max = fit > (size_t)B ? B : (int)fit;
-    const size_t cell = (size_t)T * G * sizeof(double);
     for (int b0 = 0; b0 < B; b0 += nb_max) {
-        const int nb = B - b0 < nb_max ? B - b0 : nb_max;
-        double *y = reinterpret_cast<double *>(reg);
-        double *env = reinterpret_cast<double *>(reg + (size_t)nb * align256(cpx ? 2 * cell : cell));
-        int nch = 0;
-        if (cpx)
-            HIP_TRY(launch_planar_beamform(p->W, static_cast<const double *>(src) + (size_t)b0 * p->C * Ts, nb, T, Ts, y, 1, nullptr, st, &nch));
-        else
-            HIP_TRY(launch_lif_beamform(p->W, p->ntab, static_cast<const int8_t *>(src) + (size_t)b0 * T * p->C, nb, T, y, nullptr, st, &nch));
-        HIP_TRY(launch_envelope_track(y, cpx ? MICLOC_ENV_C128 : MICLOC_ENV_F64, nb, T, G, a_rise, i_rise, a_fall, env, nullptr, st));
-        HIP_TRY(launch_track_rows(env, nb, T, G, index + (size_t)b0 * T, peak_env ? peak_env + (size_t)b0 * T : nullptr,
-                                  env_last ? env_last + (size_t)b0 * G : nullptr, st));
+        const int rc = body(b0, B - b0 < nb_max ? B - b0 : nb_max);
+        if (rc != MICLOC_OK) return rc;
     }
     return MICLOC_OK;
 }
+
+// the two-step route's tail for the trials b0 .. b0 + nb: envelope_kernel on `in` (kind: MICLOC_ENV_*), then the row read-out
+int envelope_rows(const void *in, int kind, int b0, int nb, int T, int G, double a_rise, double i_rise, double a_fall, double *env, int32_t *index,
+                  double *peak_env, double *env_last, hipStream_t st)
+{
+    HIP_TRY(launch_envelope_track(in, kind, nb, T, G, a_rise, i_rise, a_fall, env, nullptr, st));
+    HIP_TRY(launch_track_rows(env, nb, T, G, index + (size_t)b0 * T, peak_env ? peak_env + (size_t)b0 * T : nullptr,
+                              env_last ? env_last + (size_t)b0 * G : nullptr, st));
+    return MICLOC_OK;
+}
+
+bool bands_track_fused(const micloc_plan *const *plans, int F, bool cpx)
+{
+    const BeamformW *W[MICLOC_MAX_BANDS];
+    const NeuronTab *nt[MICLOC_MAX_BANDS];
+    for (int f = 0; f < F; ++f) {
+        W[f] = &plans[f]->W;
+        nt[f] = &plans[f]->ntab;
+    }
+    return track_bands_fused_eligible(W, nt, F, cpx);
+}
+
+// the checks and the layout of the four single-plan entries in the header's order; in: the entry's input array, Ts: the planar stage
+// entry's argument (else NULL)
+int track_checked(const micloc_plan *p, bool cpx, const void *in, int B, int T, const int *Ts, const int32_t *index, const void *ws,
+                  size_t ws_bytes, TrackLayout *L)
+{
+    if (!p || !index || bad_batch(B)) return MICLOC_ERR_INVALID;
+    if (T < 1 || (long long)B * T > 0x7fffffffll) return MICLOC_ERR_SHAPE;
+    if (!in) return MICLOC_ERR_INVALID;
+    if (Ts && *Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
+    const int rc = plan_kind(p, cpx);
+    if (rc != MICLOC_OK) return rc;
+    *L = track_layout(&p, 1, cpx, false, B, T);
+    return bad_ws(ws, ws_bytes, L->min_total) ? MICLOC_ERR_WORKSPACE : MICLOC_OK;
+}
+
+}  // namespace
+
+namespace micloc {
+
+TrackLayout track_layout(const micloc_plan *const *plans, int F, bool cpx, bool banded, int B, int T)
+{
+    const micloc_plan *p0 = plans[0];
+    const size_t Ts = (size_t)micloc_padded_T(T);
+    TrackLayout L{};
+    size_t off = 0;
+    L.xf = off;
+    if (banded) off += align256((size_t)F * B * T * p0->M * sizeof(double));
+    L.h = off;
+    if (cpx) {
+        const size_t planar = align256((size_t)F * B * p0->C * Ts * sizeof(double));
+        off += planar;
+        L.pre = off;
+        off += planar;
+    } else {
+        off += align256((size_t)B * p0->C * Ts * sizeof(double));
+        size_t scratch = 0;
+        for (int f = 0; f < F; ++f) {
+            const size_t n = rzcc_scratch_bytes(B * p0->C, T, plans[f]->robust_width, plans[f]->chunk_frames);
+            if (n > scratch) scratch = n;
+            if (plans[f]->ntab.NK > L.NKmax) L.NKmax = plans[f]->ntab.NK;
+        }
+        L.scratch = off;
+        off += align256(scratch);
+        L.spikes = off;
+        L.raster = align256((size_t)B * T * p0->C);
+        off += (size_t)F * L.raster;
+    }
+    L.base = off;
+    if (banded ? bands_track_fused(plans, F, cpx) : track_fused_eligible(p0->W, p0->ntab, cpx)) {
+        L.min_total = L.base + align256(track_pairs_bytes(B, T, p0->G_out));
+    } else {
+        const size_t cell = (size_t)T * p0->G_out * sizeof(double);
+        L.per_trial = align256(cpx ? 2 * cell : cell) + (banded ? 2 : 1) * align256(cell);
+        L.min_total = L.base + L.per_trial;
+    }
+    return L;
+}
+
+int track_run(const micloc_plan *const *plans, int F, bool cpx, bool banded, const void *const *src, int B, int T, int Ts, double a_rise,
+              double i_rise, double a_fall, int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, const TrackLayout &L,
+              hipStream_t st)
+{
+    const micloc_plan *p0 = plans[0];
+    const int G = p0->G_out, C = p0->C;
+    unsigned char *reg = static_cast<unsigned char *>(ws) + L.base;
+    if (L.per_trial == 0 && !banded) {
+        HIP_TRY(launch_track_fused(p0->W, p0->ntab, cpx, src[0], B, T, Ts, G, a_rise, i_rise, a_fall, index, peak_env, env_last, reg, st));
+        return MICLOC_OK;
+    }
+    if (L.per_trial == 0) {
+        TrackBandsArgs a{};
+        for (int f = 0; f < F; ++f) {
+            a.src[f] = src[f];
+            a.tab[f] = plans[f]->ntab.tab;
+            a.Wp[f] = plans[f]->W.Wp;
+            a.NK[f] = plans[f]->ntab.NK;
+            a.GT[f] = plans[f]->W.GT;
+        }
+        HIP_TRY(launch_track_bands_fused(a, F, L.NKmax, cpx, C, B, T, Ts, G, a_rise, i_rise, a_fall, index, peak_env, env_last, reg, st));
+        return MICLOC_OK;
+    }
+    // the two-step route, over sub-batches of independent trials
+    const size_t cell = (size_t)T * G * sizeof(double);
+    return sub_batches(B, (ws_bytes - L.base) / L.per_trial, [&](int b0, int nb) {
+        double *y = reinterpret_cast<double *>(reg);
+        unsigned char *after_y = reg + (size_t)nb * align256(cpx ? 2 * cell : cell);
+        double *m = reinterpret_cast<double *>(after_y);  // (banded)
+        double *env = reinterpret_cast<double *>(banded ? after_y + (size_t)nb * align256(cell) : after_y);
+        for (int f = 0; f < F; ++f) {
+            const micloc_plan *p = plans[f];
+            int nch = 0;
+            if (cpx)
+                HIP_TRY(launch_planar_beamform(p->W, static_cast<const double *>(src[f]) + (size_t)b0 * C * Ts, nb, T, Ts, y, 1, nullptr, st, &nch));
+            else
+                HIP_TRY(launch_lif_beamform(p->W, p->ntab, static_cast<const int8_t *>(src[f]) + (size_t)b0 * T * C, nb, T, y, nullptr, st, &nch));
+            if (banded) HIP_TRY(launch_track_bands_magnitude(y, cpx, (size_t)nb * T * G, f == 0, m, st));
+        }
+        return envelope_rows(banded ? m : y, !banded && cpx ? MICLOC_ENV_C128 : MICLOC_ENV_F64, b0, nb, T, G, a_rise, i_rise, a_fall, env, index,
+                             peak_env, env_last, st);
+    });
+}
+
+}  // namespace micloc
+
+namespace {
 
 // ---- Xylo ----
 // ws of micloc_xylo_lif_track_i16.  Fused networks: the pairs.  Others (the two-step route): the uint8 raster [T][N] and its envelope
@@ -145,26 +213,20 @@ int micloc_xylo_lif_track_i16(const void *spikes_in, int ternary_C, int B, int T
         return MICLOC_OK;
     }
     // the two-step route over sub-batches of independent trials: the LIF with its raster stored, envelope_kernel, the row read-out
-    const size_t fit = ws_bytes / lay.per_trial;
-    const int nb_max = fit > (size_t)B ? B : (int)fit;
     const int Crow = ternary_C > 0 ? ternary_C : Cin;
-    for (int b0 = 0; b0 < B; b0 += nb_max) {
-        const int nb = B - b0 < nb_max ? B - b0 : nb_max;
+    return sub_batches(B, ws_bytes / lay.per_trial, [&](int b0, int nb) {
         uint8_t *raster = static_cast<uint8_t *>(ws);
         double *env = reinterpret_cast<double *>(static_cast<unsigned char *>(ws) + align256((size_t)nb * T * N));
         HIP_TRY(launch_xylo_resident(static_cast<const uint8_t *>(spikes_in) + (size_t)b0 * T * Crow, ternary_C, nb, T, Cin, N, w_rec, max_spikes,
                                      raster, rate ? rate + (size_t)b0 * N : nullptr, net_ws, st));
-        HIP_TRY(launch_envelope_track(raster, MICLOC_ENV_U8, nb, T, N, a_rise, i_rise, a_fall, env, nullptr, st));
-        HIP_TRY(launch_track_rows(env, nb, T, N, index + (size_t)b0 * T, peak_env ? peak_env + (size_t)b0 * T : nullptr,
-                                  env_last ? env_last + (size_t)b0 * N : nullptr, st));
-    }
-    return MICLOC_OK;
+        return envelope_rows(raster, MICLOC_ENV_U8, b0, nb, T, N, a_rise, i_rise, a_fall, env, index, peak_env, env_last, st);
+    });
 }
 
 size_t micloc_track_workspace_bytes(const micloc_plan *p, int B, int T)
 {
     if (!p || bad_batch(B) || T < 1 || (long long)B * T > 0x7fffffffll || plan_kind(p, p->W_is_complex) != MICLOC_OK) return 0;
-    return track_layout(p, B, T).min_total;
+    return track_layout(&p, 1, p->W_is_complex, false, B, T).min_total;
 }
 
 int micloc_track_is_fused(const micloc_plan *p)
@@ -177,59 +239,49 @@ int micloc_track_is_fused(const micloc_plan *p)
 int micloc_lif_beamform_track_f64(const micloc_plan *p, const int8_t *spikes, int B, int T, double a_rise, double i_rise, double a_fall,
                                   int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    int rc = track_args(p, spikes, B, T, index);
+    TrackLayout L;
+    const int rc = track_checked(p, false, spikes, B, T, nullptr, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     DeviceGuard guard(p->device);
-    rc = plan_kind(p, false);
-    if (rc != MICLOC_OK) return rc;
-    const TrackLayout lay = track_layout(p, B, T);
-    if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    return track_run(p, spikes, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
+    const void *src = spikes;
+    return track_run(&p, 1, false, false, &src, B, T, 0, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
 }
 
 int micloc_beamform_c128_track_f64(const micloc_plan *p, const double *pre, int B, int T, int Ts, double a_rise, double i_rise, double a_fall,
                                    int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    int rc = track_args(p, pre, B, T, index);
+    TrackLayout L;
+    const int rc = track_checked(p, true, pre, B, T, &Ts, index, ws, ws_bytes, &L);
     if (rc != MICLOC_OK) return rc;
     DeviceGuard guard(p->device);
-    if (Ts != micloc_padded_T(T)) return MICLOC_ERR_SHAPE;
-    rc = plan_kind(p, true);
-    if (rc != MICLOC_OK) return rc;
-    const TrackLayout lay = track_layout(p, B, T);
-    if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    return track_run(p, pre, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
+    const void *src = pre;
+    return track_run(&p, 1, true, false, &src, B, T, Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, (hipStream_t)stream);
 }
 
-// the first two launches of micloc_snn_pipeline_f64, then the tracking read-out of their raster
+// the first two launches of the plan's pipeline entry (micloc_snn_pipeline_f64 / micloc_beamformer_pipeline_f64), then the tracking read-out
+// of their raster / planar rows
+static int pipeline_track(const micloc_plan *p, bool cpx, const double *x, int B, int T, double a_rise, double i_rise, double a_fall, int32_t *index,
+                          double *peak_env, double *env_last, void *ws, size_t ws_bytes, hipStream_t st)
+{
+    TrackLayout L;
+    const int rc = track_checked(p, cpx, x, B, T, nullptr, index, ws, ws_bytes, &L);
+    if (rc != MICLOC_OK) return rc;
+    DeviceGuard guard(p->device);
+    const Front f = front_end(p, cpx, x, B, T, ws, L, nullptr, MICLOC_STAGE_ALL, st);
+    if (f.rc != MICLOC_OK) return f.rc;
+    return track_run(&p, 1, cpx, false, &f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, L, st);
+}
+
 int micloc_snn_pipeline_track_f64(const micloc_plan *p, const double *x, int B, int T, double a_rise, double i_rise, double a_fall,
                                   int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    int rc = track_args(p, x, B, T, index);
-    if (rc != MICLOC_OK) return rc;
-    DeviceGuard guard(p->device);
-    rc = plan_kind(p, false);
-    if (rc != MICLOC_OK) return rc;
-    const TrackLayout lay = track_layout(p, B, T);
-    if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    const Front f = front_end(p, false, x, B, T, ws, lay, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
-    if (f.rc != MICLOC_OK) return f.rc;
-    return track_run(p, f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
+    return pipeline_track(p, false, x, B, T, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int micloc_beamformer_pipeline_track_f64(const micloc_plan *p, const double *x, int B, int T, double a_rise, double i_rise, double a_fall,
                                          int32_t *index, double *peak_env, double *env_last, void *ws, size_t ws_bytes, void *stream)
 {
-    int rc = track_args(p, x, B, T, index);
-    if (rc != MICLOC_OK) return rc;
-    DeviceGuard guard(p->device);
-    rc = plan_kind(p, true);
-    if (rc != MICLOC_OK) return rc;
-    const TrackLayout lay = track_layout(p, B, T);
-    if (bad_ws(ws, ws_bytes, lay.min_total)) return MICLOC_ERR_WORKSPACE;
-    const Front f = front_end(p, true, x, B, T, ws, lay, nullptr, MICLOC_STAGE_ALL, (hipStream_t)stream);
-    if (f.rc != MICLOC_OK) return f.rc;
-    return track_run(p, f.src, B, T, f.Ts, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, lay, (hipStream_t)stream);
+    return pipeline_track(p, true, x, B, T, a_rise, i_rise, a_fall, index, peak_env, env_last, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- time-resolved DoA, Xylo: counts, rate and peak per window (the rule: include/micloc_hip.h; every refusal in front of any launch) ----

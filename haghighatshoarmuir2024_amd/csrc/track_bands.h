@@ -1,5 +1,5 @@
 // Wideband moving-target tracking (the rule: include/micloc_hip.h, "wideband moving-target tracking"): what track.hip offers to the C-ABI
-// unit of the wideband entries, api_bands.hip.  Only those two include this header.
+// unit that runs the tracking read-out of a set of plans, api_track.hip.  Only those two include this header.
 #pragma once
 #include "micloc_internal.h"
 

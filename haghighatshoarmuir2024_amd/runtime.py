@@ -347,45 +347,7 @@ class Plan:
         without y or its envelope in device memory.  kind: "pipeline" (src = x [B, T, M]), "spikes" (src = int8 raster [B, T, 2M],
         real bf_mat) or "planar" (src = band-passed rows [B, 2M, Ts], complex bf_mat, with T).  Plans the fused kernels do not serve
         run the two-step route over sub-batches whose y + envelope stay under `budget_bytes` (one trial at least)."""
-        torch = _torch()
-        if int(win_fall) < 1 or int(win_rise) < 1:
-            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
-        if kind == "planar":
-            B = src.shape[0]
-            Ts = src.shape[2]
-        else:
-            B, T = src.shape[0], src.shape[1]
-            if kind == "pipeline" and src.shape[2] != self.num_mic:
-                raise ValueError(f"number of channels in the input siganl {src.shape[2]} should be the same as the number of microphones {self.num_mic}!")
-        B, T, G = int(B), int(T), self.G
-        if B * T > 0x7FFFFFFF:
-            raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
-        # NumPy's own arithmetic for the filter constants, as envelope_track
-        wl = np.asarray([int(win_fall), int(win_rise)])
-        inv = 1 / wl
-        a = 1 - inv
-        consts = (float(a[1]), float(inv[1]), float(a[0]))
-        nbytes = self.lib.micloc_track_workspace_bytes(self.handle, B, T)
-        if nbytes == 0:
-            raise _lib.MiclocError("track: the plan needs bf_mat (and, for a real one, the neuron kernel) first")
-        if not self.track_is_fused() and B > 1:
-            per_trial = (24 if self.w_complex else 16) * T * G + 512
-            nbytes = max(nbytes, min(nbytes + (B - 1) * per_trial, nbytes - per_trial + max(per_trial, int(budget_bytes))))
-        ws = self.ws.get(nbytes)
-        out = dict(index=torch.empty((B, T), dtype=torch.int32, device=self.device),
-                   peak_envelope=torch.empty((B, T), dtype=torch.float64, device=self.device),
-                   envelope_last=torch.empty((B, G), dtype=torch.float64, device=self.device) if want_envelope_last else None)
-        tail = (_ptr(out["index"]), _ptr(out["peak_envelope"]), _ptr(out["envelope_last"]), _ptr(ws), nbytes, _stream(self.device))
-        if kind == "pipeline":
-            fn = self.lib.micloc_beamformer_pipeline_track_f64 if self.w_complex else self.lib.micloc_snn_pipeline_track_f64
-            _lib.check(fn(self.handle, _ptr(src), B, T, *consts, *tail), "pipeline_track")
-        elif kind == "spikes":
-            _lib.check(self.lib.micloc_lif_beamform_track_f64(self.handle, _ptr(src), B, T, *consts, *tail), "lif_beamform_track")
-        elif kind == "planar":
-            _lib.check(self.lib.micloc_beamform_c128_track_f64(self.handle, _ptr(src), B, T, int(Ts), *consts, *tail), "beamform_c128_track")
-        else:
-            raise ValueError("kind must be 'pipeline', 'spikes' or 'planar'")
-        return out
+        return _track_call(None, [self], src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, self.ws)
 
     # ---- single stages (used by tests and by Demo.spike_encoding-style callers) --------------------------
     def stht(self, x):
@@ -615,60 +577,70 @@ def bands_track_is_fused(plans, complex_bands=False):
     return bool(r)
 
 
-def _bands_track(name, plans, ba_list, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws):
-    """The caller of the wideband tracking entries (the rule: include/micloc_hip.h, "wideband moving-target tracking").  name: "snn"
-    or "beamformer"; kind: "pipeline" (src = x [B, T, M], with ba_list), "spikes" (snn: src = int8 rasters [F, B, T, 2M]) or "planar"
-    (beamformer: src = band-passed rows [F * B, 2M, Ts], with T)."""
+def _track_call(name, plans, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws, ba_list=None):
+    """The caller of the tracking entries (the rules: include/micloc_hip.h, "moving-target tracking" and "wideband moving-target tracking").
+    name: None (Plan.track: plans = [the plan]), "snn" or "beamformer" (a set of bands); kind: "pipeline" (src = x [B, T, M]; bands: with
+    ba_list), "spikes" (real bf_mat: src = the int8 raster [B, T, 2M], bands [F, B, T, 2M]) or "planar" (complex bf_mat: src = the
+    band-passed rows [B, 2M, Ts], bands [F * B, 2M, Ts], with T)."""
     torch = _torch()
     lib = _lib.load()
-    F, handles = _band_handles(plans)
     p0 = plans[0]
-    if any(p.G != p0.G for p in plans):
-        raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
-    if int(win_fall) < 1 or int(win_rise) < 1:
-        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
-    if kind == "pipeline":
-        if len(ba_list) != F:
-            raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
-        bb, aa, n = pad_ba_list(ba_list)
-        B, T, M = src.shape
-        if M != p0.num_mic:
-            raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {p0.num_mic}!")
-    elif kind == "spikes" and name == "snn":
-        if src.dim() != 4 or src.shape[0] != F or src.shape[3] != 2 * p0.num_mic or src.dtype != torch.int8 or not src.is_contiguous():
-            raise ValueError(f"the rasters must be a contiguous int8 device tensor [{F}, B, T, {2 * p0.num_mic}]")
-        B, T = src.shape[1], src.shape[2]
-    elif kind == "planar" and name == "beamformer":
-        if src.dim() != 3 or src.shape[0] % F or src.shape[1] != 2 * p0.num_mic or src.dtype != torch.float64 or not src.is_contiguous() or T is None:
-            raise ValueError(f"the planar rows must be a contiguous float64 device tensor [{F} * B, {2 * p0.num_mic}, Ts], with T")
-        B, Ts = src.shape[0] // F, src.shape[2]
+    cpx = p0.w_complex if name is None else name == "beamformer"
+    if name is None:
+        consts = envelope_consts(win_fall, win_rise)
+        if kind not in ("pipeline", "spikes", "planar"):
+            raise ValueError("kind must be 'pipeline', 'spikes' or 'planar'")
+        lead, entry = (p0.handle,), {"pipeline": "beamformer_pipeline_track" if cpx else "snn_pipeline_track", "spikes": "lif_beamform_track",
+                                     "planar": "beamform_c128_track"}[kind]
+        B, T = (src.shape[0], T) if kind == "planar" else src.shape[:2]
     else:
-        raise ValueError("kind must be 'pipeline', 'spikes' (snn) or 'planar' (beamformer)")
+        F, handles = _band_handles(plans)
+        if any(p.G != p0.G for p in plans):
+            raise ValueError("the bands of a wideband localizer share the microphones and the DoA grid")
+        consts = envelope_consts(win_fall, win_rise)
+        lead, entry = (handles, F), {"pipeline": f"{name}_pipeline_bands_track", "spikes": "lif_beamform_bands_track",
+                                     "planar": "beamform_c128_bands_track"}.get(kind)
+        if kind == "pipeline":
+            if len(ba_list) != F:
+                raise ValueError(f"{len(ba_list)} filterbank sections for {F} bands")
+            bb, aa, n = pad_ba_list(ba_list)
+            lead += (_dptr(bb), _dptr(aa), n)
+            B, T = src.shape[:2]
+        elif kind == "spikes" and not cpx:
+            if src.dim() != 4 or src.shape[0] != F or src.shape[3] != 2 * p0.num_mic or src.dtype != torch.int8 or not src.is_contiguous():
+                raise ValueError(f"the rasters must be a contiguous int8 device tensor [{F}, B, T, {2 * p0.num_mic}]")
+            B, T = src.shape[1], src.shape[2]
+        elif kind == "planar" and cpx:
+            if src.dim() != 3 or src.shape[0] % F or src.shape[1] != 2 * p0.num_mic or src.dtype != torch.float64 or not src.is_contiguous() or T is None:
+                raise ValueError(f"the planar rows must be a contiguous float64 device tensor [{F} * B, {2 * p0.num_mic}, Ts], with T")
+            B = src.shape[0] // F
+        else:
+            raise ValueError("kind must be 'pipeline', 'spikes' (snn) or 'planar' (beamformer)")
+    if kind == "pipeline" and src.shape[2] != p0.num_mic:
+        raise ValueError(f"number of channels in the input siganl {src.shape[2]} should be the same as the number of microphones {p0.num_mic}!")
     B, T, G, dev = int(B), int(T), p0.G, p0.device
     if B * T > 0x7FFFFFFF:
         raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
-    # NumPy's own arithmetic for the filter constants, as envelope_track
-    wl = np.asarray([int(win_fall), int(win_rise)])
-    inv = 1 / wl
-    a = 1 - inv
-    consts = (float(a[1]), float(inv[1]), float(a[0]))
-    nbytes = getattr(lib, f"micloc_{name}_bands_track_workspace_bytes")(handles, F, B, T)
-    if nbytes == 0:
-        raise ValueError(f"micloc {name}_bands_track_workspace_bytes: the plans or the batch do not fit the wideband tracking rule")
-    if B > 1 and not bands_track_is_fused(plans, name == "beamformer"):
-        per_trial = (32 if name == "beamformer" else 24) * T * G + 768  # y, the band sum and its envelope of one trial
+    if name is None:
+        nbytes = lib.micloc_track_workspace_bytes(p0.handle, B, T)
+        if nbytes == 0:
+            raise _lib.MiclocError("track: the plan needs bf_mat (and, for a real one, the neuron kernel) first")
+    else:
+        nbytes = getattr(lib, f"micloc_{name}_bands_track_workspace_bytes")(handles, F, B, T)
+        if nbytes == 0:
+            raise ValueError(f"micloc {name}_bands_track_workspace_bytes: the plans or the batch do not fit the wideband tracking rule")
+    if B > 1 and not (p0.track_is_fused() if name is None else bands_track_is_fused(plans, cpx)):
+        # one trial of the two-step route: y (two cells of T x G doubles when complex), for bands their sum, and the envelope -- 256 B each
+        regions = 2 if name is None else 3
+        per_trial = (regions + cpx) * 8 * T * G + regions * 256
         nbytes = max(nbytes, min(nbytes + (B - 1) * per_trial, nbytes - per_trial + max(per_trial, int(budget_bytes))))
-    buf = (ws or p0.ws).get(nbytes)
+    buf = ws.get(nbytes)
     out = dict(index=torch.empty((B, T), dtype=torch.int32, device=dev), peak_envelope=torch.empty((B, T), dtype=torch.float64, device=dev),
                envelope_last=torch.empty((B, G), dtype=torch.float64, device=dev) if want_envelope_last else None)
-    tail = (*consts, _ptr(out["index"]), _ptr(out["peak_envelope"]), _ptr(out["envelope_last"]), _ptr(buf), nbytes, _stream(dev))
-    if kind == "pipeline":
-        _lib.check(getattr(lib, f"micloc_{name}_pipeline_bands_track_f64")(handles, F, _dptr(bb), _dptr(aa), n, _ptr(src), B, T, *tail),
-                   f"{name}_pipeline_bands_track")
-    elif kind == "spikes":
-        _lib.check(lib.micloc_lif_beamform_bands_track_f64(handles, F, _ptr(src), B, T, *tail), "lif_beamform_bands_track")
-    else:
-        _lib.check(lib.micloc_beamform_c128_bands_track_f64(handles, F, _ptr(src), B, T, int(Ts), *tail), "beamform_c128_bands_track")
+    Ts = (int(src.shape[2]),) if kind == "planar" else ()
+    _lib.check(getattr(lib, f"micloc_{entry}_f64")(*lead, _ptr(src), B, T, *Ts, *consts, _ptr(out["index"]), _ptr(out["peak_envelope"]),
+                                                  _ptr(out["envelope_last"]), _ptr(buf), nbytes, _stream(dev)),
+               "pipeline_track" if name is None and kind == "pipeline" else entry)
     return out
 
 
@@ -679,14 +651,14 @@ def snn_bands_track(plans, ba_list, src, win_fall, win_rise, kind="pipeline", wa
     without an array of size T x G where the fused kernel serves the set (bands_track_is_fused); other sets run the two-step route over
     sub-batches whose arrays stay under `budget_bytes`.  kind="spikes": src = the bands' int8 rasters [F, B, T, 2M]
     (micloc_lif_beamform_bands_track_f64; ba_list is not read)."""
-    return _bands_track("snn", plans, ba_list, src, win_fall, win_rise, kind, None, want_envelope_last, budget_bytes, ws)
+    return _track_call("snn", plans, src, win_fall, win_rise, kind, None, want_envelope_last, budget_bytes, ws or plans[0].ws, ba_list)
 
 
 def beamformer_bands_track(plans, ba_list, src, win_fall, win_rise, kind="pipeline", T=None, want_envelope_last=False, budget_bytes=1 << 30,
                            ws=None):
     """micloc_beamformer_pipeline_bands_track_f64: snn_bands_track for the complex Beamformer chains of all bands (|y| = hypot(re, im)).
     kind="planar": src = the bands' band-passed rows [F * B, 2M, Ts] with T (micloc_beamform_c128_bands_track_f64)."""
-    return _bands_track("beamformer", plans, ba_list, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws)
+    return _track_call("beamformer", plans, src, win_fall, win_rise, kind, T, want_envelope_last, budget_bytes, ws or plans[0].ws, ba_list)
 
 
 def beamformer_bands_bandpass(plans, xf, one_launch=True, pre=None, h=None):
@@ -969,6 +941,18 @@ def doa_peaks(power, doa_list, grid_kind, num_sources, min_separation, rel_thres
     return idx, val
 
 
+def envelope_consts(win_fall, win_rise):
+    """The filter constants of utils.Envelope.evolve for windows of win_fall / win_rise samples -> (a_rise, i_rise, a_fall), the arguments
+    of every tracking entry.  NumPy's own arithmetic on an int array (utils.py:70-76: `1 / win_len_state`, `1 - 1 / win_len_state`), which is
+    what makes them the reference's bits.  ValueError for a window below one sample."""
+    if int(win_fall) < 1 or int(win_rise) < 1:
+        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+    wl = np.asarray([int(win_fall), int(win_rise)])
+    inv = 1 / wl
+    a = 1 - inv
+    return float(a[1]), float(inv[1]), float(a[0])
+
+
 def envelope_track(y, win_fall, win_rise, want_index=True, env_out=None):
     """micloc_envelope_track_any: y [T, G] or [B, T, G] device tensor (float64: the SNN beamformer's output; complex128: the complex
     Beamformer's, paper_plots/target_localization.py:597-600; uint8 / int32 / int64: a spike raster, paper_plots/target_xylo_localization.py:757-768)
@@ -978,18 +962,12 @@ def envelope_track(y, win_fall, win_rise, want_index=True, env_out=None):
     kinds = {torch.float64: 0, torch.complex128: 1, torch.uint8: 2, torch.int32: 3, torch.int64: 4}  # MICLOC_ENV_*
     if y.dtype not in kinds or y.dim() not in (2, 3) or not y.is_cuda:
         raise ValueError("envelope_track: a device tensor [T, G] or [B, T, G] of float64 / complex128 / uint8 / int32 / int64 is required")
-    if int(win_fall) < 1 or int(win_rise) < 1:
-        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+    consts = envelope_consts(win_fall, win_rise)
     yc = y.contiguous()
     B, T, G = (1, *yc.shape) if yc.dim() == 2 else yc.shape
-    # NumPy's own arithmetic for the two filter constants (utils.py:70-76: `1 / win_len_state`, `1 - 1 / win_len_state`)
-    wl = np.asarray([int(win_fall), int(win_rise)])
-    inv = 1 / wl
-    a = 1 - inv
     env = env_out if env_out is not None else torch.empty(yc.shape, dtype=torch.float64, device=yc.device)
     idx = torch.empty(yc.shape[:-1], dtype=torch.int32, device=yc.device) if want_index else None
-    _lib.check(_lib.load().micloc_envelope_track_any(_ptr(yc), kinds[y.dtype], int(B), int(T), int(G), float(a[1]), float(inv[1]), float(a[0]),
-                                                     _ptr(env), _ptr(idx) if idx is not None else None, _stream(yc.device)), "envelope_track")
+    _lib.check(_lib.load().micloc_envelope_track_any(_ptr(yc), kinds[y.dtype], int(B), int(T), int(G), *consts, _ptr(env), _ptr(idx) if idx is not None else None, _stream(yc.device)), "envelope_track")
     return env, idx
 
 

@@ -90,12 +90,7 @@ def track_ring(envelope, most, total_frames=None, max_track=None):
     """track_setup's constants-and-ring part, which does not depend on the kernels behind the stream (the Xylo stream's tracked read-out is
     the packed LIF walk, not csrc/track.hip): -> (a_rise, i_rise, a_fall, R), with track_setup's refusals of an envelope window below one
     sample and of a ring shorter than `most`, and its default for R."""
-    win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
-    if win_fall < 1 or win_rise < 1:
-        raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
-    wl = np.asarray([win_fall, win_rise])
-    inv = 1 / wl
-    a = 1 - inv
+    consts = runtime.envelope_consts(envelope.win_lens[0], envelope.win_lens[1])
     most = int(most)
     if max_track is not None:
         R = int(max_track)
@@ -105,7 +100,7 @@ def track_ring(envelope, most, total_frames=None, max_track=None):
         R = -(-4 * most // 64) * 64
     if R < most:
         raise ValueError(f"max_track must be at least the {most} frames one tile can make final (got {R})")
-    return float(a[1]), float(inv[1]), float(a[0]), R
+    return (*consts, R)
 
 
 class _TileStream:

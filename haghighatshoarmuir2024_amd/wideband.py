@@ -106,8 +106,7 @@ class _WidebandLocalizer:
         B, T, M = sig_batch.shape
         if M != self.num_mic:
             raise ValueError(f"number of channels in the input siganl {M} should be the same as the number of microphones {self.num_mic}!")
-        if int(envelope.win_lens[0]) < 1 or int(envelope.win_lens[1]) < 1:
-            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        runtime.envelope_consts(envelope.win_lens[0], envelope.win_lens[1])  # (its refusal of a window below one sample)
         return B, T
 
 
@@ -213,13 +212,10 @@ class WidebandBeamformerLocalizer(_WidebandLocalizer):
 
     def trials_per_call(self, plans, B, T, window, hop, budget_bytes):
         """The largest sub-batch of B whose workspace stays inside budget_bytes (one trial at least)."""
-        import ctypes
-
         from . import _lib
 
-        lib = _lib.load()
-        handles = (ctypes.c_void_p * len(plans))(*[p.handle.value for p in plans])
-        one = lib.micloc_beamformer_bands_workspace_bytes(handles, len(plans), 1, T, window or 0, hop or 0)
+        F, handles = runtime._band_handles(plans)
+        one = _lib.load().micloc_beamformer_bands_workspace_bytes(handles, F, 1, T, window or 0, hop or 0)
         if one == 0 or budget_bytes is None:
             return B  # (bad arguments: the call itself names them)
         return int(max(1, min(B, int(budget_bytes) // one)))

@@ -238,16 +238,10 @@ class XyloNetwork:
             raise ValueError(f"number of input spike channels {2 * C if ternary else C} should match the weight matrix {self.Cin}")
         if spikes.dtype != (torch.int8 if ternary else torch.uint8) or not spikes.is_contiguous():
             raise ValueError("spikes must be a contiguous int8 (ternary) / uint8 (events) device tensor")
-        win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
-        if win_fall < 1 or win_rise < 1:
-            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
+        consts = runtime.envelope_consts(envelope.win_lens[0], envelope.win_lens[1])
         B, T = int(B), int(T)
         if B * T > 0x7FFFFFFF:
             raise ValueError(f"{B} trials x {T} frames exceed the 2^31 - 1 rows of one call")
-        # NumPy's own arithmetic for the filter constants, as runtime.envelope_track
-        wl = np.asarray([win_fall, win_rise])
-        inv = 1 / wl
-        a = 1 - inv
         tc = C if ternary else 0
         nbytes = int(self.lib.micloc_xylo_track_workspace_bytes(tc, self.Cin, self.N, self.w_rec, B, T))
         if nbytes == 0:
@@ -262,10 +256,10 @@ class XyloNetwork:
                    env_last=torch.empty((B, self.N), dtype=torch.float64, device=self.device))
         if want_rate:
             out["rate"] = torch.empty((B, self.N), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.micloc_xylo_lif_track_i16(runtime._ptr(spikes), tc, B, T, self.Cin, self.N, self.w_rec, int(max_spikes), float(a[1]),
-                                                      float(inv[1]), float(a[0]), runtime._ptr(out["index"]), runtime._ptr(out["peak_env"]),
-                                                      runtime._ptr(out["env_last"]), runtime._ptr(out.get("rate")), runtime._ptr(self.ws),
-                                                      self.nbytes, runtime._ptr(ws), nbytes, runtime._stream(self.device)), "xylo_lif_track")
+        _lib.check(self.lib.micloc_xylo_lif_track_i16(runtime._ptr(spikes), tc, B, T, self.Cin, self.N, self.w_rec, int(max_spikes), *consts,
+                                                      runtime._ptr(out["index"]), runtime._ptr(out["peak_env"]), runtime._ptr(out["env_last"]),
+                                                      runtime._ptr(out.get("rate")), runtime._ptr(self.ws), self.nbytes, runtime._ptr(ws), nbytes,
+                                                      runtime._stream(self.device)), "xylo_lif_track")
         return out
 
     # ---- resumable across launches (micloc_xylo_lif_resume_i16; PARITY UNPINNED like run) ------------------------------------------
@@ -351,12 +345,7 @@ class XyloNetwork:
         if B != state["B"] or B != track_state["B"] or t0 < 0 or n < 0 or t0 + n > T:
             raise ValueError(f"the range [{t0}, {t0 + n}) or the batch {B} does not fit the raster [{B}, {T}] and the states of {state['B']} / "
                              f"{track_state['B']} trials")
-        win_fall, win_rise = int(envelope.win_lens[0]), int(envelope.win_lens[1])
-        if win_fall < 1 or win_rise < 1:
-            raise ValueError("envelope windows must hold at least one sample (int(fs * time) >= 1)")
-        wl = np.asarray([win_fall, win_rise])  # NumPy's own arithmetic for the filter constants, as track()
-        inv = 1 / wl
-        a = 1 - inv
+        consts = runtime.envelope_consts(envelope.win_lens[0], envelope.win_lens[1])
         if out is None:
             out = dict(index=torch.zeros((B, T), dtype=torch.int32, device=self.device),
                        peak_env=torch.zeros((B, T), dtype=torch.float64, device=self.device),
@@ -371,7 +360,7 @@ class XyloNetwork:
         ws = torch.empty(nws, dtype=torch.uint8, device=self.device)  # one per call: calls of several streams run side by side
         _lib.check(self.lib.micloc_xylo_lif_track_resume_i16(runtime._ptr(raster), C, T, B, t0, n, self.Cin, self.N, int(max_spikes),
                                                              runtime._ptr(state["state"]), state["nbytes"], runtime._ptr(track_state["state"]),
-                                                             track_state["nbytes"], float(a[1]), float(inv[1]), float(a[0]), R,
+                                                             track_state["nbytes"], *consts, R,
                                                              runtime._ptr(out["index"]), runtime._ptr(out["peak_env"]),
                                                              runtime._ptr(out["latest_index"]), runtime._ptr(out["latest_peak"]),
                                                              runtime._ptr(out["env_last"]), runtime._ptr(state["counts"]), runtime._ptr(self.ws),

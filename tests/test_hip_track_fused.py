@@ -155,6 +155,73 @@ def test_forty_channel_plan_takes_the_two_step_route_inside_the_call(torch):
         assert torch.equal(a[k], b[k]), k
 
 
+def _call_pipeline_track(torch, plan, x, env, nbytes, want_rc=0):
+    """The plan's pipeline tracking entry itself with a workspace of exactly nbytes."""
+    B, T, _ = x.shape
+    inv = 1 / np.asarray([int(env.win_lens[0]), int(env.win_lens[1])])  # (fall, rise)
+    a = 1 - inv
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=x.device)
+    out = dict(index=torch.empty((B, T), dtype=torch.int32, device=x.device), peak_envelope=torch.empty((B, T), dtype=torch.float64, device=x.device),
+               envelope_last=torch.empty((B, plan.G), dtype=torch.float64, device=x.device))
+    fn = plan.lib.micloc_beamformer_pipeline_track_f64 if plan.w_complex else plan.lib.micloc_snn_pipeline_track_f64
+    rc = fn(plan.handle, x.data_ptr(), B, T, float(a[1]), float(inv[1]), float(a[0]), out["index"].data_ptr(), out["peak_envelope"].data_ptr(),
+            out["envelope_last"].data_ptr(), ws.data_ptr(), int(nbytes), torch.cuda.current_stream().cuda_stream)
+    assert rc == want_rc, rc
+    torch.cuda.synchronize()
+    return out
+
+
+def _sub_batch_cases(torch, bf, plan, W, sigs, env, cells_y, trials):
+    """The entry with workspaces that hold exactly `trials` trials of the two-step route at a time, against the Python two-step route.
+    One trial's region: y (cells_y cells of T x G doubles, one 256-B aligned block) and its envelope (one cell)."""
+    from haghighatshoarmuir2024_amd import _lib
+
+    assert not plan.track_is_fused()
+    B, T, G = len(sigs), sigs[0].shape[0], plan.G
+    want = [np.stack(v) for v in zip(*(_two_step(bf, W, s, env) for s in sigs))]
+    x = plan.to_device(np.stack(sigs))
+    al = lambda v: (v + 255) // 256 * 256  # noqa: E731
+    per_trial = al(cells_y * 8 * T * G) + al(8 * T * G)
+    need = plan.lib.micloc_track_workspace_bytes(plan.handle, B, T)
+    assert need > per_trial
+    for n in trials:  # n == 2 of B == 3: sub-batches of 2 and 1
+        out = _call_pipeline_track(torch, plan, x, env, need + (n - 1) * per_trial)
+        for k, w in zip(("index", "peak_envelope", "envelope_last"), want):
+            np.testing.assert_array_equal(out[k].cpu().numpy(), w, err_msg=f"{k}, {n} trials at a time")
+    _call_pipeline_track(torch, plan, x, env, need - 256, want_rc=_lib.MICLOC_ERR_WORKSPACE)
+
+
+def test_forty_channel_plan_with_a_ragged_last_sub_batch(torch):
+    """The shape above (the encoder needs the frames to spike) with the workspace of two trials out of three."""
+    from micloc.snn_beamformer import neuron_impulse_response
+
+    bf = _snn(num_mic=20)
+    rng = np.random.RandomState(40)
+    W = rng.randn(40, 97)
+    W /= np.linalg.norm(W, axis=0, keepdims=True)
+    sigs = [rng.randn(1500, 20) for _ in range(3)]
+    plan = bf.plan()
+    plan.set_neuron_kernel(neuron_impulse_response(np.arange(1500) / FS, bf.tau_vec))
+    plan.set_bf_mat(W)
+    _sub_batch_cases(torch, bf, plan, W, sigs, _env(), 1, (2,))
+
+
+def test_forty_channel_complex_plan_takes_the_two_step_route_inside_the_call(torch):
+    """20 microphones are 40 channels, off the fused route: the complex two-step route inside the call, one, two (then one) and three
+    trials at a time."""
+    from micloc.array_geometry import CenterCircularArray
+    from micloc.beamformer import Beamformer
+
+    bm = Beamformer(CenterCircularArray(4.5e-2, 20), 10e-3, [1000.0, 2000.0], fs=FS)
+    rng = np.random.RandomState(41)
+    W = (rng.randn(20, 97) + 1j * rng.randn(20, 97)) / np.sqrt(40)
+    sigs = [rng.randn(130, 20) for _ in range(3)]
+    plan = bm.plan()
+    plan.set_bf_mat(W)
+    _sub_batch_cases(torch, bm, plan, W, sigs, _env(2e-3, 13e-3), 2, (1, 2, 3))
+    _check_batch(bm, W, sigs, _env(2e-3, 13e-3), 97)  # and through track_batch
+
+
 # ---- 3. a seeded random campaign against the oracle on the device's own y -------------------------------------------------------------
 def _plan(cfg2, bipolar=True):
     from haghighatshoarmuir2024_amd.runtime import Plan

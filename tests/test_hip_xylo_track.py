@@ -123,7 +123,9 @@ def test_other_networks_take_the_two_step_route_inside_the_call(torch):
     ref = R.track_reference(out, rate, 2, 5)
     small = net.track(dev, env, want_rate=True, budget_bytes=0)  # the minimum workspace: one trial per sub-batch
     big = net.track(dev, env, want_rate=True, budget_bytes=10 * 5 * 9 * 300 * 100)
+    two = net.track(dev, env, want_rate=True, budget_bytes=2 * (9 * 300 * 100 + 512))  # two trials out of five: sub-batches of 2, 2 and 1
     R.assert_equal_bits(small, ref, "recurrent, minimum workspace")
+    R.assert_equal_bits(two, ref, "recurrent, two trials at a time")
     R.assert_equal_bits(big, ref, "recurrent, ten times the workspace")
     R.assert_equal_bits(small, _two_step(net, dev, env, False), "recurrent vs two-step")
     # the same recurrent network fed the ternary raster: still not fused

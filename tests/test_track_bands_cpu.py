@@ -105,7 +105,10 @@ def test_sources_keep_the_contract():
     assert "hipStreamSynchronize" not in trk and "hipDeviceSynchronize" not in trk and "hipMalloc" not in trk
     api = open(os.path.join(csrc, "api_bands.hip")).read()
     assert "__global__" not in api and "hipMalloc" not in api and "Synchronize" not in api
-    assert '#include "track_bands.h"' in trk and '#include "track_bands.h"' in api
+    run = open(os.path.join(csrc, "api_track.hip")).read()  # the unit that calls launch_track_bands_fused: the run of a set (api_sets.h)
+    assert "launch_track_bands_fused(" in run and "launch_track_bands_fused(" not in api
+    assert "__global__" not in run and "hipMalloc" not in run and "Synchronize" not in run
+    assert '#include "track_bands.h"' in trk and '#include "track_bands.h"' in run
 
 
 def _localizers():

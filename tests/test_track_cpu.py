@@ -237,3 +237,21 @@ def test_moving_sweep_world2_equals_world1(tmp_path):
         for k in ("phase", "err", "med", "track_mae_deg", "track_median_deg", "mae_deg"):
             np.testing.assert_array_equal(got[k], ref[k], err_msg=f"rank {r} {k}")
         assert json.load(open(outs[2] / f"w2_r{r}.json"))["exchange"]["collectives"] == 1
+
+
+def test_envelope_consts_are_numpys_own_arithmetic():
+    """runtime.envelope_consts -> (a_rise, i_rise, a_fall): `1 - 1 / wl` and `1 / wl` of NumPy on the int array [fall, rise], element for
+    element, and the refusal of a window below one sample.  Needs no device."""
+    from haghighatshoarmuir2024_amd.runtime import envelope_consts
+
+    for wf, wr in [(1, 1), (624, 96), (96, 624), (4800, 480), (3, 7), (2**31 - 1, 1)]:
+        wl = np.asarray([wf, wr])
+        a, inv = 1 - 1 / wl, 1 / wl
+        got = envelope_consts(wf, wr)
+        assert all(type(v) is float for v in got)
+        assert got == (a[1], inv[1], a[0]), (wf, wr)
+    assert envelope_consts(1, 1) == (0.0, 1.0, 0.0)
+    assert envelope_consts(np.int64(5), 5.9) == envelope_consts(5, 5)  # int() of what Envelope.win_lens holds
+    for wf, wr in [(0, 5), (5, 0), (0, 0), (-1, 3)]:
+        with pytest.raises(ValueError, match="at least one sample"):
+            envelope_consts(wf, wr)
