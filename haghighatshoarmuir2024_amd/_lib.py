@@ -4,19 +4,16 @@ There is deliberately NO fallback: if the HIP library is missing or a call fails
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmicloc_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "micloc_hip.h")
 
-MICLOC_OK = 0
-MICLOC_ERR_INVALID = -1
-MICLOC_ERR_SHAPE = -2
-MICLOC_ERR_WORKSPACE = -3
-MICLOC_ERR_NOT_SET = -4
-MICLOC_ERR_HIP = -5
-MICLOC_ERR_NO_DEVICE = -6
-MICLOC_MAX_IIR = 9
-MICLOC_MAX_BANDS = 16
+
+class MiclocError(RuntimeError):
+    pass
+
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_void_p = ctypes.c_void_p
@@ -55,232 +52,49 @@ class MiclocSynthArgs(ctypes.Structure):
     ]
 
 
-# every symbol include/micloc_hip.h declares: name -> (restype, argtypes)
-SYMBOLS = {
-    "micloc_plan_create": (c_int, [ctypes.POINTER(MiclocConfig), ctypes.POINTER(c_void_p)]),
-    "micloc_plan_destroy": (None, [c_void_p]),
-    "micloc_plan_set_neuron_kernel": (c_int, [c_void_p, c_double_p, c_int]),
-    "micloc_plan_set_bf_mat": (c_int, [c_void_p, c_double_p, c_int, c_int]),
-    "micloc_plan_set_bf_mat_c128": (c_int, [c_void_p, c_double_p, c_double_p, c_int, c_int]),
-    "micloc_plan_generation": (c_int, [c_void_p]),
-    "micloc_plan_set_encoder_chunk": (c_int, [c_void_p, c_int]),
-    "micloc_plan_encoder_chunks": (c_int, [c_void_p, c_int, c_int]),
-    "micloc_stream_create_cu_range": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
-    "micloc_stream_destroy": (c_int, [c_void_p]),
-    "micloc_padded_T": (c_int, [c_int]),
-    "micloc_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_stht_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
-    "micloc_bandpass_rzcc_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_lif_beamform_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamform_c128_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_stages_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int]),
-    "micloc_beamformer_pipeline_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_rzcc_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_rzcc_encode_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_rzcc_workspace_bytes_ex": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "micloc_rzcc_encode_ex_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_lfilter_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_lfilter_f64": (c_int, [c_double_p, c_double_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_lif_beamform_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_lif_covariance_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_planar_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "micloc_planar_gram_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_cov_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_synth_delay_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
-    "micloc_synth_targets_f64": (c_int, [c_void_p, c_void_p]),
-    "micloc_delay_min_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
-    "micloc_uniform_f64": (c_int, [c_void_p, c_size_t, ctypes.c_uint64, ctypes.c_uint32, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p]),
-    "micloc_counter_add_u32": (c_int, [c_void_p, ctypes.c_uint32, c_void_p]),
-    "micloc_awgn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_awgn_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_void_p, ctypes.c_uint32,
-                                c_void_p, c_size_t, c_void_p]),
-    "micloc_synth_awgn_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "micloc_synth_awgn_f64": (c_int, [c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_void_p, c_size_t, c_void_p]),
-    "micloc_doa_error_f64": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "micloc_xylo_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "micloc_xylo_lif_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_upload": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_lif_resident_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_sweep_scratch_bytes": (c_size_t, [c_int]),
-    "micloc_xylo_sweep_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_pack_events_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "micloc_rate_from_counts_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
-    "micloc_xylo_lif_sweep_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p]),
-    "micloc_lif_beamform_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_stream_state_bytes": (c_size_t, [c_void_p, c_int]),
-    "micloc_stream_overflow": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_stream_localize_state_bytes": (c_size_t, [c_void_p, c_int]),
-    "micloc_stream_chunk_frames": (c_int, [c_void_p]),
-    "micloc_stream_localize_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_stream_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_void_p]),
-    "micloc_stream_begin_tile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_wrap_rows_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "micloc_stream_encode_tile_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "micloc_stream_localize_tile_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                c_size_t, c_void_p]),
-    "micloc_stream_localize_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_stream_window_state_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
-    "micloc_stream_window_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_localize_tile_windows_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                        c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "micloc_stream_window_count": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_stream_window_count_ptr": (c_void_p, [c_void_p]),
-    "micloc_stream_complex_state_bytes": (c_size_t, [c_void_p, c_int]),
-    "micloc_stream_complex_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_stream_complex_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_complex_bandpass_tile_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
-                                                        c_void_p]),
-    "micloc_stream_complex_localize_tile_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                        c_void_p]),
-    "micloc_stream_complex_window_state_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
-    "micloc_stream_complex_window_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_complex_localize_tile_windows_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                                c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                                c_void_p, c_void_p]),
-    "micloc_stream_complex_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_design_vectors_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_int, c_int, c_void_p]),
-    "micloc_peak_location_i32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "micloc_doa_peaks_f64": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
-    "micloc_window_quantum": (c_int, [c_void_p]),
-    "micloc_window_count": (c_int, [c_int, c_int, c_int, c_int]),
-    "micloc_window_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
-    "micloc_lif_beamform_windows_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_size_t, c_void_p]),
-    "micloc_beamform_c128_windows_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                 c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_windows_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                c_void_p, c_size_t, c_void_p]),
-    "micloc_beamformer_pipeline_windows_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                       c_void_p, c_size_t, c_void_p]),
-    "micloc_envelope_track_f64": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
-    "micloc_envelope_track_any": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
-    "micloc_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_track_is_fused": (c_int, [c_void_p]),
-    "micloc_lif_beamform_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamform_c128_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamformer_pipeline_track_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_track_is_fused": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "micloc_xylo_track_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
-    "micloc_xylo_lif_track_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_window_quantum": (c_int, []),
-    "micloc_xylo_windows_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_xylo_lif_windows_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                            c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_window_readout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p]),
-    "micloc_stream_track_state_bytes": (c_size_t, [c_void_p, c_int]),
-    "micloc_stream_track_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
-    "micloc_stream_track_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_localize_tile_track_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                                      c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                      c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
-                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_complex_localize_tile_track_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                                              c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                              c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p,
-                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_filterbank_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "micloc_band_sum_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "micloc_snn_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
-    "micloc_snn_pipeline_bands_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamformer_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int]),
-    "micloc_beamformer_pipeline_bands_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int, c_int,
-                                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamformer_bands_bandpass_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                     c_void_p]),
-    "micloc_snn_bands_track_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
-    "micloc_beamformer_bands_track_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
-    "micloc_snn_bands_track_is_fused": (c_int, [ctypes.POINTER(c_void_p), c_int]),
-    "micloc_beamformer_bands_track_is_fused": (c_int, [ctypes.POINTER(c_void_p), c_int]),
-    "micloc_lif_beamform_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double,
-                                                    ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_beamform_c128_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double,
-                                                     ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_snn_pipeline_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int,
-                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                    c_size_t, c_void_p]),
-    "micloc_beamformer_pipeline_bands_track_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_double_p, c_double_p, c_int, c_void_p, c_int, c_int,
-                                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p,
-                                                           c_void_p, c_size_t, c_void_p]),
-    "micloc_filterbank_stream_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "micloc_filterbank_stream_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
-    "micloc_filterbank_tile_f64": (c_int, [c_double_p, c_double_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "micloc_stream_bands_state_bytes": (c_size_t, []),
-    "micloc_stream_bands_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_band_sum_f64": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_void_p), c_int, c_int, c_int, ctypes.POINTER(c_void_p),
-                                           ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p]),
-    "micloc_stream_bands_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_stream_complex_bands_state_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int]),
-    "micloc_stream_complex_bands_workspace_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
-    "micloc_stream_complex_bands_reset": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_complex_bands_bandpass_tile_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                              c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_complex_bands_localize_tile_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
-                                                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_complex_bands_window_state_bytes": (c_size_t, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
-    "micloc_stream_complex_bands_window_reset": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_int, c_int,
-                                                         c_void_p]),
-    "micloc_stream_complex_bands_localize_tile_windows_f64": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_int,
-                                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int,
-                                                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "micloc_stream_complex_bands_status": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_music_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "micloc_music_f64": (c_int, [c_void_p, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
-                                 c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_music_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "micloc_stream_music_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_music_tile_f64": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_double_p, c_double_p, c_int, c_int, c_int, c_int,
-                                             c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_void_p, c_void_p, c_void_p]),
-    "micloc_stream_music_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_xylo_stream_state_bytes": (c_size_t, [c_int, c_int]),
-    "micloc_xylo_stream_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
-    "micloc_xylo_lif_resume_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                           c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_xylo_state_bytes": (c_size_t, []),
-    "micloc_stream_xylo_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_stream_xylo_reset": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_size_t,
-                                         c_void_p, c_void_p]),
-    "micloc_stream_xylo_begin_tile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_xylo_tile_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                            c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_xylo_window_state_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "micloc_stream_xylo_window_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "micloc_stream_xylo_tile_windows_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                                    c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
-                                                    c_int, c_void_p]),
-    "micloc_stream_xylo_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_stream_xylo_readout_state_bytes": (c_size_t, []),
-    "micloc_stream_xylo_readout_reset": (c_int, [c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_xylo_readout": (c_int, [c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int,
-                                           c_int, c_int, c_int, ctypes.POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "micloc_stream_xylo_readout_status": (c_int, [c_void_p, ctypes.POINTER(c_int), c_void_p]),
-    "micloc_xylo_stream_track_state_bytes": (c_size_t, [c_int, c_int]),
-    "micloc_xylo_stream_track_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "micloc_xylo_stream_track_reset": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p]),
-    "micloc_xylo_lif_track_resume_i16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
-                                                 c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p,
-                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
-    "micloc_stream_xylo_tile_track_i16": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_int,
-                                                  c_int, c_void_p, c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
-                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "micloc_abi_version": (c_int, []),
-    "micloc_status_string": (ctypes.c_char_p, [c_int]),
-    "micloc_last_hip_error": (c_int, []),
-}
+_SCALARS = {"int": c_int, "size_t": c_size_t, "double": ctypes.c_double, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32}
+_PROTOTYPE = re.compile(r"\b((?:const\s+)?\w+[\s*]+)(micloc_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl, symbol, is_return=False):
+    """The ctypes type of a return type or of a parameter (its type, then its name) as the header spells it.  There is no default: a type
+    outside the mapping raises."""
+    ctype = decl if is_return else re.sub(r"\w+\s*$", "", decl)
+    stars = ctype.count("*")
+    base = " ".join(w for w in ctype.replace("*", " ").split() if w != "const")
+    if stars >= 2:  # T **, T *const *: an array of handles or an out-handle
+        return ctypes.POINTER(c_void_p)
+    if stars == 1:  # host or device memory: the header cannot say which
+        return ctypes.c_char_p if is_return and base == "char" else c_void_p
+    if is_return and base == "void":
+        return None
+    if base not in _SCALARS:
+        raise MiclocError(f"{symbol}: no ctypes mapping for '{' '.join(decl.split())}'")
+    return _SCALARS[base]
+
+
+def parse_header(text):
+    """(symbols, constants) of the header text: name -> (restype, argtypes) for every prototype, and the value of every integer
+    `#define MICLOC_*` and `micloc_status` enumerator."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    symbols = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        params = [] if params.strip() == "void" else params.split(",")
+        symbols[name] = (_ctype(ret, name, True), [_ctype(p, name) for p in params])
+    constants = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MICLOC_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)
+    status = re.search(r"enum\s*\{([^}]*)\}\s*micloc_status\b", text)
+    constants += re.findall(r"(MICLOC_\w+)\s*=\s*(-?\d+)", status.group(1)) if status else []
+    return symbols, {name: int(value) for name, value in constants}
+
+
+if not os.path.exists(HEADER_PATH):
+    raise MiclocError(f"{HEADER_PATH} not found: the binding is derived from the header, which lies next to the package")
+with open(HEADER_PATH) as _f:
+    # SYMBOLS: every symbol include/micloc_hip.h declares, name -> (restype, argtypes); the MICLOC_* constants become attributes
+    SYMBOLS, _constants = parse_header(_f.read())
+globals().update(_constants)
 
 _lib = None
-
-
-class MiclocError(RuntimeError):
-    pass
 
 
 def load():

@@ -231,13 +231,13 @@ class Plan:
         return x.contiguous()
 
     # ---- pipelines -----------------------------------------------------------------------------------
-    def snn_pipeline(self, x, want_spikes=False, want_y=False, want_power=True, stages=7, out=None, window=None, hop=None):
+    def snn_pipeline(self, x, want_spikes=False, want_y=False, want_power=True, stages=_lib.MICLOC_STAGE_ALL, out=None, window=None, hop=None):
         """x: device tensor [B, T, M]. Returns dict of device tensors (spikes int8, y, power, argmax).
         `window` (frames; `hop` defaults to it; multiples of window_quantum()): also window_power [B, nW, G] and window_argmax [B, nW],
         the power and arg-max per window of the rule in include/micloc_hip.h, from the same beamforming launch (whole pipeline, no y).
-        `stages` (MICLOC_STAGE_* bits: 1 STHT, 2 band-pass + RZCC, 4 LIF + beamforming + power; 8 / 16: only the serial scan of a
-        chunked band-pass + RZCC stage / the stage without it) launches a part of the pipeline; the parts of one batch share this
-        plan's workspace and, via `out`, the output tensors."""
+        `stages` (bits: STAGE_STHT, STAGE_ENCODE for band-pass + RZCC, STAGE_BEAMFORM for LIF + beamforming + power; STAGE_ENCODE_SCAN /
+        STAGE_ENCODE_REST: only the serial scan of a chunked band-pass + RZCC stage / the stage without it) launches a part of the
+        pipeline; the parts of one batch share this plan's workspace and, via `out`, the output tensors."""
         torch = _torch()
         B, T, M = x.shape
         if M != self.num_mic:
@@ -247,8 +247,8 @@ class Plan:
                        **self._beamform_out(B, T, want_y, want_power))
         ws, nbytes = self.workspace(B, T)
         if window is not None:
-            if out["y"] is not None or int(stages) != 7:
-                raise ValueError("the windowed read-out runs the whole pipeline and has no T x G output (want_y=False, stages=7)")
+            if out["y"] is not None or int(stages) != _lib.MICLOC_STAGE_ALL:
+                raise ValueError(f"the windowed read-out runs the whole pipeline and has no T x G output (want_y=False, stages={_lib.MICLOC_STAGE_ALL})")
             return self._windowed(self.lib.micloc_snn_pipeline_windows_f64, "snn_pipeline_windows", x, B, T, window, hop, out, ws, nbytes,
                                   spikes=(_ptr(out["spikes"]),))
         _lib.check(
@@ -790,7 +790,7 @@ def _synth_args(template, mode, delays, doa, geometry, moving, shift, gain, out)
     args.moving = int(bool(moving))
     args.shift = sh.data_ptr() if sh is not None else None
     args.gain = gn.data_ptr() if gn is not None else None
-    args.mode = {"apply_to_template": 0, "signal_from_template": 1}[mode]
+    args.mode = {"apply_to_template": _lib.MICLOC_SYNTH_APPLY_TO_TEMPLATE, "signal_from_template": _lib.MICLOC_SYNTH_SIGNAL_FROM_TEMPLATE}[mode]
     args.fs = template.fs
     args.x = x.data_ptr()
     return args, x, (keep, sh, gn)
@@ -916,7 +916,7 @@ def peak_location(counts, G, win_size, out=None):
     return idx
 
 
-GRID_KINDS = {"linear": 0, "circular": 1, "circular_closed": 2}  # MICLOC_GRID_*
+GRID_KINDS = {"linear": _lib.MICLOC_GRID_LINEAR, "circular": _lib.MICLOC_GRID_CIRCULAR, "circular_closed": _lib.MICLOC_GRID_CIRCULAR_CLOSED}
 
 
 def doa_peaks(power, doa_list, grid_kind, num_sources, min_separation, rel_threshold=0.0, index_out=None, value_out=None):
@@ -959,7 +959,8 @@ def envelope_track(y, win_fall, win_rise, want_index=True, env_out=None):
     -> (env float64 of y's shape, index int32 [T] / [B, T] or None).
     Envelope.evolve (micloc/utils.py:36-81) + np.argmax(axis=1) (paper_plots/target_snn_localization.py:599-622) on the device."""
     torch = _torch()
-    kinds = {torch.float64: 0, torch.complex128: 1, torch.uint8: 2, torch.int32: 3, torch.int64: 4}  # MICLOC_ENV_*
+    kinds = {torch.float64: _lib.MICLOC_ENV_F64, torch.complex128: _lib.MICLOC_ENV_C128, torch.uint8: _lib.MICLOC_ENV_U8,
+             torch.int32: _lib.MICLOC_ENV_I32, torch.int64: _lib.MICLOC_ENV_I64}
     if y.dtype not in kinds or y.dim() not in (2, 3) or not y.is_cuda:
         raise ValueError("envelope_track: a device tensor [T, G] or [B, T, G] of float64 / complex128 / uint8 / int32 / int64 is required")
     consts = envelope_consts(win_fall, win_rise)
@@ -997,7 +998,8 @@ def doa_error(argmax, doa_list, doa_true, groups=1, want_err=True):
     return err, mae
 
 
-STAGE_STHT, STAGE_ENCODE, STAGE_BEAMFORM, STAGE_ENCODE_SCAN, STAGE_ENCODE_REST = 1, 2, 4, 8, 16  # include/micloc_hip.h MICLOC_STAGE_*
+STAGE_STHT, STAGE_ENCODE, STAGE_BEAMFORM = _lib.MICLOC_STAGE_STHT, _lib.MICLOC_STAGE_ENCODE, _lib.MICLOC_STAGE_BEAMFORM
+STAGE_ENCODE_SCAN, STAGE_ENCODE_REST = _lib.MICLOC_STAGE_ENCODE_SCAN, _lib.MICLOC_STAGE_ENCODE_REST
 
 
 class CuRangeStream:

@@ -429,7 +429,7 @@ class Demo:
         out = []
         for plan in self._plans():
             x = plan.to_device(sig_batch)
-            out.append(plan.snn_pipeline(x, want_spikes=True, want_power=False, stages=3)["spikes"])
+            out.append(plan.snn_pipeline(x, want_spikes=True, want_power=False, stages=runtime.STAGE_STHT | runtime.STAGE_ENCODE)["spikes"])
         return out
 
     def _pack(self, rasters, mode):
@@ -439,8 +439,8 @@ class Demo:
 
         B, T, C = rasters[0].shape
         F = len(rasters)
-        width = F * C * (2 if mode == 2 else 1)
-        out = torch.empty((B, T, width), dtype=torch.uint8 if mode else torch.int8, device=rasters[0].device)
+        width = F * C * (2 if mode == _lib.MICLOC_PACK_BIPOLAR else 1)
+        out = torch.empty((B, T, width), dtype=torch.int8 if mode == _lib.MICLOC_PACK_TERNARY else torch.uint8, device=rasters[0].device)
         for f, r in enumerate(rasters):
             _lib.check(_lib.load().micloc_pack_events_u8(runtime._ptr(r), B, T, C, f, F, mode, runtime._ptr(out), runtime._stream(r.device)),
                        "pack_events")
@@ -448,7 +448,7 @@ class Demo:
 
     def spike_encoding_device(self, sig_batch):
         """[B, T, M] -> uint8 device tensor [B, T, 2M * F * (2 if bipolar else 1)] of 0/1 events."""
-        return self._pack(self._band_rasters(sig_batch), 2 if self.bipolar_spikes else 1)
+        return self._pack(self._band_rasters(sig_batch), _lib.MICLOC_PACK_BIPOLAR if self.bipolar_spikes else _lib.MICLOC_PACK_UNIPOLAR)
 
     def spike_encoding(self, sig_in):
         sig_in = np.ascontiguousarray(sig_in, dtype=np.float64)
@@ -468,7 +468,7 @@ class Demo:
         """[B, T, M] -> the encoder's int8 raster [B, T, 2M * F] in {-1, 0, +1} (bands concatenated on the channel axis);
         the +/- split of spike_encoding happens inside the LIF kernel's staging loop."""
         per_band = self._band_rasters(sig_batch)
-        return per_band[0] if len(per_band) == 1 else self._pack(per_band, 0)
+        return per_band[0] if len(per_band) == 1 else self._pack(per_band, _lib.MICLOC_PACK_TERNARY)
 
     def counts_batch(self, sig_batch, queued=True):
         """[B, T, M] noisy array signals -> output spike counts per hidden neuron, int32 device tensor [B, F * G]; nothing of

@@ -1,5 +1,6 @@
 """CPU-only checks of the drop-in boundary: the C-ABI library loads, exports every symbol that
-include/micloc_hip.h declares, and the product path fails loudly (no CPU fallback) without a GPU."""
+include/micloc_hip.h declares, _lib's signatures and constants are that header's and its two struct classes lay out as the C compiler
+does, and the product path fails loudly (no CPU fallback) without a GPU."""
 import ctypes
 import os
 import re
@@ -28,6 +29,75 @@ def test_library_exports_every_declared_symbol():
         assert n in _lib.SYMBOLS, f"{n} is declared in the header but not bound in _lib.SYMBOLS"
     assert sorted(_lib.SYMBOLS) == names
     assert lib.micloc_abi_version() == 1
+
+
+I, Z, D, V = ctypes.c_int, ctypes.c_size_t, ctypes.c_double, ctypes.c_void_p
+U64, U32, PP = ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)
+# written by hand from the prototypes in include/micloc_hip.h, one entry per kind of the mapping; independent of _lib's parser
+SPOT = {
+    "micloc_awgn_f64": (I, [V, I, I, I, V, V, U64, U32, V, U32, V, Z, V]),
+    "micloc_uniform_f64": (I, [V, Z, U64, U32, V, D, D, V]),
+    "micloc_lif_beamform_track_f64": (I, [V, V, I, I, D, D, D, V, V, V, V, Z, V]),
+    "micloc_stream_reset": (I, [V, I, V, Z, V, Z, V, I, V]),
+    "micloc_workspace_bytes": (Z, [V, I, I]),
+    "micloc_plan_create": (I, [V, PP]),
+    "micloc_snn_pipeline_bands_f64": (I, [PP, I, V, V, I, V, I, I, I, I, V, V, V, V, Z, V]),
+    "micloc_status_string": (ctypes.c_char_p, [I]),
+    "micloc_plan_destroy": (None, [V]),
+    "micloc_abi_version": (I, []),
+    "micloc_stream_window_count_ptr": (V, [V]),  # const int32_t * return: a device address, not a string
+    "micloc_stream_xylo_tile_track_i16": (I, [V, V, V, Z, V, I, I, I, I, I, V, V, Z, V, Z, V, Z, V, Z, I, I, I, V, Z, D, D, D, I, V, V, V, V, V, V,
+                                              Z, V]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SPOT))
+def test_derived_signature_is_the_hand_written_one(name):
+    res, args = _lib.SYMBOLS[name]
+    assert res is SPOT[name][0], name
+    assert len(args) == len(SPOT[name][1]), name
+    for i, (got, want) in enumerate(zip(args, SPOT[name][1])):
+        assert got is want, (name, i, got, want)
+
+
+def test_the_spot_table_holds_the_longest_signature():
+    assert max(len(args) for _, args in _lib.SYMBOLS.values()) == len(SPOT["micloc_stream_xylo_tile_track_i16"][1]) == 36
+
+
+def test_parser_refuses_an_unknown_type_and_names_it():
+    with pytest.raises(_lib.MiclocError, match=r"micloc_x.*float gain"):
+        _lib.parse_header("int micloc_x(const double *a, float gain);")
+    with pytest.raises(_lib.MiclocError, match=r"micloc_x.*int64_t"):
+        _lib.parse_header("int64_t micloc_x(void);")
+    with pytest.raises(_lib.MiclocError, match="micloc_x"):  # `void` is a return type only
+        _lib.parse_header("int micloc_x(void v);")
+
+
+def test_parser_ignores_comments():
+    text = "/* int micloc_x(float a); calls micloc_x(1.0f)\n * on two lines */\nint micloc_y(int a); // void micloc_x(float a);\n"
+    assert _lib.parse_header(text) == ({"micloc_y": (I, [I])}, {})
+
+
+def test_parser_reads_a_prototype_over_several_lines():
+    text = "size_t\nmicloc_y(const micloc_plan *const *plans,\n        int F, /* bands */\n        double\n        gain,\n  void **out\n);\n"
+    assert _lib.parse_header(text)[0] == {"micloc_y": (Z, [PP, I, D, PP])}
+
+
+def test_parser_gives_no_arguments_for_void():
+    assert _lib.parse_header("int micloc_y(void);\nvoid micloc_z( void );")[0] == {"micloc_y": (I, []), "micloc_z": (None, [])}
+
+
+def test_constants_are_the_headers():
+    """Every integer #define MICLOC_* and every micloc_status enumerator, found here line by line, is an attribute of _lib."""
+    found = {}
+    for line in open(os.path.join(ROOT, "include", "micloc_hip.h")):
+        m = re.match(r"\s*#define\s+(MICLOC_\w+)\s+(-?\d+)\b", line) or re.match(r"\s*(MICLOC_\w+)\s*=\s*(-?\d+)\b", line)
+        if m:
+            found[m.group(1)] = int(m.group(2))
+    assert len(found) >= 29 and found["MICLOC_ERR_NO_DEVICE"] == -6 and found["MICLOC_MAX_BANDS"] == 16 and found["MICLOC_STAGE_ENCODE_REST"] == 16
+    for name, value in found.items():
+        assert getattr(_lib, name) == value, name
+    assert sorted(n for n in vars(_lib) if n.startswith("MICLOC_")) == sorted(found)
 
 
 def test_plain_helpers_without_gpu():
@@ -154,18 +224,22 @@ def test_product_does_not_import_the_oracle():
 
 def test_header_is_plain_c_and_links_from_c(tmp_path):
     """include/micloc_hip.h is the drop-in boundary: it must be usable from plain C (C99, -pedantic), and a C program must be able to
-    link against libmicloc_hip.so and call the entry points that need no GPU."""
+    link against libmicloc_hip.so and call the entry points that need no GPU.  The same program prints sizeof and every offsetof of the two
+    argument structs: _lib's hand-written ctypes classes must lay their fields out as the C compiler does, in the same order."""
     import shutil
     import subprocess
 
     if shutil.which("gcc") is None:
         pytest.skip("no gcc on this host")
+    structs = (("micloc_config", _lib.MiclocConfig), ("micloc_synth_args", _lib.MiclocSynthArgs))
+    layout = "".join(f'    printf("%zu{" %zu" * len(cls._fields_)}\\n", sizeof({c})'
+                     + "".join(f", offsetof({c}, {f})" for f, _ in cls._fields_) + ");\n" for c, cls in structs)
     src = tmp_path / "abi_c.c"
     src.write_text(
         '#include "micloc_hip.h"\n#include <stdio.h>\n'
         "int main(void) {\n"
         '    printf("%d %s %d %zu\\n", micloc_abi_version(), micloc_status_string(MICLOC_ERR_SHAPE), micloc_padded_T(4799),\n'
-        "           micloc_rzcc_workspace_bytes(2, 100, 14));\n"
+        "           micloc_rzcc_workspace_bytes(2, 100, 14));\n" + layout +
         "    return micloc_abi_version() == MICLOC_ABI_VERSION ? 0 : 1;\n}\n")
     inc = os.path.join(ROOT, "include")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", inc, "-fsyntax-only", str(src)])
@@ -180,5 +254,9 @@ def test_header_is_plain_c_and_links_from_c(tmp_path):
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     out = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
-    fields = out.stdout.decode().split()
+    lines = out.stdout.decode().splitlines()
+    fields = lines[0].split()
     assert fields[0] == "1" and fields[-2] == "4800" and int(fields[-1]) > 0
+    assert len(lines) == 1 + len(structs)
+    for line, (c, cls) in zip(lines[1:], structs):
+        assert [int(v) for v in line.split()] == [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f, _ in cls._fields_], c
