@@ -1,9 +1,10 @@
 // C-ABI of libmicloc_hip.so (see include/micloc_hip.h for the contract and reference citations): recordings that arrive tile by tile --
 // the filterbank's state carry and the band sum per tile, the SNN stream, the complex stream (each with or without the window read-out and the tracked read-out), the complex stream of F bands, and
-// the MUSIC stream.
+// the MUSIC stream; the tracked read-out of the two wideband streams.
 #include "api_sets.h"
 #include "stream_music.h"
 #include "stream_track.h"
+#include "stream_track_bands.h"
 
 using namespace micloc;
 
@@ -631,7 +632,7 @@ int scb_window_args(int rc, const micloc_plan *const *plans, int window, int hop
 // the launches behind the band-pass of a tile: contraction per band, accumulation, (windows,) slide + commit over the F * B rows, band sum
 int scb_localize(const micloc_plan *const *plans, int F, int B, const ScbArgs &s, void *state, int final_tile, double *band_power, double *power,
                  int32_t *argmax, void *ws, void *win_state, int window, int hop, int max_windows, double *window_power, int32_t *window_argmax,
-                 double *latest_power, int32_t *latest_argmax, hipStream_t st)
+                 double *latest_power, int32_t *latest_argmax, hipStream_t st, const TrackArgs *trk = nullptr)
 {
     const micloc_plan *p0 = plans[0];
     const ScArgs &a = s.a;
@@ -651,6 +652,16 @@ int scb_localize(const micloc_plan *const *plans, int F, int B, const ScbArgs &s
     if (win_state)  // every band's windows into its rows of the ring, window n in row n % Kb; the one count word serves all bands
         HIP_TRY(launch_stream_windows(partial, s.FB, a.Ks, a.Gp, G, 1, a.Gp / 2, a.CH, reinterpret_cast<const int *>(state), final_tile ? 1 : 0, window,
                                       hop, s.Kb, win_state, ring, nullptr, nullptr, nullptr, st));
+    if (trk) {  // in front of the slide: the carry fill and the clock as they were before the tile; band f's rows of the staging array
+        TrackBandsArgs ta{};
+        for (int f = 0; f < F; ++f) {
+            ta.src[f] = staging + f * band_rows;
+            ta.Wp[f] = plans[f]->W.Wp;
+            ta.GT[f] = plans[f]->W.GT;
+        }
+        HIP_TRY(launch_stream_track_bands_complex(ta, F, reinterpret_cast<const int *>(state), p0->C, B, a.S, G, trk->a_rise, trk->i_rise, trk->a_fall,
+                                                  trk->state, trk->R, trk->index, trk->peak, trk->latest_index, trk->latest_peak, trk->ws, st));
+    }
     HIP_TRY(launch_stream_complex_slide(staging, s.FB * p0->C, a.S, a.CH, state, a.L, st));
     StreamBandsArgs args{};
     for (int f = 0; f < F; ++f) {
@@ -787,6 +798,160 @@ int micloc_stream_complex_bands_status(const void *state, const void *win_state,
     status6[3] = ctl[STREAM_CLK_T];
     status6[4] = w[0];
     status6[5] = w[1];
+    return MICLOC_OK;
+}
+
+}  // extern "C"
+
+// ---- wideband streaming, tracking (stream_track_bands.hip; the rule: include/micloc_hip.h) --------------------------------------------------
+namespace {
+
+// what the stream serves of a set: MICLOC_OK, *cpx = the set's kind and (SNN) *CH = the bands' one chunk length -- or the status of the set
+// rule (INVALID / NOT_SET from micloc_*_bands_track_is_fused), MICLOC_ERR_SHAPE for a set off the fused route, for SNN bands whose chunk
+// lengths differ or whose LIF history 4 NK - 16 is longer than a chunk, and for complex bands that are not one chain
+int stb_served(const micloc_plan *const *plans, int F, int B, bool *cpx, int *CH)
+{
+    *CH = 0;
+    if (set_pointers(plans, F) != MICLOC_OK || bad_batch(B)) return MICLOC_ERR_INVALID;
+    *cpx = plans[0]->W_is_complex != 0;
+    const int fused = *cpx ? micloc_beamformer_bands_track_is_fused(plans, F) : micloc_snn_bands_track_is_fused(plans, F);
+    if (fused < 0) return fused;
+    if (fused != 1) return MICLOC_ERR_SHAPE;
+    if (*cpx) {
+        ScbArgs s;
+        return scb_args(plans, F, B, 0, &s);
+    }
+    *CH = lif_beamform_chunk_frames(plans[0]->W, plans[0]->ntab);
+    for (int f = 0; f < F; ++f)
+        if (lif_beamform_chunk_frames(plans[f]->W, plans[f]->ntab) != *CH || stream_track_halo(plans[f]->ntab) > *CH) return MICLOC_ERR_SHAPE;
+    return MICLOC_OK;
+}
+
+// the rule of the tracked arguments behind stb_served: `most` frames can become final in one tile, the pairs cover `cap` positions
+int stb_track_args(const micloc_plan *p0, const TrackArgs &t, int B, int most, int cap)
+{
+    if (t.R < most) return MICLOC_ERR_SHAPE;
+    if (bad_ws(t.state, t.state_bytes, stream_track_bands_state_bytes(B, p0->G_out))) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(t.ws, t.ws_bytes, stream_track_pairs_bytes(B, cap, p0->G_out))) return MICLOC_ERR_WORKSPACE;
+    return MICLOC_OK;
+}
+
+bool stb_missing(const TrackArgs &t) { return !t.state || !t.index || !t.peak || !t.latest_index || !t.latest_peak || t.R < 1; }
+
+}  // namespace
+
+extern "C" {
+
+size_t micloc_stream_bands_track_state_bytes(const micloc_plan *const *plans, int F, int B)
+{
+    bool cpx;
+    int CH;
+    if (stb_served(plans, F, B, &cpx, &CH) != MICLOC_OK || plans[0]->G_out < 1) return 0;
+    return stream_track_bands_state_bytes(B, plans[0]->G_out);
+}
+
+size_t micloc_stream_bands_track_workspace_bytes(const micloc_plan *const *plans, int F, int B, int frames)
+{
+    bool cpx;
+    int CH;
+    if (frames < 1 || stb_served(plans, F, B, &cpx, &CH) != MICLOC_OK || plans[0]->G_out < 1) return 0;
+    int cap = frames;
+    if (cpx) {  // the staging array of a complex stream whose longest tile has `frames` frames
+        ScbArgs s;
+        if (scb_args(plans, F, B, frames, &s) != MICLOC_OK) return 0;
+        cap = s.a.S;
+    } else if (frames % CH != 0) {
+        return 0;
+    }
+    return stream_track_pairs_bytes(B, cap, plans[0]->G_out);
+}
+
+int micloc_stream_bands_track_reset(const micloc_plan *const *plans, int F, int B, void *track_state, size_t track_bytes, void *stream)
+{
+    if (!plans || !track_state) return MICLOC_ERR_INVALID;
+    bool cpx;
+    int CH;
+    const int rc = stb_served(plans, F, B, &cpx, &CH);
+    if (rc != MICLOC_OK) return rc;
+    const size_t need = stream_track_bands_state_bytes(B, plans[0]->G_out);
+    if (bad_ws(track_state, track_bytes, need)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    HIP_TRY(launch_zero_fill(track_state, need, (hipStream_t)stream));  // the frontier at frame 0, the envelope rows
+    return MICLOC_OK;
+}
+
+int micloc_stream_bands_track_tile_f64(const micloc_plan *const *plans, int F, const void *const *loc_states, const int8_t *const *windows, int B,
+                                       int window_frames, void *track_state, size_t track_bytes, double a_rise, double i_rise, double a_fall,
+                                       int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index, double *latest_peak,
+                                       void *track_ws, size_t track_ws_bytes, void *stream)
+{
+    const TrackArgs trk{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, track_ws,
+                        track_ws_bytes};
+    if (set_pointers(plans, F) != MICLOC_OK || !loc_states || !windows || bad_batch(B) || window_frames < 1 || stb_missing(trk)) return MICLOC_ERR_INVALID;
+    for (int f = 0; f < F; ++f)
+        if (!loc_states[f] || !windows[f]) return MICLOC_ERR_INVALID;
+    bool cpx;
+    int CH;
+    int rc = stb_served(plans, F, B, &cpx, &CH);
+    if (rc != MICLOC_OK) return rc;
+    if (cpx || window_frames % CH != 0) return MICLOC_ERR_SHAPE;
+    const micloc_plan *p0 = plans[0];
+    rc = stb_track_args(p0, trk, B, window_frames, window_frames);  // a tile can make every frame of the windows final
+    if (rc != MICLOC_OK) return rc;
+    DeviceGuard guard(p0->device);
+    TrackBandsArgs ta{};
+    TrackBandsCtl tc{};
+    int NKmax = 0;
+    for (int f = 0; f < F; ++f) {
+        ta.src[f] = windows[f];
+        ta.tab[f] = plans[f]->ntab.tab;
+        ta.Wp[f] = plans[f]->W.Wp;
+        ta.NK[f] = plans[f]->ntab.NK;
+        ta.GT[f] = plans[f]->W.GT;
+        tc.ctl[f] = reinterpret_cast<const int *>(loc_states[f]);
+        if (ta.NK[f] > NKmax) NKmax = ta.NK[f];
+    }
+    HIP_TRY(launch_stream_track_bands(ta, tc, F, NKmax, p0->C, B, window_frames, CH, p0->G_out, a_rise, i_rise, a_fall, track_state, max_track,
+                                      track_index, track_peak, latest_index, latest_peak, track_ws, (hipStream_t)stream));
+    return MICLOC_OK;
+}
+
+int micloc_stream_complex_bands_localize_tile_track_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B, int max_tile,
+                                                        int final_tile, double *band_power, double *power, int32_t *argmax, void *ws,
+                                                        size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop, int max_windows,
+                                                        double *window_power, int32_t *window_argmax, double *latest_power,
+                                                        int32_t *latest_argmax, void *track_state, size_t track_bytes, double a_rise,
+                                                        double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak,
+                                                        int32_t *latest_index, double *latest_peak, void *track_ws, size_t track_ws_bytes,
+                                                        void *stream)
+{
+    const TrackArgs trk{track_state, track_bytes, a_rise, i_rise, a_fall, max_track, track_index, track_peak, latest_index, latest_peak, track_ws,
+                        track_ws_bytes};
+    if (!plans || !state || !ws || (win_state && !window_argmax) || max_tile < 1 || stb_missing(trk)) return MICLOC_ERR_INVALID;
+    ScbArgs s;
+    int rc = scb_args(plans, F, B, max_tile, &s);
+    if (win_state) rc = scb_window_args(rc, plans, window, hop, max_windows, &s);
+    if (rc != MICLOC_OK) return rc;
+    bool cpx;
+    int CH;
+    rc = stb_served(plans, F, B, &cpx, &CH);
+    if (rc != MICLOC_OK) return rc;
+    rc = stb_track_args(plans[0], trk, B, max_tile, s.a.S);  // a tile makes its own frames final, no more
+    if (rc != MICLOC_OK) return rc;
+    if (bad_ws(state, state_bytes, s.a.L.total)) return MICLOC_ERR_WORKSPACE;
+    if (bad_ws(ws, ws_bytes, s.ws_total)) return MICLOC_ERR_WORKSPACE;
+    if (win_state && bad_ws(win_state, win_bytes, s.win_total)) return MICLOC_ERR_WORKSPACE;
+    DeviceGuard guard(plans[0]->device);
+    return scb_localize(plans, F, B, s, state, final_tile, band_power, power, argmax, ws, win_state, window, hop, max_windows, window_power,
+                        window_argmax, latest_power, latest_argmax, (hipStream_t)stream, &trk);
+}
+
+/* the tracked frontier of the SNN bands in absolute frames: every frame below it has been emitted (synchronises the stream) */
+int micloc_stream_bands_track_status(const void *track_state, int *frontier, void *stream)
+{
+    if (!track_state || !frontier) return MICLOC_ERR_INVALID;
+    HIP_TRY(hipMemcpyAsync(frontier, reinterpret_cast<const int *>(track_state) + STB_FRONT, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return MICLOC_OK;
 }
 

@@ -3,7 +3,7 @@
 //
 // track.hip's workgroup -- 64 DoA columns of ONE trial, chunks of 64 frames, stages 1 to 4 of its header: the same text, track_ws_walk /
 // track_wsc_walk of track_rows.h -- walks the frames a tile made final instead of a recording from frame 0 to T.  What stands here is what
-// differs: the range read from the stream's words, the state load and store, the ring store of a finished row:
+// differs: whose words give the range, the state load and store (the range, the ring store and the pair store: stream_track_rows.h):
 //   track_ws_stream_kernel    the SNN stream: the window-relative chunks ctl[4] .. ctl[5] of CH frames that rz_stream_horizon_kernel left,
 //                             cut at ctl[10], the frames of the raster window that exist; window row 0 is frame ctl[STREAM_CLK_BASE];
 //   track_wsc_stream_kernel   the complex stream: the staging columns [fill, fill + n), fill = ctl[2] (the carry), n = ctl[SC_N]; column
@@ -19,79 +19,12 @@
 // window / the staging array, and track_stream_combine_kernel finishes them by track_combine_kernel's rule.
 #include "bandpass_rows.h"
 #include "stream_track.h"
+#include "stream_track_rows.h"
 #include "track_rows.h"
 
 namespace micloc {
 
 namespace {
-
-// the frames [f0, f1) of the window (SNN) or of the staging array (complex) that this tile made final; position p is frame abs0 + p
-struct TrackSpan {
-    int f0, f1, abs0;
-};
-
-template <bool COMPLEX>
-__device__ __forceinline__ TrackSpan track_span(const int *__restrict__ ctl, int CH, int cap)
-{
-    TrackSpan s;
-    if (COMPLEX) {
-        const int fill = ctl[2], n = ctl[SC_N];
-        s.f0 = fill;
-        s.f1 = fill + n;
-        s.abs0 = ctl[STREAM_CLK_T] - fill;
-    } else {
-        const int exist = ctl[10];
-        s.f0 = ctl[4] * CH;
-        s.f1 = ctl[5] * CH < exist ? ctl[5] * CH : exist;
-        s.abs0 = ctl[STREAM_CLK_BASE];
-    }
-    if (s.f0 < 0) s.f0 = 0;  // (never: the words are the stream's own)
-    if (s.f1 > cap) s.f1 = cap;
-    return s;
-}
-
-struct TrackSink {
-    int R;  // ring depth
-    int32_t *index;
-    double *peak;
-    int32_t *latest_index;
-    double *latest_peak;
-};
-
-// a finished row of trial b: frame `abs` into its ring row, the newest frame of the launch also into the latest words
-__device__ __forceinline__ void track_ring_store(const TrackSink &o, int b, int abs, bool newest, double best, int bi)
-{
-    const size_t r = (size_t)b * o.R + (size_t)((unsigned)abs % (unsigned)o.R);  // (abs >= 0: the clock's)
-    const int idx = track_row_index(bi);
-    const double pk = track_row_peak(best, bi);
-    o.index[r] = idx;
-    o.peak[r] = pk;
-    if (newest) {
-        o.latest_index[b] = idx;
-        o.latest_peak[b] = pk;
-    }
-}
-
-// the emit of both kernels for the chunk at position cs.  Built where it is called, from the kernel's locals: one object that lives across
-// the walk was not split into registers by the compiler (24 to 112 bytes of scratch per lane)
-struct TrackEmit {
-    const TrackSink &o;
-    const TrackSpan &sp;
-    int b, cg, ncg, cap, cs;
-    double *__restrict__ pval;
-    int32_t *__restrict__ pidx;
-    __device__ __forceinline__ void operator()(int row, double best, int bi) const
-    {
-        const int f = cs + row;
-        if (ncg == 1) {
-            track_ring_store(o, b, sp.abs0 + f, f == sp.f1 - 1, best, bi);
-        } else {
-            const size_t e = ((size_t)b * cap + f) * ncg + cg;
-            pidx[e] = bi;
-            pval[e] = best;
-        }
-    }
-};
 
 // SNN: the raster window [B][cap][C] int8, C <= 16; CH: frames per chunk of the stream (a multiple of TRK_CH, 4 NK - 16 <= CH)
 __global__ __launch_bounds__(TRK_THREADS) void track_ws_stream_kernel(const int8_t *__restrict__ win, const int *__restrict__ ctl, int CH, int cap,
@@ -136,19 +69,12 @@ __global__ __launch_bounds__(TRK_THREADS) void track_wsc_stream_kernel(const dou
     if (wv == 0) *sg = state;
 }
 
-// one thread per position of the window / the staging array; positions outside the tile's range return
+// the combine of a tile (track_stream_combine of stream_track_rows.h) on the range of the stream's own words
 template <bool COMPLEX>
 __global__ __launch_bounds__(256) void track_stream_combine_kernel(const double *__restrict__ pval, const int32_t *__restrict__ pidx,
                                                                    const int *__restrict__ ctl, int CH, int cap, int ncg, const TrackSink out)
 {
-    const TrackSpan sp = track_span<COMPLEX>(ctl, CH, cap);
-    const int f = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (f < sp.f0 || f >= sp.f1) return;
-    const size_t e = ((size_t)b * cap + f) * ncg;
-    double best;
-    int bi;
-    track_combine_row(pval + e, pidx + e, ncg, best, bi);
-    track_ring_store(out, b, sp.abs0 + f, f == sp.f1 - 1, best, bi);
+    track_stream_combine(track_span<COMPLEX>(ctl, CH, cap), pval, pidx, cap, ncg, out);
 }
 
 }  // namespace

@@ -22,10 +22,11 @@
 // others' staging and matrix phases.
 // The four stages are written once, in track_rows.h (track_ws_walk / track_wsc_walk over track_chain_reduce), for these kernels and for
 // the streaming ones of stream_track.hip, with the channel-count table and the pairs layout of the launchers.  Here: the kernels as a walk
-// from frame 0 with a zero chain state, the store of a pair, the last envelope row; the combine; the walks and kernels over F bands
-// (wideband tracking: one magnitude tile summed over the bands); the read-out of the two-step route.
+// from frame 0 with a zero chain state, the store of a pair, the last envelope row; the combine; the kernels over F bands (wideband
+// tracking: one magnitude tile summed over the bands, the walk of track_bands_rows.h); the read-out of the two-step route.
 #include "track_rows.h"
 #include "track_bands.h"
+#include "track_bands_rows.h"
 
 namespace micloc {
 
@@ -153,81 +154,15 @@ hipError_t launch_track_fused(const BeamformW &W, const NeuronTab &nt, int is_co
 }
 
 // ---- wideband: F bands, one magnitude tile (the rule: include/micloc_hip.h, "wideband moving-target tracking") ----
-// The launch shape above: a workgroup owns 64 DoA columns of one trial and walks it in 64-frame chunks.  Per chunk it loops over the
-// bands in ascending order; band f runs the per-chunk step of the single-plan walks with ITS operands -- rows, neuron table, bf_mat --
-// in that step's order, so y_f[t][g] has the bits of band f's own chain.  Band 0 stores |y_0| into the tile, every later band adds |y_f| with
-// one rounded add: m = ((a_0 + a_1) + a_2) + ...  Behind the last band track_chain_reduce runs on the summed tile, unchanged.  The
-// bf_mat fragments of F bands do not fit in registers: they are loaded again per band and chunk (16 KB per band and column group at
-// most, which stays in L2) in front of the barrier, so the loads are in flight while the rows are staged.  No workgroup waits for
-// another; nothing of size T x G exists.  (TrackBandPut of track_rows.h stores or adds.)
-// SNN bands: trial b of every band's raster [B][T][C], the whole recording from frame 0; the LDS regions are sized for NKmax
-template <class Emit>
-__device__ __forceinline__ void track_bands_ws_walk(unsigned char *smem, const TrackBandsArgs &a, int F, int NKmax, int b, int C, int T, int G,
-                                                    int cg, double a_rise, double i_rise, double a_fall, double &state, const Emit &emit)
-{
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;
-    const int lc = l & 15;
-    const int q = l >> 4;
-    double *Y = reinterpret_cast<double *>(smem);  // [TRK_CH][TRK_LD]
-    double *ntab = Y + TRK_CH * TRK_LD;
-    double *S = ntab + 4 * NKmax + 16;
-
-    for (int cs = 0; cs < T; cs += TRK_CH) {
-        for (int f = 0; f < F; ++f) {
-            const int NK = a.NK[f];
-            if (f > 0) __syncthreads();  // every wave is done with the previous band's table and rows
-            double Wf[4][4];
-            track_ws_weights(Wf, a.Wp[f], a.GT[f], cg, lc, q);
-            track_ws_table(ntab, a.tab[f], NK, tid);
-            track_ws_stage(S, static_cast<const int8_t *>(a.src[f]) + (size_t)b * T * C, C, cs, T, NK, tid);
-            __syncthreads();  // (f == 0 also: the previous chunk's row reduction is done with Y)
-            track_ws_tile(S, ntab, NK, cs, T, wv, lc, q, Wf, TrackBandPut{Y, f == 0});
-        }
-        __syncthreads();
-        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, emit);
-    }
-}
-
-// complex bands: trial b of every band's planar rows [B][C][Ts]
-template <int KM, int KV, class Emit>
-__device__ __forceinline__ void track_bands_wsc_walk(unsigned char *smem, const TrackBandsArgs &a, int F, int b, int C, int Ts, int T, int G, int cg,
-                                                     double a_rise, double i_rise, double a_fall, double &state, const Emit &emit)
-{
-    constexpr int KF = KM + (KV > 0 ? 1 : 0);
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;
-    const int lc = l & 15;
-    const int q = l >> 4;
-    double *Y = reinterpret_cast<double *>(smem);
-    double *tail = Y + TRK_CH * TRK_LD + wv * 64;
-
-    for (int cs = 0; cs < T; cs += TRK_CH) {
-        for (int f = 0; f < F; ++f) {
-            double V[KF];
-            TrackCW<KM, KV> w;
-            track_wsc_weights<KM, KV>(w, a.Wp[f], a.GT[f], cg, lc, q);
-            if (f > 0) __syncthreads();  // the reads of the previous band's tail fragment are done
-            track_wsc_frags<KM, KV>(V, tail, static_cast<const double *>(a.src[f]) + (size_t)b * C * Ts, C, Ts, cs, T, wv, l);
-            __syncthreads();  // (f == 0 also: the previous chunk's row reduction is done with Y)
-            track_wsc_tile<KM, KV>(V, tail, w, wv, lc, q, TrackBandPut{Y, f == 0});
-        }
-        __syncthreads();
-        const int nrow = T - cs < TRK_CH ? T - cs : TRK_CH;
-        track_chain_reduce(Y, wv, l, tid, cs, cs == 0, nrow, G, cg, a_rise, i_rise, a_fall, state, emit);
-    }
-}
-
+// The walks over the bands of a chunk are track_bands_ws_walk / track_bands_wsc_walk of track_bands_rows.h, which the streaming band
+// kernels of stream_track_bands.hip run as well; here they walk a whole recording: the range (0, T, 0), the rows' stride the recording's.
 __global__ __launch_bounds__(TRK_THREADS) void track_bands_ws_kernel(TrackBandsArgs a, int F, int NKmax, int C, int T, int G, double a_rise,
                                                                      double i_rise, double a_fall, double *__restrict__ pval,
                                                                      int32_t *__restrict__ pidx, double *__restrict__ env_last)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
-        track_bands_ws_walk(smem, a, F, NKmax, blockIdx.y, C, T, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
+        track_bands_ws_walk(smem, a, F, NKmax, blockIdx.y, C, T, 0, T, 0, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
     });
 }
 
@@ -238,7 +173,7 @@ __global__ __launch_bounds__(TRK_THREADS) void track_bands_wsc_kernel(TrackBands
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     track_one_shot(T, G, pval, pidx, env_last, [&](double &state, const auto &emit) {
-        track_bands_wsc_walk<KM, KV>(smem, a, F, blockIdx.y, C, Ts, T, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
+        track_bands_wsc_walk<KM, KV>(smem, a, F, blockIdx.y, C, Ts, 0, T, 0, G, blockIdx.x, a_rise, i_rise, a_fall, state, emit);
     });
 }
 

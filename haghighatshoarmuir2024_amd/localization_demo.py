@@ -43,7 +43,9 @@ class Demo:
 
     def localizer(self):
         """The batched form of this demo's chain (wideband.WidebandBeamformerLocalizer over the same beamformers, matrices and
-        filterbank): B packs per call, every band's chain in one batch, the band sum and its arg-max on the device."""
+        filterbank): B packs per call, every band's chain in one batch, the band sum and its arg-max on the device.  Its
+        streaming_localizer(batch, **kw) is the live form (streaming.WidebandComplexStreamingLocalizer), which with track= (a utils.Envelope)
+        and max_track= also follows a talker who moves while the packs arrive (latest_track() / tracked())."""
         loc = WidebandBeamformerLocalizer(self.beamfs, self.bf_mats, self.filterbank)
         loc.doa_list = self.doa_list
         return loc

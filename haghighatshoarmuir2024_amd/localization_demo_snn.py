@@ -53,7 +53,9 @@ class Demo:
     def streaming_localizer(self, batch=1, **kw):
         """The live form of this demo's chain: streaming.WidebandStreamingLocalizer over the same bands -- the packs of `batch` sources are
         tiles of ONE stream each (the filterbank, the STHT, the band-pass, the encoder and the LIF carry their state from pack to pack instead
-        of restarting as `process_frame` does), one graph launch per pack through push_replay.  **kw: WidebandStreamingLocalizer's."""
+        of restarting as `process_frame` does), one graph launch per pack through push_replay.  **kw: WidebandStreamingLocalizer's -- among
+        them track= (a utils.Envelope) and max_track=, the per-frame read-out of localizer().track_batch for a talker who moves while the
+        packs arrive (latest_track() / tracked())."""
         from .streaming import WidebandStreamingLocalizer
 
         return WidebandStreamingLocalizer(self.localizer(), batch, **kw)

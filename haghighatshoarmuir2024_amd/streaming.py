@@ -40,6 +40,9 @@ finish().  The state is the envelope in front of the next frame, 64 doubles per 
 tile is still one graph.  track_setup is the host-side rule (which plans, which ring depths), ring_rows the arithmetic of a ring's rows.
 XyloStreamingLocalizer (one band) takes track= too: Demo.track_batch's rows, from the tracking form of the packed integer LIF walk -- its
 ring rule is track_ring, track_setup's without the limits of the fused kernels of csrc/track.hip (LIF parity unpinned).
+The two wideband streams take track= as well (include/micloc_hip.h "wideband streaming, tracking"): the rows of the wideband localizers'
+track_batch, one magnitude summed over the bands.  The complex bands advance in lock step; the SNN bands finish chunks at different pushes,
+and a frame is tracked once EVERY band has beamformed its chunk -- bands_track_span is that frontier rule as host arithmetic.
 
 THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
@@ -101,6 +104,17 @@ def track_ring(envelope, most, total_frames=None, max_track=None):
     if R < most:
         raise ValueError(f"max_track must be at least the {most} frames one tile can make final (got {R})")
     return (*consts, R)
+
+
+def bands_track_span(prev, done, chunk_frames, t_end):
+    """The frontier rule of a tracked stream of SNN bands (include/micloc_hip.h "wideband streaming, tracking"), as the device's frontier
+    kernel applies it after a tile: -> (first, last), the tile tracks the frames [first, last).  prev: the frontier before the tile (frames
+    tracked so far); done: every band's committed chunk count (status()["chunks"] of the bands); chunk_frames: the bands' one chunk
+    length; t_end: frames pushed so far.  A frame is final once the chunk that holds it has been beamformed by every band, the last
+    chunk of a recording may be ragged, and the frontier never moves back.  Pure host arithmetic."""
+    prev = int(prev)
+    front = min(min(int(d) for d in done) * int(chunk_frames), int(t_end))
+    return prev, max(front, prev)
 
 
 class _TileStream:
@@ -173,24 +187,30 @@ class _TileStream:
         else:
             *self.track, self.max_track = track_ring(envelope, most, self.T, max_track)
 
-    def _alloc_track(self, capacity):
+    _track_head = 0  # bytes in front of the envelope rows in `tst` (a set of plans: the frontier words)
+
+    def _alloc_track(self, capacity, plans=None):
         """The device side of track=: the envelope state (zero-filled on the stream), the pair scratch for `capacity` (the raster window's
-        frames / max_tile), the ring and the newest frame."""
+        frames / max_tile), the ring and the newest frame.  plans: (handles, F) of a wideband stream -- the state, the scratch and the
+        reset of a set of plans (micloc_stream_bands_track_*), whose state has a 256-byte head; default: this stream's one plan."""
         if self.track is None:
             return
         torch = runtime._torch()
-        dev, lib, h = self.device, self.lib, self.plan.handle
-        self.ntst = int(lib.micloc_stream_track_state_bytes(h, self.B))
-        self.ntws = int(lib.micloc_stream_track_workspace_bytes(h, self.B, int(capacity)))
+        dev, lib = self.device, self.lib
+        lead, name = ((self.plan.handle,), "stream_track") if plans is None else (tuple(plans), "stream_bands_track")
+        self._track_head = 0 if plans is None else 256
+        self.ntst = int(getattr(lib, f"micloc_{name}_state_bytes")(*lead, self.B))
+        self.ntws = int(getattr(lib, f"micloc_{name}_workspace_bytes")(*lead, self.B, int(capacity)))
         if self.ntst == 0 or self.ntws == 0:
-            raise ValueError("micloc stream_track_state_bytes: the fused tracking kernels do not serve this plan and bf_mat")
+            raise ValueError(f"micloc {name}_state_bytes: the fused tracking kernels do not serve " +
+                             ("this plan and bf_mat" if plans is None else "this set of plans; use track_batch on the whole recording"))
         self.tst = torch.empty(self.ntst, dtype=torch.uint8, device=dev)
         self.tws = torch.empty(self.ntws, dtype=torch.uint8, device=dev)
         self.track_index = torch.zeros((self.B, self.max_track), dtype=torch.int32, device=dev)
         self.track_peak = torch.zeros((self.B, self.max_track), dtype=torch.float64, device=dev)
         self.latest_index = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         self.latest_peak = torch.zeros((self.B,), dtype=torch.float64, device=dev)
-        _lib.check(lib.micloc_stream_track_reset(h, self.B, runtime._ptr(self.tst), self.ntst, runtime._stream(dev)), "stream_track_reset")
+        _lib.check(getattr(lib, f"micloc_{name}_reset")(*lead, self.B, runtime._ptr(self.tst), self.ntst, runtime._stream(dev)), f"{name}_reset")
 
     def _reset_window_state(self, name, lead=None, who="the plan", hint=""):
         """wst / nwst, the device state of the open windows (None / 0 without window=): sized by micloc_<name>_state_bytes, zero-filled by
@@ -396,7 +416,7 @@ class _TileStream:
                                        "tracked() while the stream runs)")
             w = self.tracked()
             if env_last is None:
-                env_last = self.tst.view(runtime._torch().float64).view(self.B, -1)[:, : self.G]  # [B][column groups x 64]
+                env_last = self.tst[self._track_head :].view(runtime._torch().float64).view(self.B, -1)[:, : self.G]  # [B][column groups x 64]
             out.update(track_index=w["index"], track_peak_envelope=w["peak_envelope"], track_count=w["count"], envelope_last=env_last.clone())
         return out
 
@@ -640,16 +660,22 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
     of slack, or the number of windows of the recording where that is known and smaller.  The band sum counts a failure instead of
     summing an overwritten row should the bound ever be exceeded (only after a band's own lag failure); finish() then raises."""
 
-    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, window=None, hop=None, max_windows=None):
+    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, window=None, hop=None, max_windows=None,
+                 track=None, max_track=None, time_vec=None):
         """loc: wideband.WidebandSNNLocalizer; the other arguments as StreamingLocalizer's, except
         wrap_tail  [F, batch, L // 2, M]: the last L // 2 frames of every band's FILTERED recording (np.roll's wrap-around happens after
-                   the filterbank), or None (zeros, as for a live source)."""
+                   the filterbank), or None (zeros, as for a live source).
+        track, max_track   the tracked read-out of WidebandSNNLocalizer.track_batch (module docstring, TRACKING); min_track = the bands'
+                   raster window capacity.  None: exactly the launches without it.
+        time_vec   handed to every band's neuron kernel, where the one-shot call to be matched was given one (track_batch(time_vec=))."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
         self._check_bands(loc, batch, wrap_tail)
         F = self.F
         self.T = None if total_frames is None else int(total_frames)
+        # the refusals of track= that need no plan, before any device work (the ring depth follows the bands' window, below)
+        self._set_track(track, max_track, 2 * self.M, self.G, False, 0)
         if window is not None and hop is not None:
             self._check_hop(int(hop), int(window))
         if max_windows is not None:
@@ -665,7 +691,7 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
                     Kb = self._ring_depth(window, hop, lag_frames)
                 kw = dict(window=window, hop=hop, max_windows=Kb)
             tail = None if wrap_tail is None else wrap_tail[f]
-            self.bands.append(StreamingLocalizer(beamf, W, self.B, self.T, wrap_tail=tail, max_tile=max_tile, lag_frames=lag_frames,
+            self.bands.append(StreamingLocalizer(beamf, W, self.B, self.T, wrap_tail=tail, max_tile=max_tile, lag_frames=lag_frames, time_vec=time_vec,
                                                  _share=self.bands[0] if self.bands else None, **kw))
         b0 = self.bands[0]
         self.device, self.lib, self.plan = b0.device, b0.lib, b0.plan
@@ -686,6 +712,16 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
             self._p_rows = (vp * F)(*[b.window_power.data_ptr() for b in self.bands])
             self._p_count = (vp * F)(*[self.lib.micloc_stream_window_count_ptr(runtime._ptr(b.wst)) for b in self.bands])
         _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, runtime._stream(self.device)), "stream_bands_reset")
+        # track=: one tracked state over the bands' plans, localize states and raster windows (which share cap and CH)
+        self.CH, self.cap = b0.CH, b0.cap
+        self._set_track(track, max_track, 2 * self.M, self.G, False, self.cap)
+        if self.track is not None:
+            if any(b.cap != self.cap for b in self.bands):
+                raise ValueError("a tracked wideband stream needs one raster window capacity in every band")
+            self.handles = (vp * F)(*[b.plan.handle.value for b in self.bands])
+            self._p_loc = (vp * F)(*[b.loc.data_ptr() for b in self.bands])
+            self._p_win = (vp * F)(*[b.win.data_ptr() for b in self.bands])
+            self._alloc_track(self.cap, plans=(self.handles, F))
 
     MAX_CHUNK = 512  # the longest chunk of the beamforming kernels (include/micloc_hip.h: 256 frames up to 64 channels, 512 beyond)
 
@@ -720,6 +756,11 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
                                                   self._p_count, runtime._ptr(self.bands_state), self.nbs, runtime._ptr(self.power), runtime._ptr(self.argmax),
                                                   runtime._ptr(self.window_power), runtime._ptr(self.window_argmax),
                                                   runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax), st), "stream_band_sum")
+        if self.track is not None:  # behind every band's commit and tick (and behind the band sum, with which it shares no word)
+            _lib.check(lib.micloc_stream_bands_track_tile_f64(self.handles, F, self._p_loc, self._p_win, B, self.cap, runtime._ptr(self.tst), self.ntst,
+                                                              *self.track, self.max_track, runtime._ptr(self.track_index), runtime._ptr(self.track_peak),
+                                                              runtime._ptr(self.latest_index), runtime._ptr(self.latest_peak), runtime._ptr(self.tws),
+                                                              self.ntws, st), "stream_bands_track_tile")
 
     def _advance(self, n, final):
         for band in self.bands:
@@ -734,10 +775,20 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
 
     def status(self):
         """StreamingLocalizer.status() over the bands -- chunks / frames: the slowest band's; lag_failures / overflow: summed -- plus
-        bands (the per-band dicts) and band_sum_failures (windows given up because a band's ring had overwritten them).  Synchronises."""
+        bands (the per-band dicts) and band_sum_failures (windows given up because a band's ring had overwritten them); with track= also
+        tracked, the frames tracked so far (the joint frontier of the bands).  Synchronises."""
         per = [b.status() for b in self.bands]
-        return dict(chunks=min(s["chunks"] for s in per), frames=min(s["frames"] for s in per), lag_failures=sum(s["lag_failures"] for s in per),
-                    overflow=sum(s["overflow"] for s in per), bands=per, band_sum_failures=self._bands_status()[1])
+        out = dict(chunks=min(s["chunks"] for s in per), frames=min(s["frames"] for s in per), lag_failures=sum(s["lag_failures"] for s in per),
+                   overflow=sum(s["overflow"] for s in per), bands=per, band_sum_failures=self._bands_status()[1])
+        if self.track is not None:
+            out["tracked"] = self._track_count()  # the joint frontier: frames every band has beamformed (bands_track_span)
+        return out
+
+    def _track_count(self):
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.micloc_stream_bands_track_status(runtime._ptr(self.tst), ctypes.byref(c), runtime._stream(self.device)),
+                   "stream_bands_track_status")
+        return int(c.value)
 
     def _window_count(self):
         """The smallest of the bands' counts at the last push."""
@@ -745,7 +796,8 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
 
     def finish(self):
         """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
-        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows()); with track= also
+        track_index [B, T] int32, track_peak_envelope [B, T], track_count and envelope_last [B, G] (a live source: the max_track newest)."""
         torch = runtime._torch()
         self._need_done()
         s = self.status()
@@ -753,7 +805,7 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up: a band's ring of {self.Kb} windows had overwritten them")
         out = dict(power=self.power, argmax=self.argmax, band_power=torch.stack([b.power for b in self.bands]))
-        return self._finish_windows(out)
+        return self._finish_track(self._finish_windows(out))
 
 
 class ComplexStreamingLocalizer(_TileStream):
@@ -871,14 +923,17 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
     length.  The bands complete every window in the same tile, so the bands' ring (inside the window state) is as deep as the number of
     windows one tile can complete plus the one cut at the end of the recording, and no window is ever given up."""
 
-    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None):
+    def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None, track=None,
+                 max_track=None):
         """loc: wideband.WidebandBeamformerLocalizer; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
                       final=True with the last tile.
         wrap_tail     [F, batch, L // 2, M]: np.roll's wrap-around rows of every band's FILTERED recording (the roll happens after the
                       filterbank; ComplexStreamingLocalizer.wrap_rows of each band's filterbank output), or None (zeros: a live source).
         max_tile      longest tile push() will be given.
-        window, hop, max_windows   the windowed read-out, as ComplexStreamingLocalizer's."""
+        window, hop, max_windows   the windowed read-out, as ComplexStreamingLocalizer's.
+        track, max_track           the tracked read-out of WidebandBeamformerLocalizer.track_batch (module docstring, TRACKING); a tile makes
+                                   its own frames final in every band, so min_track = max_tile."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
@@ -891,6 +946,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         self.max_tile = int(max_tile)
         if self.max_tile < 1:
             raise ValueError("max_tile must be at least 1")
+        self._set_track(track, max_track, 2 * self.M, self.G, True, self.max_tile)  # (refusals before any device work)
         # the stream's own plans, one per band (the band-pass coefficients and the bf_mat of that band)
         self.plans = []
         for beamf, W in zip(loc.beamfs, loc.bf_mats):
@@ -915,6 +971,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         self.band_power = torch.zeros((F, self.B, self.G), dtype=torch.float64, device=dev)
         self._alloc_results()
         self._reset_window_state("stream_complex_bands_window", lead=(self.handles, F, self.B, self.max_tile), who="the plans")
+        self._alloc_track(self.max_tile, plans=(self.handles, F))
         self._set_wrap(wrap_tail, bands=True)
         _lib.check(self.lib.micloc_stream_complex_bands_reset(self.handles, F, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
                    "stream_complex_bands_reset")
@@ -939,25 +996,32 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
     def status(self):
         """dict(chunks, frames, carry, pushed, windows, band_sum_failures): chunks and frames contracted (the same for every band), frames
         waiting in the carry, frames pushed (the device clock), wideband windows emitted, windows given up (always 0: the ring depth
-        covers what one tile can complete).  Synchronises the stream."""
+        covers what one tile can complete); with track= also tracked, the frames tracked so far (the frames pushed).  Synchronises the stream."""
         s6 = (ctypes.c_int * 6)()
         _lib.check(self.lib.micloc_stream_complex_bands_status(runtime._ptr(self.state), runtime._ptr(self.wst), s6, runtime._stream(self.device)),
                    "stream_complex_bands_status")
-        return dict(chunks=int(s6[0]), frames=int(s6[1]), carry=int(s6[2]), pushed=int(s6[3]), windows=int(s6[4]), band_sum_failures=int(s6[5]))
+        out = dict(chunks=int(s6[0]), frames=int(s6[1]), carry=int(s6[2]), pushed=int(s6[3]), windows=int(s6[4]), band_sum_failures=int(s6[5]))
+        if self.track is not None:
+            out["tracked"] = out["pushed"]  # a frame is tracked by the tile that brings it, in every band
+        return out
 
     def _window_count(self):
         return self.status()["windows"]
 
+    def _track_count(self):
+        return self.status()["pushed"]
+
     def finish(self):
         """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
-        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows())."""
+        window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows()); with track= also
+        track_index [B, T] int32, track_peak_envelope [B, T], track_count and envelope_last [B, G] (a live source: the max_track newest)."""
         self._need_done()
         s = self.status()
         self._need_clock(s)
         if s["band_sum_failures"]:
             raise _lib.MiclocError(f"{s['band_sum_failures']} wideband window(s) were given up by the band sum")
         out = dict(power=self.power, argmax=self.argmax, band_power=self.band_power)
-        return self._finish_windows(out)
+        return self._finish_track(self._finish_windows(out))
 
 
 class MusicStreamingLocalizer(_TileStream):

@@ -1173,6 +1173,41 @@ def wideband_track_localizer(loc, envelope, max_batch=1100):
     return run
 
 
+def wideband_stream_track_localizer(loc, envelope, tile, max_batch=1100):
+    """stream_track_localizer's twin for a wideband localizer in wideband_moving_target_sweep(localizer=): every batch is pushed in tiles of
+    `tile` frames through the tracked wideband stream (streaming.WidebandStreamingLocalizer / WidebandComplexStreamingLocalizer with
+    track=envelope; SNN bands take multiples of 16) and the index [B, T] of finish() comes back -- the bits of loc.track_batch on the whole
+    batch, which the wrap-around rows of every band's filtered batch (known here: the batch is complete), total_frames and the sweep's
+    time axis of the neuron kernels make possible."""
+    from . import runtime
+    from .streaming import WidebandComplexStreamingLocalizer, WidebandStreamingLocalizer
+
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("tile must be at least 1 frame")
+    snn = hasattr(loc.beamfs[0], "tau_vec")
+    half = len(loc.beamfs[0].kernel) // 2
+
+    def run(sig_batch, time_vec):
+        def one(x):
+            import torch
+
+            B, T, _ = x.shape
+            xf = runtime.filterbank(loc.filterbank.ba_list, x, device=getattr(loc.beamfs[0], "device", None))  # [F, B, T, M]
+            tail = torch.stack([_wrap_rows(xf[f], half) for f in range(xf.shape[0])])
+            if snn:
+                s = WidebandStreamingLocalizer(loc, B, total_frames=T, wrap_tail=tail, max_tile=min(tile, T), track=envelope, time_vec=time_vec)
+            else:
+                s = WidebandComplexStreamingLocalizer(loc, B, total_frames=T, wrap_tail=tail, max_tile=min(tile, T), track=envelope)
+            for t in range(0, T, tile):
+                s.push(x[:, t : t + tile, :])
+            return (s.finish()["track_index"],)
+
+        return _in_batches(sig_batch, max_batch, one)[0]
+
+    return run
+
+
 def wideband_moving_target_sweep(loc, envelope, localizer=None, batch_trials=1100, store_key=None, **kw):
     """moving_target_sweep read out by the WIDEBAND localizer `loc` (the form the reference deploys in its live demos) instead of one
     band: that sweep's own moving test signal, path, SNR grid, lag, settle and scoring; the estimate of frame t is the arg-max of the

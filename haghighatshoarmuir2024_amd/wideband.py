@@ -205,7 +205,8 @@ class WidebandBeamformerLocalizer(_WidebandLocalizer):
     def streaming_localizer(self, batch=1, **kw):
         """localize_batch for recordings that arrive tile by tile: a streaming.WidebandComplexStreamingLocalizer (push / push_replay /
         finish; total_frames, wrap_tail, max_tile, window, hop, max_windows as there) whose results after the last tile are localize_batch's
-        on the whole recording bit for bit."""
+        on the whole recording bit for bit.  track= (a utils.Envelope) and max_track= add the per-frame read-out of track_batch for a source
+        that moves while the audio arrives (latest_track() / tracked() / finish())."""
         from .streaming import WidebandComplexStreamingLocalizer
 
         return WidebandComplexStreamingLocalizer(self, batch, **kw)

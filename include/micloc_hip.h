@@ -1015,6 +1015,62 @@ int micloc_stream_complex_bands_localize_tile_windows_f64(const micloc_plan *con
                                                           void *stream);
 int micloc_stream_complex_bands_status(const void *state, const void *win_state, int *status6, void *stream);
 
+/* ---- wideband streaming, tracking: a DoA per frame over all bands while the recording arrives ---- */
+/* The rule of "wideband moving-target tracking" for a recording that arrives tile by tile through one of the two wideband streams above.
+ *   Values.  The rows emitted for frame t of trial b are index[b][t] and peak_envelope[b][t] of "wideband moving-target tracking": the
+ *   bands' magnitudes |y_f| added with one rounded add per band in ascending band order, the envelope, the first maximum and the NaN rule
+ *   of "moving-target tracking".  The stream is that call on the whole recording, bit for bit, for any tiling; after the last tile the
+ *   first G columns of every trial's state row equal env_last.
+ *   When a frame is final.
+ *   - Complex bands advance in lock step as ONE complex stream of F * B rows: a frame is final when its tile has been band-passed, as in
+ *     "streaming, tracking".  The range of a tile comes from that stream's control words (carry fill, tile length, clock).
+ *   - SNN bands have a horizon each and finish chunks at different pushes: a frame is final when the chunk that holds it has been
+ *     beamformed by EVERY band.  The tracked frontier after a tile is min(min_f done_f * CH, t_end), done_f = band f's committed chunk
+ *     count, CH the bands' one chunk length, t_end the frames pushed; a tile tracks the frames from the previous frontier to the new one.
+ *     The frontier is a word of the tracked state of its own, in absolute frames -- not derived from any one band's range words.  The
+ *     words are written by one thread of a small launch in front of the tracking launch; no launch argument depends on time.
+ *   Why the rows are still there (SNN).  The bands share window_frames and CH, so their raster windows share the base schedule (the
+ *   stream's clock depends on the tile sizes only).  A band without a lag failure keeps chunk done_f - 1 in its window (the slide's
+ *   check).  The frontier is at most done_f * CH for every f, hence the chunk in front of the frontier is in every band's window, and the
+ *   LIF history 4 NK_f - 16 <= CH of every band with it.  A band's lag failure stops that band's done_f and with it the frontier: no
+ *   wrong row is emitted, and micloc_stream_localize_status reports the failure as it does without tracking.
+ *   Ring, latest words, scratch: as in "streaming, tracking".  max_track is at least what a tile can make final: window_frames (SNN),
+ *   max_tile (complex).  track_state (micloc_stream_bands_track_state_bytes, zero-filled once by micloc_stream_bands_track_reset) is a
+ *   256-byte head that holds the frontier words, then [B][ceil(G / 64) * 64] doubles; track_ws is scratch of
+ *   micloc_stream_bands_track_workspace_bytes (its last argument: window_frames for SNN bands, max_tile for complex ones).  Nothing grows
+ *   with the stream and nothing of size T x G exists.
+ *   Who is served.  A set that is fused by micloc_snn_bands_track_is_fused / micloc_beamformer_bands_track_is_fused (the kind is that of
+ *   plans[0]'s bf_mat); SNN sets also need one chunk length and 4 NK_f - 16 <= CH in every band, complex sets what "wideband streaming,
+ *   complex Beamformer" asks of a set.  The two-step route has no streaming form.
+ *   Entries.  micloc_stream_bands_track_tile_f64 (SNN) is called once per tile BEHIND the last band's micloc_stream_localize_tile[_windows]_f64
+ *   (its commit and tick included) and in front of or behind micloc_stream_band_sum_f64, with which it shares no word; loc_states[f] /
+ *   windows[f] are band f's loc_state and raster window.  It launches the frontier kernel, the tracking kernel and (G > 64) the combine.
+ *   micloc_stream_complex_bands_localize_tile_track_f64 is micloc_stream_complex_bands_localize_tile[_windows]_f64 with the tracking
+ *   launch (and its combine) in front of the slide; it takes the window arguments as micloc_stream_complex_localize_tile_track_f64 does:
+ *   with win_state == NULL there is no window read-out.  band_power, power, argmax and the window rows keep the bits of the entries
+ *   without tracking.  micloc_stream_bands_track_status gives the SNN frontier in frames (it synchronises the stream); the complex
+ *   frontier is the frames pushed of micloc_stream_complex_bands_status.
+ *   Status, before any launch and in this order: MICLOC_ERR_INVALID (NULL plans, a NULL plan, loc_state, window, track_state or result
+ *   buffer, F, B, window_frames / max_tile or max_track out of range) / MICLOC_ERR_NOT_SET as everywhere; MICLOC_ERR_SHAPE for a set that
+ *   is not served, a set of the other kind, window_frames that is no multiple of CH, or max_track below what a tile can make final;
+ *   MICLOC_ERR_WORKSPACE for a missing, misaligned or short state / scratch.  The size functions return 0 for a set that is not served. */
+size_t micloc_stream_bands_track_state_bytes(const micloc_plan *const *plans, int F, int B);
+size_t micloc_stream_bands_track_workspace_bytes(const micloc_plan *const *plans, int F, int B, int frames);
+int micloc_stream_bands_track_reset(const micloc_plan *const *plans, int F, int B, void *track_state, size_t track_bytes, void *stream);
+int micloc_stream_bands_track_tile_f64(const micloc_plan *const *plans, int F, const void *const *loc_states, const int8_t *const *windows,
+                                       int B, int window_frames, void *track_state, size_t track_bytes, double a_rise, double i_rise,
+                                       double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                       double *latest_peak, void *track_ws, size_t track_ws_bytes, void *stream);
+int micloc_stream_complex_bands_localize_tile_track_f64(const micloc_plan *const *plans, int F, void *state, size_t state_bytes, int B,
+                                                        int max_tile, int final_tile, double *band_power, double *power, int32_t *argmax,
+                                                        void *ws, size_t ws_bytes, void *win_state, size_t win_bytes, int window, int hop,
+                                                        int max_windows, double *window_power, int32_t *window_argmax,
+                                                        double *latest_power, int32_t *latest_argmax, void *track_state,
+                                                        size_t track_bytes, double a_rise, double i_rise, double a_fall, int max_track,
+                                                        int32_t *track_index, double *track_peak, int32_t *latest_index,
+                                                        double *latest_peak, void *track_ws, size_t track_ws_bytes, void *stream);
+int micloc_stream_bands_track_status(const void *track_state, int *frontier, void *stream);
+
 /* ---- MUSIC baseline beamformer (micloc/music_beamformer.py) ----------------------------------- */
 /* MUSIC.apply_to_signal for a batch of trials: x [B][T][M] (device) is cut into S slices, slice s = samples
  * [s hop, min(s hop + L, T)) (the reference's full slices and its leftover one); each slice is band-passed from zero state
