@@ -95,7 +95,8 @@ class Beamformer:
     def streaming_localizer(self, bf_mat, batch=1, **kw):
         """localize_batch for recordings that arrive tile by tile: a streaming.ComplexStreamingLocalizer (push / push_replay / finish;
         total_frames, wrap_tail, max_tile, window, hop, max_windows as there) whose results after the last tile are localize_batch's on
-        the whole recording bit for bit."""
+        the whole recording bit for bit.  num_sources= (with doa_list=, min_separation=, rel_threshold= as localize_batch's) adds the K
+        strongest peaks of the running power and of every window (latest_peaks() / windows() / finish())."""
         from .streaming import ComplexStreamingLocalizer
 
         return ComplexStreamingLocalizer(self, bf_mat, batch, **kw)

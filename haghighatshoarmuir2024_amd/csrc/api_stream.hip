@@ -88,6 +88,9 @@ int micloc_stream_bands_status(const void *bands_state, int *status2, void *stre
     return MICLOC_OK;
 }
 
+/* device address of word [0] of micloc_stream_bands_status (for kernels that follow the wideband windows: stream_peaks.hip) */
+const int32_t *micloc_stream_bands_window_count_ptr(const void *bands_state) { return reinterpret_cast<const int32_t *>(bands_state); }
+
 // ---- streaming: the band-pass / RZCC stage tile by tile, exact state hand-off -----------------------------------
 size_t micloc_stream_state_bytes(const micloc_plan *p, int B)
 {
@@ -801,6 +804,12 @@ int micloc_stream_complex_bands_status(const void *state, const void *win_state,
     return MICLOC_OK;
 }
 
+/* device address of word [4] of micloc_stream_complex_bands_status (for kernels that follow the wideband windows: stream_peaks.hip) */
+const int32_t *micloc_stream_complex_bands_window_count_ptr(const void *win_state)
+{
+    return win_state ? reinterpret_cast<const int32_t *>(reinterpret_cast<const unsigned char *>(win_state) + SCB_BANDS_WORDS) : nullptr;
+}
+
 }  // extern "C"
 
 // ---- wideband streaming, tracking (stream_track_bands.hip; the rule: include/micloc_hip.h) --------------------------------------------------
@@ -1029,6 +1038,12 @@ int micloc_stream_music_status(const void *state, int *status4, void *stream)
     status4[2] = clk[3];
     status4[3] = clk[2];
     return MICLOC_OK;
+}
+
+/* device address of word [1] of micloc_stream_music_status, the slices emitted (for kernels that follow the slices: stream_peaks.hip) */
+const int32_t *micloc_stream_music_slice_count_ptr(const void *state)
+{
+    return state ? reinterpret_cast<const int32_t *>(state) + 1 : nullptr;
 }
 
 }  // extern "C"

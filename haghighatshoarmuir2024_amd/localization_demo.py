@@ -45,7 +45,9 @@ class Demo:
         """The batched form of this demo's chain (wideband.WidebandBeamformerLocalizer over the same beamformers, matrices and
         filterbank): B packs per call, every band's chain in one batch, the band sum and its arg-max on the device.  Its
         streaming_localizer(batch, **kw) is the live form (streaming.WidebandComplexStreamingLocalizer), which with track= (a utils.Envelope)
-        and max_track= also follows a talker who moves while the packs arrive (latest_track() / tracked())."""
+        and max_track= also follows a talker who moves while the packs arrive (latest_track() / tracked()), and with num_sources=
+        (min_separation=, rel_threshold=; the grid is the demo's doa_list) reports the K strongest peaks per pack and per window for several
+        talkers at once (latest_peaks() / windows())."""
         loc = WidebandBeamformerLocalizer(self.beamfs, self.bf_mats, self.filterbank)
         loc.doa_list = self.doa_list
         return loc

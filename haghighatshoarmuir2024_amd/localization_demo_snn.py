@@ -55,7 +55,8 @@ class Demo:
         tiles of ONE stream each (the filterbank, the STHT, the band-pass, the encoder and the LIF carry their state from pack to pack instead
         of restarting as `process_frame` does), one graph launch per pack through push_replay.  **kw: WidebandStreamingLocalizer's -- among
         them track= (a utils.Envelope) and max_track=, the per-frame read-out of localizer().track_batch for a talker who moves while the
-        packs arrive (latest_track() / tracked())."""
+        packs arrive (latest_track() / tracked()), and num_sources= (min_separation=, rel_threshold=; the grid is the demo's doa_list), the
+        K strongest peaks per pack and per window for several talkers at once (latest_peaks() / windows())."""
         from .streaming import WidebandStreamingLocalizer
 
         return WidebandStreamingLocalizer(self.localizer(), batch, **kw)

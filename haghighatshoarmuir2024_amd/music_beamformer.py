@@ -218,13 +218,17 @@ class MUSIC:
                         want_sel=want_sel)
         return _add_peaks(out, self.doa_list, num_sources, min_separation, rel_threshold)
 
-    def streaming_localizer(self, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None):
+    def streaming_localizer(self, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None,
+                            num_sources=None, min_separation=None, rel_threshold=0.0):
         """localize_batch for recordings that arrive in tiles (streaming.MusicStreamingLocalizer): push / push_replay tiles of any
-        length, the same bits after the last one.  The ValueErrors of localize_batch are raised here, before any device work."""
+        length, the same bits after the last one.  The ValueErrors of localize_batch are raised here, before any device work.
+        num_sources (with min_separation, rel_threshold as localize_batch's): also the K strongest peaks over self.doa_list of the
+        running power and of every slice's spectrum (latest_peaks() / windows() / finish())."""
         from .streaming import MusicStreamingLocalizer
 
         return MusicStreamingLocalizer(self, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=total_frames,
-                                       max_tile=max_tile, max_slices=max_slices)
+                                       max_tile=max_tile, max_slices=max_slices, num_sources=num_sources, min_separation=min_separation,
+                                       rel_threshold=rel_threshold)
 
     def synthesize_batch(self, template, doas, device_delays=False):
         """Noise-free array signals of a batch of trials on the device (as SNNBeamformer.synthesize_batch)."""

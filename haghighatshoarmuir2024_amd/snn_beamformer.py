@@ -214,7 +214,9 @@ class SNNBeamformer:
     def streaming_localizer(self, bf_mat, batch=1, **kw):
         """localize_batch (and, with track=, track_batch) for recordings that arrive tile by tile: a streaming.StreamingLocalizer (push /
         push_replay / finish; total_frames, wrap_tail, max_tile, lag_frames, window, hop, max_windows, track, max_track as there) whose
-        results after the last tile are the one-shot calls' on the whole recording bit for bit."""
+        results after the last tile are the one-shot calls' on the whole recording bit for bit.  num_sources= (with doa_list=,
+        min_separation=, rel_threshold= as localize_batch's) adds the K strongest peaks of the running power and of every window
+        (latest_peaks() / windows() / finish())."""
         from .streaming import StreamingLocalizer
 
         return StreamingLocalizer(self, bf_mat, batch, **kw)

@@ -44,6 +44,13 @@ The two wideband streams take track= as well (include/micloc_hip.h "wideband str
 track_batch, one magnitude summed over the bands.  The complex bands advance in lock step; the SNN bands finish chunks at different pushes,
 and a frame is tracked once EVERY band has beamformed its chunk -- bands_track_span is that frontier rule as host arithmetic.
 
+SEVERAL SOURCES (num_sources=, doa_list=, min_separation=, rel_threshold=; every class but XyloStreamingLocalizer, whose read-out is the
+box-car peak of an integer rate): the read-out of localize_batch(num_sources=) -- utils.find_doa_peaks' rule, the K strongest peaks -- of the
+running power after every push and, with window=, of every window as soon as it is emitted, bit for bit the one-shot rows (include/micloc_hip.h
+"streaming, multi-source").  The read-out follows the stream's count of emitted windows on the device and is the last launch of every tile,
+inside the tile's graph: latest_peaks() / windows() / finish() / peaks_status().  _set_peaks holds the refusals, _alloc_peaks the device side,
+_peaks_tile the launch; the defaults are utils.doa_peaks_defaults, the one rule batch and stream share.  May be given together with track=.
+
 THE COMPLEX BEAMFORMER (ComplexStreamingLocalizer): the non-spiking baseline as the same kind of stream -- band-pass state, a carry of
 the frames behind the last whole chunk and the accumulators on the device, tiles of any length, Beamformer.localize_batch's bits after
 the last tile, with or without windows (include/micloc_hip.h "streaming, complex Beamformer").
@@ -211,6 +218,73 @@ class _TileStream:
         self.latest_index = torch.zeros((self.B,), dtype=torch.int32, device=dev)
         self.latest_peak = torch.zeros((self.B,), dtype=torch.float64, device=dev)
         _lib.check(getattr(lib, f"micloc_{name}_reset")(*lead, self.B, runtime._ptr(self.tst), self.ntst, runtime._stream(dev)), f"{name}_reset")
+
+    num_sources = None  # the multi-source read-out is off unless _set_peaks has been given num_sources
+
+    def _set_peaks(self, num_sources, doa_list, min_separation, rel_threshold, num_doa):
+        """self.num_sources (K, None without num_sources=), self.doa_list (host float64 [G]), self.grid, self.min_separation and
+        self.rel_threshold: the refusals of the multi-source read-out, before any device work -- num_sources without doa_list, K outside
+        1 .. 16, a doa_list that does not have the `num_doa` columns of bf_mat, a negative separation or threshold.  The defaults are
+        find_doa_peaks' (utils.doa_peaks_defaults)."""
+        self.num_sources = None
+        if num_sources is None:
+            if min_separation is not None:
+                raise ValueError("min_separation belongs to the multi-source read-out: give num_sources as well")
+            return
+        if doa_list is None:
+            raise ValueError("num_sources needs the DoA grid of bf_mat's columns (doa_list=)")
+        doa, K, grid, sep = utils.doa_peaks_defaults(doa_list, num_sources, min_separation)
+        if len(doa) != int(num_doa):
+            raise ValueError(f"doa_list has {len(doa)} entries for the {int(num_doa)} DoAs of bf_mat")
+        if not 1 <= len(doa) <= 4096:
+            raise ValueError(f"the multi-source read-out serves grids of 1 .. 4096 DoAs, got {len(doa)}")
+        sep, rel = float(sep), float(rel_threshold)
+        if not sep >= 0.0:
+            raise ValueError(f"min_separation must not be negative (got {sep})")
+        if not 0.0 <= rel < np.inf:
+            raise ValueError(f"rel_threshold must be a finite number >= 0 (got {rel})")
+        self.num_sources, self.doa_list, self.grid, self.min_separation, self.rel_threshold = K, doa, grid, sep, rel
+
+    def _window_count_ptr(self):
+        """Device address of the word that counts the windows this stream has emitted (what _peaks_tile follows)."""
+        return self.lib.micloc_stream_window_count_ptr(runtime._ptr(self.wst))
+
+    def _alloc_peaks(self):
+        """The device side of num_sources=: the read-out's state (zero-filled on the stream), the device copy of doa_list, the running
+        peaks and, with window=, the two rings and the newest window's peaks -- "no peak" (-1, NaN) until the read-out has written them."""
+        if self.num_sources is None:
+            return
+        torch = runtime._torch()
+        dev, lib, K = self.device, self.lib, self.num_sources
+
+        def slots(*shape):
+            return (torch.full(shape, -1, dtype=torch.int32, device=dev), torch.full(shape, float("nan"), dtype=torch.float64, device=dev))
+
+        self.npk = int(lib.micloc_stream_peaks_state_bytes())
+        self.pk_state = torch.empty(self.npk, dtype=torch.uint8, device=dev)
+        self.doa_dev = runtime._as_dev(self.doa_list, dev)
+        self.peaks, self.peak_power = slots(self.B, K)
+        self.window_peaks = self.window_peak_power = self.latest_window_peaks = self.latest_window_peak_power = None
+        self._pk_count = ctypes.c_void_p(0)
+        if self.window is not None:
+            self.window_peaks, self.window_peak_power = slots(self.B, self.max_windows, K)
+            self.latest_window_peaks, self.latest_window_peak_power = slots(self.B, K)
+            self._pk_count = ctypes.c_void_p(self._window_count_ptr())
+        _lib.check(lib.micloc_stream_peaks_reset(runtime._ptr(self.pk_state), self.npk, runtime._stream(dev)), "stream_peaks_reset")
+
+    def _peaks_tile(self):
+        """The last launches of every tile with num_sources=: the multi-source read-out of the running row and of the windows the tile
+        has emitted (micloc_stream_peaks_tile_f64, which follows the stream's count word on the device: nothing here depends on the tile)."""
+        if self.num_sources is None:
+            return
+        win = self.window is not None
+        _lib.check(self.lib.micloc_stream_peaks_tile_f64(runtime._ptr(self.power), runtime._ptr(self.window_power) if win else None, self._pk_count,
+                                                         self.B, self.G, self.max_windows if win else 0, runtime._ptr(self.doa_dev),
+                                                         runtime.GRID_KINDS[self.grid], self.num_sources, self.min_separation, self.rel_threshold,
+                                                         runtime._ptr(self.pk_state), self.npk, runtime._ptr(self.peaks), runtime._ptr(self.peak_power),
+                                                         runtime._ptr(self.window_peaks), runtime._ptr(self.window_peak_power),
+                                                         runtime._ptr(self.latest_window_peaks), runtime._ptr(self.latest_window_peak_power),
+                                                         runtime._stream(self.device)), "stream_peaks_tile")
 
     def _reset_window_state(self, name, lead=None, who="the plan", hint=""):
         """wst / nwst, the device state of the open windows (None / 0 without window=): sized by micloc_<name>_state_bytes, zero-filled by
@@ -383,8 +457,40 @@ class _TileStream:
         count = self._window_count()
         first, _, rows = ring_rows(count, self.max_windows)
         rows = torch.tensor(rows, dtype=torch.int64, device=self.device)
-        return dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
-                    window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+        w = dict(count=count, first=first, window_power=self.window_power.index_select(1, rows), window_argmax=self.window_argmax.index_select(1, rows),
+                 window_start=np.arange(first, count, dtype=np.int64) * self.hop)
+        if self.num_sources is not None:  # the same k rows of the peak rings: [B, k, K]
+            w.update(window_peaks=self.window_peaks.index_select(1, rows), window_peak_power=self.window_peak_power.index_select(1, rows))
+        return w
+
+    def _need_peaks(self):
+        if self.num_sources is None:
+            raise ValueError("the localizer was built without num_sources=")
+
+    def latest_peaks(self):
+        """(peaks [B, K] int32, peak_power [B, K]) of the running row -- the num_sources strongest sources of the running power after the
+        last push, find_doa_peaks' rule, -1 / NaN in unfilled slots -- and, with window=, two more: (peaks, peak_power, window_peaks [B, K],
+        window_peak_power [B, K]), the same of the most recently emitted window (-1 / NaN until the first one exists).  Device tensors,
+        overwritten by the next push.  Does not synchronise."""
+        self._need_peaks()
+        if self.window is None:
+            return self.peaks, self.peak_power
+        return self.peaks, self.peak_power, self.latest_window_peaks, self.latest_window_peak_power
+
+    def peaks_status(self):
+        """(windows whose peaks have been read, windows skipped because their ring row was overwritten first): the read-out runs behind
+        every tile, so the first equals windows()["count"] and the second stays 0.  Synchronises the stream."""
+        self._need_peaks()
+        st2 = (ctypes.c_int * 2)()
+        _lib.check(self.lib.micloc_stream_peaks_status(runtime._ptr(self.pk_state), st2, runtime._stream(self.device)), "stream_peaks_status")
+        return int(st2[0]), int(st2[1])
+
+    def _finish_peaks(self, out):
+        """finish()'s multi-source tail: `out` with peaks [B, K] int32 and peak_power [B, K], localize_batch's keys (the window rows come
+        with _finish_windows)."""
+        if self.num_sources is not None:
+            out.update(peaks=self.peaks, peak_power=self.peak_power)
+        return out
 
     def _need_track(self):
         if self.track is None:
@@ -451,7 +557,9 @@ class _TileStream:
             out.update(window_power=w["window_power"], window_argmax=w["window_argmax"], window_count=w["count"])
             if "window_counts" in w:  # (XyloStreamingLocalizer)
                 out["window_counts"] = w["window_counts"]
-        return out
+            if "window_peaks" in w:  # (num_sources=)
+                out.update(window_peaks=w["window_peaks"], window_peak_power=w["window_peak_power"])
+        return self._finish_peaks(out)
 
 
 class _FilterbankFront:
@@ -496,7 +604,8 @@ class StreamingLocalizer(_TileStream):
     TILE_MULTIPLE = 16  # the encoder takes its frames sixteen at a time
 
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, keep_raster=False,
-                 window=None, hop=None, max_windows=None, track=None, max_track=None, time_vec=None, _share=None):
+                 window=None, hop=None, max_windows=None, track=None, max_track=None, time_vec=None, num_sources=None, doa_list=None,
+                 min_separation=None, rel_threshold=0.0, _share=None):
         """beamf: SNNBeamformer; bf_mat [2M, G]; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself, and the neuron kernel is
                       normalised over exactly that many samples like apply_to_signal does, snn_beamformer.py:342-361); None: a
@@ -517,6 +626,11 @@ class StreamingLocalizer(_TileStream):
                       window's capacity; default: total_frames when that is given (never below min_track), else the smallest multiple of 64 >= 4 x min_track.
         time_vec      the time axis the neuron kernel is normalised over, where the one-shot call to be matched was given one of its own
                       (track_batch(time_vec=)); default: total_frames (or 1 s of) samples on the fs grid, from 0.
+        num_sources   K = 1 .. 16: also emit the multi-source read-out of localize_batch(num_sources=) -- the K strongest peaks of the running
+                      power after every push and, with window=, of every window as soon as it is emitted, find_doa_peaks' rule bit for bit
+                      (latest_peaks() / windows() / finish() / peaks_status()); needs doa_list.  None: exactly the launches without it.
+        doa_list      [G]: the DoA grid of bf_mat's columns (radians); min_separation, rel_threshold: as find_doa_peaks' (default
+                      separation: two grid steps).  May be given together with track=.
         _share        (WidebandStreamingLocalizer) another StreamingLocalizer whose tile-sized scratch (`ext`, `h`, `ws`, the slide's staging
                       copy) this one uses instead of allocating its own, where it is large enough: for localizers whose tiles run one
                       after the other on one stream.  None: nothing changes."""
@@ -528,6 +642,7 @@ class StreamingLocalizer(_TileStream):
         self.max_tile = -(-int(max_tile) // 16) * 16
         if track is not None:  # the refusals that need no plan, before any device work (the ring depth follows the chunk length, below)
             track_setup(track, 2 * self.M, np.shape(bf_mat)[1], False, 0)
+        self._set_peaks(num_sources, doa_list, min_separation, rel_threshold, np.shape(bf_mat)[1])
         self.plan = beamf.new_plan()
         self.device = self.plan.device
         self._set_stht(beamf.kernel)
@@ -568,6 +683,7 @@ class StreamingLocalizer(_TileStream):
         self._alloc_results()
         self._reset_window_state("stream_window", hint=" (a complex bf_mat?)")
         self._alloc_track(self.cap)
+        self._alloc_peaks()
         self._set_wrap(wrap_tail)
         self.raster = None
         if keep_raster:
@@ -593,6 +709,7 @@ class StreamingLocalizer(_TileStream):
         self._localize_tile("stream_localize_tile", plan.handle, runtime._ptr(self.state), runtime._ptr(self.loc), self.nloc, runtime._ptr(self.win), B,
                             self.cap, int(final), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         self._keep_history(ext)
+        self._peaks_tile()
 
     def _advance(self, n, final):
         """Host mirror of the device clock (rz_stream_clock_begin_kernel's schedule) and the end-of-stream bookkeeping."""
@@ -661,18 +778,21 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
     summing an overwritten row should the bound ever be exceeded (only after a band's own lag failure); finish() then raises."""
 
     def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, lag_frames=4096, window=None, hop=None, max_windows=None,
-                 track=None, max_track=None, time_vec=None):
+                 track=None, max_track=None, time_vec=None, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
         """loc: wideband.WidebandSNNLocalizer; the other arguments as StreamingLocalizer's, except
         wrap_tail  [F, batch, L // 2, M]: the last L // 2 frames of every band's FILTERED recording (np.roll's wrap-around happens after
                    the filterbank), or None (zeros, as for a live source).
         track, max_track   the tracked read-out of WidebandSNNLocalizer.track_batch (module docstring, TRACKING); min_track = the bands'
                    raster window capacity.  None: exactly the launches without it.
-        time_vec   handed to every band's neuron kernel, where the one-shot call to be matched was given one (track_batch(time_vec=))."""
+        time_vec   handed to every band's neuron kernel, where the one-shot call to be matched was given one (track_batch(time_vec=)).
+        num_sources, doa_list, min_separation, rel_threshold   the multi-source read-out of the band sum (the running power and the
+                   wideband windows), as StreamingLocalizer's; doa_list defaults to loc.doa_list.  None: exactly the launches without it."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
         self._check_bands(loc, batch, wrap_tail)
         F = self.F
+        self._set_peaks(num_sources, getattr(loc, "doa_list", None) if doa_list is None else doa_list, min_separation, rel_threshold, self.G)
         self.T = None if total_frames is None else int(total_frames)
         # the refusals of track= that need no plan, before any device work (the ring depth follows the bands' window, below)
         self._set_track(track, max_track, 2 * self.M, self.G, False, 0)
@@ -712,6 +832,7 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
             self._p_rows = (vp * F)(*[b.window_power.data_ptr() for b in self.bands])
             self._p_count = (vp * F)(*[self.lib.micloc_stream_window_count_ptr(runtime._ptr(b.wst)) for b in self.bands])
         _lib.check(self.lib.micloc_stream_bands_reset(runtime._ptr(self.bands_state), self.nbs, runtime._stream(self.device)), "stream_bands_reset")
+        self._alloc_peaks()
         # track=: one tracked state over the bands' plans, localize states and raster windows (which share cap and CH)
         self.CH, self.cap = b0.CH, b0.cap
         self._set_track(track, max_track, 2 * self.M, self.G, False, self.cap)
@@ -761,6 +882,7 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
                                                               *self.track, self.max_track, runtime._ptr(self.track_index), runtime._ptr(self.track_peak),
                                                               runtime._ptr(self.latest_index), runtime._ptr(self.latest_peak), runtime._ptr(self.tws),
                                                               self.ntws, st), "stream_bands_track_tile")
+        self._peaks_tile()  # behind the band sum's commit
 
     def _advance(self, n, final):
         for band in self.bands:
@@ -794,6 +916,9 @@ class WidebandStreamingLocalizer(_FilterbankFront, _TileStream):
         """The smallest of the bands' counts at the last push."""
         return self._bands_status()[0]
 
+    def _window_count_ptr(self):
+        return self.lib.micloc_stream_bands_window_count_ptr(runtime._ptr(self.bands_state))
+
     def finish(self):
         """-> dict(power [B, G], argmax [B] int32, band_power [F, B, G]) as device tensors; with window= also window_power [B, nW, G],
         window_argmax [B, nW] and window_count (a live source without total_frames: the max_windows newest, see windows()); with track= also
@@ -820,7 +945,7 @@ class ComplexStreamingLocalizer(_TileStream):
     stream, one graph per tile length in push_replay().  The state is 2M (CH + n_coef - 1) + 2G doubles per trial however long the stream."""
 
     def __init__(self, beamf, bf_mat, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None, track=None,
-                 max_track=None):
+                 max_track=None, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
         """beamf: beamformer.Beamformer; bf_mat [M, G] complex; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
                       final=True with the last tile.
@@ -829,7 +954,9 @@ class ComplexStreamingLocalizer(_TileStream):
         max_tile      longest tile push() will be given.
         window, hop, max_windows   the windowed read-out, as StreamingLocalizer's (multiples of the plan's window quantum, hop <= window).
         track, max_track           the tracked read-out, as StreamingLocalizer's (Beamformer.track_batch's rows; up to 8 microphones); a tile
-                                   makes its own frames final, so min_track = max_tile."""
+                                   makes its own frames final, so min_track = max_tile.
+        num_sources, doa_list, min_separation, rel_threshold   the multi-source read-out, as StreamingLocalizer's
+                                   (Beamformer.localize_batch(num_sources=)'s rows)."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         bf_mat = np.asarray(bf_mat)
@@ -844,6 +971,7 @@ class ComplexStreamingLocalizer(_TileStream):
         if self.max_tile < 1:
             raise ValueError("max_tile must be at least 1")
         self._set_track(track, max_track, 2 * self.M, bf_mat.shape[1], True, self.max_tile)  # (refusals before any device work)
+        self._set_peaks(num_sources, doa_list, min_separation, rel_threshold, bf_mat.shape[1])
         self.plan = beamf.new_plan()  # the stream's own
         self.device = self.plan.device
         self._set_stht(beamf.kernel)
@@ -863,6 +991,7 @@ class ComplexStreamingLocalizer(_TileStream):
         self._alloc_results()
         self._reset_window_state("stream_complex_window")
         self._alloc_track(self.max_tile)
+        self._alloc_peaks()
         self._set_wrap(wrap_tail)
         _lib.check(self.lib.micloc_stream_complex_reset(self.plan.handle, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
                    "stream_complex_reset")
@@ -888,6 +1017,7 @@ class ComplexStreamingLocalizer(_TileStream):
         self._localize_tile("stream_complex_localize_tile", plan.handle, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
                             runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         self._keep_history(ext)
+        self._peaks_tile()
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -924,7 +1054,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
     windows one tile can complete plus the one cut at the end of the recording, and no window is ever given up."""
 
     def __init__(self, loc, batch, total_frames=None, wrap_tail=None, max_tile=12_000, window=None, hop=None, max_windows=None, track=None,
-                 max_track=None):
+                 max_track=None, num_sources=None, doa_list=None, min_separation=None, rel_threshold=0.0):
         """loc: wideband.WidebandBeamformerLocalizer; `batch` recordings are streamed in lock step.
         total_frames  length of the recordings if known (the last tile is then recognised by itself); None: a live source -- pass
                       final=True with the last tile.
@@ -933,7 +1063,9 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         max_tile      longest tile push() will be given.
         window, hop, max_windows   the windowed read-out, as ComplexStreamingLocalizer's.
         track, max_track           the tracked read-out of WidebandBeamformerLocalizer.track_batch (module docstring, TRACKING); a tile makes
-                                   its own frames final in every band, so min_track = max_tile."""
+                                   its own frames final in every band, so min_track = max_tile.
+        num_sources, doa_list, min_separation, rel_threshold   the multi-source read-out of the band sum, as StreamingLocalizer's; doa_list
+                                   defaults to loc.doa_list."""
         self._check_window_given(window, hop, max_windows)
         torch = runtime._torch()
         self.loc_def = loc
@@ -947,6 +1079,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         if self.max_tile < 1:
             raise ValueError("max_tile must be at least 1")
         self._set_track(track, max_track, 2 * self.M, self.G, True, self.max_tile)  # (refusals before any device work)
+        self._set_peaks(num_sources, getattr(loc, "doa_list", None) if doa_list is None else doa_list, min_separation, rel_threshold, self.G)
         # the stream's own plans, one per band (the band-pass coefficients and the bf_mat of that band)
         self.plans = []
         for beamf, W in zip(loc.beamfs, loc.bf_mats):
@@ -972,6 +1105,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         self._alloc_results()
         self._reset_window_state("stream_complex_bands_window", lead=(self.handles, F, self.B, self.max_tile), who="the plans")
         self._alloc_track(self.max_tile, plans=(self.handles, F))
+        self._alloc_peaks()
         self._set_wrap(wrap_tail, bands=True)
         _lib.check(self.lib.micloc_stream_complex_bands_reset(self.handles, F, self.B, runtime._ptr(self.state), self.nstate, runtime._stream(dev)),
                    "stream_complex_bands_reset")
@@ -991,6 +1125,7 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
         self._localize_tile("stream_complex_bands_localize_tile", self.handles, F, runtime._ptr(self.state), self.nstate, B, self.max_tile, int(final),
                             runtime._ptr(self.band_power), runtime._ptr(self.power), runtime._ptr(self.argmax), runtime._ptr(self.ws), self.nws)
         self._keep_history(ext)
+        self._peaks_tile()
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -1007,6 +1142,9 @@ class WidebandComplexStreamingLocalizer(_FilterbankFront, _TileStream):
 
     def _window_count(self):
         return self.status()["windows"]
+
+    def _window_count_ptr(self):
+        return self.lib.micloc_stream_complex_bands_window_count_ptr(runtime._ptr(self.wst))
 
     def _track_count(self):
         return self.status()["pushed"]
@@ -1038,16 +1176,20 @@ class MusicStreamingLocalizer(_TileStream):
     latest_window() and windows() return slices: a slice's "power" row is its angular spectrum P [G], the row `beamforming` returns, and
     its arg-max the row's first maximum; windows() adds `spectrum` (the same rows) and `sel` (the selected in-band bins)."""
 
-    def __init__(self, music, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None):
+    def __init__(self, music, batch, num_active_freq, duration_overlap, num_fft_bin, total_frames=None, max_tile=12_000, max_slices=None,
+                 num_sources=None, min_separation=None, rel_threshold=0.0):
         """music: music_beamformer.MUSIC; `batch` recordings are streamed in lock step.
         num_active_freq, duration_overlap, num_fft_bin   as MUSIC.localize_batch's; the ValueErrors of that call are raised here.
         total_frames  length of the recordings if known (the last tile is then recognised by itself, and a recording whose leftover slice
                       is shorter than num_fft_bin is refused here); None: a live source -- pass final=True with the last tile.
         max_tile      longest tile push() will be given.
         max_slices    rows of the ring the slices are kept in (slice s in row s % max_slices); default: every slice of the recording
-                      when total_frames is given, else 64."""
+                      when total_frames is given, else 64.
+        num_sources, min_separation, rel_threshold   the multi-source read-out over music.doa_list, as StreamingLocalizer's: the peaks of
+                      the running power (MUSIC.localize_batch(num_sources=)'s rows) and of every slice's spectrum."""
         self.music = music
         self.B, self.M = int(batch), len(music.geometry)
+        self._set_peaks(num_sources, music.doa_list, min_separation, rel_threshold, len(music.doa_list))
         self.T = None if total_frames is None else int(total_frames)
         self.N, self.k = int(num_fft_bin), int(num_active_freq)
         _, _, self.L, self.slice_hop = music.slice_plan(self.T if self.T is not None else 0, duration_overlap)  # (its ValueError: overlap >= L)
@@ -1084,6 +1226,7 @@ class MusicStreamingLocalizer(_TileStream):
         self._alloc_results()
         self.window_sel = torch.zeros((self.B, self.max_windows, self.ksel), dtype=torch.int32, device=dev)
         _lib.check(self.lib.micloc_stream_music_reset(runtime._ptr(self.state), self.nstate, *self._dims, runtime._stream(dev)), "stream_music_reset")
+        self._alloc_peaks()
 
     # ---- the host mirror of the device's slice rule (stream_music.hip: ms_leftover) ---------------------------------------------
     @staticmethod
@@ -1109,6 +1252,7 @@ class MusicStreamingLocalizer(_TileStream):
                                                          runtime._ptr(self.argmax), runtime._ptr(self.latest_power), runtime._ptr(self.latest_argmax),
                                                          runtime._ptr(self.window_power), runtime._ptr(self.window_sel), runtime._ptr(self.window_argmax),
                                                          runtime._stream(self.device)), "stream_music_tile")
+        self._peaks_tile()
 
     # ---- results ----------------------------------------------------------------------------------------------------------
     def status(self):
@@ -1120,6 +1264,9 @@ class MusicStreamingLocalizer(_TileStream):
 
     def _window_count(self):
         return self.status()["slices"]
+
+    def _window_count_ptr(self):
+        return self.lib.micloc_stream_music_slice_count_ptr(runtime._ptr(self.state))
 
     def windows(self):
         """_TileStream.windows() over the slices, plus spectrum [B, k, G] (the rows of window_power under the name localize_batch gives
@@ -1145,8 +1292,12 @@ class MusicStreamingLocalizer(_TileStream):
             raise _lib.MiclocError(f"the recording has {s['slices']} slices and the ring keeps {self.max_windows}: raise max_slices (or read "
                                    "windows() while the stream runs)")
         w = self.windows()
-        return dict(spectrum=w["spectrum"], power=self.power, argmax=self.argmax, slice_argmax=w["window_argmax"], sel=w["sel"],
-                    slice_count=w["count"])
+        out = dict(spectrum=w["spectrum"], power=self.power, argmax=self.argmax, slice_argmax=w["window_argmax"], sel=w["sel"],
+                   slice_count=w["count"])
+        if self.num_sources is not None:  # the slices are this stream's windows: both names
+            out.update(slice_peaks=w["window_peaks"], slice_peak_power=w["window_peak_power"], window_peaks=w["window_peaks"],
+                       window_peak_power=w["window_peak_power"])
+        return self._finish_peaks(out)
 
 
 class XyloStreamingLocalizer(_TileStream):

@@ -1050,6 +1050,33 @@ def stream_track_localizer(beamf, bf_mat, envelope, tile, max_batch=1100):
     return run
 
 
+def stream_multi_localizer(beamf, bf_mat, doa_list, tile, num_sources, min_separation=None, rel_threshold=0.0, max_batch=1100):
+    """device_localizer(num_sources=)'s place in multi_target_sweep(localizer=) for audio that arrives while it is localised: every batch is
+    pushed in tiles of `tile` frames through a stream built with num_sources (beamf.streaming_localizer(num_sources=, doa_list=); an SNN
+    stream takes multiples of 16) and finish()'s (peaks [B, K] int64, peak_power [B, K]) come back -- the bits of
+    localize_batch(num_sources=) on the whole batch, which the wrap-around rows of np.roll (known here: the batch is complete) and the
+    one-shot call's time axis of the neuron kernel make possible."""
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("tile must be at least 1 frame")
+    snn = hasattr(beamf, "tau_vec")
+    half = len(beamf.kernel) // 2
+
+    def run(sig_batch, time_vec):
+        def one(x):
+            B, T, _ = x.shape
+            kw = dict(time_vec=time_vec) if snn else {}
+            s = beamf.streaming_localizer(bf_mat, batch=B, total_frames=T, wrap_tail=_wrap_rows(x, half), max_tile=min(tile, T),
+                                          num_sources=num_sources, doa_list=doa_list, min_separation=min_separation, rel_threshold=rel_threshold, **kw)
+            for t in range(0, T, tile):
+                s.push(x[:, t : t + tile, :])
+            return _peaks_and_power(s.finish())
+
+        return _in_batches(sig_batch, max_batch, one)
+
+    return run
+
+
 def moving_target_sweep(beamf, bf_mat, doa_list, envelope, doa_max=np.pi / 2, num_period=0.5, lag_frames=None, settle_frames=None,
                         snr_db_vec=None, num_sim=100, seed=0, mode="parity", rank=0, world_size=1, group=None, freq_design=2000.0,
                         test_duration=100e-3, snr_gain_due_to_bandwidth=None, localizer=None, batch_trials=1100, out_dir=None, store_key=None):
@@ -1311,6 +1338,8 @@ def _multi_noisy_cli(args, geometry, doa_list, fs, freq_design, freq_range, tau,
         bf_mat = sharded_design(design, doa_list, rank, world)
     else:
         bf_mat, _ = beamf.design_from_template((time_temp, sig_temp), doa_list, svd=args.svd)  # (bf_mat, cov_mat_list)
+    if getattr(args, "stream_tile", None):  # the same sweep read out by the multi-source stream, tile by tile (the same bits)
+        kw["localizer"] = stream_multi_localizer(beamf, bf_mat, doa_list, args.stream_tile, args.num_targets, min_separation=kw["min_separation"] / 2)
     return multi_target_sweep(beamf, bf_mat, doa_list, **kw)
 
 
@@ -1331,6 +1360,8 @@ def main(argv=None):
                     help="multi-noisy, wideband-speech and moving-wideband (snn | beamformer), moving-noisy and windowed-noisy (snn | beamformer | xylo): the localizer")
     ap.add_argument("--num-targets", type=int, default=2, help="multi-noisy: simultaneous targets (1 .. 4)")
     ap.add_argument("--min-separation-deg", type=float, default=45.0, help="multi-noisy: least pi-periodic distance between targets")
+    ap.add_argument("--stream-tile", type=int, default=None,
+                    help="multi-noisy with --method snn | beamformer: read the trials out by the multi-source stream in tiles of N frames (snn: a multiple of 16)")
     ap.add_argument("--num-sim", type=int, default=None, help="trials per SNR (scripts: 100 noisy / xylo, 20 speech)")
     ap.add_argument("--grid", type=int, default=None, help="DoA grid (default: 449; music-noisy: 57, the MUSIC script's)")
     ap.add_argument("--seed", type=int, default=0)
@@ -1360,6 +1391,8 @@ def main(argv=None):
     doa_list = np.linspace(-np.pi, np.pi, grid)
     if args.method == "xylo" and args.sweep not in ("moving-noisy", "windowed-noisy"):
         ap.error("--method xylo goes with --sweep moving-noisy or windowed-noisy (the Xylo accuracy sweep is --sweep xylo)")
+    if args.stream_tile is not None and (args.sweep != "multi-noisy" or args.method not in ("snn", "beamformer") or args.stream_tile < 1):
+        ap.error("--stream-tile N (at least 1 frame) goes with --sweep multi-noisy --method snn or beamformer")
     if args.sweep == "windowed-noisy" and args.method == "xylo":
         from .xylo_snn_localization import Demo
 

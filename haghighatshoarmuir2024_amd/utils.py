@@ -95,6 +95,24 @@ def doa_grid_kind(doa_list, tol=1e-9):
     return "linear"
 
 
+def doa_peaks_defaults(doa_list, num_sources, min_separation=None, grid=None):
+    """The one rule for the arguments of the multi-source read-out, batch (find_doa_peaks) and stream (streaming._TileStream._set_peaks):
+    -> (doa float64 [G] host array, K, grid, min_separation).  ValueError for a doa_list that is not 1-dim and for num_sources outside
+    1 .. 16; the grid kind is doa_grid_kind(doa_list) unless `grid` names it; min_separation defaults to two grid steps (0 for one point).
+    Host work only."""
+    doa = np.asarray(doa_list.cpu().numpy() if _is_device_tensor(doa_list) else doa_list, dtype=np.float64)
+    if doa.ndim != 1:
+        raise ValueError("doa_list should be 1-dim!")
+    K = int(num_sources)
+    if not 1 <= K <= 16:
+        raise ValueError("num_sources must be between 1 and 16")
+    if grid is None:
+        grid = doa_grid_kind(doa)
+    if min_separation is None:
+        min_separation = 2 * abs(doa[-1] - doa[0]) / (len(doa) - 1) if len(doa) > 1 else 0.0
+    return doa, K, grid, min_separation
+
+
 def find_doa_peaks(power, doa_list, num_sources, min_separation=None, rel_threshold=0.0, grid=None):
     """The `num_sources` strongest sources of a DoA power profile: power [G] or [B, G] (host array or device tensor) over doa_list
     [G] -> (index int32, value float64), [K] or [B, K], where the input was (device tensors for a device tensor, NumPy otherwise).
@@ -107,16 +125,7 @@ def find_doa_peaks(power, doa_list, num_sources, min_separation=None, rel_thresh
     np.argmax.  Runs on the device only (micloc_doa_peaks_f64: include/micloc_hip.h states the rule in full)."""
     from . import runtime
 
-    doa = np.asarray(doa_list.cpu().numpy() if _is_device_tensor(doa_list) else doa_list, dtype=np.float64)
-    if doa.ndim != 1:
-        raise ValueError("doa_list should be 1-dim!")
-    K = int(num_sources)
-    if not 1 <= K <= 16:
-        raise ValueError("num_sources must be between 1 and 16")
-    if grid is None:
-        grid = doa_grid_kind(doa)
-    if min_separation is None:
-        min_separation = 2 * abs(doa[-1] - doa[0]) / (len(doa) - 1) if len(doa) > 1 else 0.0
+    doa, K, grid, min_separation = doa_peaks_defaults(doa_list, num_sources, min_separation, grid)
     on_device = _is_device_tensor(power)
     if on_device:
         p = power

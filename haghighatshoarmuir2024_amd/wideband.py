@@ -130,6 +130,16 @@ class WidebandSNNLocalizer(_WidebandLocalizer):
         loc.doa_list = np.asarray(doa_list)
         return loc
 
+    def streaming_localizer(self, batch=1, **kw):
+        """localize_batch for recordings that arrive tile by tile: a streaming.WidebandStreamingLocalizer (push / push_replay / finish;
+        total_frames, wrap_tail, max_tile, lag_frames, window, hop, max_windows, track, max_track as there) whose results after the last
+        tile are localize_batch's on the whole recording bit for bit.  num_sources= (with min_separation=, rel_threshold=; doa_list=
+        defaults to self.doa_list) adds the K strongest peaks of the running pattern and of every window (latest_peaks() / windows() /
+        finish())."""
+        from .streaming import WidebandStreamingLocalizer
+
+        return WidebandStreamingLocalizer(self, batch, **kw)
+
     def plans(self, time_vec):
         """The bands' device plans with their neuron kernels (for this time axis) and matrices set."""
         plans = []
@@ -206,7 +216,9 @@ class WidebandBeamformerLocalizer(_WidebandLocalizer):
         """localize_batch for recordings that arrive tile by tile: a streaming.WidebandComplexStreamingLocalizer (push / push_replay /
         finish; total_frames, wrap_tail, max_tile, window, hop, max_windows as there) whose results after the last tile are localize_batch's
         on the whole recording bit for bit.  track= (a utils.Envelope) and max_track= add the per-frame read-out of track_batch for a source
-        that moves while the audio arrives (latest_track() / tracked() / finish())."""
+        that moves while the audio arrives (latest_track() / tracked() / finish()); num_sources= (with min_separation=, rel_threshold=;
+        doa_list= defaults to self.doa_list) adds the K strongest peaks of the running pattern and of every window (latest_peaks() /
+        windows() / finish())."""
         from .streaming import WidebandComplexStreamingLocalizer
 
         return WidebandComplexStreamingLocalizer(self, batch, **kw)

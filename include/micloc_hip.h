@@ -939,6 +939,9 @@ int micloc_stream_band_sum_f64(int F, int B, int G, const double *const *band_po
                                void *bands_state, size_t bands_bytes, double *power, int32_t *argmax, double *window_power,
                                int32_t *window_argmax, double *latest_power, int32_t *latest_argmax, void *stream);
 int micloc_stream_bands_status(const void *bands_state, int *status2, void *stream);
+/* device address of the int32 word [0] of micloc_stream_bands_status, the wideband windows emitted or given up (a kernel that follows the
+ * wideband windows takes it: "streaming, multi-source" below); valid as long as bands_state is */
+const int32_t *micloc_stream_bands_window_count_ptr(const void *bands_state);
 
 /* ---- wideband streaming, complex Beamformer: all bands' tiles in one batch ----------------------- */
 /* The chain of "wideband localisation, complex Beamformer" for ONE stream that arrives in tiles.  The complex chain has no encoder
@@ -1014,6 +1017,9 @@ int micloc_stream_complex_bands_localize_tile_windows_f64(const micloc_plan *con
                                                           int32_t *window_argmax, double *latest_power, int32_t *latest_argmax,
                                                           void *stream);
 int micloc_stream_complex_bands_status(const void *state, const void *win_state, int *status6, void *stream);
+/* device address of the int32 word [4] of micloc_stream_complex_bands_status, the wideband windows emitted or given up ("streaming,
+ * multi-source" below); NULL for a NULL win_state; valid as long as win_state is */
+const int32_t *micloc_stream_complex_bands_window_count_ptr(const void *win_state);
 
 /* ---- wideband streaming, tracking: a DoA per frame over all bands while the recording arrives ---- */
 /* The rule of "wideband moving-target tracking" for a recording that arrives tile by tile through one of the two wideband streams above.
@@ -1122,6 +1128,9 @@ int micloc_stream_music_tile_f64(void *state, size_t state_bytes, const double *
                                  const double *steer_im, int G, int k, int max_slices, double *power, int32_t *argmax, double *latest_spec,
                                  int32_t *latest_argmax, double *slice_spec, int32_t *slice_sel, int32_t *slice_argmax, void *stream);
 int micloc_stream_music_status(const void *state, int *status4, void *stream);
+/* device address of the int32 word [1] of micloc_stream_music_status, the slices emitted ("streaming, multi-source" below); NULL for a
+ * NULL state; valid as long as state is */
+const int32_t *micloc_stream_music_slice_count_ptr(const void *state);
 
 /* ---- streaming, Xylo ----------------------------------------------------------------------------- */
 /* The Xylo chain ("Xylo-A2 hidden-layer integer LIF" above: RZCC spikes into the integer LIF layer, rate, peak) for ONE stream of B
@@ -1245,6 +1254,47 @@ int micloc_stream_xylo_tile_track_i16(const micloc_plan *p, const void *enc_stat
                                       size_t win_bytes, int window, int hop, int ring_depth, void *track_state, size_t track_bytes, double a_rise,
                                       double i_rise, double a_fall, int max_track, int32_t *track_index, double *track_peak, int32_t *latest_index,
                                       double *latest_peak, double *env_last, void *track_ws, size_t track_ws_bytes, void *stream);
+
+/* ---- streaming, multi-source: the K strongest peaks per window while the recording arrives -------- */
+/* Every stream above ends in ONE arg-max per running row and one per window.  micloc_stream_peaks_tile_f64 is the multi-source read-out
+ * ("Multi-source read-out" above: micloc_doa_peaks_f64's rule, grid kinds, limits and outputs, unchanged) as a read-out that FOLLOWS a
+ * stream: it is called behind a tile's own read-out entry, on the same stream, and belongs to the tile's graph.  It serves every stream
+ * that keeps its windows in a ring window_power [B][max_windows][G] (window n in row n % max_windows) and counts the windows it has
+ * emitted in a device word: the SNN and the complex stream (micloc_stream_window_count_ptr), the two wideband streams
+ * (micloc_stream_bands_window_count_ptr, micloc_stream_complex_bands_window_count_ptr), the MUSIC stream, whose windows are its slices
+ * (micloc_stream_music_slice_count_ptr).  The rule:
+ *   Running estimate.
+ *   - power [B][G] (may be NULL: skipped) is the stream's running power as it stands after the tile.  On EVERY call peaks [B][K] int32
+ *     and peak_power [B][K] (may be NULL) are the multi-source rule applied to its rows.
+ *   Windows (window_power != NULL and max_windows > 0; otherwise the running read-out only).
+ *   - c = *window_count, the count word after this tile's window read-out.  r = "windows whose peaks are read", word 0 of pk_state.
+ *   - For every n in [max(r, c - max_windows), c): row n % max_windows of window_peaks [B][max_windows][K] int32 and of
+ *     window_peak_power [B][max_windows][K] (may be NULL) is the multi-source rule applied to row n % max_windows of window_power.
+ *   - If c > r, latest_peaks [B][K] and latest_peak_power [B][K] (each may be NULL) take window c - 1; they are untouched otherwise.
+ *   - Then r = c, and word 1 of pk_state grows by max(0, c - max_windows - r): the windows whose rows were overwritten before they
+ *     were read ("skipped").  A read-out that runs behind every tile of a stream whose ring holds what one tile can emit skips none.
+ *   - Rows of windows outside [max(r, c - max_windows), c) are not written.
+ *   - Row r of the peak rings is always the rule applied to the bits of row r of window_power as they stand when the read-out runs:
+ *     the read-out never looks at anything but the stored row, so a window's peaks are bit for bit micloc_doa_peaks_f64 of its row.
+ * The call works for ANY number of new windows -- none, one, more than MICLOC_STREAM_PEAKS_SLOTS, more than max_windows (the final tile
+ * of a stream may emit ceil(window / hop) at once): one wave per (trial, window), grid (B, MICLOC_STREAM_PEAKS_SLOTS), a workgroup walks
+ * the windows n_lo + slot, n_lo + slot + SLOTS, ...; the running rows ride on the last slot.  No argument depends on time or on the tile.
+ * No atomics, no host synchronisation; no workgroup reads a word that another workgroup of the same launch writes -- r and the skipped
+ * count are committed by a one-thread launch of their own behind the read-out.  A tile is still ONE capturable hipGraph.
+ * State: pk_state, micloc_stream_peaks_state_bytes() = 256 bytes, 256-B aligned, zero-filled once by micloc_stream_peaks_reset.
+ * micloc_stream_peaks_status: {windows read, windows skipped}; it synchronises the stream.
+ * Status, before any device work: MICLOC_ERR_INVALID for a NULL doa_list, G outside 1 .. 4096, K outside 1 .. 16, a negative (or NaN)
+ * min_separation or rel_threshold, an unknown grid kind, max_windows < 0, a bad B, neither a running row nor windows to read, or a
+ * missing peaks / window_count / window_peaks for the part selected; MICLOC_ERR_WORKSPACE for a NULL, short or misaligned pk_state. */
+#define MICLOC_STREAM_PEAKS_SLOTS 8
+size_t micloc_stream_peaks_state_bytes(void); /* 256 */
+int micloc_stream_peaks_reset(void *pk_state, size_t pk_bytes, void *stream);
+int micloc_stream_peaks_tile_f64(const double *power, const double *window_power, const int32_t *window_count, int B, int G,
+                                 int max_windows, const double *doa_list, int grid_kind, int K, double min_separation,
+                                 double rel_threshold, void *pk_state, size_t pk_bytes, int32_t *peaks, double *peak_power,
+                                 int32_t *window_peaks, double *window_peak_power, int32_t *latest_peaks,
+                                 double *latest_peak_power, void *stream);
+int micloc_stream_peaks_status(const void *pk_state, int *status2, void *stream); /* {windows read, windows skipped}; synchronises */
 
 /* ---- misc ------------------------------------------------------------------------------------- */
 int micloc_abi_version(void);
