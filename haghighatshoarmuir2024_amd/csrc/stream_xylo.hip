@@ -24,12 +24,13 @@
 // The lane's constants, the step functions, the MFMA `produce`, the staging loop and the walk over a range are XpLif of xylo_rows.h,
 // the one-shot kernel's; here are the range, the state's load and store and the counts.
 //
-// At the end of the file stands a one-shot kernel all the same: xylo_lif_track_kernel, the tracking form of the packed walk (why here:
-// see there), and behind it that walk as a stream, xylo_lif_track_stream_kernel: this file's range and state around that kernel's tap.
+// At the end of the file stands the tracking form of the packed walk as a stream, xylo_lif_track_stream_kernel: this file's range and
+// state around the tap of the one-shot xylo_lif_track_kernel (xylo.hip), which xylo_track_rows.h holds for both.
 #include "readout_rows.h"
 #include "stream_xylo.h"
 #include "xylo_rows.h"
 #include "xylo_track.h"
+#include "xylo_track_rows.h"
 
 namespace micloc {
 
@@ -324,214 +325,6 @@ hipError_t launch_xylo_stream_readout(XyloReadoutArgs a, void *const *win_states
     return hipGetLastError();
 }
 
-// ==== the tracking form of the packed walk (ONE-SHOT, not a stream): Envelope.evolve of the spike counts and the first maximum over the
-// neurons, per frame ========================================================================================================================
-// It stands in this unit, not beside its two siblings in xylo.hip, because of what the build already says about this object: it is
-// compiled with the accumulators in VGPRs, and it is rebuilt when xylo_rows.h or readout_rows.h change (csrc/Makefile, whose text
-// committed measurement records pin).  include/micloc_hip.h, "Xylo moving-target tracking", has the rule; DESIGN 4.23 the structure and
-// what the alternatives cost.
-// The tap of XpLif: the lane keeps the envelope of its two neurons beside isyn / vmem and the packed counts of the 16 steps of a group.
-// Once the group is settled -- after the walk from the saved state, where one was needed -- the 32 envelope steps run and leave one
-// (value, neuron) pair per frame and lane: the better of the lane's two neurons, n0 < n1 winning a tie.  The 16 pairs of the 64 lanes
-// are folded crosswise: a lane hands half of its frames to its partner at distance 32, 16, 8 and 4 and keeps the other half, so that
-// after 8 + 4 + 2 + 1 exchanges lane l holds frame l >> 2 over sixteen lanes, and wave_first_max<4> over the quad finishes it -- 17
-// exchanges for 16 frames where a butterfly per frame takes 96.  `better` orders by value, then by neuron number: the lane layout
-// ((q, lc) holds 32 q + lc and 32 q + 16 + lc) does not matter.  The wave's pairs go to its row of an LDS tile [waves][XP_TT]; behind
-// the staged tile one thread per frame takes the waves in ascending order (a strictly larger value takes over: track_combine_row's
-// rule) and writes the result.
-struct XpTrackTap {
-    static constexpr bool on = true;
-    double a_rise, i_rise, a_fall;
-    double e0, e1;  // e[t-1] of the lane's two neurons
-    int cw[16];     // packed counts of the group's steps
-    int n0, n1, l, off;
-    bool act0, act1, first;
-    double *sv;  // this wave's row of the pair tile
-    int *si;
-
-    __device__ __forceinline__ double env(double e, double m, bool f) const
-    {
-        const double up = __dadd_rn(__dmul_rn(a_rise, e), __dmul_rn(i_rise, m));
-        const double down = __dmul_rn(a_fall, e);
-        const double nx = (m >= e) ? up : down;
-        return f ? m : nx;
-    }
-    // one step of both envelopes -> the lane's pair (a lane without neurons: RO_NONE, which never wins)
-    __device__ __forceinline__ void advance(int c, bool f, double &bv, int &bi)
-    {
-        e0 = env(e0, (double)(c & 0xffff), f);
-        e1 = env(e1, (double)(c >> 16), f);
-        bv = act0 ? e0 : -1.0;
-        bi = act0 ? n0 : RO_NONE;
-        if (act1 && e1 > e0) {
-            bv = e1;
-            bi = n1;
-        }
-    }
-    // lanes at distance D swap halves of their K + K pairs: the lower lane keeps [0, K), the upper one [K, 2 K), both in [0, K)
-    template <int D, int K>
-    __device__ __forceinline__ void fold(double *bv, int *bi) const
-    {
-        const bool up = (l & D) != 0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            const double ov = __shfl_xor(up ? bv[i] : bv[i + K], D, 64);
-            const int oi = __shfl_xor(up ? bi[i] : bi[i + K], D, 64);
-            double kv = up ? bv[i + K] : bv[i];
-            int ki = up ? bi[i + K] : bi[i];
-            if (better(ov, oi, kv, ki)) {
-                kv = ov;
-                ki = oi;
-            }
-            bv[i] = kv;
-            bi[i] = ki;
-        }
-    }
-
-    __device__ __forceinline__ void begin(int off_, bool first_) { off = off_, first = first_; }
-    __device__ __forceinline__ void put(int j, int c) { cw[j] = c; }
-    __device__ __forceinline__ void group()
-    {
-        double bv[16];
-        int bi[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) advance(cw[j], first && j == 0, bv[j], bi[j]);
-        fold<32, 8>(bv, bi);
-        fold<16, 4>(bv, bi);
-        fold<8, 2>(bv, bi);
-        fold<4, 1>(bv, bi);
-        wave_first_max<4>(bv[0], bi[0]);
-        if ((l & 3) == 0) {
-            sv[off + (l >> 2)] = bv[0];
-            si[off + (l >> 2)] = bi[0];
-        }
-    }
-    __device__ __forceinline__ void single(int j, int c)
-    {
-        double bv;
-        int bi;
-        advance(c, first && j == 0, bv, bi);
-        wave_first_max<64>(bv, bi);
-        if (l == 0) {
-            sv[off + j] = bv;
-            si[off + j] = bi;
-        }
-    }
-};
-
-// What the one-shot and the stream form of the tracking walk share around the tap: its set-up from the lane's constants (the envelopes
-// e0 / e1 are the kernel's: zero, or the stream's state) ...
-template <class Lif>
-__device__ __forceinline__ void xp_track_tap_init(Lif &lif, double a_rise, double i_rise, double a_fall, double (*sv)[XP_TT], int (*si)[XP_TT])
-{
-    auto &tap = lif.tap;
-    tap.a_rise = a_rise, tap.i_rise = i_rise, tap.a_fall = a_fall;
-    tap.n0 = lif.n0, tap.n1 = lif.n1, tap.act0 = lif.act0, tap.act1 = lif.act1;
-    tap.l = lif.l, tap.off = 0, tap.first = false;
-    tap.sv = sv[lif.wv];
-    tap.si = si[lif.wv];
-}
-
-// ... and run_range's `done`: behind the staged tile one thread per frame takes the waves' pairs in ascending order (ascending neurons: a
-// strictly larger value takes over) and hands emit(f, best, bi) the result of the tile's frame f.  (The barrier at the head of the next
-// tile of run_range keeps these reads in front of the next pairs.)
-template <class Emit>
-__device__ __forceinline__ void xp_track_rows(const double (*sv)[XP_TT], const int (*si)[XP_TT], int waves, int tid, int nthreads, int steps,
-                                              Emit emit)
-{
-    __syncthreads();
-    for (int f = tid; f < steps; f += nthreads) {
-        double best = -1.0;
-        int bi = RO_NONE;
-        for (int w = 0; w < waves; ++w) {
-            const double v = sv[w][f];
-            const int i = si[w][f];
-            if (i != RO_NONE && v > best) {
-                best = v;
-                bi = i;
-            }
-        }
-        emit(f, best, bi);
-    }
-}
-
-// the pairs of one frame over the neuron blocks, ascending = ascending neurons: only a strictly larger value takes over (counts are
-// integers: every block has a winner)
-__device__ __forceinline__ void xylo_track_combine_row(const double *__restrict__ pval, const int32_t *__restrict__ pidx, int nblk, double &best,
-                                                       int &bi)
-{
-    best = -1.0;
-    bi = RO_NONE;
-    for (int c = 0; c < nblk; ++c) {
-        const double v = pval[c];
-        const int i = pidx[c];
-        if (better(v, i, best, bi)) {
-            best = v;
-            bi = i;
-        }
-    }
-}
-
-// grid (neuron blocks, trials) as xylo_lif_pk_kernel's one-shot form.  One neuron block: pval / pidx are peak_env (may be NULL) and index
-// [B][T]; more: the pairs [B T][blocks] that xylo_track_combine_kernel reduces.
-template <int KQ>
-__global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_kernel(const int8_t *__restrict__ raster, int tc, int T, int Cin,
-                                                                        const long *__restrict__ Wb /*[Npad][4 KQ]*/, int N,
-                                                                        const uint8_t *__restrict__ dash_syn,
-                                                                        const uint8_t *__restrict__ dash_mem,
-                                                                        const short *__restrict__ thr, int max_spikes, double a_rise,
-                                                                        double i_rise, double a_fall, double *__restrict__ pval,
-                                                                        int32_t *__restrict__ pidx, double *__restrict__ env_last,
-                                                                        int *__restrict__ rate)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char tile[XP_TT][32 * KQ];
-    extern __shared__ __attribute__((aligned(16))) int cur_dyn[];  // [waves][4][64][4]: only the waves that hold neurons
-    __shared__ double sv[XP_WAVES][XP_TT];
-    __shared__ int si[XP_WAVES][XP_TT];
-    XpLif<KQ, false, XpTrackTap> lif;
-    lif.init(tile, cur_dyn, blockIdx.x * XP_NEUR, Wb, N, dash_syn, dash_mem, thr, max_spikes);
-    XpTrackTap &tap = lif.tap;
-    xp_track_tap_init(lif, a_rise, i_rise, a_fall, sv, si);
-    tap.e0 = tap.e1 = 0.0;
-    const int b = blockIdx.y, nblk = gridDim.x, blk = blockIdx.x;
-    const int tid = lif.tid, nthreads = lif.nthreads, waves = nthreads >> 6;
-    const int8_t *rend = raster + (size_t)gridDim.y * T * tc;
-    auto done = [&](int t0, int steps) {
-        xp_track_rows(sv, si, waves, tid, nthreads, steps, [&](int f, double best, int bi) {
-            const size_t row = (size_t)b * T + t0 + f;
-            if (nblk == 1) {
-                pidx[row] = bi == RO_NONE ? 0 : bi;
-                if (pval) pval[row] = best;
-            } else {
-                pval[row * nblk + blk] = best;
-                pidx[row * nblk + blk] = bi;
-            }
-        });
-    };
-    lif.run_range(raster + (size_t)b * T * tc, rend, tc, Cin, 0, T, done);
-    if (env_last) {
-        if (lif.act0) env_last[(size_t)b * N + lif.n0] = tap.e0;
-        if (lif.act1) env_last[(size_t)b * N + lif.n1] = tap.e1;
-    }
-    if (rate) {
-        if (lif.act0) rate[(size_t)b * N + lif.n0] = lif.total0;
-        if (lif.act1) rate[(size_t)b * N + lif.n1] = lif.total1;
-    }
-}
-
-// the pairs of a frame over the neuron blocks -> index, peak
-__global__ __launch_bounds__(256) void xylo_track_combine_kernel(const double *__restrict__ pval, const int32_t *__restrict__ pidx, size_t rows,
-                                                                 int nblk, int32_t *__restrict__ index, double *__restrict__ peak)
-{
-    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= rows) return;
-    double best;
-    int bi;
-    xylo_track_combine_row(pval + row * nblk, pidx + row * nblk, nblk, best, bi);
-    index[row] = bi == RO_NONE ? 0 : bi;
-    if (peak) peak[row] = best;
-}
-
 // ==== the tracking walk as a STREAM: xylo_lif_stream_kernel's range, early return and state hand-off around xylo_lif_track_kernel's tap,
 // pair tile and combine over the waves (include/micloc_hip.h "streaming, Xylo tracking") ===================================
 // The walk hands its tap first = (position in the range's raster == 0).  In a stream that position is relative to the raster WINDOW; the
@@ -693,40 +486,5 @@ hipError_t launch_xylo_track_resume(const int8_t *raster, int tc, int stride_fra
     return hipGetLastError();
 }
 
-bool xylo_track_fused(int ternary_C, int Cin, int w_rec, int max_spikes)
-{
-    return w_rec == 0 && ternary_C > 0 && Cin <= 64 && max_spikes >= 1;  // (and a 16-byte aligned raster: the caller's check)
-}
-
-size_t xylo_track_pairs_bytes(int B, int T, int N)
-{
-    const int nblk = xp_npad(N) / XP_NEUR;
-    return nblk == 1 ? 256 : xylo_track_pairs_size((size_t)B * T * nblk);  // (one block writes the results itself; never 0: that is "bad arguments")
-}
-
-hipError_t launch_xylo_track(const int8_t *raster, int ternary_C, int B, int T, int Cin, int N, int max_spikes, double a_rise, double i_rise,
-                             double a_fall, int32_t *index, double *peak, double *env_last, int32_t *rate, void *ws, void *pairs,
-                             hipStream_t stream)
-{
-    if (!xylo_track_fused(ternary_C, Cin, 0, max_spikes) || (reinterpret_cast<uintptr_t>(raster) & 15) != 0) return hipErrorInvalidValue;
-    const XyloWs w = xylo_ws(ws, Cin, N);
-    const XpShape sh = xp_shape(N, ternary_C);
-    double *pval = peak;
-    int32_t *pidx = index;
-    const size_t rows = (size_t)B * T;
-    if (sh.nblk > 1) xylo_track_pairs_split(pairs, rows * sh.nblk, pval, pidx);
-    const dim3 grid(sh.nblk, B), block(sh.waves * 64);
-    if (xp_kq(Cin) == 1)
-        hipLaunchKernelGGL(xylo_lif_track_kernel<1>, grid, block, sh.lds, stream, raster, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
-                           max_spikes, a_rise, i_rise, a_fall, pval, pidx, env_last, rate);
-    else
-        hipLaunchKernelGGL(xylo_lif_track_kernel<2>, grid, block, sh.lds, stream, raster, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
-                           max_spikes, a_rise, i_rise, a_fall, pval, pidx, env_last, rate);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || sh.nblk == 1) return e;
-    hipLaunchKernelGGL(xylo_track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, sh.nblk, index,
-                       peak);
-    return hipGetLastError();
-}
 
 }  // namespace micloc

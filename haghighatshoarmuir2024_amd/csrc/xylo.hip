@@ -17,10 +17,14 @@
 // Each has a CHUNK-COUNT form for the time-resolved read-out (xylo_lif_kernel<REC, NQ, true>, xylo_lif_pk_chunks_kernel: the same walk,
 // which also leaves the spike count of every 256 frames), and xylo_window_kernel adds those rows per window: "time-resolved DoA" below,
 // PARITY UNPINNED like everything here.
+// At the end of the file stands the packed walk's TRACKING form, xylo_lif_track_kernel (the envelope of the counts and the first maximum
+// over the neurons per frame), around the tap of xylo_track_rows.h.
 #include <vector>
 
 #include "micloc_internal.h"
 #include "xylo_rows.h"
+#include "xylo_track.h"
+#include "xylo_track_rows.h"
 #include "xylo_windows.h"
 
 // (the recurrent instantiations keep a barrier inside the step loop, which the requested unrolling skips)
@@ -492,6 +496,106 @@ hipError_t launch_xylo(const uint8_t *spikes_in, int B, int T, int Cin, const in
     hipError_t e0 = xylo_upload(Cin, W_in_host, N, dash_syn_host, dash_mem_host, thr_host, ws, stream);
     if (e0 != hipSuccess) return e0;
     return launch_xylo_resident(spikes_in, 0, B, T, Cin, N, w_rec, max_spikes, spikes_out, rate, ws, stream);
+}
+
+// ==== the tracking form of the packed walk: Envelope.evolve of the spike counts and the first maximum over the neurons, per frame ========
+// The tap, its set-up and the two combines are xylo_track_rows.h's, shared with the walk as a stream (stream_xylo.hip); here are the
+// one-shot range -- every trial from zero state at frame 0 -- and what the call leaves.  include/micloc_hip.h, "Xylo moving-target
+// tracking", has the rule; DESIGN 4.23 the structure.
+// grid (neuron blocks, trials) as xylo_lif_pk_kernel's one-shot form.  One neuron block: pval / pidx are peak_env (may be NULL) and index
+// [B][T]; more: the pairs [B T][blocks] that xylo_track_combine_kernel reduces.
+template <int KQ>
+__global__ __launch_bounds__(XP_WAVES * 64) void xylo_lif_track_kernel(const int8_t *__restrict__ raster, int tc, int T, int Cin,
+                                                                        const long *__restrict__ Wb /*[Npad][4 KQ]*/, int N,
+                                                                        const uint8_t *__restrict__ dash_syn,
+                                                                        const uint8_t *__restrict__ dash_mem,
+                                                                        const short *__restrict__ thr, int max_spikes, double a_rise,
+                                                                        double i_rise, double a_fall, double *__restrict__ pval,
+                                                                        int32_t *__restrict__ pidx, double *__restrict__ env_last,
+                                                                        int *__restrict__ rate)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char tile[XP_TT][32 * KQ];
+    extern __shared__ __attribute__((aligned(16))) int cur_dyn[];  // [waves][4][64][4]: only the waves that hold neurons
+    __shared__ double sv[XP_WAVES][XP_TT];
+    __shared__ int si[XP_WAVES][XP_TT];
+    XpLif<KQ, false, XpTrackTap> lif;
+    lif.init(tile, cur_dyn, blockIdx.x * XP_NEUR, Wb, N, dash_syn, dash_mem, thr, max_spikes);
+    XpTrackTap &tap = lif.tap;
+    xp_track_tap_init(lif, a_rise, i_rise, a_fall, sv, si);
+    tap.e0 = tap.e1 = 0.0;
+    const int b = blockIdx.y, nblk = gridDim.x, blk = blockIdx.x;
+    const int tid = lif.tid, nthreads = lif.nthreads, waves = nthreads >> 6;
+    const int8_t *rend = raster + (size_t)gridDim.y * T * tc;
+    auto done = [&](int t0, int steps) {
+        xp_track_rows(sv, si, waves, tid, nthreads, steps, [&](int f, double best, int bi) {
+            const size_t row = (size_t)b * T + t0 + f;
+            if (nblk == 1) {
+                pidx[row] = bi == RO_NONE ? 0 : bi;
+                if (pval) pval[row] = best;
+            } else {
+                pval[row * nblk + blk] = best;
+                pidx[row * nblk + blk] = bi;
+            }
+        });
+    };
+    lif.run_range(raster + (size_t)b * T * tc, rend, tc, Cin, 0, T, done);
+    if (env_last) {
+        if (lif.act0) env_last[(size_t)b * N + lif.n0] = tap.e0;
+        if (lif.act1) env_last[(size_t)b * N + lif.n1] = tap.e1;
+    }
+    if (rate) {
+        if (lif.act0) rate[(size_t)b * N + lif.n0] = lif.total0;
+        if (lif.act1) rate[(size_t)b * N + lif.n1] = lif.total1;
+    }
+}
+
+// the pairs of a frame over the neuron blocks -> index, peak
+__global__ __launch_bounds__(256) void xylo_track_combine_kernel(const double *__restrict__ pval, const int32_t *__restrict__ pidx, size_t rows,
+                                                                 int nblk, int32_t *__restrict__ index, double *__restrict__ peak)
+{
+    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    double best;
+    int bi;
+    xylo_track_combine_row(pval + row * nblk, pidx + row * nblk, nblk, best, bi);
+    index[row] = bi == RO_NONE ? 0 : bi;
+    if (peak) peak[row] = best;
+}
+
+bool xylo_track_fused(int ternary_C, int Cin, int w_rec, int max_spikes)
+{
+    return w_rec == 0 && ternary_C > 0 && Cin <= 64 && max_spikes >= 1;  // (and a 16-byte aligned raster: the caller's check)
+}
+
+size_t xylo_track_pairs_bytes(int B, int T, int N)
+{
+    const int nblk = xp_npad(N) / XP_NEUR;
+    return nblk == 1 ? 256 : xylo_track_pairs_size((size_t)B * T * nblk);  // (one block writes the results itself; never 0: that is "bad arguments")
+}
+
+hipError_t launch_xylo_track(const int8_t *raster, int ternary_C, int B, int T, int Cin, int N, int max_spikes, double a_rise, double i_rise,
+                             double a_fall, int32_t *index, double *peak, double *env_last, int32_t *rate, void *ws, void *pairs,
+                             hipStream_t stream)
+{
+    if (!xylo_track_fused(ternary_C, Cin, 0, max_spikes) || (reinterpret_cast<uintptr_t>(raster) & 15) != 0) return hipErrorInvalidValue;
+    const XyloWs w = xylo_ws(ws, Cin, N);
+    const XpShape sh = xp_shape(N, ternary_C);
+    double *pval = peak;
+    int32_t *pidx = index;
+    const size_t rows = (size_t)B * T;
+    if (sh.nblk > 1) xylo_track_pairs_split(pairs, rows * sh.nblk, pval, pidx);
+    const dim3 grid(sh.nblk, B), block(sh.waves * 64);
+    if (xp_kq(Cin) == 1)
+        hipLaunchKernelGGL(xylo_lif_track_kernel<1>, grid, block, sh.lds, stream, raster, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                           max_spikes, a_rise, i_rise, a_fall, pval, pidx, env_last, rate);
+    else
+        hipLaunchKernelGGL(xylo_lif_track_kernel<2>, grid, block, sh.lds, stream, raster, ternary_C, T, Cin, w.dWb, N, w.dds, w.ddm, w.dth,
+                           max_spikes, a_rise, i_rise, a_fall, pval, pidx, env_last, rate);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || sh.nblk == 1) return e;
+    hipLaunchKernelGGL(xylo_track_combine_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, pval, pidx, rows, sh.nblk, index,
+                       peak);
+    return hipGetLastError();
 }
 
 }  // namespace micloc

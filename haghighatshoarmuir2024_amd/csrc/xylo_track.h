@@ -1,5 +1,5 @@
-// What the tracking form of the packed integer LIF (the envelope and the per-frame arg-max on its step counts; the kernel stands in
-// csrc/stream_xylo.hip) offers to the C-ABI unit api_track.hip.  A header of its own: micloc_internal.h is among the sources that committed measurement records pin.
+// What the tracking form of the packed integer LIF (the envelope and the per-frame arg-max on its step counts; csrc/xylo.hip) offers to
+// the C-ABI unit api_track.hip.  A header of its own: micloc_internal.h is among the sources that committed measurement records pin.
 #pragma once
 #include "micloc_internal.h"
 

@@ -6,6 +6,7 @@ import glob
 import json
 import os
 
+import csrc_build
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
@@ -13,7 +14,7 @@ UNITS = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "api_*.
 
 
 def test_every_api_unit_is_in_the_makefile_and_api_hip_is_gone():
-    srcs = open(os.path.join(CSRC, "Makefile")).read().split("SRCS", 1)[1].split("\n", 1)[0].split()
+    srcs = csrc_build.built_sources()
     assert len(UNITS) >= 2 and not os.path.exists(os.path.join(CSRC, "api.hip"))
     for unit in UNITS:
         assert unit in srcs, unit

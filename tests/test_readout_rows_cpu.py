@@ -3,6 +3,8 @@ whose source includes the header is rebuilt when it changes."""
 import os
 import re
 
+import csrc_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
 HEADER = "readout_rows.h"
@@ -67,23 +69,8 @@ def test_the_emitted_window_count_is_written_once():
     assert "(window + hop - 1) / hop" not in src["stream_xylo.hip"] and "stream_window_slots(" in src["stream_xylo.hip"]
 
 
-def _includes(src, f, seen=None):
-    """Project headers f includes, directly or through another project header."""
-    seen = set() if seen is None else seen
-    for h in re.findall(r'#include "([^"/]+)"', src[f]):
-        if h in src and h not in seen:
-            seen.add(h)
-            _includes(src, h, seen)
-    return seen
-
-
 def test_makefile_names_the_header_for_exactly_the_objects_that_include_it():
-    src = _sources()
-    users = {f[:-4] + ".o" for f in src if f.endswith(".hip") and HEADER in _includes(src, f)}
+    users = csrc_build.including_objects(HEADER)
     assert {"windows.o", "stream_windows.o", "stream_xylo.o", "track.o", "stream_track.o"} <= users
-    named = set()
-    for line in open(os.path.join(CSRC, "Makefile")).read().splitlines():
-        targets, sep, prereq = line.partition(":")
-        if sep and not line.startswith(("\t", "#")) and HEADER in prereq.split():
-            named |= set(targets.split())
+    named = csrc_build.rebuilt_after_edit(HEADER)
     assert named == users, (sorted(named - users), sorted(users - named))

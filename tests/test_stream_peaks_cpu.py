@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import csrc_build
 from conftest import ROOT
 
 from haghighatshoarmuir2024_amd import _lib, streaming, utils
@@ -81,7 +82,7 @@ def test_tile_entry_status_codes_without_a_gpu():
 
 def test_the_api_unit_and_the_kernel_are_built():
     assert os.path.exists(os.path.join(CSRC, "api_stream_peaks.hip")) and "__global__" not in open(os.path.join(CSRC, "api_stream_peaks.hip")).read()
-    srcs = open(os.path.join(CSRC, "Makefile")).read().split("SRCS", 1)[1].split("\n", 1)[0].split()
+    srcs = csrc_build.built_sources()
     assert "api_stream_peaks.hip" in srcs and "stream_peaks.hip" in srcs
     for f in ("peaks_rows.h", "stream_peaks.h", "stream_peaks.hip"):
         assert os.path.exists(os.path.join(CSRC, f)), f

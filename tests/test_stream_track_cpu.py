@@ -7,6 +7,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+import csrc_build
 from oracle import oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,8 +63,7 @@ def test_header_declares_and_lib_binds_the_symbols():
         assert re.search(r"\b%s\s*\(" % n, text), n
         assert n in _lib.SYMBOLS, n
     assert "streaming, tracking" in open(os.path.join(ROOT, "include", "micloc_hip.h")).read()
-    mk = open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "Makefile")).read()
-    assert "stream_track.hip" in mk.split("SRCS", 1)[1].split("\n", 1)[0]
+    assert "stream_track.hip" in csrc_build.built_sources()
     src = open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "stream_track.hip")).read()
     assert "atomic" not in src.lower() and "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src
 
@@ -73,16 +73,14 @@ def test_the_chunk_walk_is_written_once():
     with the comments stripped the fp64 matrix-core product occurs there three times (membrane loop, SNN product, complex product) and the
     complex magnitude once, and neither occurs in a kernel file; both objects are rebuilt when the header changes."""
     csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
-    text = {f: open(os.path.join(csrc, f)).read() for f in ("track_rows.h", "track.hip", "stream_track.hip", "Makefile")}
+    text = {f: open(os.path.join(csrc, f)).read() for f in ("track_rows.h", "track.hip", "stream_track.hip")}
     code = re.sub(r"//[^\n]*|/\*.*?\*/", "", text["track_rows.h"], flags=re.S)
     for word, times in (("mfma_f64_16x16x4f64", 3), ("hypot(", 1)):
         assert code.count(word) == times, word
         assert word not in text["track.hip"] and word not in text["stream_track.hip"], word
     for f in ("track.hip", "stream_track.hip"):
         assert '#include "track_rows.h"' in text[f], f
-    rules = [m.group(1).split() for m in re.finditer(r"^([^\t#\n:]+):[^\n]*\btrack_rows\.h\b", text["Makefile"], re.M)]
-    targets = {t for rule in rules for t in rule}
-    assert {"track.o", "stream_track.o"} <= targets, rules
+    assert {"track.o", "stream_track.o"} <= csrc_build.rebuilt_after_edit("track_rows.h")
 
 
 def test_size_entries_return_zero_and_entries_refuse_null_before_any_device_work():

@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import csrc_build
 from conftest import ROOT
 from test_stream_complex_cpu import bookkeeping, random_tiling
 
@@ -61,7 +62,7 @@ def test_header_declares_and_lib_binds_the_new_entries():
     code = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "stream_bands_complex.hip")).read())
     assert "stream_bands_bandpass_tile_kernel" in code
     assert "atomic" not in code.lower() and "hipStreamSynchronize" not in code and "hipDeviceSynchronize" not in code and "hipMalloc" not in code
-    assert "stream_bands_complex.hip" in open(os.path.join(csrc, "Makefile")).read()
+    assert "stream_bands_complex.hip" in csrc_build.built_sources()
 
 
 def test_every_entry_refuses_null_plans_and_a_bad_band_count():

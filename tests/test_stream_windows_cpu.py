@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import csrc_build
 from conftest import ROOT
 
 from haghighatshoarmuir2024_amd import _lib
@@ -38,8 +39,7 @@ def test_stream_windows_source_has_no_atomics_and_is_built():
     text = open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "stream_windows.hip")).read().lower()
     assert "atomic" not in text.replace("no atomics", "")
     assert "stream_window_kernel" in text
-    mk = open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "Makefile")).read()
-    assert "stream_windows.hip" in mk.split("SRCS", 1)[1].split("\n", 1)[0]
+    assert "stream_windows.hip" in csrc_build.built_sources()
 
 
 def test_windows_complete_hand_cases():

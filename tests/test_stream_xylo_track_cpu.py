@@ -270,13 +270,22 @@ def test_header_with_the_xylo_tracking_section_is_plain_c(tmp_path):
 
 def test_the_envelope_recurrence_is_written_once():
     """The stream kernel wraps the one-shot tap: the recurrence, the per-frame combine over the waves and the block combine stand once in
-    csrc/stream_xylo.hip, which holds every kernel of the feature; the C-ABI unit holds none."""
+    csrc/ -- in xylo_track_rows.h, which the one-shot kernel (xylo.hip) and the stream kernel (stream_xylo.hip) include; the C-ABI unit
+    holds no kernel.  The names are counted over every source and header of csrc/, the rounded products over the Xylo files (the
+    float-beamformer trackers of track_rows.h and sweep.hip keep a recurrence of their own on other state)."""
     csrc = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
-    text = open(os.path.join(csrc, "stream_xylo.hip")).read()
-    assert text.count("__dmul_rn(a_fall") == 1
-    assert text.count("__dmul_rn(") == 3  # two rounded products going up, one going down
+    files = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    text = "\n".join(files.values())
+    xylo = "\n".join(t for f, t in files.items() if "xylo" in f)
+    assert len([f for f in files if "xylo" in f]) >= 8 and "__dmul_rn(a_fall" in files["xylo_track_rows.h"]
+    assert xylo.count("__dmul_rn(a_fall") == 1
+    assert xylo.count("__dmul_rn(") == 3  # two rounded products going up, one going down
     assert text.count("struct XpTrackStreamTap : XpTrackTap") == 1
     assert text.count("xp_track_rows(") == 3 and text.count("xylo_track_combine_row(") == 3  # the definition and its two callers
+    for name in ("xp_track_rows(", "xylo_track_combine_row("):  # defined in the header, called once by each form
+        assert [files[f].count(name) for f in ("xylo_track_rows.h", "xylo.hip", "stream_xylo.hip")] == [1, 1, 1], name
+    assert "xylo_lif_track_kernel" in files["xylo.hip"] and "xylo_track_combine_kernel" in files["xylo.hip"]
+    text = files["stream_xylo.hip"]
     for kernel in ("xylo_lif_track_stream_kernel", "xylo_track_stream_combine_kernel"):
         assert kernel in text, kernel
     assert "__global__" not in open(os.path.join(csrc, "api_xylo_stream.hip")).read()

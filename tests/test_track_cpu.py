@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import csrc_build
 from conftest import ROOT
 
 FS = 48_000
@@ -183,7 +184,7 @@ def test_header_declares_and_lib_binds_the_tracking_symbols():
     assert lib.micloc_beamform_c128_track_f64(None, one, 1, 10, 16, 0.9, 0.1, 0.99, one, None, None, one, 1 << 20, None) == _lib.MICLOC_ERR_INVALID
     src = open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "track.hip")).read()
     assert "atomic" not in src.lower() and "hipStreamSynchronize" not in src and "hipDeviceSynchronize" not in src
-    assert "track.hip" in open(os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc", "Makefile")).read()
+    assert "track.hip" in csrc_build.built_sources()
 
 
 # ---- moving_target_sweep over gloo ----------------------------------------------------------------------------------------------

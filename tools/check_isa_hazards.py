@@ -18,6 +18,8 @@ import re
 import subprocess
 import sys
 
+from make_cmd import compiler_and_flags  # (csrc/Makefile states the flags, per unit)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 LABEL = re.compile(r"^([.\w$]+):")
@@ -42,9 +44,7 @@ def emit(src):
     deps = [path, os.path.join(os.path.dirname(path), "micloc_internal.h")]
     if os.path.exists(dst) and os.path.getmtime(dst) >= max(os.path.getmtime(d) for d in deps):
         return dst
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if src == "xylo.hip" else []
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-                           "--cuda-device-only", "-S"] + extra + ["-o", dst, path], stderr=subprocess.DEVNULL)
+    subprocess.check_call(compiler_and_flags(os.path.splitext(src)[0]) + ["--cuda-device-only", "-S", "-o", dst, path], stderr=subprocess.DEVNULL)
     return dst
 
 

@@ -5,9 +5,8 @@ set -e
 src=$1; pat=${2:-.}
 root=$(cd "$(dirname "$0")/../.." && pwd)
 out=$root/build_dev/isa; mkdir -p $out
-extra=""
-case "$src" in xylo.hip|stream_xylo.hip) extra="-mllvm -amdgpu-mfma-vgpr-form" ;; esac  # (as the Makefile does)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --cuda-device-only -S $extra \
+cmd=$(python3 $root/tools/make_cmd.py ${src%.hip})  # compiler and flags as csrc/Makefile states them for this unit
+$cmd --cuda-device-only -S \
     -o $out/${src%.hip}.s $root/haghighatshoarmuir2024_amd/csrc/$src 2>/dev/null
 python3 - "$out/${src%.hip}.s" "$pat" <<'PY'
 import re, subprocess, sys

@@ -4,6 +4,8 @@ a device array indexed by the hardware wave id, read back through micloc_debug_r
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CS = os.path.join(ROOT, "haghighatshoarmuir2024_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from make_cmd import compiler_and_flags  # (csrc/Makefile states the flags, per unit)
 s = open(os.path.join(CS, "rzcc.hip")).read()
 pre = '''
 __device__ unsigned long long rz_prof_work[8], rz_prof_wait[8], rz_prof_n[8];
@@ -98,12 +100,14 @@ if "only4" in abl:
         resolve_cluster_regs<16>(s, stride, remaining, w, emit, word_at, val_at, sgn);
         return;
     }""", "")
-tmp = os.path.join(CS, "rzcc_prof_tmp_%s.hip" % (abl or "plain"))
+# (outside csrc/, where every *.hip is a unit of the library; -I finds the headers the copy includes)
+work = os.path.join(ROOT, "build_dev", "rz_prof")
+os.makedirs(work, exist_ok=True)
+tmp = os.path.join(work, "rzcc_prof_tmp_%s.hip" % (abl or "plain"))
 obj = "/tmp/rzcc_prof_%s.o" % (abl or "plain")
 open(tmp, "w").write(s)
 try:
-    flags = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-unused-result".split()
-    subprocess.check_call(["/opt/rocm/bin/hipcc"] + flags + ["-c", "-o", obj, tmp])
+    subprocess.check_call(compiler_and_flags("rzcc") + ["-I", CS, "-c", "-o", obj, tmp])
 finally:
     if "--keep" not in sys.argv:
         os.remove(tmp)

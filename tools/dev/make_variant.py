@@ -29,8 +29,8 @@ VARIANTS = {"stht_wide2": ("VARIANT_STHT_WIDE_TWO_TILES", "stht"), "stht_valu": 
             "ws_sparse_lif": (os.path.join(ROOT, "tools", "experiments", "ws_sparse_lif", "ws_sparse_lif.patch"), "beamform")}
 # further units of a variant: recompiled against the variant's header with the listed constant set as well
 COMPANIONS = {"beamform": (("beamform_lean", "VARIANT_WS_GENERAL_ONLY"),)}
-FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result".split()
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from make_cmd import compiler_and_flags  # noqa: E402  (csrc/Makefile states the flags, per unit)
 
 
 def build(name):
@@ -70,9 +70,9 @@ def build(name):
     new_objs = []
     for u in units:
         new_objs.append(os.path.join(work, u + ".o"))
-        subprocess.check_call([HIPCC] + FLAGS + ["-c", "-o", new_objs[-1], os.path.join(work, u + ".hip")])
+        subprocess.check_call(compiler_and_flags(u) + ["-c", "-o", new_objs[-1], os.path.join(work, u + ".hip")])
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + new_objs + objs)
+    subprocess.check_call([compiler_and_flags(unit)[0], "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + new_objs + objs)
     return out
 
 
