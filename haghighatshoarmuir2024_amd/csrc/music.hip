@@ -14,7 +14,8 @@
 //                            built on the host once per plan.  Only the in-band bins are ever used (34 of 2048 at the scripts' shape),
 //                            so this is a skinny GEMM rather than an FFT; any N works, odd sizes included.
 //   3. music_select_kernel   bin power = mean over (mic, frame) of |X|^2, and the k strongest bins in np.argsort order (ascending
-//                            power; exact ties: the later bin sorts later -- the stable "later index wins" contract of DESIGN section 2).
+//                            power; exact ties: the later bin sorts later -- the stable "later index wins" contract of DESIGN section 2;
+//                            a NaN power sorts behind every number: music_rows.h's rank rule, which fills every position of sel).
 //   4. music_steer_kernel    P[g] = sum over the selected bins, in that order, of mean_f |a(bin, g)^H X[:, f, bin]|^2, with the
 //                            steering table a = exp(-1j 2 pi freq_vec[bin] delays) computed by NumPy (the reference's own expression).
 //   5. music_readout_kernel  optional: power[b][g] = mean_s P[b][s][g]^2 and its first arg-max.

@@ -3,7 +3,10 @@
 //   music_df2t_step     one sample of the band-pass (music.hip's own statement: the last state is fma(b, x, 0.0), NC == 1 is b0 * x --
 //                       not Df2tChain's of bandpass_rows.h)
 //   music_dft_rows      the k-loop of the band-limited DFT of 64 frame rows on the fp64 matrix cores
-//   music_bin_power, music_bin_rank      mean |X|^2 of a bin over (mic, frame); its place in the stable ascending sort
+//   music_bin_power, music_bin_rank      mean |X|^2 of a bin over (mic, frame); its place in the stable ascending sort.  THE RANK RULE:
+//                       a total order -- ascending power, a NaN behind every number, equal powers and NaNs by bin index (the later bin
+//                       sorts later).  Every position of sel is written exactly once, by one thread, with a bin in [0, nbin), whatever
+//                       the samples hold (a NaN or Inf sample makes every bin power of its slice NaN)
 //   music_steer_sum     P[g] over the selected bins, in their order
 //   music_power_add, music_first_max, music_first_argmax      the read-out  sum_s P^2  and the first maximum
 // The frame rows of a slice are rows (base M + m) Fs + f of xf / X: base = trial x slice (one-shot) or trial x slot (stream), Fs the
@@ -118,14 +121,17 @@ __device__ __forceinline__ double music_bin_power(const double *__restrict__ X, 
     return sum / inv;
 }
 
-// position of bin j in a stable ascending sort of pw[0 .. nbin): the last ksel positions are the selection, in that order
+// position of bin j in a stable ascending sort of pw[0 .. nbin): the last ksel positions are the selection, in that order.  The order
+// is total (np.argsort(kind="stable")'s): a NaN sorts behind every number, and among NaNs as among equal numbers the later bin sorts
+// later -- so the ranks of the nbin bins are a permutation of 0 .. nbin - 1, whatever pw holds
 __device__ __forceinline__ int music_bin_rank(const double *pw, int nbin, int j)
 {
     const double p = pw[j];
+    const bool pnan = p != p;
     int rank = 0;
     for (int i = 0; i < nbin; ++i) {
         const double pi = pw[i];
-        rank += (pi < p) || (pi == p && i < j);
+        rank += pnan ? (pi == pi || i < j) : ((pi < p) || (pi == p && i < j));
     }
     return rank;
 }

@@ -196,7 +196,6 @@ __global__ __launch_bounds__(256) void music_stream_slice_kernel(const double *_
     } else {
         return;  // (the whole workgroup)
     }
-    for (int i = threadIdx.x; i < d.ksel; i += 256) sel[i] = 0;  // a NaN bin power leaves positions of the rank unfilled
     for (int i = threadIdx.x; i < d.nbin; i += 256) pw[i] = music_bin_power(X, (size_t)bk, d.M, d.F, F, d.Cp, i);
     __syncthreads();
     for (int i = threadIdx.x; i < d.nbin; i += 256) {

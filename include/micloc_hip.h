@@ -1084,7 +1084,9 @@ int micloc_stream_bands_track_status(const void *track_state, int *frontier, voi
  * transformed at the in-band bins only: W (device) is [Np][Cp] with Np = N rounded up to 64, Cp = 2 nbin rounded up to 16,
  * W[n][2j] = cos(2 pi ((k_j n) mod N) / N), W[n][2j + 1] = -sin(...) for bin k_j, zero elsewhere.  Bin power = mean over
  * (mic, frame) of |X|^2; the k strongest bins are taken in np.argsort order (ascending power, exact ties: the later bin sorts
- * later); k == 0 or k > nbin takes all.  spec[b][s][g] = sum over those bins of mean_f |a^H X[:, f, bin]|^2 with the steering
+ * later; a NaN power sorts behind every number, NaNs among themselves by bin as well -- a total order, so sel always holds ksel
+ * distinct bins in [0, nbin), also for a slice with a NaN or Inf sample, whose bin powers and spectrum row are NaN while the
+ * other slices and trials keep their bits); k == 0 or k > nbin takes all.  spec[b][s][g] = sum over those bins of mean_f |a^H X[:, f, bin]|^2 with the steering
  * table steer_re / steer_im [nbin][M][G] (device; a = exp(-1j 2 pi freq delays), conjugated here).  Outputs (device, each may be
  * NULL): sel [B][S][ksel] int32 (the selected in-band bin indices, in order), spec [B][S][G], power [B][G] = mean_s spec^2 and
  * argmax [B] (first maximum).  MICLOC_ERR_SHAPE: a slice shorter than N (the reference's broadcast ValueError) or a slice start
